@@ -38,6 +38,15 @@ replica on one GPU, the case the driver can record on a one-GPU box; N = 8 is co
 --config 4: BASELINE.json configs[3] instead -- Llama-2-13B avg-3-bit, 16 x 2048 prompt
 rows in one batched prompt pass (the harness' GeMM mode, amq/utils/speed.py:61-71); a step
 is one pass, the roofline object is the MFMA one (linears' flop / time of the linears).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+Everything else -- the roofline objects, the per-layer table, the parity gate, the CPU baseline and the figures beyond the
+metric -- takes runs of its own and is measured only with --full (--no-* trim that set).
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as DIR/<name>.npy (float32; token
+ids as float64), rank 0 only: decode -- logits.npy [vocab] and next_token.npy [1] (the greedy choice the step fed back);
+--config 4 -- logits.npy [16, vocab] of the last prompt pass.  Inputs and weights are seeded, so the same arguments give
+the same inputs on every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -510,6 +519,23 @@ def load_traffic():
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as path/<name>.npy, floats as float32 and integers (token ids) as float64"""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes is more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def run_decode(args, rep, dev):
     rank, n_gpus = rep.rank, rep.world
     max_seq = PROMPT + args.warmup + args.steps + 8
@@ -530,7 +556,8 @@ def run_decode(args, rep, dev):
     ok = bool(torch.isfinite(m.logits.float()).all().item())
     if rank != 0:
         return
-    roof = gemv_roofline(m)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": m.logits, "next_token": m.token})
     out = {
         "metric": "decode tokens/s, Llama-2-%s AMQ mixed 2/3/4-bit avg-3-bit, batch 1%s" % (
             "70B" if big else "7B", ", %d independent streams" % n_gpus if big else ""),
@@ -549,11 +576,6 @@ def run_decode(args, rep, dev):
                                "batch 1 decode after a 64-token prefill, one stream per GPU%s" % (
                                    "70B" if big else "7B", usage, " (BASELINE.json configs[4])" if big else ""),
                    "parallelism": "replicas x%d" % n_gpus, "prompt": PROMPT, "group_size": 128},
-        "roofline": {"bound": "hbm", "achieved": roof["gbps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": roof["gbps"] / HBM_PEAK_GBPS, "traffic": None if big else load_traffic(),
-                     "kernel": "amq::gemv_kernel (grouped 2/3/4-bit weight-streaming GEMV; arithmetic: %s)" % gemv_math_name(),
-                     "bytes_per_launch": roof["bytes_per_launch"], "us_per_launch": roof["us_per_launch"],
-                     "launches_per_token": roof["launches_per_token"]},
         "finite_logits": ok,
         # what "parity-green" means in tests/ (north_star: 1e-3 relative fp16 tolerance): element-wise
         # |y - y_ref| <= 1e-3 |y_ref| + 1e-3 rms(y_ref) against the CPU nn.Linear-on-dequantized-weights oracle -- the rms term is
@@ -566,6 +588,15 @@ def run_decode(args, rep, dev):
         "linear_gb_per_token": m.linear_bytes_per_token() / 1e9,
         "model_gbps": m.total_bytes_per_token(PROMPT + args.warmup + args.steps // 2) / (elapsed / args.steps) / 1e9,
     }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
+    roof = gemv_roofline(m)
+    out["roofline"] = {"bound": "hbm", "achieved": roof["gbps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                       "frac": roof["gbps"] / HBM_PEAK_GBPS, "traffic": None if big else load_traffic(),
+                       "kernel": "amq::gemv_kernel (grouped 2/3/4-bit weight-streaming GEMV; arithmetic: %s)" % gemv_math_name(),
+                       "bytes_per_launch": roof["bytes_per_launch"], "us_per_launch": roof["us_per_launch"],
+                       "launches_per_token": roof["launches_per_token"]}
     if big:
         args.no_layer_table = args.no_mfma = args.no_cpu_baseline = True      # 7B / 13B-specific extras of the default line
     if n_gpus == 1 and not args.no_layer_table:
@@ -609,17 +640,37 @@ def run_gemm_mode(args, rep, dev):
     B, S = 16, 2048
     m, a, usage = build_model(dev, seed=rank, max_seq=S, model="Llama-2-13b-hf", pinned=())
     ids = torch.randint(0, m.vocab - 1, (B, S), generator=torch.Generator().manual_seed(rank)).to(dev)
+    last = {}
     with torch.inference_mode():
         for _ in range(args.warmup):
             m.prefill_batch(ids)
-        elapsed = rep.timed(lambda: m.prefill_batch(ids), args.steps, sync=lambda: torch.cuda.synchronize(dev))
-        logits = m.prefill_batch(ids)
+        elapsed = rep.timed(lambda: last.update(logits=m.prefill_batch(ids)), args.steps, sync=lambda: torch.cuda.synchronize(dev))
+    logits = last["logits"]                         # what the last timed pass returned
     ok = bool(torch.isfinite(logits.float()).all().item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": logits})
+    M = B * S
+    total_flops = sum(2.0 * M * blk[name].N * blk[name].K for blk in m.blocks for name in m.cfg["linear"])
+    out = {
+        "metric": "batched prompt passes/s (GeMM mode), Llama-2-13B AMQ mixed 2/3/4-bit avg-3-bit, 16 x 2048 rows",
+        "value": n_gpus * args.steps / elapsed, "unit": "passes/s", "n_gpus": n_gpus, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+        "config": {"workload": "Llama-2-13B shapes, synthesized avg-3.0-bit arch (bits_usage %.3f), one batched prompt pass "
+                               "of 16 x 2048 rows (BASELINE.json configs[3])" % usage,
+                   "parallelism": "replicas x%d" % n_gpus, "group_size": 128, "gemm_route": ops.gemm_route_name(M)},
+        "prompt_tokens_per_s": n_gpus * args.steps * M / elapsed,
+        "linear_tflop_per_pass": total_flops / 1e12,
+        "whole_pass_tflops": total_flops * args.steps / elapsed / 1e12,
+        "finite_logits": ok,
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     # the dominant kernel family: the seven linears of every block at M = 32768 (what ops.gemm dispatches to),
     # timed alone with HIP events on the launch stream
-    M = B * S
     xs = {k: torch.randn(M, k, device=dev, dtype=torch.float16) * 0.05 for k in (m.H, m.I)}
     flops = 0
     with torch.inference_mode():
@@ -650,24 +701,10 @@ def run_gemm_mode(args, rep, dev):
         torch.cuda.synchronize(dev)
     ops.LIB_GEMM_ROWS = 0
     tf_lib = flops / (e0.elapsed_time(e1) * 1e-3) / 1e12
-    total_flops = sum(2.0 * M * blk[name].N * blk[name].K for blk in m.blocks for name in m.cfg["linear"])
-    out = {
-        "metric": "batched prompt passes/s (GeMM mode), Llama-2-13B AMQ mixed 2/3/4-bit avg-3-bit, 16 x 2048 rows",
-        "value": n_gpus * args.steps / elapsed, "unit": "passes/s", "n_gpus": n_gpus, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-        "config": {"workload": "Llama-2-13B shapes, synthesized avg-3.0-bit arch (bits_usage %.3f), one batched prompt pass "
-                               "of 16 x 2048 rows (BASELINE.json configs[3])" % usage,
-                   "parallelism": "replicas x%d" % n_gpus, "group_size": 128, "gemm_route": ops.gemm_route_name(M)},
-        "roofline": {"bound": "mfma", "achieved": tf, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_PEAK_TFLOPS,
-                     "traffic": None, "kernel": ops.gemm_route_name(M),
-                     "note": "the seven linears of 4 blocks at M = 32768 through ops.gemm, HIP events on the launch stream"},
-        "prompt_tokens_per_s": n_gpus * args.steps * M / elapsed,
-        "linear_tflop_per_pass": total_flops / 1e12,
-        "whole_pass_tflops": total_flops * args.steps / elapsed / 1e12,
-        "comparison_library_route_tflops": tf_lib,
-        "finite_logits": ok,
-    }
+    out["roofline"] = {"bound": "mfma", "achieved": tf, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_PEAK_TFLOPS,
+                       "traffic": None, "kernel": ops.gemm_route_name(M),
+                       "note": "the seven linears of 4 blocks at M = 32768 through ops.gemm, HIP events on the launch stream"}
+    out["comparison_library_route_tflops"] = tf_lib
     print(json.dumps(out), flush=True)
 
 
@@ -706,6 +743,11 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=(3, 4, 5),
                     help="3 (default): BASELINE.json configs[2], the headline decode metric; 4: configs[3], GeMM mode; "
                          "5: configs[4], Llama-2-70B decode streams (one per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline objects, per-layer table, parity gate, CPU baseline, "
+                         "figures beyond the metric (the --no-* options below trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64), rank 0 only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-layer-table", action="store_true")
     ap.add_argument("--engine", action="store_true", help="A/B: decode steps through the one-launch-per-token engine")
@@ -721,6 +763,8 @@ def main():
         args.steps = {3: 256, 5: 64}.get(args.config, 3)
     if args.warmup is None:
         args.warmup = {3: 16, 5: 8}.get(args.config, 1)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become one.  Nothing above has touched the GPU (`import torch` does not), and the children are

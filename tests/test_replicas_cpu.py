@@ -201,6 +201,13 @@ def test_bench_extras_run_after_the_timed_region():
         assert src.index(leg) > timed, leg
     # ... and only rank 0 at N = 1 runs them
     assert "if rank != 0:\n        return" in src and src.count("n_gpus == 1") >= 3
+    # ... and only with --full: a plain run prints its headline line and returns before the first of them (the same in GeMM mode)
+    plain_exit = src.index("if not args.full:\n        print(json.dumps(out), flush=True)\n        return")
+    for leg in ("gemv_layer_table(", "beyond_the_metric(", "mfma_roofline(", "parity_gate(", "cpu_baseline()", "gemv_roofline("):
+        assert src.index(leg) > plain_exit, leg
+    fn = next(n for n in ast.walk(tree) if isinstance(n, ast.FunctionDef) and n.name == "run_gemm_mode")
+    src = ast.get_source_segment(open(os.path.join(root, "bench.py")).read(), fn)
+    assert src.index("rep.timed(") < src.index("if not args.full:\n        print(json.dumps(out), flush=True)\n        return") < src.index("ops.LIB_GEMM_ROWS = 1024")
 
 
 _RANK8_SCRIPT = """
