@@ -850,6 +850,36 @@ int amq_decode_tail_suppress_f16(const void* logits, int vocab, const void* embe
                                              suppress_ids), "decode_tail_suppress");
 }
 
+int amq_sample_f16(const void* logits, int rows, int vocab, void* state, const int* suppress_ids, const float* u_in, long long* token_out,
+                   unsigned char* kept_out, int seq0, int flags, void* stream) {
+    if (!state) return fail(AMQ_EINVAL, "state: the 128-byte device block of sampling parameters is required (null)");
+    if (!logits || !token_out) return fail(AMQ_EINVAL, "null pointer");
+    if (vocab < 1) return fail(AMQ_EINVAL, "vocab must be >= 1 (got %d)", vocab);
+    if (rows < 1) return fail(AMQ_EINVAL, "rows must be >= 1 (got %d)", rows);
+    if (flags & ~3) return fail(AMQ_EINVAL, "unknown flags %d", flags);
+    if ((flags & AMQ_SAMPLE_EOS) && rows > 8) return fail(AMQ_ESHAPE, "EOS bookkeeping serves at most 8 sequences (the state block holds 8 flags), got %d rows", rows);
+    if ((long long)rows * vocab >= (1ll << 40)) return fail(AMQ_ESHAPE, "rows * vocab too large");
+    amq::SampleArgs a{(const _Float16*)logits, vocab, nullptr, 0, token_out, nullptr, nullptr, nullptr, nullptr, 0, suppress_ids, (int*)state,
+                      u_in, kept_out, seq0, flags};
+    return check_hip(amq::launch_sample(a, rows, (hipStream_t)stream), "sample");
+}
+
+int amq_decode_tail_sample_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
+                               const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids, void* state,
+                               void* stream) {
+    if (!state) return fail(AMQ_EINVAL, "state: the 128-byte device block of sampling parameters is required (null)");
+    if (!logits || !embed || !token || !pos || !x) return fail(AMQ_EINVAL, "null pointer");
+    if ((rope_table == nullptr) != (rope_cur == nullptr)) return fail(AMQ_EINVAL, "rope_table and rope_cur go together");
+    if (rope_cur && rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
+    if (vocab < 1) return fail(AMQ_EINVAL, "vocab must be >= 1 (got %d)", vocab);
+    if (batch < 1) return fail(AMQ_EINVAL, "rows must be >= 1 (got %d)", batch);
+    if (hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need hidden %% 8 == 0 (got %d)", hidden);
+    if (batch > 8) return fail(AMQ_ESHAPE, "at most 8 sequences (the state block holds 8 finished flags), got %d", batch);
+    amq::SampleArgs a{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, pos, (_Float16*)x, (const _Float16*)rope_table,
+                      (_Float16*)rope_cur, rope_rows, suppress_ids, (int*)state, nullptr, nullptr, 0, AMQ_SAMPLE_ADVANCE | AMQ_SAMPLE_EOS};
+    return check_hip(amq::launch_sample(a, batch, (hipStream_t)stream), "decode_tail_sample");
+}
+
 int amq_set_token_f16(const long long* token_in, int n_in, const void* embed, int vocab, int hidden, long long* token, const int* pos, void* x,
                       const void* rope_table, void* rope_cur, int rope_rows, int batch, void* stream) {
     if (!token_in || !embed || !token || !pos || !x) return fail(AMQ_EINVAL, "null pointer");

@@ -195,6 +195,30 @@ hipError_t launch_set_token(const void* token_in, int n_in, const void* embed, i
 hipError_t launch_gemv_f16w(const void* x, const void* W, const void* bias, void* y, const void* gamma, float eps,
                             int N, int K, hipStream_t st, int M = 1);      // x [M, K], y [M, N], M <= 8
 
+// sampling tail / row sampler (amq_sample.hip).  state: the 128-byte device block of include/amq_hip.h (int32 word indices below)
+enum { SMP_TEMPERATURE = 0, SMP_TOP_K = 1, SMP_TOP_P = 2, SMP_PAD_ID = 3, SMP_SEED = 4, SMP_DRAW = 6, SMP_EOS = 8, SMP_FINISHED = 16,
+       SMP_UNFINISHED = 24, SMP_ARRIVE = 25, SMP_FIRST_KEPT = 26, SMP_WORDS = 32 };
+enum { SMP_FLAG_ADVANCE = 1, SMP_FLAG_EOS = 2 };
+struct SampleArgs {
+    const _Float16* logits;     // [rows, vocab], contiguous
+    int vocab;
+    const _Float16* embed;      // null: rows -> tokens only (no position / x / cos-sin row update)
+    int hidden;
+    long long* token;           // [rows]
+    int* pos;
+    _Float16* x;
+    const _Float16* rope_table;
+    _Float16* rope_cur;
+    int rope_rows;
+    const int* suppress;        // int32 [8] or null
+    int* state;
+    const float* u_in;          // [rows] uniform numbers given by the caller, or null: generated
+    unsigned char* kept;        // [rows, vocab] kept-set mask out, or null
+    int seq0;                   // sequence index of row 0 (the generator's counter word)
+    int flags;                  // SMP_FLAG_*
+};
+hipError_t launch_sample(const SampleArgs& a, int rows, hipStream_t st);
+
 // q / k / v GEMV + decode attention in one launch (amq_gemv.hip): a's segments 0 .. 2 = q, k, v (M = 1, RMSNorm prologue, gamma / eps
 // set); t: caches, output, step-state block (rope_cur), head counts, max_seq; tickets: int32 [n_heads], zero before and after
 hipError_t launch_gemv_qkv_attn(GemvArgs& a, const AttnArgs& t, int* tickets, hipStream_t st);

@@ -15,7 +15,17 @@ buffers (QuantLlama.from_hf: no weight copies) and gives THIS model instance
   * ``model.generate(ids, min_new_tokens=n, max_new_tokens=n, do_sample=False, num_beams=1, attention_mask=all ones)`` -- greedy, fixed length,
     batch 1..8: prefill + n - 1 graph replays without a host sync in between; returns ``[B, S + n]`` ids like HF.
 
-Anything else -- sampling, beams, an attention mask with holes, ``past_key_values``, ``labels``, ``inputs_embeds``, hidden-state / attention outputs,
+With ``convert_model_to_hip(model, sampling=True)`` (opt-in; the default routing above is unchanged) ``generate`` additionally serves, on the runner,
+
+  * ``do_sample=True`` with ``temperature`` / ``top_k`` / ``top_p`` (call arguments, else ``generation_config``, else HF's defaults: top_k = 50),
+    one beam, batch 1..8: the sampled tail of the captured step (amq_decode_tail_sample_f16).  The seed of a call is one ``torch.randint`` from
+    torch's global CPU generator, so ``torch.manual_seed(s)`` before ``generate`` reproduces a call; the tokens are NOT ``torch.multinomial``'s
+    (a counter-based generator of (seed, draw, sequence); the kept set is HF's warpers' except that a tie class at the top-p boundary is kept whole);
+  * ``max_new_tokens`` without an equal ``min_new_tokens``, greedy or sampled: a sequence stops at its first ``eos_token_id`` (int or list, at most
+    8) and is padded with ``pad_token_id`` from there on, the call returns at the longest sequence's length as HF's does; ``min_new_tokens = m``
+    keeps the EOS ids suppressed for the first m tokens.
+
+Anything else -- sampling and open-ended calls without that flag, ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``, beams, an attention mask with holes, ``past_key_values``, ``labels``, ``inputs_embeds``, hidden-state / attention outputs,
 stopping criteria, streamers, more than 8 sequences, a call without ``start_pos`` -- falls through to the model's original ``forward`` / ``generate``
 (HF's own, over the fused modules).  ``state_dict`` / ``deepcopy`` / ``.to()`` are untouched: the runners live outside the module, keyed weakly by it.
 """
@@ -36,6 +46,8 @@ _GC_PROCESSORS = ("repetition_penalty", "encoder_repetition_penalty", "no_repeat
                   "force_words_ids", "constraints", "forced_bos_token_id", "forced_eos_token_id", "exponential_decay_length_penalty", "suppress_tokens",
                   "begin_suppress_tokens", "sequence_bias", "guidance_scale", "watermarking_config", "renormalize_logits", "remove_invalid_values",
                   "penalty_alpha", "dola_layers", "prompt_lookup_num_tokens", "num_beam_groups", "diversity_penalty")
+# ... and the warpers the runner's sampled tail does not apply (temperature, top_k and top_p it does)
+_GC_WARPERS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff", "top_h")
 MAX_BATCH = 8
 
 
@@ -136,47 +148,86 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     if inputs is not None and "input_ids" in kw:
         return fall()
     gc = getattr(self, "generation_config", None)
+    sampling = self.__dict__.get("_amq_sampling", False)       # convert_model_to_hip(model, sampling=True): sampled and open-ended calls served too
     n = kw.pop("max_new_tokens", None)
     nmin = kw.pop("min_new_tokens", None)
-    greedy = kw.pop("do_sample", getattr(gc, "do_sample", False)) in (False, None) and kw.pop("num_beams", getattr(gc, "num_beams", 1)) in (1, None)
+    do_sample = kw.pop("do_sample", getattr(gc, "do_sample", False)) not in (False, None)
+    one_beam = kw.pop("num_beams", getattr(gc, "num_beams", 1)) in (1, None)
     mask = kw.pop("attention_mask", None)
     eos = kw.pop("eos_token_id", getattr(gc, "eos_token_id", None))
-    kw.pop("pad_token_id", None)                             # (fixed-length greedy decoding never pads)
+    pad = kw.pop("pad_token_id", None)                         # (fixed-length decoding never pads)
+    warp = {}
+    if sampling:                                                # call arguments, else generation_config, else HF's defaults (top_k = 50)
+        for k, default in (("temperature", 1.0), ("top_k", 50), ("top_p", 1.0)):
+            v = kw.pop(k, None)
+            v = getattr(gc, k, None) if v is None else v
+            warp[k] = default if v is None else v
+        if pad is None:
+            pad = getattr(gc, "pad_token_id", None)
     for k in ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states", "use_cache"):
         if kw.get(k) in (None, False) or (k == "use_cache" and kw.get(k) is True):
             kw.pop(k, None)
     others = [generation_config, logits_processor, stopping_criteria, prefix_allowed_tokens_fn, assistant_model, streamer, negative_prompt_ids,
               negative_prompt_attention_mask, custom_generate]
     eos = [] if eos is None else ([int(e) for e in eos] if isinstance(eos, (list, tuple)) else [int(eos)])
-    if (kw or any(o is not None and (not hasattr(o, "__len__") or len(o)) for o in others) or synced_gpus or not greedy or n is None or nmin != n
+    fixed = nmin == n
+    if (kw or any(o is not None and (not hasattr(o, "__len__") or len(o)) for o in others) or synced_gpus or not one_beam or n is None
+            or ((do_sample or not fixed) and not sampling)
             or not _plain_ids(ids) or not ids.is_cuda or int(n) < 1 or len(eos) > 8 or not _mask_is_full(mask, ids)):
         return fall()
-    # the model's own generation defaults must ask for plain greedy decoding too (any logits processor HF would add changes the tokens)
-    if gc is not None and any(getattr(gc, k, None) not in (None, False, 0, 1, 1.0, [], ()) for k in _GC_PROCESSORS):
+    # the model's own generation defaults must ask for nothing else (any other logits processor / warper HF would add changes the tokens)
+    if gc is not None and any(getattr(gc, k, None) not in (None, False, 0, 1, 1.0, [], ()) for k in _GC_PROCESSORS + (_GC_WARPERS if do_sample else ())):
         return fall()
     B, S = ids.shape
     n = int(n)
+    nmin = 0 if nmin is None else int(nmin)
+    if do_sample and not (float(warp["temperature"]) > 0.0 and int(warp["top_k"]) >= 0 and 0.0 < float(warp["top_p"]) <= 1.0):
+        return fall()                                           # (HF raises its own error for these)
+    if nmin > n or (not fixed and pad is not None and not 0 <= int(pad) < int(self.config.vocab_size)):
+        return fall()
     r = _runner(self, B, S + n)
-    # min_new_tokens = max_new_tokens: HF never lets an EOS id through (MinNewTokensLengthLogitsProcessor sets their logits to -inf on every step)
-    if tuple(eos) != getattr(r, "_suppressed", ()):
-        r.set_suppressed(eos)
-    new = r.generate(ids if B > 1 else ids[0], n)
-    return torch.cat([ids, new.view(B, n).to(ids.dtype)], dim=1)
+    if not do_sample and fixed:
+        # min_new_tokens = max_new_tokens: HF never lets an EOS id through (MinNewTokensLengthLogitsProcessor sets their logits to -inf on every step)
+        if tuple(eos) != getattr(r, "_suppressed", ()):
+            r.set_suppressed(eos)
+        new = r.generate(ids if B > 1 else ids[0], n)
+        return torch.cat([ids, new.view(B, n).to(ids.dtype)], dim=1)
+    try:
+        if do_sample:
+            # one number from torch's global CPU generator per call: torch.manual_seed(s) before generate() makes the call reproducible, as under HF
+            # (the tokens are not torch.multinomial's: the runner draws with its own counter-based generator)
+            r.set_sampling(float(warp["temperature"]), int(warp["top_k"]), float(warp["top_p"]), seed=int(torch.randint(0, 2 ** 62, (1,)).item()))
+        if fixed:
+            if tuple(eos) != getattr(r, "_suppressed", ()):
+                r.set_suppressed(eos)
+            new = r.generate(ids if B > 1 else ids[0], n)
+        else:
+            # open-ended: a sequence stops at its first EOS id and is padded from there on (HF pads with eos[0] when no pad id is set)
+            if getattr(r, "_suppressed", ()) != ():
+                r.set_suppressed(())
+            r.set_eos(eos, pad_id=int(pad) if pad is not None else (eos[0] if eos else 0))
+            new = r.generate(ids if B > 1 else ids[0], n, stop_at_eos=True, min_new_tokens=nmin)
+    finally:
+        r.set_sampling(None)                                    # (model(ids, start_pos=) steps of this runner stay greedy)
+    return torch.cat([ids, new.view(B, -1).to(ids.dtype)], dim=1)
 
 
-def convert_model_to_hip(model):
+def convert_model_to_hip(model, sampling=False):
     """convert_model_to_ft(model) + replace_generate_functions() (ftllama_modeling.py:569-580, ftllama_generate.py:613-622) for the HIP backend:
     call it on the model ``prepare_for_inference(model, backend='hip')`` returned (a Llama-family ``*ForCausalLM`` whose decoder linears are
     HIPQuantLinear modules on one GPU).  Patches THIS instance's ``forward`` and ``generate`` (see the module docstring); idempotent; returns the
-    model.  ``revert_model_to_hf(model)`` undoes it."""
+    model.  ``sampling=True`` also routes ``generate(do_sample=True, temperature / top_k / top_p)`` and open-ended calls (EOS stop) to the runner;
+    calling it again on a converted model only updates that flag.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
     if "_amq_orig_forward" in model.__dict__:
+        model.__dict__["_amq_sampling"] = bool(sampling)
         return model
     from .llama import QuantLlama
     QuantLlama.check_hf(model)                               # refuse now, with the reason, what the runner cannot serve
     model.__dict__["_amq_orig_forward"] = model.forward
     model.__dict__["_amq_orig_generate"] = model.generate
+    model.__dict__["_amq_sampling"] = bool(sampling)
     model.forward = types.MethodType(_fast_forward, model)
     model.generate = types.MethodType(_fast_generate, model)
     return model
@@ -187,6 +238,7 @@ def revert_model_to_hf(model):
         if "_amq_orig_" + name in model.__dict__:
             model.__dict__.pop(name, None)
             model.__dict__.pop("_amq_orig_" + name)
+    model.__dict__.pop("_amq_sampling", None)
     _RUNNERS.pop(model, None)
     return model
 

@@ -234,6 +234,12 @@ class QuantLlama:
         # token ids the greedy choice never takes (8 slots, -1 = unused; read by the step's tail kernel): what HF's min_new_tokens does to the EOS ids
         # (set_suppressed; the values may change between replays of the captured step)
         self.suppress = torch.full((8,), -1, dtype=torch.int32, device=dev)
+        # sampled decoding (set_sampling / set_eos): the device block the sampled tail reads on every replay, and the sampled step's own graph beside
+        # the greedy one (captured on first use; self.graph stays the greedy step)
+        self.sampling = None        # None = greedy; else dict(temperature, top_k, top_p, seed)
+        self.eos, self.pad_id = (), 0
+        self.sample_state = None
+        self.sample_graph = None
         self.has_bias = any(blk[n].bias is not None for blk in self.blocks for n in config["linear"])
         # down_proj's launch: the GEMV with the fused SiLU*mul prologue while the rows' x fits LDS whole; past that (7B: 7 - 8 rows of 11008) one
         # silu_mul launch + the GEMV without a prologue, x staged in two K phases (fusing the prologue there would make every workgroup take in gate
@@ -342,14 +348,14 @@ class QuantLlama:
         return self.linear_bytes_per_token() + self.lm_head.numel() * 2 + kv
 
     # ----------------------------------------------------------------- decode
-    def _step(self):
+    def _step(self, sampled=False):
         """one token: reads self.x (= embed[self.token], kept in step by set_token / the step's own tail) and self.pos
         (device), writes self.logits, self.token, self.pos and the next step's self.x"""
         H = self.H
         if self.engine is not None:
             self.engine.step()
             ops.gemv_f16w(self.x.reshape(-1), self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
-            ops.decode_tail(self.logits, self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur, suppress=self.suppress)
+            self._tail(sampled)
             return
         have_sums = False                       # self.ss holds the sums of squares of self.x's rows (written by the launch that produced them)
         for blk in self.blocks:
@@ -394,8 +400,62 @@ class QuantLlama:
                 ops.gemm(ops.silu_mul(self.gate, self.up, out=self.gate), d.qn, d.mn, d.bits, d.mode, d.N, d.K, bias=d.bias, residual=self.x, out=self.x)
                 have_sums = False
         ops.gemv_f16w(self.x.reshape(-1) if self.B == 1 else self.x, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
-        # argmax, pos += 1, x = embed[token], rope_cur = cos/sin row of the new position (per sequence; the position is shared)
-        ops.decode_tail(self.logits, self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur, suppress=self.suppress)
+        self._tail(sampled)
+
+    def _tail(self, sampled):
+        """the end of a token step: the next token (arg-max, or a draw with the device block's parameters + EOS bookkeeping), pos += 1,
+        x = embed[token], rope_cur = cos/sin row of the new position (per sequence; the position is shared)"""
+        if sampled:
+            ops.decode_tail_sample(self.logits, self.embed, self.token, self.pos, self.x, self.sample_state, table=self.rope_tab, cur=self.rope_cur,
+                                   suppress=self.suppress)
+        else:
+            ops.decode_tail(self.logits, self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur, suppress=self.suppress)
+
+    # ------------------------------------------------------------- sampling
+    sampling, sample_state, sample_graph, eos, pad_id = None, None, None, (), 0      # (class defaults: greedy)
+    EOS_POLL_STEPS = 16         # generate(stop_at_eos=True) reads the unfinished count every this many steps: fewer = less work after the last EOS, more host syncs
+
+    def _write_sampling_state(self):
+        if self.sample_state is None:
+            self.sample_state = ops.new_sampling_state(self.dev)
+        if self.sampling is not None:
+            ops.set_sampling_state(self.sample_state, eos_ids=self.eos, pad_id=self.pad_id, **self.sampling)
+        else:                                   # greedy with EOS stop: top_k = 1 and the first kept token = the first maximum, as the greedy tail takes it
+            ops.set_sampling_state(self.sample_state, top_k=1, eos_ids=self.eos, pad_id=self.pad_id, first_kept=True)
+
+    def set_sampling(self, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+        """Sampled decoding from the next prompt pass on: temperature, then top-k (0 = off), then top-p (1 = off), HF's order; ``seed`` fixes the
+        whole sequence (counter-based generator: draw i of sequence b is a function of (seed, i, b) -- not torch.multinomial's stream).
+        ``set_sampling(None)``: back to greedy.  Writes the device block only: the greedy step (self.graph) and the sampled step (self.sample_graph)
+        are two graphs, each captured once, and switching re-captures neither."""
+        if temperature is None:
+            self.sampling = None
+            return
+        self.sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed))
+        self._write_sampling_state()
+
+    def set_eos(self, ids=(), pad_id=0):
+        """EOS ids (at most 8) and the pad id of the sampled tail's bookkeeping: a sequence that emits an EOS id is finished and emits ``pad_id``
+        from then on (HF: next * unfinished + pad * (1 - unfinished))"""
+        ids = tuple(int(i) for i in ids)
+        if len(ids) > 8:
+            raise ValueError("at most 8 EOS ids")
+        self.eos, self.pad_id = ids, int(pad_id)
+        if self.sample_state is not None:
+            self._write_sampling_state()
+
+    def _sampled_tail(self):
+        """the token steps end in the sampled tail: sampling is on, or generate() runs greedy with EOS stop (the sampled tail taking the first maximum)"""
+        return self.sampling is not None or self.__dict__.get("_greedy_eos", False)
+
+    def _first_token(self):
+        """the first token after a prompt pass when the sampled tail is in use: draw 0 of every sequence from the last rows' logits"""
+        tok = ops.sample(self.logits, self.sample_state, suppress=self.suppress, flags=ops.SAMPLE_ADVANCE | ops.SAMPLE_EOS)
+        self.set_token(tok)
+
+    def unfinished(self):
+        """number of sequences that have not emitted an EOS id yet (one 4-byte read; synchronises)"""
+        return int(self.sample_state[24].item())
 
     def set_suppressed(self, ids=()):
         """token ids greedy decoding must not pick (at most 8; () = none): HF's generate(min_new_tokens = max_new_tokens) never emits an EOS id.
@@ -450,39 +510,48 @@ class QuantLlama:
         torch.index_select(self.rope_tab.view(self.max_seq, 128), 0, self.pos.to(torch.int64).clamp_(0, self.max_seq - 1),
                            out=self.rope_cur.view(1, 128))
 
-    def capture(self):
-        """capture one token step into a hipGraph (replayed by decode_step)"""
-        if self.graph is not None:
+    def capture(self, sampled=False):
+        """capture one token step into a hipGraph (replayed by decode_step); ``sampled``: the step that ends in the sampled tail, kept beside the greedy one"""
+        if (self.sample_graph if sampled else self.graph) is not None:
             return
         if self.host_pos >= self.max_seq:
             raise ValueError(f"cannot capture a decode step at position {self.host_pos}: the KV cache holds {self.max_seq} rows")
+        if sampled and self.sample_state is None:
+            self._write_sampling_state()
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream(self.dev))
         saved = (self.token.clone(), self.pos.clone())
+        saved_state = self.sample_state.clone() if sampled else None       # (the warm-up and the capture's own launch-free recording must not consume a draw)
         with torch.cuda.stream(side):
-            self._step()                       # warm-up outside capture (allocator, lazy init)
+            self._step(True) if sampled else self._step()                # warm-up outside capture (allocator, lazy init)
             side.synchronize()
             self.pos.copy_(saved[1]); self.set_token(saved[0])
             g = torch.cuda.CUDAGraph()
             with _no_gc(), torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                self._step()
+                self._step(True) if sampled else self._step()
         torch.cuda.current_stream(self.dev).wait_stream(side)
         torch.cuda.synchronize(self.dev)
         self.pos.copy_(saved[1]); self.set_token(saved[0])
-        self.graph = g
+        if sampled:
+            self.sample_state.copy_(saved_state)
+            self.sample_graph = g
+        else:
+            self.graph = g
 
-    def decode_step(self, use_graph=True):
+    def decode_step(self, use_graph=True, sampled=None):
         # the step appends cache row host_pos: refuse on the host (the kernels also guard the device-side position:
         # a step past the cache is skipped there and raises the sticky error word, see check())
         if self.host_pos >= self.max_seq:
             raise ValueError(f"decode step at position {self.host_pos} does not fit the KV cache (max_seq={self.max_seq})")
-        if use_graph and self.graph is None:
-            self.capture()
+        if sampled is None:
+            sampled = self._sampled_tail()
+        if use_graph and (self.sample_graph if sampled else self.graph) is None:
+            self.capture(sampled)
         self.host_pos += 1
         if use_graph:
-            self.graph.replay()
+            (self.sample_graph if sampled else self.graph).replay()
         else:
-            self._step()
+            self._step(True) if sampled else self._step()
 
     # ---------------------------------------------------------------- prefill
     def _rope(self, t, positions):
@@ -510,7 +579,10 @@ class QuantLlama:
         if start_pos < 0 or start_pos + S > self.max_seq:
             raise ValueError("prompt longer than the KV cache")
         if not use_graph:
-            return self._prefill_rows(ids, start_pos)
+            logits = self._prefill_rows(ids, start_pos)
+            if self._sampled_tail():
+                self._first_token()
+            return logits
         cache = self.__dict__.setdefault("_prefill_graphs", {})
         ent = cache.get((S, start_pos))
         if ent is None:
@@ -531,6 +603,8 @@ class QuantLlama:
         if rows is not None:
             self.logits_rows = rows             # (this graph's own output buffer: valid until its next replay)
         self.host_pos = start_pos + S           # (the replay sets the device-side position; the host mirror is not part of it)
+        if self._sampled_tail():
+            self._first_token()                 # (outside the prompt graph, which ends in the arg-max: one graph per prompt length serves both)
         return self.logits
 
     def _ids_rows(self, ids):
@@ -762,21 +836,60 @@ class QuantLlama:
         self.set_pos(0)
         self.set_token(0)
 
-    def generate(self, ids, gen_len, use_graph=True):
-        """greedy: prefill + gen_len tokens (min_new_tokens = max_new_tokens = gen_len,
-        amq/utils/speed.py:34-39).  Returns the generated ids (device tensor)."""
+    def generate(self, ids, gen_len, use_graph=True, stop_at_eos=False, min_new_tokens=0):
+        """prefill + gen_len tokens (min_new_tokens = max_new_tokens = gen_len, amq/utils/speed.py:34-39): greedy, or sampled after
+        ``set_sampling``.  Returns the generated ids (device tensor).  ``stop_at_eos`` (ids from ``set_eos``): a sequence that emits an EOS id is
+        padded with the pad id from there on, and the loop ends once every sequence has (polled every EOS_POLL_STEPS steps): returns [B, n] with
+        n = the longest sequence's length, as HF does; the EOS ids stay suppressed for the first ``min_new_tokens`` tokens."""
         S = ids.shape[-1]
         if S + gen_len > self.max_seq:
             raise ValueError("sequence does not fit the KV cache")
-        out = torch.empty(self.B, gen_len, dtype=torch.int64, device=self.dev)
-        self.prefill(ids)
-        out[:, 0] = self.token
-        for i in range(1, gen_len):
-            self.decode_step(use_graph)
-            out[:, i] = self.token
-        if self.engine is not None:
-            self.check()                        # a barrier time-out of the one-launch-per-token engine must not pass as tokens
+        if not stop_at_eos and self.sampling is None:   # greedy, fixed length
+            out = torch.empty(self.B, gen_len, dtype=torch.int64, device=self.dev)
+            self.prefill(ids)
+            out[:, 0] = self.token
+            for i in range(1, gen_len):
+                self.decode_step(use_graph)
+                out[:, i] = self.token
+            if self.engine is not None:
+                self.check()                    # a barrier time-out of the one-launch-per-token engine must not pass as tokens
+            return out[0] if self.B == 1 else out
+        self._greedy_eos = self.sampling is None
+        suppressed = getattr(self, "_suppressed", ())
+        try:
+            self._write_sampling_state()        # draw counter 0, nobody finished: one seed fixes the whole sequence
+            if not stop_at_eos:
+                self.sample_state[8:16].fill_(-1)       # fixed length: no EOS bookkeeping
+            elif min_new_tokens > 0:
+                self.set_suppressed(tuple(suppressed) + tuple(e for e in self.eos if e not in suppressed))
+            out = torch.full((self.B, gen_len), self.pad_id, dtype=torch.int64, device=self.dev)
+            self.prefill(ids)                   # (draws the first token: draw 0)
+            out[:, 0] = self.token
+            for i in range(1, gen_len):
+                if stop_at_eos and i == min_new_tokens:
+                    self.set_suppressed(suppressed)
+                if stop_at_eos and i % self.EOS_POLL_STEPS == 0 and self.unfinished() == 0:
+                    break
+                self.decode_step(use_graph, sampled=True)
+                out[:, i] = self.token
+            if self.engine is not None:
+                self.check()
+            if stop_at_eos:
+                out = self._trim_after_eos(out)
+        finally:
+            self._greedy_eos = False
+            if getattr(self, "_suppressed", ()) != suppressed:
+                self.set_suppressed(suppressed)
         return out[0] if self.B == 1 else out
+
+    def _trim_after_eos(self, out):
+        """cut the columns behind the last sequence's EOS (they hold the pad id only)"""
+        if not self.eos or out.shape[1] == 0:
+            return out
+        hit = torch.isin(out, torch.tensor(self.eos, dtype=out.dtype, device=out.device))
+        cols = torch.arange(1, out.shape[1] + 1, device=out.device)
+        length = torch.where(hit.any(dim=1), (hit.int().argmax(dim=1) + 1), cols[-1]).max()
+        return out[:, :int(length.item())]
 
 
 class DenseLlama(QuantLlama):
@@ -835,6 +948,9 @@ class DenseLlama(QuantLlama):
 
     def linear_bytes_per_token(self):
         return sum(blk[name].numel() * 2 for blk in self.blocks for name in self.cfg["linear"])
+
+    def set_sampling(self, *args, **kwargs):
+        raise NotImplementedError("sampled decoding is served by QuantLlama; the fp16 baseline decodes greedily")
 
     def _step(self):
         F = torch.nn.functional

@@ -672,6 +672,95 @@ def decode_tail(logits, embed, token, pos, x, table=None, cur=None, suppress=Non
                                                          _lib.current_stream()))
 
 
+# ---- sampled decoding (include/amq_hip.h: "sampled decoding"; amq_sample.hip)
+SAMPLE_ADVANCE, SAMPLE_EOS = 1, 2
+_SMP_WORDS, _SMP_DRAW, _SMP_EOS, _SMP_FINISHED, _SMP_UNFINISHED = 32, 6, 8, 16, 24
+
+
+def new_sampling_state(device):
+    """-> int32 [32] device block of sampling parameters (the layout include/amq_hip.h documents), set to temperature 1, no top-k / top-p, seed 0,
+    no EOS ids.  The captured sampled step reads it on every replay: :func:`set_sampling_state` changes what the next replay does."""
+    state = torch.zeros(_SMP_WORDS, dtype=torch.int32, device=device)
+    set_sampling_state(state)
+    return state
+
+
+def set_sampling_state(state, temperature=1.0, top_k=0, top_p=1.0, seed=0, eos_ids=(), pad_id=0, first_kept=False):
+    """write the parameters, reset the draw counter and the finished flags (one 128-byte copy; nothing is re-captured).  ``first_kept``: no draw,
+    the first kept token in token order is taken -- with top_k = 1 the greedy arg-max (first maximum) with the sampled tail's EOS bookkeeping."""
+    temperature, top_k, top_p, seed, pad_id = float(temperature), int(top_k), float(top_p), int(seed), int(pad_id)
+    eos_ids = [int(e) for e in eos_ids]
+    if not temperature > 0.0 or temperature == float("inf"):
+        raise ValueError(f"temperature must be a positive finite number (got {temperature})")
+    if not 0 <= top_k < 2 ** 31:
+        raise ValueError(f"top_k must be >= 0 (0 = off), got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    if len(eos_ids) > 8 or any(e < 0 for e in eos_ids):
+        raise ValueError("at most 8 EOS ids, each >= 0")
+    if not 0 <= pad_id < 2 ** 31:
+        raise ValueError(f"pad_id must be a token id, got {pad_id}")
+    _need(state, torch.int32, "state", _SMP_WORDS)
+    seed &= (1 << 64) - 1
+    host = torch.zeros(_SMP_WORDS, dtype=torch.int32)
+    host[0:1].view(torch.float32)[0] = temperature
+    host[1] = top_k
+    host[2:3].view(torch.float32)[0] = top_p
+    host[3] = pad_id
+    host[4:6].view(torch.int64)[0] = seed - (1 << 64) if seed >= 1 << 63 else seed
+    host[26] = 1 if first_kept else 0
+    host[_SMP_EOS:_SMP_EOS + 8] = torch.tensor(eos_ids + [-1] * (8 - len(eos_ids)), dtype=torch.int32)
+    state.copy_(host)
+    return state
+
+
+def set_draw_counter(state, draw):
+    """the generator's draw counter (advanced by the sampled tail itself; a sequence starts at 0)"""
+    state[_SMP_DRAW:_SMP_DRAW + 2].copy_(torch.tensor([int(draw)], dtype=torch.int64).view(torch.int32))
+
+
+def sample(logits, state, u=None, kept_out=None, suppress=None, out=None, seq0=0, flags=0):
+    """tokens int64 [rows] drawn from fp16 logits [rows, vocab] (or [vocab]) with the parameters in ``state``: amq_sample_f16.  ``u``: float32 [rows]
+    uniform numbers used instead of the generator (tests); ``kept_out``: uint8 [rows, vocab] receives the kept-set mask; ``flags``: SAMPLE_ADVANCE
+    (the draw counter moves on), SAMPLE_EOS (finished flags / pad filling, at most 8 rows)."""
+    vocab = logits.shape[-1]
+    rows = logits.numel() // vocab
+    _need(logits, torch.float16, "logits", rows * vocab)
+    _need(state, torch.int32, "state", _SMP_WORDS)
+    if u is not None:
+        _need(u, torch.float32, "u", rows)
+    if kept_out is not None:
+        _need(kept_out, torch.uint8, "kept_out", rows * vocab)
+    if suppress is not None:
+        _need(suppress, torch.int32, "suppress", 8)
+    tok = out if out is not None else torch.empty(rows, dtype=torch.int64, device=logits.device)
+    _need(tok, torch.int64, "token", rows)
+    _lib.check(_lib.load().amq_sample_f16(_lib.ptr(logits), rows, vocab, _lib.ptr(state), _lib.ptr(suppress), _lib.ptr(u), _lib.ptr(tok),
+                                          _lib.ptr(kept_out), int(seq0), int(flags), _lib.current_stream()))
+    return tok
+
+
+def decode_tail_sample(logits, embed, token, pos, x, state, table=None, cur=None, suppress=None):
+    """:func:`decode_tail` with the token drawn by :func:`sample` (draw counter advanced, EOS bookkeeping) instead of the arg-max -- one launch"""
+    vocab, hidden = embed.shape
+    B = token.numel()
+    _need(logits, torch.float16, "logits", B * vocab)
+    _need(embed, torch.float16, "embed", vocab * hidden)
+    _need(token, torch.int64, "token", B)
+    _need(pos, torch.int32, "pos", 1)
+    _need(x, torch.float16, "x", B * hidden)
+    _need(state, torch.int32, "state", _SMP_WORDS)
+    if cur is not None:
+        _need(cur, torch.float16, "rope_cur", 128)
+        _need(table, torch.float16, "rope table")
+    if suppress is not None:
+        _need(suppress, torch.int32, "suppress", 8)
+    _lib.check(_lib.load().amq_decode_tail_sample_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), _lib.ptr(pos), _lib.ptr(x),
+                                                      _lib.ptr(table) if cur is not None else None, _lib.ptr(cur),
+                                                      table.numel() // 128 if cur is not None else 0, B, _lib.ptr(suppress), _lib.ptr(state),
+                                                      _lib.current_stream()))
+
+
 def set_token(token_in, embed, token, pos, x, table=None, cur=None):
     """token = token_in (int64 CUDA tensor: one id, or one per sequence), x = embed[token], cur = table[pos] -- one launch (amq_set_token_f16); pos unchanged"""
     vocab, hidden = embed.shape
@@ -1052,7 +1141,7 @@ def _on_tensor_device(fn):
 
 
 for _name in ("repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
-              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "rope_cache",
+              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name

@@ -308,6 +308,43 @@ int amq_decode_tail_suppress_f16(const void* logits, int vocab, const void* embe
 int amq_decode_tail_batch_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
                               const void* rope_table, void* rope_cur, int rope_rows, int batch, void* stream);
 
+/* ---- sampled decoding ---------------------------------------------------------------------------------
+ * Temperature / top-k / top-p sampling and EOS stop (what HF's `_sample` does with its logits warpers, torch.multinomial, unfinished_sequences
+ * and pad filling -- amq/kernel/monkeypatch/ftllama_generate.py:257-325 -- between two token steps), as one launch that a captured step can end in.
+ * Everything that may change between replays is read from ONE 128-byte device block, `state`, of 32 int32 words:
+ *     word  0      float  temperature (> 0)
+ *     word  1      int32  top_k (0 = off)
+ *     word  2      float  top_p (>= 1 = off)
+ *     word  3      int32  pad_id
+ *     words 4-5    uint64 seed (low word first)
+ *     words 6-7    uint64 draw counter (low word first); advanced by the kernel under AMQ_SAMPLE_ADVANCE
+ *     words 8-15   int32  EOS token ids, -1 = unused slot
+ *     words 16-23  int32  finished flag of sequence 0 .. 7 (0 = still generating)
+ *     word  24     int32  number of unfinished sequences after the last launch with AMQ_SAMPLE_EOS (written by the kernel)
+ *     word  25     int32  arrival ticket of the launch's workgroups: zero before the first launch, left zero by every launch
+ *     word  26     int32  non-zero: no draw, u = 0 -- the first kept token in token order (with top_k = 1: the greedy arg-max, first maximum)
+ *     words 27-31  reserved, zero
+ * Per row, in HF's order: suppressed ids (suppress_ids: device int32 [8], -1 = unused, or NULL), NaN and -inf are no candidates;
+ * z = logit / temperature; top-k keeps z >= the k-th largest value (ties with it all kept, TopKLogitsWarper); top-p keeps a token iff the
+ * probability of the tokens with a STRICTLY larger logit is < top_p (TopPLogitsWarper with min_tokens_to_keep = 1, except that a tie class at the
+ * boundary is kept whole where HF cuts inside it in sort order); u = (Philox4x32-10(key = seed, counter = {draw counter, sequence index, 0})[0] >> 8)
+ * * 2^-24; the token is the first one, in ascending token index over the kept set, whose inclusive cumulative probability exceeds u * kept mass.
+ * Weights are rounded once to 2^-40 fixed point and summed as integers: same inputs -> same token, in any launch order.  This is NOT
+ * torch.multinomial's stream.
+ * amq_sample_f16: logits fp16 [rows, vocab] contiguous (any row alignment) -> token_out int64 [rows]; row r is sequence seq0 + r.  u_in: float
+ * [rows] in [0, 1) used instead of the generator, or NULL; kept_out: uint8 [rows, vocab] kept-set mask, or NULL.  flags: AMQ_SAMPLE_ADVANCE = the
+ * draw counter is advanced by one after the launch; AMQ_SAMPLE_EOS (rows <= 8) = a finished sequence emits pad_id, one that draws an EOS id
+ * emits it and becomes finished, word 24 is updated.  The state block must not be shared by launches that can run concurrently. */
+#define AMQ_SAMPLE_ADVANCE 1
+#define AMQ_SAMPLE_EOS 2
+int amq_sample_f16(const void* logits, int rows, int vocab, void* state, const int* suppress_ids, const float* u_in, long long* token_out,
+                   unsigned char* kept_out, int seq0, int flags, void* stream);
+/* The end of a SAMPLED token step in one launch: the above for logits [batch, vocab] (batch <= 8, sequence index = row, both flags set), then
+ * amq_decode_tail_suppress_f16's duties unchanged: token[b], pos += 1 (saturating at rope_rows), x[b] = embed[token[b]], rope_cur. */
+int amq_decode_tail_sample_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
+                               const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids, void* state,
+                               void* stream);
+
 /* ---- many-row (prefill) glue --------------------------------------------------------------------------
  * The reference runs these steps as framework ops between the linears of a HF Llama block
  * (transformers LlamaAttention / LlamaMLP / LlamaDecoderLayer as driven by amq/utils/speed.py:150-200); on this path
