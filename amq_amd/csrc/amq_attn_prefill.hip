@@ -328,6 +328,10 @@ constexpr int AG_OM_STRIDE = 132;       // floats per (wave, query row) of the c
 constexpr int AG_STAGE = 512;           // bytes in front of the stage buffers: rotated new key [128], new value [128]
 constexpr int AG_STAGE_KEYS = 128;      // keys per stage: two tiles of 64
 
+// SEQ (amq_attn_decode_seq_f16; step-state mode): a.state is block 0 of an array of gridDim.y step-state blocks STEP_STRIDE bytes apart, sequence
+// blockIdx.y reads ITS block (position, cos / sin row) and raises ITS error word; chunks and the appending workgroup follow from that position.
+// The !SEQ instantiation is the shared-position kernel as it was.
+template <bool SEQ>
 __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(AttnGqaArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, tid = threadIdx.x;
@@ -335,12 +339,13 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(AttnGqaArgs a) {
     const int r = lane & 15, o = lane >> 4;
     const int kvh = blockIdx.x, b = blockIdx.y, z = blockIdx.z;
     const int G = a.n_heads / a.n_kv_heads, h0 = kvh * G;
+    const void* const state = SEQ ? (const void*)((const char*)a.state + (size_t)b * STEP_STRIDE) : a.state;
     int pos;
-    if (a.cur_mode) pos = *(const int*)((const char*)a.state + 256);
-    else if (a.state) pos = *(const int*)a.state;
+    if (a.cur_mode) pos = *(const int*)((const char*)state + 256);
+    else if (state) pos = *(const int*)state;
     else pos = a.pos;
     if (pos < 0 || pos >= a.max_seq) {              // a position outside the cache: nothing is appended or written (attn_decode_kernel's guard)
-        if (a.cur_mode && tid == 0 && z == 0 && kvh == 0) *(int*)((char*)const_cast<void*>(a.state) + 260) = 1;
+        if (a.cur_mode && tid == 0 && z == 0 && kvh == 0) *(int*)((char*)const_cast<void*>(state) + 260) = 1;
         return;
     }
     const int chunk = AG_STAGE_KEYS * a.iters;
@@ -381,7 +386,7 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(AttnGqaArgs a) {
     h8 qf[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) qf[t] = *(const h8*)(qb + 32 * t);
-    const h2* const cs_src = a.cur_mode ? (const h2*)a.state : (a.rope_table ? (const h2*)a.rope_table + (size_t)pos * 64 : nullptr);
+    const h2* const cs_src = a.cur_mode ? (const h2*)state : (a.rope_table ? (const h2*)a.rope_table + (size_t)pos * 64 : nullptr);
     h8 cs[2][2];                                    // [t][half]: (cos, sin) of pairs 32 t + 8 o .. + 3 and .. + 4 .. + 7
     _Float16 k0 = 0, k1 = 0, v0 = 0, v1 = 0;
     h2 csk = {(_Float16)1.f, (_Float16)0.f};
@@ -578,10 +583,12 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(AttnGqaArgs a) {
 // attn_decode_gqa_kernel it was ONE workgroup per kv head reading G x n_act x 528 bytes through dependent round trips: 25 of the launch's 40 us at
 // 8192 keys of a 32 / 8-head model, growing with G x n_act -- profiles/r06_attn_gqa.txt.  The kernel boundary is the hand-over: no tickets, no
 // agent-scope publish.)  One active chunk: attn_decode_gqa_kernel has written the output itself, nothing to do.
+template <bool SEQ>
 __global__ __launch_bounds__(128) void attn_gqa_combine_kernel(const float* ws, void* out, const void* state, int pos_host, int cur_mode,
                                                                int n_heads, int max_seq, int n_splits, int chunk) {
     __shared__ float ml[2 * 1024];
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+    if (SEQ) state = (const char*)state + (size_t)b * STEP_STRIDE;      // the sequence's own position decides its number of active chunks
     const float* const wsh = ws + ((size_t)b * n_heads + h) * (size_t)n_splits * AG_WS_STRIDE;
     // Everything the first 32 chunks hold is requested before the position (hence the number of active chunks) is known: the workspace has n_splits
     // slots per head whatever the position, a slot past the active chunks holds an older step's values and is not used.  One round trip for the
@@ -654,14 +661,15 @@ hipError_t launch_attn_decode_gqa(const AttnArgs& a, int batch, int n_splits, vo
                   (float*)ws, a.pos, a.n_heads, a.n_kv_heads, a.max_seq, n_splits, (int)cur, a.rope_theta, attn_decode_gqa_iters(a.max_seq, n_splits)};
     const size_t lds = AG_STAGE + (size_t)2 * 4 * AP_TILE;         // two stage buffers of two tiles x (K | V); the cross-wave merge reuses them
     static_assert((size_t)(4 * 16 * AG_OM_STRIDE + 4 * 16 * 2) * sizeof(float) <= (size_t)2 * 4 * AP_TILE, "merge area inside the stage buffers");
-    static unsigned long long attr_done = 0;
-    if (hipError_t e = ensure_dyn_lds(attr_done, (const void*)attn_decode_gqa_kernel, (int)lds)) return e;
-    hipLaunchKernelGGL(attn_decode_gqa_kernel, dim3(g.n_kv_heads, batch, g.n_splits), dim3(256), lds, st, g);
+    static unsigned long long attr_done = 0, attr_seq_done = 0;
+    if (hipError_t e = a.seq ? ensure_dyn_lds(attr_seq_done, (const void*)attn_decode_gqa_kernel<true>, (int)lds)
+                             : ensure_dyn_lds(attr_done, (const void*)attn_decode_gqa_kernel<false>, (int)lds)) return e;
+    hipLaunchKernelGGL(a.seq ? attn_decode_gqa_kernel<true> : attn_decode_gqa_kernel<false>, dim3(g.n_kv_heads, batch, g.n_splits), dim3(256), lds, st, g);
     if (hipError_t e = hipGetLastError()) return e;
 #ifdef AMQ_GQA_ABL_NO_COMBINE          /* timing-only ablation: what the combine launch adds to the step (results wrong beyond one chunk) */
     return hipSuccess;
 #endif
-    hipLaunchKernelGGL(attn_gqa_combine_kernel, dim3(g.n_heads, batch), dim3(128), 0, st, (const float*)g.ws, g.out, g.state, g.pos, g.cur_mode,
+    hipLaunchKernelGGL(a.seq ? attn_gqa_combine_kernel<true> : attn_gqa_combine_kernel<false>, dim3(g.n_heads, batch), dim3(128), 0, st, (const float*)g.ws, g.out, g.state, g.pos, g.cur_mode,
                        g.n_heads, g.max_seq, g.n_splits, AG_STAGE_KEYS * g.iters);
     return hipGetLastError();
 }

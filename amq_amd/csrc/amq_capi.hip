@@ -890,6 +890,70 @@ int amq_set_token_f16(const long long* token_in, int n_in, const void* embed, in
     return check_hip(amq::launch_set_token(token_in, n_in, embed, vocab, hidden, token, pos, x, rope_table, rope_cur, rope_rows, batch, (hipStream_t)stream), "set_token");
 }
 
+/* ---- sequences at positions of their own: an array of `batch` step-state blocks AMQ_STEP_STATE_STRIDE bytes apart ---- */
+static_assert(AMQ_STEP_STATE_STRIDE == amq::STEP_STRIDE && AMQ_STEP_STATE_STRIDE % 16 == 0 && AMQ_STEP_STATE_STRIDE >= 264, "step-state stride");
+
+int amq_attn_decode_seq_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int batch,
+                            int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
+                            void* tickets, void* stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out || !step_states) return fail(AMQ_EINVAL, "null pointer");
+    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
+    if (batch < 1 || batch > 65535 || n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
+        return fail(AMQ_ESHAPE, "bad head configuration (batch %d, %d q heads, %d kv heads)", batch, n_heads, n_kv_heads);
+    if (max_seq < 1) return fail(AMQ_ESHAPE, "bad max_seq %d", max_seq);
+    if (n_splits < 0 || n_splits > 1024) return fail(AMQ_EINVAL, "n_splits must be 0 (one workgroup per head) or 1..1024 (got %d)", n_splits);
+    amq::AttnArgs a{q, k, v, kcache, vcache, out, nullptr, 0, n_heads, n_kv_heads, max_seq, 10000.0f, nullptr, step_states, true};
+    if (n_splits == 0) {
+        if (6 * 128 + (size_t)max_seq * 4 + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
+        return check_hip(amq::launch_attn_decode(a, batch, (hipStream_t)stream), "attn_decode_seq");
+    }
+    if (!workspace || !tickets) return fail(AMQ_EINVAL, "null pointer (workspace / tickets are required with n_splits >= 1)");
+    int chunk = (((max_seq + n_splits - 1) / n_splits) + 31) & ~31;
+    chunk = chunk < amq::ATT_MIN_CHUNK ? amq::ATT_MIN_CHUNK : chunk;
+    if (6 * 128 + (size_t)chunk * 4 + 17 * 1024 > LDS_LIMIT)
+        return fail(AMQ_ESHAPE, "max_seq=%d over %d splits leaves chunks of %d keys: too long", max_seq, n_splits, chunk);
+    const size_t need = amq_attn_decode_split_workspace_bytes(batch, n_heads, n_splits);
+    if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    return check_hip(amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream), "attn_decode_seq (split)");
+}
+
+static int tail_seq_check(const void* logits, int vocab, const void* embed, int hidden, const void* token, const void* step_states, const void* x,
+                          const void* rope_table, int rope_rows, int batch) {
+    if (!logits || !embed || !token || !step_states || !x || !rope_table) return fail(AMQ_EINVAL, "null pointer");
+    if (rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
+    if (vocab < 1 || hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need vocab >= 1 and hidden %% 8 == 0 (got %d, %d)", vocab, hidden);
+    if (batch < 1 || batch > 65535) return fail(AMQ_ESHAPE, "bad batch %d", batch);
+    return AMQ_OK;
+}
+
+int amq_decode_tail_seq_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
+                            const void* rope_table, int rope_rows, int batch, const int* suppress_ids, void* stream) {
+    if (int rc = tail_seq_check(logits, vocab, embed, hidden, token, step_states, x, rope_table, rope_rows, batch)) return rc;
+    if (batch > 1 && (vocab % 8) != 0) return fail(AMQ_ESHAPE, "batched rows need vocab %% 8 == 0 (16-byte aligned logits rows)");
+    return check_hip(amq::launch_decode_tail(logits, vocab, embed, hidden, token, (char*)step_states + 256, x, rope_table, step_states, rope_rows,
+                                             (hipStream_t)stream, batch, suppress_ids, true), "decode_tail_seq");
+}
+
+int amq_decode_tail_sample_seq_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
+                                   const void* rope_table, int rope_rows, int batch, const int* suppress_ids, void* state, void* stream) {
+    if (!state) return fail(AMQ_EINVAL, "state: the 128-byte device block of sampling parameters is required (null)");
+    if (int rc = tail_seq_check(logits, vocab, embed, hidden, token, step_states, x, rope_table, rope_rows, batch)) return rc;
+    if (batch > 8) return fail(AMQ_ESHAPE, "at most 8 sequences (the state block holds 8 finished flags), got %d", batch);
+    amq::SampleArgs a{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, (int*)((char*)step_states + 256), (_Float16*)x,
+                      (const _Float16*)rope_table, (_Float16*)step_states, rope_rows, suppress_ids, (int*)state, nullptr, nullptr, 0,
+                      AMQ_SAMPLE_ADVANCE | AMQ_SAMPLE_EOS};
+    return check_hip(amq::launch_sample(a, batch, (hipStream_t)stream, true), "decode_tail_sample_seq");
+}
+
+int amq_set_token_seq_f16(const long long* token_in, int n_in, const void* embed, int vocab, int hidden, long long* token, void* step_states, void* x,
+                          const void* rope_table, int rope_rows, int batch, void* stream) {
+    if (!token_in) return fail(AMQ_EINVAL, "null pointer");
+    if (int rc = tail_seq_check(token_in, vocab, embed, hidden, token, step_states, x, rope_table, rope_rows, batch)) return rc;
+    if (n_in != 1 && n_in != batch) return fail(AMQ_ESHAPE, "batch %d with %d input ids (1 or one per sequence)", batch, n_in);
+    return check_hip(amq::launch_set_token(token_in, n_in, embed, vocab, hidden, token, (const char*)step_states + 256, x, rope_table, step_states,
+                                           rope_rows, batch, (hipStream_t)stream, true), "set_token_seq");
+}
+
 int amq_rope_table_f16(void* table, int max_seq, float rope_theta, void* stream) {
     if (!table || max_seq < 1) return fail(AMQ_EINVAL, "bad rope table request");
     return check_hip(amq::launch_rope_table(table, max_seq, rope_theta, (hipStream_t)stream), "rope_table");

@@ -213,7 +213,11 @@ hipError_t launch_gemv_f16w(const void* x, const void* W, const void* bias, void
 // suppress: up to 8 token ids (device int32, -1 = unused slot) that are never chosen -- what HF's MinNewTokensLengthLogitsProcessor does to the EOS
 // ids while min_new_tokens has not been reached (generate(min_new_tokens = max_new_tokens = n): speed.py:31-36): their logits count as -inf.
 // Checked only where a thread finds a new maximum (a handful of times per thread), not per element.
+// SEQ (sequences at positions of their OWN: amq_decode_tail_seq_f16): pos / rope_cur are those of step-state block 0 of an array of gridDim.x blocks
+// STEP_STRIDE bytes apart; every workgroup advances ITS block's position (saturating) and writes ITS cos/sin row.  The !SEQ instantiation is the
+// shared-position kernel as it was.
 constexpr int TAIL_MAX_SUPPRESS = 8;
+template <bool SEQ>
 __global__ __launch_bounds__(1024) void decode_tail_kernel(const _Float16* logits, int vocab, const _Float16* embed, int hidden,
                                                             long long* token, int* pos, _Float16* x, const _Float16* rope_table,
                                                             _Float16* rope_cur, int rope_rows, const int* suppress) {
@@ -224,7 +228,10 @@ __global__ __launch_bounds__(1024) void decode_tail_kernel(const _Float16* logit
     logits += (size_t)blockIdx.x * vocab;
     token += blockIdx.x;
     x += (size_t)blockIdx.x * hidden;
-    if (blockIdx.x != 0) rope_cur = nullptr;
+    if (SEQ) {
+        pos = (int*)((char*)pos + (size_t)blockIdx.x * STEP_STRIDE);
+        if (rope_cur) rope_cur = (_Float16*)((char*)rope_cur + (size_t)blockIdx.x * STEP_STRIDE);
+    } else if (blockIdx.x != 0) rope_cur = nullptr;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     int sup[TAIL_MAX_SUPPRESS];
@@ -265,7 +272,7 @@ __global__ __launch_bounds__(1024) void decode_tail_kernel(const _Float16* logit
         if (ix == 0x7fffffff) ix = 0;                            // all NaN / empty: torch returns 0-ish; keep it in range
         stok = ix;
         token[0] = (long long)ix;
-        if (blockIdx.x == 0) {
+        if (SEQ || blockIdx.x == 0) {
             spos = pos[0] + 1;
             if (rope_table && spos > rope_rows) spos = rope_rows;    // saturate at the end of the cache: the attention kernel
             pos[0] = spos;                                           // treats pos == max_seq as "out of range" (no-op + error word)
@@ -281,22 +288,30 @@ __global__ __launch_bounds__(1024) void decode_tail_kernel(const _Float16* logit
 }
 
 hipError_t launch_decode_tail(const void* logits, int vocab, const void* embed, int hidden, void* token, void* pos, void* x,
-                              const void* rope_table, void* rope_cur, int rope_rows, hipStream_t st, int batch, const void* suppress) {
-    hipLaunchKernelGGL(decode_tail_kernel, dim3(batch), dim3(1024), 0, st, (const _Float16*)logits, vocab, (const _Float16*)embed, hidden,
-                       (long long*)token, (int*)pos, (_Float16*)x, (const _Float16*)rope_table, (_Float16*)rope_cur, rope_rows, (const int*)suppress);
+                              const void* rope_table, void* rope_cur, int rope_rows, hipStream_t st, int batch, const void* suppress, bool seq) {
+    hipLaunchKernelGGL(seq ? decode_tail_kernel<true> : decode_tail_kernel<false>, dim3(batch), dim3(1024), 0, st, (const _Float16*)logits, vocab,
+                       (const _Float16*)embed, hidden, (long long*)token, (int*)pos, (_Float16*)x, (const _Float16*)rope_table, (_Float16*)rope_cur,
+                       rope_rows, (const int*)suppress);
     return hipGetLastError();
 }
 
 // The step-state side of "this is the next input token" in one launch (what a caller that feeds tokens itself -- model(ids, start_pos=...) token by
 // token, speed.py:76-90 -- otherwise does with an index copy, an embedding gather and a table-row gather): token[b] = token_in[b] (one id broadcast
 // when n_in == 1), x[b] = embed[token[b]], rope_cur = rope_table[min(pos, rope_rows - 1)].  The position itself is not touched.
+// SEQ (amq_set_token_seq_f16): pos / rope_cur are those of block 0 of an array of step-state blocks STEP_STRIDE bytes apart; sequence b's row is
+// written from ITS position.
+template <bool SEQ>
 __global__ __launch_bounds__(256) void set_token_kernel(const long long* token_in, int n_in, const _Float16* embed, int vocab, int hidden, long long* token,
                                                          const int* pos, _Float16* x, const _Float16* rope_table, _Float16* rope_cur, int rope_rows) {
     const int b = blockIdx.x, tid = threadIdx.x;
     long long t = token_in[n_in == 1 ? 0 : b];
     t = t < 0 ? 0 : t >= vocab ? vocab - 1 : t;                      // (an id outside the vocabulary must not become an out-of-bounds gather)
     if (tid == 0) token[b] = t;
-    if (b == 0 && rope_cur && tid < 128) {
+    if (SEQ) {
+        pos = (const int*)((const char*)pos + (size_t)b * STEP_STRIDE);
+        if (rope_cur) rope_cur = (_Float16*)((char*)rope_cur + (size_t)b * STEP_STRIDE);
+    }
+    if ((SEQ || b == 0) && rope_cur && tid < 128) {
         int p = pos[0];
         p = p < 0 ? 0 : p < rope_rows ? p : rope_rows - 1;
         rope_cur[tid] = rope_table[(size_t)p * 128 + tid];
@@ -307,9 +322,10 @@ __global__ __launch_bounds__(256) void set_token_kernel(const long long* token_i
 }
 
 hipError_t launch_set_token(const void* token_in, int n_in, const void* embed, int vocab, int hidden, void* token, const void* pos, void* x,
-                            const void* rope_table, void* rope_cur, int rope_rows, int batch, hipStream_t st) {
-    hipLaunchKernelGGL(set_token_kernel, dim3(batch), dim3(256), 0, st, (const long long*)token_in, n_in, (const _Float16*)embed, vocab, hidden,
-                       (long long*)token, (const int*)pos, (_Float16*)x, (const _Float16*)rope_table, (_Float16*)rope_cur, rope_rows);
+                            const void* rope_table, void* rope_cur, int rope_rows, int batch, hipStream_t st, bool seq) {
+    hipLaunchKernelGGL(seq ? set_token_kernel<true> : set_token_kernel<false>, dim3(batch), dim3(256), 0, st, (const long long*)token_in, n_in,
+                       (const _Float16*)embed, vocab, hidden, (long long*)token, (const int*)pos, (_Float16*)x, (const _Float16*)rope_table,
+                       (_Float16*)rope_cur, rope_rows);
     return hipGetLastError();
 }
 
@@ -397,9 +413,14 @@ extern unsigned long long* g_stamp_ptr;
 // p_state: mode 0 -> device int32 position (or null: rest.pos); mode 1 ("cur") -> the step-state block
 // {fp16 cos/sin [64][2] of the current position; int32 position at byte 256} that amq_decode_tail_f16 maintains: the
 // rotation inputs AND the position are then fetched by the first instructions of the kernel, with no dependent load.
+// SEQ (amq_attn_decode_seq_f16; step-state mode only): p_state is block 0 of an array of gridDim.y step-state blocks STEP_STRIDE bytes apart and
+// sequence blockIdx.y reads ITS block -- one scalar multiply-add in front of the same first loads; everything behind is the same code at the
+// sequence's own position.  The !SEQ instantiations are the shared-position kernels as they were.
+template <bool SEQ>
 __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, void* p_vc, const void* p_state, int p_heads,
                                                                    int p_max_seq, const void* p_q, const void* p_k,
                                                                    const void* p_v, AttnRest rest) {
+    if (SEQ) p_state = (const char*)p_state + (size_t)blockIdx.y * STEP_STRIDE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* qs = (_Float16*)smem;                 // [128] rotated q
     _Float16* ks = (_Float16*)smem + ATT_D;         // [128] rotated new key (also what is appended)
@@ -619,10 +640,11 @@ constexpr int ATT_WS_STRIDE = ATT_D + 4;       // floats per (head, chunk): O[12
 #else
 #define ATT_KV_LOAD(p) (*(const h8*)(p))
 #endif
-template <int RING>
+template <int RING, bool SEQ>
 __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_kc, void* p_vc, const void* p_state, int p_heads,
                                                                          int p_max_seq, const void* p_q, const void* p_k,
                                                                          const void* p_v, AttnRest rest, AttnSplit sp) {
+    if (SEQ) p_state = (const char*)p_state + (size_t)blockIdx.y * STEP_STRIDE;      // (attn_decode_kernel: the sequence's own step-state block)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* qs = (_Float16*)smem;                 // [128] rotated q
     _Float16* ks = (_Float16*)smem + ATT_D;         // [128] rotated new key (also what is appended)
@@ -1044,8 +1066,9 @@ static int att_chunk_max(int max_seq, int n_splits) {
 
 template <int RING>
 static hipError_t launch_attn_decode_split_ring(const AttnArgs& a, int batch, int n_splits, void* ws, void* tickets, size_t lds, hipStream_t st) {
+    const auto kern = a.seq ? attn_decode_split_kernel<RING, true> : attn_decode_split_kernel<RING, false>;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_decode_split_kernel<RING>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     AttnRest rest{a.out, a.rope_table, a.pos, a.rope_theta};
@@ -1054,7 +1077,7 @@ static hipError_t launch_attn_decode_split_ring(const AttnArgs& a, int batch, in
 #endif
     AttnSplit sp{(float*)ws, (int*)tickets, n_splits};
     const bool cur = a.rope_cur != nullptr;
-    hipLaunchKernelGGL(attn_decode_split_kernel<RING>, dim3(a.n_heads, batch, n_splits), dim3(ATT_THREADS), lds, st, a.kcache, a.vcache,
+    hipLaunchKernelGGL(kern, dim3(a.n_heads, batch, n_splits), dim3(ATT_THREADS), lds, st, a.kcache, a.vcache,
                        cur ? a.rope_cur : (const void*)a.pos_dev, a.n_heads | (a.n_kv_heads << 8) | ((int)cur << 16), a.max_seq,
                        a.q, a.k, a.v, rest, sp);
     return hipGetLastError();
@@ -1079,8 +1102,9 @@ hipError_t launch_attn_decode_split(const AttnArgs& a, int batch, int n_splits, 
 hipError_t launch_attn_decode(const AttnArgs& a, int batch, hipStream_t st) {
     StreamDevice sd_(st);                                  // kernel attributes are per device: the stream's, not the current one
     const size_t lds = 6 * ATT_D + (size_t)a.max_seq * 4;
+    const auto kern = a.seq ? attn_decode_kernel<true> : attn_decode_kernel<false>;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     AttnRest rest{a.out, a.rope_table, a.pos, a.rope_theta};
@@ -1088,7 +1112,7 @@ hipError_t launch_attn_decode(const AttnArgs& a, int batch, hipStream_t st) {
     rest.stamps = g_stamp_ptr;
 #endif
     const bool cur = a.rope_cur != nullptr;
-    hipLaunchKernelGGL(attn_decode_kernel, dim3(a.n_heads, batch), dim3(ATT_THREADS), lds, st, a.kcache, a.vcache,
+    hipLaunchKernelGGL(kern, dim3(a.n_heads, batch), dim3(ATT_THREADS), lds, st, a.kcache, a.vcache,
                        cur ? a.rope_cur : (const void*)a.pos_dev, a.n_heads | (a.n_kv_heads << 8) | ((int)cur << 16), a.max_seq,
                        a.q, a.k, a.v, rest);
     return hipGetLastError();

@@ -148,7 +148,10 @@ struct AttnArgs {
     const void* rope_table;   // fp16 [max_seq][64][2] (cos, sin) from launch_rope_table, or null -> computed in-kernel
     const void* rope_cur;     // step-state block {fp16 [64][2] (cos, sin) of the CURRENT position; int32 position at byte 256}
                               // maintained by launch_decode_tail, or null
+    bool seq = false;         // rope_cur is block 0 of an array of `batch` step-state blocks STEP_STRIDE bytes apart: every sequence at ITS position
 };
+// bytes between the step-state blocks of sequences decoded at positions of their own (include/amq_hip.h: AMQ_STEP_STATE_STRIDE)
+constexpr int STEP_STRIDE = 272;
 hipError_t launch_rope_table(void* tab, int max_seq, float theta, hipStream_t st);
 hipError_t launch_rope_table_freqs(void* tab, int max_seq, const void* inv_freq, float scale, hipStream_t st);   // explicit inverse frequencies (rope_scaling)
 hipError_t launch_attn_decode(const AttnArgs& a, int batch, hipStream_t st);
@@ -189,9 +192,10 @@ hipError_t launch_rope_rows(void* q, void* k, const void* rope_table, int rope_r
                             int n_kv_heads, hipStream_t st);
 hipError_t launch_silu_mul(const void* gate, const void* up, void* out, long n, hipStream_t st);
 hipError_t launch_decode_tail(const void* logits, int vocab, const void* embed, int hidden, void* token, void* pos, void* x,
-                              const void* rope_table, void* rope_cur, int rope_rows, hipStream_t st, int batch = 1, const void* suppress = nullptr);
+                              const void* rope_table, void* rope_cur, int rope_rows, hipStream_t st, int batch = 1, const void* suppress = nullptr,
+                              bool seq = false);       // seq: pos / rope_cur = block 0 of `batch` step-state blocks, each sequence advances its own
 hipError_t launch_set_token(const void* token_in, int n_in, const void* embed, int vocab, int hidden, void* token, const void* pos, void* x,
-                            const void* rope_table, void* rope_cur, int rope_rows, int batch, hipStream_t st);
+                            const void* rope_table, void* rope_cur, int rope_rows, int batch, hipStream_t st, bool seq = false);
 hipError_t launch_gemv_f16w(const void* x, const void* W, const void* bias, void* y, const void* gamma, float eps,
                             int N, int K, hipStream_t st, int M = 1);      // x [M, K], y [M, N], M <= 8
 
@@ -217,7 +221,7 @@ struct SampleArgs {
     int seq0;                   // sequence index of row 0 (the generator's counter word)
     int flags;                  // SMP_FLAG_*
 };
-hipError_t launch_sample(const SampleArgs& a, int rows, hipStream_t st);
+hipError_t launch_sample(const SampleArgs& a, int rows, hipStream_t st, bool seq = false);   // seq: a.pos / a.rope_cur = block 0 of `rows` step-state blocks
 
 // q / k / v GEMV + decode attention in one launch (amq_gemv.hip): a's segments 0 .. 2 = q, k, v (M = 1, RMSNorm prologue, gamma / eps
 // set); t: caches, output, step-state block (rope_cur), head counts, max_seq; tickets: int32 [n_heads], zero before and after

@@ -71,6 +71,10 @@ __device__ __forceinline__ u64 smp_block_scan_excl(u64 v, bool reverse, u64* swa
     return other + incl - v;
 }
 
+// SEQ (amq_decode_tail_sample_seq_f16): a.pos / a.rope_cur are those of block 0 of an array of step-state blocks STEP_STRIDE bytes apart; every row's
+// workgroup advances ITS block's position and writes ITS cos/sin row.  Draws and EOS bookkeeping are the same.  The !SEQ instantiation is the
+// shared-position kernel as it was.
+template <bool SEQ>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     __shared__ u64 m12[SMP_BINS];                              // fixed-point mass per 12-bit key prefix
     __shared__ unsigned c12[SMP_BINS];                         // candidates per 12-bit key prefix
@@ -340,26 +344,28 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
             }
             __hip_atomic_store(&st[SMP_ARRIVE], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (a.embed && row == 0) {
-            spos = a.pos[0] + 1;
+        if (a.embed && (SEQ || row == 0)) {
+            int* const pp = SEQ ? (int*)((char*)a.pos + (size_t)row * STEP_STRIDE) : a.pos;
+            spos = pp[0] + 1;
             if (a.rope_table && spos > a.rope_rows) spos = a.rope_rows;        // saturating, as in the greedy tail
-            a.pos[0] = spos;
+            pp[0] = spos;
         }
     }
     if (!a.embed) return;
     // ---- the greedy tail's duties: x = embed[token], the next position's cos/sin row
     __syncthreads();
-    if (row == 0 && a.rope_cur && tid < 128) {
+    if ((SEQ || row == 0) && a.rope_cur && tid < 128) {
         const int rr = spos < a.rope_rows ? spos : a.rope_rows - 1;
-        a.rope_cur[tid] = a.rope_table[(size_t)rr * 128 + tid];
+        _Float16* const rc = SEQ ? (_Float16*)((char*)a.rope_cur + (size_t)row * STEP_STRIDE) : a.rope_cur;
+        rc[tid] = a.rope_table[(size_t)rr * 128 + tid];
     }
     const _Float16* erow = a.embed + (size_t)s_tok * a.hidden;
     _Float16* x = a.x + (size_t)row * a.hidden;
     for (int c = tid; c < (a.hidden >> 3); c += SMP_THREADS) *(h8*)(x + 8 * c) = *(const h8*)(erow + 8 * c);
 }
 
-hipError_t launch_sample(const SampleArgs& a, int rows, hipStream_t st) {
-    hipLaunchKernelGGL(sample_kernel, dim3(rows), dim3(SMP_THREADS), 0, st, a);
+hipError_t launch_sample(const SampleArgs& a, int rows, hipStream_t st, bool seq) {
+    hipLaunchKernelGGL(seq ? sample_kernel<true> : sample_kernel<false>, dim3(rows), dim3(SMP_THREADS), 0, st, a);
     return hipGetLastError();
 }
 

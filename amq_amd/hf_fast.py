@@ -25,7 +25,15 @@ With ``convert_model_to_hip(model, sampling=True)`` (opt-in; the default routing
     8) and is padded with ``pad_token_id`` from there on, the call returns at the longest sequence's length as HF's does; ``min_new_tokens = m``
     keeps the EOS ids suppressed for the first m tokens.
 
-Anything else -- sampling and open-ended calls without that flag, ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``, beams, an attention mask with holes, ``past_key_values``, ``labels``, ``inputs_embeds``, hidden-state / attention outputs,
+With ``convert_model_to_hip(model, padded=True)`` (opt-in beside ``sampling``; the default routing is unchanged) ``generate`` also accepts the
+standard way to batch prompts of unequal length -- ``tokenizer(prompts, padding=True, padding_side="left")`` then ``model.generate(**enc)``: an
+``attention_mask`` whose every row is ``0...0 1...1`` with at least one 1.  HF gives such a row the position ids ``cumsum(mask) - 1`` and masks the
+pad keys, so each row decodes as if it were alone; here each row is stored compactly from cache row 0 and decoded at a position of its own
+(``left_padded_to_right`` -> ``QuantLlama(ragged=True).generate(ids, n, lengths=...)``; such runners are cached under ``("ragged", B)``).  The
+call returns ``cat([input_ids, new], 1)`` with the caller's left-padded ids untouched, as HF does.  Greedy fixed-length calls always; sampled and
+open-ended ones with ``sampling=True`` as well.
+
+Anything else -- sampling and open-ended calls without that flag, a padded mask without ``padded=True``, right padding, an all-zero mask row, ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``, beams, an attention mask with holes, ``past_key_values``, ``labels``, ``inputs_embeds``, hidden-state / attention outputs,
 stopping criteria, streamers, more than 8 sequences, a call without ``start_pos`` -- falls through to the model's original ``forward`` / ``generate``
 (HF's own, over the fused modules).  ``state_dict`` / ``deepcopy`` / ``.to()`` are untouched: the runners live outside the module, keyed weakly by it.
 """
@@ -39,7 +47,7 @@ try:
 except Exception:                                   # (transformers is needed only once a model is converted)
     CausalLMOutputWithPast = None
 
-_RUNNERS = weakref.WeakKeyDictionary()      # model -> {batch: QuantLlama}
+_RUNNERS = weakref.WeakKeyDictionary()      # model -> {batch: QuantLlama, ("ragged", batch): QuantLlama(ragged=True)}
 _BUCKETS = (256, 512, 1024, 2048, 4096, 8192, 16384, 32768)
 # generation_config fields that make HF add a logits processor / warper / constraint to a greedy run: any of them set -> HF's own generate
 _GC_PROCESSORS = ("repetition_penalty", "encoder_repetition_penalty", "no_repeat_ngram_size", "encoder_no_repeat_ngram_size", "bad_words_ids",
@@ -58,18 +66,24 @@ def _bucket(n, limit):
     return n
 
 
-def _runner(model, batch, need):
+def _runner(model, batch, need, ragged=False):
     """the runner for ``batch`` sequences with room for ``need`` positions (built on first use; rebuilt larger -- cache contents carried over -- when a
-    sequence outgrows it: the attention launch is chosen by the cache's size, so the cache is not made larger than asked for)"""
+    sequence outgrows it: the attention launch is chosen by the cache's size, so the cache is not made larger than asked for).  ``ragged``: the runner
+    with a position per sequence (left-padded generate calls), kept under a key of its own; every call on it starts with a prompt pass, so a rebuilt
+    one carries nothing over."""
     from .llama import QuantLlama
     per = _RUNNERS.setdefault(model, {})
-    r = per.get(batch)
+    key = ("ragged", batch) if ragged else batch
+    r = per.get(key)
     limit = int(getattr(model.config, "max_position_embeddings", 1 << 30) or (1 << 30))
     if need > limit:
         raise ValueError(f"{need} positions exceed the model's max_position_embeddings ({limit})")
     if r is not None and r.max_seq >= need and _same_weights(r, model):
         return r
-    new = QuantLlama.from_hf(model, max_seq=_bucket(need, limit), batch=batch)
+    new = QuantLlama.from_hf(model, max_seq=_bucket(need, limit), batch=batch, ragged=ragged)
+    if ragged:
+        per[key] = new
+        return new
     new.all_logits = True
     if r is not None and _same_weights(r, model) and r.host_pos > 0:
         for nb, ob in zip(new.blocks, r.blocks):
@@ -77,7 +91,7 @@ def _runner(model, batch, need):
             nb["vc"][:, :, :r.host_pos].copy_(ob["vc"][:, :, :r.host_pos])
         new.set_pos(r.host_pos)
         new.set_token(r.token)
-    per[batch] = new
+    per[key] = new
     return new
 
 
@@ -98,6 +112,31 @@ def _mask_is_full(mask, ids):
     if mask is None:
         return True
     return isinstance(mask, torch.Tensor) and mask.shape == ids.shape and bool(mask.ne(0).all())
+
+
+def left_padded_to_right(mask, ids, fill=0):
+    """A LEFT-padded batch as the ragged runner takes it.  mask, ids: [B, S]; every row of ``mask`` must be ``0...0 1...1`` with at least one 1
+    (integer or bool values 0 / 1).  -> (ids RIGHT-padded: row b holds its L_b real tokens in columns 0 .. L_b - 1, ``fill`` behind them;
+    lengths int64 [B]), or None for anything else (holes, right padding, an all-zero row, other values, a floating / additive mask).  A full mask
+    gives the ids back with every length S.  Pure torch, any device."""
+    if not (isinstance(mask, torch.Tensor) and isinstance(ids, torch.Tensor) and ids.dim() == 2 and mask.shape == ids.shape):
+        return None
+    if mask.dtype.is_floating_point or mask.dtype.is_complex:
+        return None
+    B, S = ids.shape
+    if B < 1 or S < 1:
+        return None
+    m = mask.to(torch.int64)
+    if bool(((m != 0) & (m != 1)).any()):
+        return None
+    lengths = m.sum(dim=1)
+    cols = torch.arange(S, device=ids.device)[None, :]
+    shift = (S - lengths)[:, None]
+    if bool((lengths < 1).any()) or not bool((m == (cols >= shift).to(torch.int64)).all()):
+        return None
+    src = (cols + shift).clamp_(max=S - 1)
+    right = torch.where(cols < lengths[:, None], ids.gather(1, src), torch.full_like(ids, int(fill)))
+    return right, lengths
 
 
 def _fast_forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, start_pos=None, inputs_embeds=None,
@@ -149,6 +188,7 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
         return fall()
     gc = getattr(self, "generation_config", None)
     sampling = self.__dict__.get("_amq_sampling", False)       # convert_model_to_hip(model, sampling=True): sampled and open-ended calls served too
+    padded = self.__dict__.get("_amq_padded", False)           # convert_model_to_hip(model, padded=True): left-padded batches served too
     n = kw.pop("max_new_tokens", None)
     nmin = kw.pop("min_new_tokens", None)
     do_sample = kw.pop("do_sample", getattr(gc, "do_sample", False)) not in (False, None)
@@ -173,8 +213,13 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     fixed = nmin == n
     if (kw or any(o is not None and (not hasattr(o, "__len__") or len(o)) for o in others) or synced_gpus or not one_beam or n is None
             or ((do_sample or not fixed) and not sampling)
-            or not _plain_ids(ids) or not ids.is_cuda or int(n) < 1 or len(eos) > 8 or not _mask_is_full(mask, ids)):
+            or not _plain_ids(ids) or not ids.is_cuda or int(n) < 1 or len(eos) > 8):
         return fall()
+    compact = None                                              # (right-padded ids, lengths) of a left-padded batch
+    if not _mask_is_full(mask, ids):
+        compact = left_padded_to_right(mask, ids) if padded and isinstance(mask, torch.Tensor) and mask.device == ids.device else None
+        if compact is None:
+            return fall()
     # the model's own generation defaults must ask for nothing else (any other logits processor / warper HF would add changes the tokens)
     if gc is not None and any(getattr(gc, k, None) not in (None, False, 0, 1, 1.0, [], ()) for k in _GC_PROCESSORS + (_GC_WARPERS if do_sample else ())):
         return fall()
@@ -185,12 +230,16 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
         return fall()                                           # (HF raises its own error for these)
     if nmin > n or (not fixed and pad is not None and not 0 <= int(pad) < int(self.config.vocab_size)):
         return fall()
-    r = _runner(self, B, S + n)
+    r = _runner(self, B, S + n, ragged=compact is not None)
+    if compact is not None:                                     # each row from cache row 0 at a position of its own; the caller's ids come back untouched
+        prompt, gkw = compact[0], dict(lengths=compact[1].tolist())
+    else:
+        prompt, gkw = (ids if B > 1 else ids[0]), {}
     if not do_sample and fixed:
         # min_new_tokens = max_new_tokens: HF never lets an EOS id through (MinNewTokensLengthLogitsProcessor sets their logits to -inf on every step)
         if tuple(eos) != getattr(r, "_suppressed", ()):
             r.set_suppressed(eos)
-        new = r.generate(ids if B > 1 else ids[0], n)
+        new = r.generate(prompt, n, **gkw)
         return torch.cat([ids, new.view(B, n).to(ids.dtype)], dim=1)
     try:
         if do_sample:
@@ -200,34 +249,37 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
         if fixed:
             if tuple(eos) != getattr(r, "_suppressed", ()):
                 r.set_suppressed(eos)
-            new = r.generate(ids if B > 1 else ids[0], n)
+            new = r.generate(prompt, n, **gkw)
         else:
             # open-ended: a sequence stops at its first EOS id and is padded from there on (HF pads with eos[0] when no pad id is set)
             if getattr(r, "_suppressed", ()) != ():
                 r.set_suppressed(())
             r.set_eos(eos, pad_id=int(pad) if pad is not None else (eos[0] if eos else 0))
-            new = r.generate(ids if B > 1 else ids[0], n, stop_at_eos=True, min_new_tokens=nmin)
+            new = r.generate(prompt, n, stop_at_eos=True, min_new_tokens=nmin, **gkw)
     finally:
         r.set_sampling(None)                                    # (model(ids, start_pos=) steps of this runner stay greedy)
     return torch.cat([ids, new.view(B, -1).to(ids.dtype)], dim=1)
 
 
-def convert_model_to_hip(model, sampling=False):
+def convert_model_to_hip(model, sampling=False, padded=False):
     """convert_model_to_ft(model) + replace_generate_functions() (ftllama_modeling.py:569-580, ftllama_generate.py:613-622) for the HIP backend:
     call it on the model ``prepare_for_inference(model, backend='hip')`` returned (a Llama-family ``*ForCausalLM`` whose decoder linears are
     HIPQuantLinear modules on one GPU).  Patches THIS instance's ``forward`` and ``generate`` (see the module docstring); idempotent; returns the
     model.  ``sampling=True`` also routes ``generate(do_sample=True, temperature / top_k / top_p)`` and open-ended calls (EOS stop) to the runner;
-    calling it again on a converted model only updates that flag.  ``revert_model_to_hf(model)`` undoes it."""
+    ``padded=True`` also routes ``generate`` calls whose ``attention_mask`` is LEFT padding (``padding_side="left"``) to a runner that decodes every
+    row at a position of its own.  Calling it again on a converted model only updates the two flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
     if "_amq_orig_forward" in model.__dict__:
         model.__dict__["_amq_sampling"] = bool(sampling)
+        model.__dict__["_amq_padded"] = bool(padded)
         return model
     from .llama import QuantLlama
     QuantLlama.check_hf(model)                               # refuse now, with the reason, what the runner cannot serve
     model.__dict__["_amq_orig_forward"] = model.forward
     model.__dict__["_amq_orig_generate"] = model.generate
     model.__dict__["_amq_sampling"] = bool(sampling)
+    model.__dict__["_amq_padded"] = bool(padded)
     model.forward = types.MethodType(_fast_forward, model)
     model.generate = types.MethodType(_fast_generate, model)
     return model
@@ -239,6 +291,7 @@ def revert_model_to_hf(model):
             model.__dict__.pop(name, None)
             model.__dict__.pop("_amq_orig_" + name)
     model.__dict__.pop("_amq_sampling", None)
+    model.__dict__.pop("_amq_padded", None)
     _RUNNERS.pop(model, None)
     return model
 

@@ -122,7 +122,7 @@ class QuantLlama:
     fine = False                # any layer with groups of 64 / 32 (set by __init__)
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
-                 hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None):
+                 hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False):
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
@@ -131,6 +131,9 @@ class QuantLlama:
         group: group size of the SYNTHETIC layers (128; 64 / 32: see ``fine``).
         batch: sequences decoded together, 1 .. 8 (same prompt length; one step = the same launches with ``batch`` rows: the
         weights are streamed once per step for all of them).  batch = 1 is the reference's FT configuration.
+        ragged: every sequence keeps a position of its own (prompts of unequal length: ``prefill(ids, lengths=...)``): one step-state block per
+        sequence, the per-sequence forms of the attention / tail / set_token launches.  False: ONE position for the batch -- the object, graphs and
+        bits the runner has always had.
         rope: (inv_freq fp32 [64], attention_scaling) of the rotary embedding when it is not the plain ``rope_theta`` form (from_hf hands over
         the HF module's own; otherwise derived from config["rope_scaling"]: Llama-3.1's "llama3")."""
         if isinstance(config, str):
@@ -138,6 +141,11 @@ class QuantLlama:
         if not 1 <= int(batch) <= 8:
             raise ValueError("batch must be 1..8")
         self.B = int(batch)
+        self.ragged = bool(ragged)
+        if self.ragged and engine:
+            raise ValueError("the decode engine keeps one position (batch 1): not offered with ragged=True")
+        if self.ragged and self.FUSE_QKV_ATTN:
+            raise ValueError("the fused q/k/v + attention launch keeps one position (batch 1): not offered with ragged=True")
         self.cfg = config
         self.dev = torch.device(device)
         _prime_graph_state(self.dev)
@@ -227,10 +235,12 @@ class QuantLlama:
         self.inv_freq, self.rope_scale = rope if rope is not None else rope_inv_freq(config)
         self.rope_tab = ops.rope_table(max_seq, self.theta, dev, inv_freq=self.inv_freq, scale=self.rope_scale)
         # step state: cos/sin row of self.pos + the position itself in one block (set_token / the step's tail keep it)
-        self.rope_cur, self.pos, self.step_err = ops.new_step_state(dev)
+        # (ragged: one block per sequence -- rope_cur [B, 128], pos [B], step_err [B] -- and the prompt lengths the captured prompt pass reads)
+        self.rope_cur, self.pos, self.step_err = ops.new_step_state(dev, batch=B) if self.ragged else ops.new_step_state(dev)
         self.rope_cur.copy_(self.rope_tab.view(max_seq, 128)[0])
+        self.lengths = torch.ones(B, dtype=torch.int64, device=dev) if self.ragged else None
         self.graph = None
-        self.host_pos = 0          # host mirror of self.pos (decode_step refuses to run past the cache without a device sync)
+        self.host_pos = 0          # host mirror of self.pos (decode_step refuses to run past the cache without a device sync); ragged: of the LARGEST position
         # token ids the greedy choice never takes (8 slots, -1 = unused; read by the step's tail kernel): what HF's min_new_tokens does to the EOS ids
         # (set_suppressed; the values may change between replays of the captured step)
         self.suppress = torch.full((8,), -1, dtype=torch.int32, device=dev)
@@ -246,7 +256,8 @@ class QuantLlama:
         # AND up -- 352 KB per CU at 8 rows: 23.9 us against 4.9 + ~11); past that too, the few-row MFMA kernel
         self._down_rows_fit = self.B <= min(ops.gemv_max_rows(self.I, plain=not self.fine), self.DOWN_FUSED_ROWS)
         self._down_rows_phased = not self._down_rows_fit and self.B <= ops.gemv_max_rows(self.I, plain=not self.fine, norm=False)
-        self.can_fuse_qkv_attn = self.B == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
+        self.can_fuse_qkv_attn = (self.B == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
+                                  and not self.ragged)
         self.fuse_qkv_attn = self.FUSE_QKV_ATTN and self.can_fuse_qkv_attn
         self._tickets = torch.zeros(max(self.nh, 64), dtype=torch.int32, device=dev)
         # 2 .. 8 sequences: the RMSNorms ride on per-row-tile sums of squares that o_proj / down_proj leave in their epilogues (ops.gemv_grouped_sums:
@@ -255,7 +266,7 @@ class QuantLlama:
         self._norm_sums = (self.NORM_SUMS and 2 <= self.B <= 8 and not self.fine and 2048 <= self.H <= 8192 and self.I >= 2048
                            and self.B <= ops.gemv_max_rows(self.H, plain=True))
         self.ss = torch.zeros(self.B, self.H // 16, dtype=torch.float32, device=dev) if self._norm_sums else None
-        eligible = self.B == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias
+        eligible = self.B == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias and not self.ragged
         if engine and not eligible:
             raise ValueError("the decode engine needs batch 1 and max_seq <= %d" % self.ENGINE_MAX_SEQ)
         self.engine = None
@@ -309,7 +320,7 @@ class QuantLlama:
         return cfg, rope
 
     @classmethod
-    def from_hf(cls, model, max_seq=256, batch=1, engine=None):
+    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False):
         """The hipGraph runner over a SWAPPED HF causal LM of the Llama family (``HF_MODEL_TYPES``: Llama 2 / 3.x, Mistral, Qwen2.5) -- what
         ``prepare_for_inference(model, backend="hip")`` (or the reference's deepcopy + setattr assembly of a mixed-precision model,
         amq_speed_benchmark.py:231-256) leaves behind.  The runner shares the modules' native weight buffers and biases, the embedding, lm_head and
@@ -336,7 +347,8 @@ class QuantLlama:
                 arch_linear[name].append(m.bits)
         dense = {"embed": f16(model.model.embed_tokens.weight), "lm_head": f16(model.lm_head.weight), "norm": f16(model.model.norm.weight),
                  "ln1": [f16(l.input_layernorm.weight) for l in layers], "ln2": [f16(l.post_attention_layernorm.weight) for l in layers]}
-        return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope)
+        return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
+                   ragged=ragged)
 
     # ----------------------------------------------------------------- sizes
     def linear_bytes_per_token(self):
@@ -358,6 +370,8 @@ class QuantLlama:
             self._tail(sampled)
             return
         have_sums = False                       # self.ss holds the sums of squares of self.x's rows (written by the launch that produced them)
+        if self.ragged and self.fuse_qkv_attn:
+            raise ValueError("the fused q/k/v + attention launch keeps one position (batch 1): not offered with ragged=True")
         for blk in self.blocks:
             if self.fuse_qkv_attn:
                 ops.gemv_qkv_attn(self.x, [blk["self_attn.q_proj"].seg(self.q.view(-1)), blk["self_attn.k_proj"].seg(self.k.view(-1)),
@@ -413,6 +427,7 @@ class QuantLlama:
 
     # ------------------------------------------------------------- sampling
     sampling, sample_state, sample_graph, eos, pad_id = None, None, None, (), 0      # (class defaults: greedy)
+    ragged, lengths = False, None       # (class defaults: one position for the whole batch)
     EOS_POLL_STEPS = 16         # generate(stop_at_eos=True) reads the unfinished count every this many steps: fewer = less work after the last EOS, more host syncs
 
     def _write_sampling_state(self):
@@ -475,7 +490,15 @@ class QuantLlama:
         return torch.argmax(logits.float() + m[:self.vocab], dim=dim, keepdim=keepdim)
 
     def set_pos(self, pos):
-        """set the position of the next decode step (device state + its host mirror); follow with set_token()"""
+        """set the position of the next decode step (device state + its host mirror); follow with set_token().  A ragged runner also takes one
+        position per sequence (a list or tensor of B)."""
+        if self.ragged and not isinstance(pos, int) and (not isinstance(pos, torch.Tensor) or pos.numel() > 1 or self.B == 1):
+            each = [int(p) for p in (pos.reshape(-1).tolist() if isinstance(pos, torch.Tensor) else pos)]
+            if len(each) != self.B or not all(0 <= p <= self.max_seq for p in each):
+                raise ValueError(f"expected {self.B} positions inside the KV cache (max_seq={self.max_seq}), got {each}")
+            self.pos.copy_(torch.tensor(each, dtype=torch.int32))
+            self.host_pos = max(each)
+            return
         pos = int(pos)
         if not 0 <= pos <= self.max_seq:
             raise ValueError(f"position {pos} outside the KV cache (max_seq={self.max_seq})")
@@ -507,8 +530,8 @@ class QuantLlama:
         else:
             self.token.fill_(int(token))
         torch.index_select(self.embed, 0, self.token, out=self.x)
-        torch.index_select(self.rope_tab.view(self.max_seq, 128), 0, self.pos.to(torch.int64).clamp_(0, self.max_seq - 1),
-                           out=self.rope_cur.view(1, 128))
+        rows = torch.index_select(self.rope_tab.view(self.max_seq, 128), 0, self.pos.to(torch.int64).clamp_(0, self.max_seq - 1))
+        self.rope_cur.copy_(rows if self.ragged else rows[0])
 
     def capture(self, sampled=False):
         """capture one token step into a hipGraph (replayed by decode_step); ``sampled``: the step that ends in the sampled tail, kept beside the greedy one"""
@@ -565,21 +588,37 @@ class QuantLlama:
         rot = torch.cat([-t2, t1], dim=-1)
         return t * cos + rot * sin
 
-    def prefill(self, ids, use_graph=True, start_pos=0):
+    def prefill(self, ids, use_graph=True, start_pos=0, lengths=None):
         """ids: int64 [S] prompt.  Fills the KV caches, leaves the next token in self.token and pos = start_pos + S.
         The ~25 framework launches per block make an eager prefill host-bound for short prompts (13 ms at S = 64,
         of which ~1 ms is GPU work); with ``use_graph`` the whole prefill of a given prompt LENGTH is captured once
         into a hipGraph and replayed for later prompts of that length.
         ``start_pos`` > 0 (the reference's patched forward takes the same argument, ftllama_modeling.py:76,98-104): the rows
         are appended behind ``start_pos`` cached positions -- a prompt fed in chunks, or the next turn of a conversation --
-        and attend the whole cache; the graph cache is keyed by (length, start_pos)."""
+        and attend the whole cache; the graph cache is keyed by (length, start_pos).
+        ``lengths`` (ragged runners): int [B], 1 <= L_b <= S -- ids [B, S] holds prompt b in its first L_b columns (RIGHT-padded with any valid id).
+        Still one pass over B * S rows: under causal attention the pad rows behind a prompt cannot reach its rows, and what they leave in cache
+        rows L_b .. S - 1 is overwritten by the decode steps before any step reads it (the step at position p writes row p, then reads 0 .. p).
+        Afterwards pos[b] = L_b and the first token comes from row L_b - 1.  The lengths live in a device tensor: the captured pass of (S, 0) serves any."""
         ids = self._ids_rows(ids)
         S = ids.shape[1]
         start_pos = int(start_pos)
         if start_pos < 0 or start_pos + S > self.max_seq:
             raise ValueError("prompt longer than the KV cache")
+        if lengths is not None and not self.ragged:
+            raise ValueError("lengths needs a runner built with ragged=True (this one keeps one position for the whole batch)")
+        longest = S
+        if self.ragged:
+            if start_pos != 0:
+                raise ValueError("a ragged prompt pass starts at position 0 (chunked ragged prompts are not served)")
+            each = [S] * self.B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+            if len(each) != self.B or not all(1 <= v <= S for v in each):
+                raise ValueError(f"lengths: expected {self.B} values in 1..{S}, got {each}")
+            self.lengths.copy_(torch.tensor(each, dtype=torch.int64))
+            longest = max(each)
         if not use_graph:
             logits = self._prefill_rows(ids, start_pos)
+            self.host_pos = start_pos + longest
             if self._sampled_tail():
                 self._first_token()
             return logits
@@ -602,7 +641,7 @@ class QuantLlama:
         g.replay()
         if rows is not None:
             self.logits_rows = rows             # (this graph's own output buffer: valid until its next replay)
-        self.host_pos = start_pos + S           # (the replay sets the device-side position; the host mirror is not part of it)
+        self.host_pos = start_pos + longest     # (the replay sets the device-side position; the host mirror is not part of it)
         if self._sampled_tail():
             self._first_token()                 # (outside the prompt graph, which ends in the arg-max: one graph per prompt length serves both)
         return self.logits
@@ -618,6 +657,8 @@ class QuantLlama:
 
     def _prefill_rows(self, ids, start_pos):
         """the prompt pass of every sequence (each into its own slice of the caches), then the shared position / next tokens"""
+        if self.ragged:
+            return self._prefill_rows_ragged(ids)
         if self.B == 1:
             return self._prefill_eager(ids[0], start_pos)
         B, S = ids.shape
@@ -630,12 +671,28 @@ class QuantLlama:
         self.set_token(self._argmax(self.logits, 1))
         return self.logits
 
-    def _rows_pass(self, ids, start_pos, cache):
+    def _prefill_rows_ragged(self, ids):
+        """the prompt pass of a ragged runner: the same ONE many-row pass, then per sequence (from self.lengths, on the device: graph-capturable)
+        the last REAL row's logits, pos[b] = L_b and the first token"""
+        B, S = ids.shape
+        last = self._rows_pass(ids, 0, cache=True, lengths=self.lengths)
+        logits = self.logits.view(B, self.vocab)
+        if self.all_logits:
+            self.logits_rows = self._logits_of_rows(self.__dict__.pop("_rows_x"), B, S, self.logits)
+            logits.copy_(self.logits_rows[torch.arange(B, device=self.dev), self.lengths - 1])
+        else:
+            ops.gemv_f16w(last.reshape(-1) if B == 1 else last, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
+        self.pos.copy_(self.lengths)            # (the host mirror: prefill())
+        self.set_token(self._argmax(logits, 1))
+        return self.logits
+
+    def _rows_pass(self, ids, start_pos, cache, lengths=None):
         """ONE many-row pass over B prompts of S rows (ids [B, S]): the linears see all B * S rows at once (one pass over
         the weights), RoPE and the causal attention run as ONE launch each over all sequences.  ``cache``: the rotated keys /
         values are written into the runner's KV caches (rows start_pos .. start_pos + S - 1 of every sequence) and the
         attention reads them there (a batched decode runner's prompt); otherwise q / k are rotated in place and the
-        attention reads the projection outputs (the harness' GeMM mode, no cache).  Returns the last rows [B, H]."""
+        attention reads the projection outputs (the harness' GeMM mode, no cache).  Returns the last rows [B, H] (``lengths``, device int64 [B]:
+        row lengths[b] - 1 of sequence b)."""
         B, S = ids.shape
         H, nh, nkv = self.H, self.nh, self.nkv
         x = self.embed.index_select(0, ids.reshape(-1).to(self.dev))
@@ -655,6 +712,8 @@ class QuantLlama:
             x = lin(blk["mlp.down_proj"], act, residual=x)
         if self.all_logits:
             self._rows_x = x                    # (picked up by _prefill_rows)
+        if lengths is not None:
+            return x.view(B, S, H)[torch.arange(B, device=x.device), lengths - 1].contiguous()
         return x.view(B, S, H)[:, S - 1].contiguous()
 
     def _logits_of_rows(self, x, B, S, last_logits):
@@ -756,6 +815,8 @@ class QuantLlama:
         harness times in GeMM mode with batch_size > 1 (amq/utils/speed.py:61-71; BASELINE.json configs[3] = 16 x 2048 on
         13B).  Returns the last-token logits [B, vocab].  The runner's KV cache is batch-1 (like the reference's FT path),
         so this pass does not write it and cannot be followed by decode steps."""
+        if self.ragged:
+            raise ValueError("prefill_batch writes no cache and keeps no positions: not offered with ragged=True")
         B, S = ids.shape
         if S > self.max_seq:
             raise ValueError("prompt longer than the RoPE table")
@@ -836,17 +897,23 @@ class QuantLlama:
         self.set_pos(0)
         self.set_token(0)
 
-    def generate(self, ids, gen_len, use_graph=True, stop_at_eos=False, min_new_tokens=0):
+    def generate(self, ids, gen_len, use_graph=True, stop_at_eos=False, min_new_tokens=0, lengths=None):
         """prefill + gen_len tokens (min_new_tokens = max_new_tokens = gen_len, amq/utils/speed.py:34-39): greedy, or sampled after
         ``set_sampling``.  Returns the generated ids (device tensor).  ``stop_at_eos`` (ids from ``set_eos``): a sequence that emits an EOS id is
         padded with the pad id from there on, and the loop ends once every sequence has (polled every EOS_POLL_STEPS steps): returns [B, n] with
-        n = the longest sequence's length, as HF does; the EOS ids stay suppressed for the first ``min_new_tokens`` tokens."""
+        n = the longest sequence's length, as HF does; the EOS ids stay suppressed for the first ``min_new_tokens`` tokens.
+        ``lengths`` (ragged runners): see :meth:`prefill`; the longest prompt + gen_len must fit the cache."""
         S = ids.shape[-1]
+        if lengths is not None:
+            if not self.ragged:
+                raise ValueError("lengths needs a runner built with ragged=True (this one keeps one position for the whole batch)")
+            lengths = [int(v) for v in (lengths.reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+            S = max(lengths) if lengths else S
         if S + gen_len > self.max_seq:
             raise ValueError("sequence does not fit the KV cache")
         if not stop_at_eos and self.sampling is None:   # greedy, fixed length
             out = torch.empty(self.B, gen_len, dtype=torch.int64, device=self.dev)
-            self.prefill(ids)
+            self.prefill(ids, lengths=lengths)
             out[:, 0] = self.token
             for i in range(1, gen_len):
                 self.decode_step(use_graph)
@@ -863,7 +930,7 @@ class QuantLlama:
             elif min_new_tokens > 0:
                 self.set_suppressed(tuple(suppressed) + tuple(e for e in self.eos if e not in suppressed))
             out = torch.full((self.B, gen_len), self.pad_id, dtype=torch.int64, device=self.dev)
-            self.prefill(ids)                   # (draws the first token: draw 0)
+            self.prefill(ids, lengths=lengths)  # (draws the first token: draw 0)
             out[:, 0] = self.token
             for i in range(1, gen_len):
                 if stop_at_eos and i == min_new_tokens:
@@ -897,7 +964,9 @@ class DenseLlama(QuantLlama):
     amq_speed_benchmark.py:171-197): plain library GEMMs (torch / hipBLASLt) for the seven
     linears, the same RMSNorm / attention / lm_head kernels around them."""
 
-    def __init__(self, config, device="cuda:0", max_seq=256, seed=0, batch=1):
+    def __init__(self, config, device="cuda:0", max_seq=256, seed=0, batch=1, ragged=False):
+        if ragged:
+            raise ValueError("the fp16 baseline keeps one position for the whole batch: ragged=True is served by QuantLlama")
         if isinstance(config, str):
             config = MODEL_CONFIGS[config]
         if not 1 <= int(batch) <= 8:

@@ -651,8 +651,18 @@ def decode_tail(logits, embed, token, pos, x, table=None, cur=None, suppress=Non
     _need(logits, torch.float16, "logits", B * vocab)
     _need(embed, torch.float16, "embed", vocab * hidden)
     _need(token, torch.int64, "token", B)
-    _need(pos, torch.int32, "pos", 1)
     _need(x, torch.float16, "x", B * hidden)
+    states, nseq = _seq_state(cur, pos)
+    if states is not None:                      # every sequence advances its own position and cos/sin row
+        if nseq != B:
+            raise ValueError(f"a step state of {nseq} sequences for {B} tokens")
+        _need(table, torch.float16, "rope table")
+        if suppress is not None:
+            _need(suppress, torch.int32, "suppress", 8)
+        _lib.check(_lib.load().amq_decode_tail_seq_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), states, _lib.ptr(x),
+                                                       _lib.ptr(table), table.numel() // 128, B, _lib.ptr(suppress), _lib.current_stream()))
+        return
+    _need(pos, torch.int32, "pos", 1)
     if cur is not None:
         _need(cur, torch.float16, "rope_cur", 128)
         _need(table, torch.float16, "rope table")
@@ -747,14 +757,23 @@ def decode_tail_sample(logits, embed, token, pos, x, state, table=None, cur=None
     _need(logits, torch.float16, "logits", B * vocab)
     _need(embed, torch.float16, "embed", vocab * hidden)
     _need(token, torch.int64, "token", B)
-    _need(pos, torch.int32, "pos", 1)
     _need(x, torch.float16, "x", B * hidden)
     _need(state, torch.int32, "state", _SMP_WORDS)
+    if suppress is not None:
+        _need(suppress, torch.int32, "suppress", 8)
+    states, nseq = _seq_state(cur, pos)
+    if states is not None:
+        if nseq != B:
+            raise ValueError(f"a step state of {nseq} sequences for {B} tokens")
+        _need(table, torch.float16, "rope table")
+        _lib.check(_lib.load().amq_decode_tail_sample_seq_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), states, _lib.ptr(x),
+                                                              _lib.ptr(table), table.numel() // 128, B, _lib.ptr(suppress), _lib.ptr(state),
+                                                              _lib.current_stream()))
+        return
+    _need(pos, torch.int32, "pos", 1)
     if cur is not None:
         _need(cur, torch.float16, "rope_cur", 128)
         _need(table, torch.float16, "rope table")
-    if suppress is not None:
-        _need(suppress, torch.int32, "suppress", 8)
     _lib.check(_lib.load().amq_decode_tail_sample_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), _lib.ptr(pos), _lib.ptr(x),
                                                       _lib.ptr(table) if cur is not None else None, _lib.ptr(cur),
                                                       table.numel() // 128 if cur is not None else 0, B, _lib.ptr(suppress), _lib.ptr(state),
@@ -769,8 +788,16 @@ def set_token(token_in, embed, token, pos, x, table=None, cur=None):
     _need(token_in, torch.int64, "token_in", n_in)
     _need(embed, torch.float16, "embed", vocab * hidden)
     _need(token, torch.int64, "token", B)
-    _need(pos, torch.int32, "pos", 1)
     _need(x, torch.float16, "x", B * hidden)
+    states, nseq = _seq_state(cur, pos)
+    if states is not None:
+        if nseq != B:
+            raise ValueError(f"a step state of {nseq} sequences for {B} tokens")
+        _need(table, torch.float16, "rope table")
+        _lib.check(_lib.load().amq_set_token_seq_f16(_lib.ptr(token_in), n_in, _lib.ptr(embed), vocab, hidden, _lib.ptr(token), states, _lib.ptr(x),
+                                                     _lib.ptr(table), table.numel() // 128, B, _lib.current_stream()))
+        return
+    _need(pos, torch.int32, "pos", 1)
     if cur is not None:
         _need(cur, torch.float16, "rope_cur", 128)
         _need(table, torch.float16, "rope table")
@@ -873,17 +900,44 @@ def silu_mul(gate, up, out=None):
     return y
 
 
-def new_step_state(device):
+STEP_STATE_STRIDE = _lib.STEP_STATE_STRIDE       # bytes between the blocks of a per-sequence step state
+_STEP_WORDS = STEP_STATE_STRIDE // 4
+
+
+def new_step_state(device, batch=None):
     """-> (rope_cur fp16 [128], pos int32 [1], err int32 [1]): three views of one 264-byte block, the layout
     amq_attn_decode_cur_f16 reads.  ``err`` is the sticky error word the attention kernel raises when the device-side
-    position is outside the cache (see :func:`check_step_state`)."""
-    block = torch.zeros(66, dtype=torch.int32, device=device)
-    return block[:64].view(torch.float16), block[64:65], block[65:66]
+    position is outside the cache (see :func:`check_step_state`).
+    ``batch``: the per-sequence form (sequences at positions of their own, include/amq_hip.h: amq_*_seq_f16) -- (rope_cur fp16 [batch, 128],
+    pos int32 [batch], err int32 [batch]), strided views of ``batch`` such blocks STEP_STATE_STRIDE bytes apart."""
+    if batch is None:
+        block = torch.zeros(66, dtype=torch.int32, device=device)
+        return block[:64].view(torch.float16), block[64:65], block[65:66]
+    blocks = torch.zeros(int(batch), _STEP_WORDS, dtype=torch.int32, device=device)
+    return blocks[:, :64].view(torch.float16), blocks[:, 64], blocks[:, 65]
+
+
+def _seq_state(cur, pos):
+    """the base pointer and sequence count of a per-sequence step state, after checking that ``cur`` [B, 128] and ``pos`` [B] are the views
+    :func:`new_step_state` made of ONE array of blocks (None, 0 when ``cur`` is not the per-sequence form)"""
+    if not isinstance(cur, torch.Tensor) or cur.dim() != 2:
+        return None, 0
+    B = cur.shape[0]
+    ok = (cur.is_cuda and cur.dtype is torch.float16 and cur.shape[1] == 128 and cur.stride(1) == 1 and isinstance(pos, torch.Tensor)
+          and pos.dtype is torch.int32 and pos.device == cur.device and tuple(pos.shape) == (B,) and pos.data_ptr() == cur.data_ptr() + 256
+          and (B == 1 or (cur.stride(0) == STEP_STATE_STRIDE // 2 and pos.stride(0) == _STEP_WORDS)))
+    if not ok:
+        raise ValueError("cur [B, 128] / pos [B] must be the views of one per-sequence step state (ops.new_step_state(device, batch=B))")
+    return ctypes.c_void_p(cur.data_ptr()), B
 
 
 def check_step_state(err):
-    """raise if a decode step ran with its device-side position outside the KV cache (synchronises)"""
-    if int(err.item()) != 0:
+    """raise if a decode step ran with its device-side position outside the KV cache (synchronises); per-sequence state: ANY sequence's"""
+    if err.numel() == 1:
+        bad = int(err.item()) != 0
+    else:
+        bad = bool((err != 0).any().item())
+    if bad:
         raise _lib.AmqError("a decode step ran with its position outside the KV cache (step skipped on the device)")
 
 
@@ -1074,7 +1128,8 @@ def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_the
     caches [B, n_kv_heads, max_seq, 128]; ``pos`` is an int or a device int32 tensor.  ``cur``: fp16 [128] cos/sin row
     of the current position (maintained by decode_tail) -- needs ``pos`` as a device tensor.
     ``n_splits``: workgroups per head (include/amq_hip.h: amq_attn_decode_split_f16); 0 = by cache length, 1 = the
-    single-workgroup kernel."""
+    single-workgroup kernel.
+    ``cur`` [B, 128] with ``pos`` [B] (ops.new_step_state(device, batch=B)): every sequence at its own position (amq_attn_decode_seq_f16)."""
     B = kcache.shape[0]
     max_seq = kcache.shape[2]
     if n_splits == 0:
@@ -1085,6 +1140,20 @@ def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_the
     _need(kcache, torch.float16, "kcache", B * n_kv_heads * max_seq * 128)
     _need(vcache, torch.float16, "vcache", B * n_kv_heads * max_seq * 128)
     _need(out, torch.float16, "out", B * n_heads * 128)
+    states, nseq = _seq_state(cur, pos)
+    if states is not None:                      # per-sequence step state: sequence b appends at ITS pos[b] and attends rows 0 .. pos[b]
+        if nseq != B:
+            raise ValueError(f"a step state of {nseq} sequences for caches of {B}")
+        lib = _lib.load()
+        if n_splits > 1:
+            wsb = lib.amq_attn_decode_split_workspace_bytes(B, n_heads, n_splits)
+            ws, tk = _ATTN_WS.get(q.device, wsb // 4), _ATTN_TICKETS.get(q.device, B * n_heads)
+            _lib.check(lib.amq_attn_decode_seq_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, B,
+                                                   n_heads, n_kv_heads, 128, max_seq, n_splits, _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
+        else:
+            _lib.check(lib.amq_attn_decode_seq_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, B,
+                                                   n_heads, n_kv_heads, 128, max_seq, 0, None, 0, None, _lib.current_stream()))
+        return out
     if isinstance(pos, torch.Tensor):
         _need(pos, torch.int32, "pos", 1)
         pos_dev, pos_i = ctypes.cast(pos.data_ptr(), ctypes.c_void_p), 0

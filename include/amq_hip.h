@@ -45,7 +45,8 @@
 extern "C" {
 #endif
 
-#define AMQ_VERSION 521            /* 0.5.2: amq_rope_table_freqs_f16 (rope_scaling) and amq_decode_tail_suppress_f16 added, nothing else changed.  0.5.1: the bfloat16 entry points
+#define AMQ_VERSION 521            /* 0.5.2: the per-sequence step-state entry points (amq_*_seq_f16) added, nothing else changed (additions keep the number).
+                                    * amq_rope_table_freqs_f16 (rope_scaling) and amq_decode_tail_suppress_f16 added, nothing else changed.  0.5.1: the bfloat16 entry points
                                     * (amq_*_bf16) added.  0.5.0: amq_gemv_opts.math renumbered
                                     * (0 = the build's default), amq_default_gemv_math added; the decode-engine and fused q/k/v-attention entry points live in
                                     * libamq_hip_ab.so (include/amq_hip_ab.h) since 0.4 */
@@ -344,6 +345,34 @@ int amq_sample_f16(const void* logits, int rows, int vocab, void* state, const i
 int amq_decode_tail_sample_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
                                const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids, void* state,
                                void* stream);
+
+/* ---- sequences at positions of their OWN (batched decode over prompts of unequal length) ----------------
+ * The batched entry points above keep ONE step state: every sequence is at the same position.  Here `step_states` is an ARRAY of `batch` blocks
+ * with the layout of amq_attn_decode_cur_f16's block
+ *     { fp16 cos/sin [64][2] of sequence b's CURRENT position ; int32 position at byte 256 ; int32 sticky error word at byte 260 ; pad }
+ * AMQ_STEP_STATE_STRIDE bytes apart (block b at step_states + b * AMQ_STEP_STATE_STRIDE).  Sequence b occupies rows 0 .. pos[b] - 1 of its slice
+ * of the caches -- a left-padded HF batch stored compactly: with position ids cumsum(mask) - 1 and the pad keys masked, HF's result for a row is
+ * that of the row alone -- so no attention mask reaches a kernel.  Same kernels as the shared-position entry points, instantiated with the block
+ * chosen by the sequence index: with equal positions in every block the results are theirs bit for bit. */
+#define AMQ_STEP_STATE_STRIDE 272
+/* RoPE + KV append + attention: sequence b rotates with block b's row, appends at row pos[b] and attends rows 0 .. pos[b].  n_splits == 0: one
+ * workgroup per head (amq_attn_decode_cur_f16; workspace / tickets may be NULL); n_splits >= 1: amq_attn_decode_split_f16's kernels -- chunks follow
+ * from each sequence's own position; grouped-query models take the matrix-core kernel and its combine launch as there; workspace (
+ * amq_attn_decode_split_workspace_bytes) and tickets as there.  A sequence whose position is outside 0 .. max_seq-1 is a no-op for THAT sequence
+ * and raises ITS block's error word; the others proceed. */
+int amq_attn_decode_seq_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int batch,
+                            int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
+                            void* tickets, void* stream);
+/* amq_decode_tail_suppress_f16 (suppress_ids may be NULL: none) with every sequence advancing ITS position (saturating at rope_rows) and writing ITS
+ * cos/sin row: token[b] = argmax(logits[b]), pos[b] += 1, x[b] = embed[token[b]], row[b] = rope_table[min(pos[b], rope_rows - 1)]. */
+int amq_decode_tail_seq_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
+                            const void* rope_table, int rope_rows, int batch, const int* suppress_ids, void* stream);
+/* amq_decode_tail_sample_f16 likewise (draw (seed, i, b) and EOS bookkeeping unchanged; batch <= 8). */
+int amq_decode_tail_sample_seq_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
+                                   const void* rope_table, int rope_rows, int batch, const int* suppress_ids, void* state, void* stream);
+/* amq_set_token_f16 likewise: row[b] = rope_table[min(pos[b], rope_rows - 1)]; the positions are not changed. */
+int amq_set_token_seq_f16(const long long* token_in, int n_in, const void* embed, int vocab, int hidden, long long* token, void* step_states, void* x,
+                          const void* rope_table, int rope_rows, int batch, void* stream);
 
 /* ---- many-row (prefill) glue --------------------------------------------------------------------------
  * The reference runs these steps as framework ops between the linears of a HF Llama block

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """decode throughput against the batch (graph replay, 64-token prompts, Llama-2-7B avg-3 synthetic weights): sequences per step
-share one pass over the weights.  usage: decode_batch.py [batches, comma separated] [steps]
+share one pass over the weights.  usage: decode_batch.py [--ragged | --ragged=spread] [batches, comma separated] [steps]
+--ragged: the runner with a position per sequence (QuantLlama(ragged=True)) at equal 64-token prompts -- the same work as the plain step, so the
+difference is what the per-sequence step state costs; --ragged=spread: prompt lengths spread evenly over 16 .. 256 (right-padded to 256).
 (NORM_SUMS=0: the 5 .. 8-row steps with one rmsnorm launch per norm instead of the partial-sum RMSNorm, A/B)"""
 import os, sys, time
 import torch
@@ -13,16 +15,24 @@ if os.environ.get("GEMV_WAVES") or os.environ.get("GEMV_DEPTH") or os.environ.ge
 
 if os.environ.get("NORM_SUMS") == "0":
     QuantLlama.NORM_SUMS = False
-batches = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else "1,2,4,8".split(","))]
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 128
+ragged = next((v for v in sys.argv[1:] if v.startswith("--ragged")), None)
+argv = [v for v in sys.argv[1:] if not v.startswith("--")]
+batches = [int(v) for v in (argv[0].split(",") if len(argv) > 0 else "1,2,4,8".split(","))]
+steps = int(argv[1]) if len(argv) > 1 else 128
+spread = ragged == "--ragged=spread"
+S = 256 if spread else 64
 name = os.environ.get("SWEEP_MODEL", "Llama-2-7b-hf")
 dev = torch.device("cuda:0")
 cfg = arch.MODEL_CONFIGS[name]
 a, usage = arch.synthesize_arch(cfg, 3.0, seed=0, pinned=arch.PINNED_7B if "7b" in name else ())
 for B in batches:
-    m = QuantLlama(cfg, a["linear"], device=dev, max_seq=64 + steps + 24, seed=0, batch=B)
-    ids = torch.randint(0, m.vocab - 1, (B, 64), generator=torch.Generator().manual_seed(0)).to(dev)
-    m.prefill(ids if B > 1 else ids[0], use_graph=False)
+    m = QuantLlama(cfg, a["linear"], device=dev, max_seq=S + steps + 24, seed=0, batch=B, ragged=ragged is not None)
+    ids = torch.randint(0, m.vocab - 1, (B, S), generator=torch.Generator().manual_seed(0)).to(dev)
+    if ragged is not None:
+        lengths = [16 + (240 * b) // max(1, B - 1) for b in range(B)] if spread else [S] * B
+        m.prefill(ids, use_graph=False, lengths=lengths)
+    else:
+        m.prefill(ids if B > 1 else ids[0], use_graph=False)
     m.capture()
     for _ in range(8):
         m.decode_step()
@@ -33,6 +43,7 @@ for B in batches:
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     m.check()
-    print(f"{name} batch {B}: {dt*1e3:.3f} ms/step  {1/dt:7.1f} steps/s  {B/dt:8.1f} tokens/s aggregate", flush=True)
+    tag = "" if ragged is None else (f" ragged, lengths {lengths[0]} .. {lengths[-1]}")
+    print(f"{name} batch {B}{tag}: {dt*1e3:.3f} ms/step  {1/dt:7.1f} steps/s  {B/dt:8.1f} tokens/s aggregate", flush=True)
     del m
     torch.cuda.empty_cache()
