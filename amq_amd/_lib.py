@@ -22,6 +22,7 @@ MAX_SEGMENTS = 4
 MATH_DEFAULT, MATH_LINEAR, MATH_GROUPSCALE, MATH_EXACT = 0, 1, 2, 3
 FEWROW_AUTO, FEWROW_TILE, FEWROW_STREAM = 0, 1, 2      # kernel form of the grouped few-row launch (amq_gemm_xfrag_grouped_form_f16)
 ABI_VERSION = 521            # include/amq_hip.h AMQ_VERSION these bindings mirror (checked at load)
+LOOKUP_STATE_WORDS = 32     # include/amq_hip.h AMQ_LOOKUP_STATE_WORDS: int32 words of the lookup state block of amq_decode_tail_lookup_f16
 STEP_STATE_STRIDE = 272     # include/amq_hip.h AMQ_STEP_STATE_STRIDE: bytes between the step-state blocks of the amq_*_seq_f16 entry points
 GEMM_AUTO, GEMM_TILED, GEMM_SKINNY, GEMM_RING, GEMM_RING128, GEMM_WS, GEMM_DEQ = 0, 1, 2, 3, 4, 5, 6
 
@@ -108,6 +109,9 @@ SIGNATURES = {
     "amq_decode_tail_seq_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "amq_decode_tail_sample_seq_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "amq_set_token_seq_f16": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    # prompt-lookup speculative decoding: `rows` consecutive positions of one sequence per step
+    "amq_attn_decode_rows_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "amq_decode_tail_lookup_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "amq_attn_prefill_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 + [_vp]),
     "amq_rope_cache_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "amq_rope_cache_batch_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

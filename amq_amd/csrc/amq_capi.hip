@@ -954,6 +954,51 @@ int amq_set_token_seq_f16(const long long* token_in, int n_in, const void* embed
                                            rope_rows, batch, (hipStream_t)stream, true), "set_token_seq");
 }
 
+/* ---- prompt-lookup speculative decoding: `rows` consecutive positions of ONE sequence per step ---- */
+static_assert(AMQ_LOOKUP_STATE_WORDS == amq::LK_WORDS && AMQ_LOOKUP_MAX_ROWS == 8, "lookup state block");
+
+int amq_attn_decode_rows_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int rows,
+                             int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
+                             void* tickets, void* stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out || !step_states) return fail(AMQ_EINVAL, "null pointer");
+    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
+    if (rows < 2 || rows > AMQ_LOOKUP_MAX_ROWS) return fail(AMQ_ESHAPE, "rows must be 2..%d (got %d)", AMQ_LOOKUP_MAX_ROWS, rows);
+    if (n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
+        return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads)", n_heads, n_kv_heads);
+    if (max_seq < 1) return fail(AMQ_ESHAPE, "bad max_seq %d", max_seq);
+    if (n_splits < 0 || n_splits > 1024) return fail(AMQ_EINVAL, "n_splits must be 0 (one workgroup per head) or 1..1024 (got %d)", n_splits);
+    amq::AttnArgs a{q, k, v, kcache, vcache, out, nullptr, 0, n_heads, n_kv_heads, max_seq, 10000.0f, nullptr, step_states, true, true};
+    const size_t rows_lds = 2 * 7 * 128 * 2 + 16;      // the earlier rows' rotated keys and values behind the score array
+    if (n_splits == 0) {
+        if (6 * 128 + (size_t)max_seq * 4 + rows_lds + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
+        return check_hip(amq::launch_attn_decode(a, rows, (hipStream_t)stream), "attn_decode_rows");
+    }
+    if (!workspace || !tickets) return fail(AMQ_EINVAL, "null pointer (workspace / tickets are required with n_splits >= 1)");
+    int chunk = (((max_seq + n_splits - 1) / n_splits) + 31) & ~31;
+    chunk = chunk < amq::ATT_MIN_CHUNK ? amq::ATT_MIN_CHUNK : chunk;
+    if (6 * 128 + (size_t)chunk * 4 + rows_lds + 17 * 1024 > LDS_LIMIT)
+        return fail(AMQ_ESHAPE, "max_seq=%d over %d splits leaves chunks of %d keys: too long", max_seq, n_splits, chunk);
+    const size_t need = amq_attn_decode_split_workspace_bytes(rows, n_heads, n_splits);
+    if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    return check_hip(amq::launch_attn_decode_split(a, rows, n_splits, workspace, tickets, (hipStream_t)stream), "attn_decode_rows (split)");
+}
+
+int amq_decode_tail_lookup_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
+                               const void* rope_table, int rope_rows, int rows, const int* suppress_ids, void* lookup_state, int* history,
+                               int history_cap, void* stream) {
+    if (!lookup_state || !history) return fail(AMQ_EINVAL, "lookup_state (the 128-byte device block) and history are required (null)");
+    if (!logits || !embed || !token || !step_states || !x || !rope_table) return fail(AMQ_EINVAL, "null pointer");
+    if (rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
+    if (vocab < 1 || hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need vocab >= 1 and hidden %% 8 == 0 (got %d, %d)", vocab, hidden);
+    if (rows < 2 || rows > AMQ_LOOKUP_MAX_ROWS) return fail(AMQ_ESHAPE, "rows must be 2..%d (got %d)", AMQ_LOOKUP_MAX_ROWS, rows);
+    if ((vocab % 8) != 0) return fail(AMQ_ESHAPE, "several rows need vocab %% 8 == 0 (16-byte aligned logits rows)");
+    if (history_cap < rope_rows || history_cap > (1 << 24))
+        return fail(AMQ_ESHAPE, "history_cap must hold the whole cache (max_seq = rope_rows = %d) and at most 2^24 tokens, got %d", rope_rows, history_cap);
+    amq::LookupArgs a{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, step_states, (_Float16*)x, (const _Float16*)rope_table,
+                      rope_rows, suppress_ids, (int*)lookup_state, history, history_cap};
+    return check_hip(amq::launch_decode_tail_lookup(a, rows, (hipStream_t)stream), "decode_tail_lookup");
+}
+
 int amq_rope_table_f16(void* table, int max_seq, float rope_theta, void* stream) {
     if (!table || max_seq < 1) return fail(AMQ_EINVAL, "bad rope table request");
     return check_hip(amq::launch_rope_table(table, max_seq, rope_theta, (hipStream_t)stream), "rope_table");

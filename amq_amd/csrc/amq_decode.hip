@@ -416,10 +416,19 @@ extern unsigned long long* g_stamp_ptr;
 // SEQ (amq_attn_decode_seq_f16; step-state mode only): p_state is block 0 of an array of gridDim.y step-state blocks STEP_STRIDE bytes apart and
 // sequence blockIdx.y reads ITS block -- one scalar multiply-add in front of the same first loads; everything behind is the same code at the
 // sequence's own position.  The !SEQ instantiations are the shared-position kernels as they were.
-template <bool SEQ>
+// ROWS (amq_attn_decode_rows_f16; with SEQ): the gridDim.y rows are CONSECUTIVE positions p .. p + rows - 1 of ONE sequence (a verify step of
+// speculative decoding: row 0 the current token, rows 1 .. the guessed continuations).  There is one cache slice; row j (block j: position p + j)
+// appends cache row p + j and attends rows 0 .. p - 1 of the cache plus THIS step's rows 0 .. j.  Rows p .. p + j - 1 are being appended by other
+// workgroups of the same launch, so nobody reads them from the cache: waves 1 .. j rotate those rows themselves from the k / v inputs (block r's
+// cos/sin row, rotate_and_append's fp16 expression) into LDS, and the score / output loops take keys t >= p from there.  Same expressions in the
+// same order as the SEQ kernel at position p + j over a cache that already holds those rows: the same bits.
+constexpr int ATT_ROWS_MAX = 8;                              // rows of a ROWS launch (7 earlier rows at most = waves 1 .. 7)
+constexpr int ATT_ROWS_LDS = 2 * (ATT_ROWS_MAX - 1) * ATT_D * 2;   // bytes behind the score array: rotated keys and values of the earlier rows
+template <bool SEQ, bool ROWS = false>
 __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, void* p_vc, const void* p_state, int p_heads,
                                                                    int p_max_seq, const void* p_q, const void* p_k,
                                                                    const void* p_v, AttnRest rest) {
+    const void* const p_state0 = p_state;           // (ROWS: block 0 of the step's rows)
     if (SEQ) p_state = (const char*)p_state + (size_t)blockIdx.y * STEP_STRIDE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* qs = (_Float16*)smem;                 // [128] rotated q
@@ -429,6 +438,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
     __shared__ float red[2 * ATT_THREADS / 64];
     __shared__ float part[ATT_GROUPS][ATT_D];
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int cb = ROWS ? 0 : b;                    // the sequence whose cache slice this is
     const int n_heads = p_heads & 0xFF, n_kv_heads = (p_heads >> 8) & 0xFF, max_seq = p_max_seq;
     const bool cur_mode = (p_heads >> 16) & 1;
     const void* p_cur = cur_mode ? p_state : nullptr;
@@ -445,8 +455,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
     const _Float16* q = (const _Float16*)p_q + ((size_t)b * n_heads + h) * ATT_D;
     const _Float16* kn = (const _Float16*)p_k + ((size_t)b * n_kv_heads + kvh) * ATT_D;
     const _Float16* vn = (const _Float16*)p_v + ((size_t)b * n_kv_heads + kvh) * ATT_D;
-    _Float16* kc = (_Float16*)p_kc + ((size_t)b * n_kv_heads + kvh) * (size_t)max_seq * ATT_D;
-    _Float16* vc = (_Float16*)p_vc + ((size_t)b * n_kv_heads + kvh) * (size_t)max_seq * ATT_D;
+    _Float16* kc = (_Float16*)p_kc + ((size_t)cb * n_kv_heads + kvh) * (size_t)max_seq * ATT_D;
+    _Float16* vc = (_Float16*)p_vc + ((size_t)cb * n_kv_heads + kvh) * (size_t)max_seq * ATT_D;
 
     ATT_STAMP(0);
     // vmcnt waits are in issue order: what the rotation needs (raw q / k / v of the new token, later the cos/sin pair) is
@@ -475,14 +485,18 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
     // A position outside the cache (a graph replayed past max_seq, a corrupted step state) must not index the cache or
     // the LDS score array: the whole workgroup leaves (pos is wave-uniform), nothing is appended or written, and in
     // step-state mode the sticky error word at byte 260 of the block is raised for the host to read.
-    if (pos < 0 || pos >= max_seq) {
+    const int p0 = ROWS ? pos - b : pos;             // ROWS: the position of row 0 = the first cache row this launch appends
+    if (pos < 0 || pos >= max_seq || (ROWS && p0 < 0)) {
         if (cur_mode && tid == 0) *(int*)((char*)const_cast<void*>(p_state) + 260) = 1;
         return;
     }
     const int T = pos + 1;
     ATT_STAMP(1);
     if (tid < 64 && !p_cur && rest.rope_table) cs_tab = ((const h2*)rest.rope_table)[(size_t)pos * 64 + tid];
-    const int last_old = pos > 0 ? pos - 1 : 0;      // rows >= pos are never used; clamp keeps every load inside rows already written
+    // rows >= pos are never used; clamp keeps every load inside rows already written (ROWS: rows >= p0 -- those of this launch -- come from LDS)
+    const int last_old = ROWS ? (p0 > 0 ? p0 - 1 : 0) : (pos > 0 ? pos - 1 : 0);
+    _Float16* const kd = (_Float16*)(smem + ((6 * ATT_D + (size_t)max_seq * 4 + 15) & ~(size_t)15));    // ROWS: [b][128] rotated keys of rows 0 .. b - 1
+    _Float16* const vd = kd + (ATT_ROWS_MAX - 1) * ATT_D;                                                //       [b][128] their values
     // rows past the context are not requested at all (wave-uniform skip): every wave-load costs the CU's texture
     // addresser >= 16 cycles whether or not its lanes point at the same clamped row, and at T ~ 200 half of the 24 loads
     // per wave were such duplicates (2.2 us from position to barrier, profiles/r01b_attn_stamps.txt)
@@ -528,6 +542,20 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
             rotate_and_append(c16, s16);
         }
     }
+    if constexpr (ROWS) {                           // waves 1 .. b: the earlier rows of this step, rotated with THEIR blocks' cos/sin rows
+        const int w = tid >> 6;
+        if (w >= 1 && w <= b && w < ATT_ROWS_MAX) {
+            const int r = w - 1, i = tid & 63;
+            const _Float16* kr = (const _Float16*)p_k + ((size_t)r * n_kv_heads + kvh) * ATT_D;
+            const _Float16* vr = (const _Float16*)p_v + ((size_t)r * n_kv_heads + kvh) * ATT_D;
+            const h2 cs = ((const h2*)((const char*)p_state0 + (size_t)r * STEP_STRIDE))[i];
+            const _Float16 a0 = kr[i], a1 = kr[i + 64], c16 = cs.x, s16 = cs.y;
+            kd[r * ATT_D + i] = a0 * c16 + (-a1) * s16;
+            kd[r * ATT_D + i + 64] = a1 * c16 + a0 * s16;
+            vd[r * ATT_D + i] = vr[i];
+            vd[r * ATT_D + i + 64] = vr[i + 64];
+        }
+    }
     __syncthreads();
     ATT_STAMP(2);
 
@@ -549,12 +577,20 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
         load_v(i);                                   // V's row i leaves as score i is taken (the split kernel's order at one workgroup per CU)
         if (ATT_GROUPS * i < T) {                   // wave-uniform: iterations wholly past the context never touch their row
             const int t = grp + ATT_GROUPS * i;
-            const float sv = score(t == pos ? knew : krow[i]);
+            float sv;
+            if constexpr (ROWS) {               // (selected by VALUE: a select among lvalues picks an address and sends krow[] through scratch)
+                h8 kv = krow[i];
+                if (t == pos) kv = knew;
+                else if (t >= p0 && t < pos) kv = *(const h8*)(kd + (t - p0) * ATT_D + 8 * l16);
+                sv = score(kv);
+            } else sv = score(t == pos ? knew : krow[i]);
             if (t < T && l16 == 0) sc[t] = sv;
         }
     }
     for (int t = grp + ATT_GROUPS * ATT_PF; t < T; t += ATT_GROUPS) {       // contexts beyond the register prefetch
-        const h8 kv = (t == pos) ? knew : *(const h8*)(kc + (size_t)t * ATT_D + 8 * l16);
+        h8 kv;
+        if constexpr (ROWS) kv = (t == pos) ? knew : t >= p0 ? *(const h8*)(kd + (t - p0) * ATT_D + 8 * l16) : *(const h8*)(kc + (size_t)t * ATT_D + 8 * l16);
+        else kv = (t == pos) ? knew : *(const h8*)(kc + (size_t)t * ATT_D + 8 * l16);
         const float sv = score(kv);
         if (l16 == 0) sc[t] = sv;
     }
@@ -591,14 +627,21 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
         const int t = grp + ATT_GROUPS * i;
         if (ATT_GROUPS * i < T && t < T) {
             const _Float16 p16 = (_Float16)(sc[t] * inv);        // softmax(...).to(fp16)
-            const h8 vv = (t == pos) ? vnew : vrow[i];
+            h8 vv;
+            if constexpr (ROWS) {
+                vv = vrow[i];
+                if (t == pos) vv = vnew;
+                else if (t >= p0 && t < pos) vv = *(const h8*)(vd + (t - p0) * ATT_D + 8 * l16);
+            } else vv = (t == pos) ? vnew : vrow[i];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] += (float)p16 * (float)vv[e];
         }
     }
     for (int t = grp + ATT_GROUPS * ATT_PF; t < T; t += ATT_GROUPS) {
         const _Float16 p16 = (_Float16)(sc[t] * inv);
-        const h8 vv = (t == pos) ? vnew : *(const h8*)(vc + (size_t)t * ATT_D + 8 * l16);
+        h8 vv;
+        if constexpr (ROWS) vv = (t == pos) ? vnew : t >= p0 ? *(const h8*)(vd + (t - p0) * ATT_D + 8 * l16) : *(const h8*)(vc + (size_t)t * ATT_D + 8 * l16);
+        else vv = (t == pos) ? vnew : *(const h8*)(vc + (size_t)t * ATT_D + 8 * l16);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] += (float)p16 * (float)vv[e];
     }
@@ -640,10 +683,13 @@ constexpr int ATT_WS_STRIDE = ATT_D + 4;       // floats per (head, chunk): O[12
 #else
 #define ATT_KV_LOAD(p) (*(const h8*)(p))
 #endif
-template <int RING, bool SEQ>
+// ROWS: attn_decode_kernel's -- every workgroup of row b (whatever its chunk) rotates rows 0 .. b - 1 of this step into LDS; the chunks follow from the row's
+// own position and the workgroup of the chunk that holds it appends it.
+template <int RING, bool SEQ, bool ROWS = false>
 __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_kc, void* p_vc, const void* p_state, int p_heads,
                                                                          int p_max_seq, const void* p_q, const void* p_k,
                                                                          const void* p_v, AttnRest rest, AttnSplit sp) {
+    const void* const p_state0 = p_state;           // (ROWS: block 0 of the step's rows)
     if (SEQ) p_state = (const char*)p_state + (size_t)blockIdx.y * STEP_STRIDE;      // (attn_decode_kernel: the sequence's own step-state block)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* qs = (_Float16*)smem;                 // [128] rotated q
@@ -654,6 +700,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
     __shared__ float part[ATT_GROUPS][ATT_D];
     __shared__ int last_flag;
     const int b = blockIdx.y, z = blockIdx.z, tid = threadIdx.x;
+    const int cb = ROWS ? 0 : b;                    // the sequence whose cache slice this is
     const int n_heads = p_heads & 0xFF, n_kv_heads = (p_heads >> 8) & 0xFF, max_seq = p_max_seq;
     // Grouped-query models: the query heads of one kv head read the same K / V chunk.  Workgroups are dealt round-robin over
     // the 8 XCDs (linear id % 8 = blockIdx.x % 8 when the head count is a multiple of 8), so the heads of a kv group are given
@@ -675,8 +722,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
     const _Float16* q = (const _Float16*)p_q + ((size_t)b * n_heads + h) * ATT_D;
     const _Float16* kn = (const _Float16*)p_k + ((size_t)b * n_kv_heads + kvh) * ATT_D;
     const _Float16* vn = (const _Float16*)p_v + ((size_t)b * n_kv_heads + kvh) * ATT_D;
-    _Float16* kc = (_Float16*)p_kc + ((size_t)b * n_kv_heads + kvh) * (size_t)max_seq * ATT_D;
-    _Float16* vc = (_Float16*)p_vc + ((size_t)b * n_kv_heads + kvh) * (size_t)max_seq * ATT_D;
+    _Float16* kc = (_Float16*)p_kc + ((size_t)cb * n_kv_heads + kvh) * (size_t)max_seq * ATT_D;
+    _Float16* vc = (_Float16*)p_vc + ((size_t)cb * n_kv_heads + kvh) * (size_t)max_seq * ATT_D;
 
     _Float16 q0 = 0, q1 = 0, k0 = 0, k1 = 0, v0 = 0, v1 = 0;
     h2 cs_cur = {(_Float16)1.f, (_Float16)0.f}, cs_tab = {(_Float16)1.f, (_Float16)0.f};
@@ -687,7 +734,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
         v0 = vn[tid]; v1 = vn[tid + 64];
     }
     // a position outside the cache: nothing is appended or written (attn_decode_kernel's guard)
-    if (pos < 0 || pos >= max_seq) {
+    const int p0 = ROWS ? pos - b : pos;             // ROWS: the position of row 0 = the first cache row this launch appends
+    if (pos < 0 || pos >= max_seq || (ROWS && p0 < 0)) {
         if (cur_mode && tid == 0 && z == 0) *(int*)((char*)const_cast<void*>(p_state) + 260) = 1;
         return;
     }
@@ -701,7 +749,11 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
     const int Tl = t1 - t0;
     const bool has_new = t1 == T;                    // the chunk that holds the new token (the last active one)
     if (tid < 64 && !p_cur && rest.rope_table) cs_tab = ((const h2*)rest.rope_table)[(size_t)pos * 64 + tid];
-    const int last_old = pos > 0 ? pos - 1 : 0;      // rows >= pos are never read from the cache
+    const int last_old = ROWS ? (p0 > 0 ? p0 - 1 : 0) : (pos > 0 ? pos - 1 : 0);      // rows >= pos (ROWS: >= p0) are never read from the cache
+    int chunk_max = (((max_seq + sp.n_splits - 1) / sp.n_splits) + 31) & ~31;             // (att_chunk_max: the launch's score array)
+    chunk_max = chunk_max < ATT_MIN_CHUNK ? ATT_MIN_CHUNK : chunk_max;
+    _Float16* const kd = (_Float16*)(smem + 6 * ATT_D + (size_t)chunk_max * 4);           // ROWS: [b][128] rotated keys of rows 0 .. b - 1
+    _Float16* const vd = kd + (ATT_ROWS_MAX - 1) * ATT_D;                                  //       [b][128] their values
     // The chunk's K and V rows travel through a RING of row loads per thread: RING rows of K leave here, a row's successor when the row is about to be
     // used, V's first rows behind K's last, the rest of V as the output accumulates.  All 2 x 9 rows of a thread at once (the first form) put 144 KB per
     // workgroup in flight -- 37 MB over the chip at 2048 keys, more than the launch reads -- and the rows then arrive at 3.9 TB/s at the margin; the memory
@@ -748,6 +800,20 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
             vc[(size_t)pos * ATT_D + i + 64] = v1;
         }
     }
+    if constexpr (ROWS) {                           // waves 1 .. b: the earlier rows of this step (attn_decode_kernel)
+        const int w = tid >> 6;
+        if (w >= 1 && w <= b && w < ATT_ROWS_MAX) {
+            const int r = w - 1, i = tid & 63;
+            const _Float16* kr = (const _Float16*)p_k + ((size_t)r * n_kv_heads + kvh) * ATT_D;
+            const _Float16* vr = (const _Float16*)p_v + ((size_t)r * n_kv_heads + kvh) * ATT_D;
+            const h2 cs = ((const h2*)((const char*)p_state0 + (size_t)r * STEP_STRIDE))[i];
+            const _Float16 a0 = kr[i], a1 = kr[i + 64], c16 = cs.x, s16 = cs.y;
+            kd[r * ATT_D + i] = a0 * c16 + (-a1) * s16;
+            kd[r * ATT_D + i + 64] = a1 * c16 + a0 * s16;
+            vd[r * ATT_D + i] = vr[i];
+            vd[r * ATT_D + i + 64] = vr[i + 64];
+        }
+    }
     __syncthreads();
 
     const float scale = rsqrtf((float)ATT_D);
@@ -767,12 +833,20 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
         else load_v(i + RING - ATT_PF);
         if (ATT_GROUPS * i < Tl) {
             const int t = t0 + grp + ATT_GROUPS * i;
-            const float sv = score(t == pos ? knew : krow[i]);
+            float sv;
+            if constexpr (ROWS) {               // (selected by VALUE: a select among lvalues picks an address and sends krow[] through scratch)
+                h8 kv = krow[i];
+                if (t == pos) kv = knew;
+                else if (t >= p0 && t < pos) kv = *(const h8*)(kd + (t - p0) * ATT_D + 8 * l16);
+                sv = score(kv);
+            } else sv = score(t == pos ? knew : krow[i]);
             if (t < t1 && l16 == 0) sc[t - t0] = sv;
         }
     }
     for (int t = t0 + grp + ATT_GROUPS * ATT_PF; t < t1; t += ATT_GROUPS) {       // chunks beyond the register prefetch
-        const h8 kv = (t == pos) ? knew : *(const h8*)(kc + (size_t)t * ATT_D + 8 * l16);
+        h8 kv;
+        if constexpr (ROWS) kv = (t == pos) ? knew : t >= p0 ? *(const h8*)(kd + (t - p0) * ATT_D + 8 * l16) : *(const h8*)(kc + (size_t)t * ATT_D + 8 * l16);
+        else kv = (t == pos) ? knew : *(const h8*)(kc + (size_t)t * ATT_D + 8 * l16);
         const float sv = score(kv);
         if (l16 == 0) sc[t - t0] = sv;
     }
@@ -811,14 +885,21 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
         const int t = t0 + grp + ATT_GROUPS * i;
         if (ATT_GROUPS * i < Tl && t < t1) {
             const float p = weight(t - t0);
-            const h8 vv = (t == pos) ? vnew : vrow[i];
+            h8 vv;
+            if constexpr (ROWS) {
+                vv = vrow[i];
+                if (t == pos) vv = vnew;
+                else if (t >= p0 && t < pos) vv = *(const h8*)(vd + (t - p0) * ATT_D + 8 * l16);
+            } else vv = (t == pos) ? vnew : vrow[i];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] += p * (float)vv[e];
         }
     }
     for (int t = t0 + grp + ATT_GROUPS * ATT_PF; t < t1; t += ATT_GROUPS) {
         const float p = weight(t - t0);
-        const h8 vv = (t == pos) ? vnew : *(const h8*)(vc + (size_t)t * ATT_D + 8 * l16);
+        h8 vv;
+        if constexpr (ROWS) vv = (t == pos) ? vnew : t >= p0 ? *(const h8*)(vd + (t - p0) * ATT_D + 8 * l16) : *(const h8*)(vc + (size_t)t * ATT_D + 8 * l16);
+        else vv = (t == pos) ? vnew : *(const h8*)(vc + (size_t)t * ATT_D + 8 * l16);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] += p * (float)vv[e];
     }
@@ -1066,7 +1147,8 @@ static int att_chunk_max(int max_seq, int n_splits) {
 
 template <int RING>
 static hipError_t launch_attn_decode_split_ring(const AttnArgs& a, int batch, int n_splits, void* ws, void* tickets, size_t lds, hipStream_t st) {
-    const auto kern = a.seq ? attn_decode_split_kernel<RING, true> : attn_decode_split_kernel<RING, false>;
+    const auto kern = a.rows ? attn_decode_split_kernel<RING, true, true> : a.seq ? attn_decode_split_kernel<RING, true> : attn_decode_split_kernel<RING, false>;
+    if (a.rows) lds += ATT_ROWS_LDS;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -1084,7 +1166,7 @@ static hipError_t launch_attn_decode_split_ring(const AttnArgs& a, int batch, in
 }
 
 hipError_t launch_attn_decode_split(const AttnArgs& a, int batch, int n_splits, void* ws, void* tickets, hipStream_t st) {
-    if (attn_decode_takes_gqa(a.n_heads, a.n_kv_heads, a.max_seq, n_splits)) return launch_attn_decode_gqa(a, batch, n_splits, ws, tickets, st);
+    if (!a.rows && attn_decode_takes_gqa(a.n_heads, a.n_kv_heads, a.max_seq, n_splits)) return launch_attn_decode_gqa(a, batch, n_splits, ws, tickets, st);
     StreamDevice sd_(st);                                  // kernel attributes are per device: the stream's, not the current one
     const size_t lds = 6 * ATT_D + (size_t)att_chunk_max(a.max_seq, n_splits) * 4;
     // row loads in flight per thread (the kernel's RING): while the launch is at most one workgroup per CU all of K at once and V behind it as the scores
@@ -1101,8 +1183,8 @@ hipError_t launch_attn_decode_split(const AttnArgs& a, int batch, int n_splits, 
 
 hipError_t launch_attn_decode(const AttnArgs& a, int batch, hipStream_t st) {
     StreamDevice sd_(st);                                  // kernel attributes are per device: the stream's, not the current one
-    const size_t lds = 6 * ATT_D + (size_t)a.max_seq * 4;
-    const auto kern = a.seq ? attn_decode_kernel<true> : attn_decode_kernel<false>;
+    const size_t lds = a.rows ? ((6 * ATT_D + (size_t)a.max_seq * 4 + 15) & ~(size_t)15) + ATT_ROWS_LDS : 6 * ATT_D + (size_t)a.max_seq * 4;
+    const auto kern = a.rows ? attn_decode_kernel<true, true> : a.seq ? attn_decode_kernel<true> : attn_decode_kernel<false>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

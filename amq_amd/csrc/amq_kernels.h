@@ -149,6 +149,7 @@ struct AttnArgs {
     const void* rope_cur;     // step-state block {fp16 [64][2] (cos, sin) of the CURRENT position; int32 position at byte 256}
                               // maintained by launch_decode_tail, or null
     bool seq = false;         // rope_cur is block 0 of an array of `batch` step-state blocks STEP_STRIDE bytes apart: every sequence at ITS position
+    bool rows = false;        // (with seq) the `batch` rows are consecutive positions of ONE sequence: one cache slice, causal among the rows (amq_attn_decode_rows_f16)
 };
 // bytes between the step-state blocks of sequences decoded at positions of their own (include/amq_hip.h: AMQ_STEP_STATE_STRIDE)
 constexpr int STEP_STRIDE = 272;
@@ -222,6 +223,25 @@ struct SampleArgs {
     int flags;                  // SMP_FLAG_*
 };
 hipError_t launch_sample(const SampleArgs& a, int rows, hipStream_t st, bool seq = false);   // seq: a.pos / a.rope_cur = block 0 of `rows` step-state blocks
+
+// verify-and-propose tail of a prompt-lookup speculative step (amq_lookup.hip).  state: the 128-byte device block of include/amq_hip.h (int32 word indices below)
+enum { LK_DRAFTS = 0, LK_NGRAM = 1, LK_MODE = 2, LK_COUNT = 3, LK_STEPS = 4, LK_ACCEPTED = 5, LK_TICKET = 6, LK_DRAFT = 8, LK_ARGMAX = 16, LK_WORDS = 32 };
+struct LookupArgs {
+    const _Float16* logits;     // [rows, vocab], contiguous
+    int vocab;
+    const _Float16* embed;
+    int hidden;
+    long long* token;           // [rows]
+    void* step_states;          // `rows` step-state blocks STEP_STRIDE bytes apart
+    _Float16* x;                // [rows, hidden]
+    const _Float16* rope_table;
+    int rope_rows;
+    const int* suppress;        // int32 [8] or null
+    int* state;                 // LK_WORDS int32
+    int* history;               // int32 [history_cap]
+    int history_cap;
+};
+hipError_t launch_decode_tail_lookup(const LookupArgs& a, int rows, hipStream_t st);
 
 // q / k / v GEMV + decode attention in one launch (amq_gemv.hip): a's segments 0 .. 2 = q, k, v (M = 1, RMSNorm prologue, gamma / eps
 // set); t: caches, output, step-state block (rope_cur), head counts, max_seq; tickets: int32 [n_heads], zero before and after

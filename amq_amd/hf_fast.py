@@ -33,6 +33,12 @@ pad keys, so each row decodes as if it were alone; here each row is stored compa
 call returns ``cat([input_ids, new], 1)`` with the caller's left-padded ids untouched, as HF does.  Greedy fixed-length calls always; sampled and
 open-ended ones with ``sampling=True`` as well.
 
+With ``convert_model_to_hip(model, lookup=True)`` (opt-in as well) ``generate(ids, prompt_lookup_num_tokens=k, max_matching_ngram_size=g,
+do_sample=False, num_beams=1, ...)`` for ONE sequence, 1 <= k <= 7 and 1 <= g <= 4 (HF's default 2 when absent) runs prompt-lookup speculative decoding
+on the runner (``QuantLlama(lookup=k, ngram_max=g)``, cached under ``("lookup", k)``; g is one word of its device block): every step verifies k continuations guessed from the
+sequence's own history in one pass of the weights.  The tokens are the greedy decode's whatever is guessed; the guesses follow the MOST RECENT earlier
+occurrence of the last g .. 1 tokens (HF takes the earliest: only the acceptance rate differs).  ``lookup_request`` is the routing predicate.
+
 Anything else -- sampling and open-ended calls without that flag, a padded mask without ``padded=True``, right padding, an all-zero mask row, ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``, beams, an attention mask with holes, ``past_key_values``, ``labels``, ``inputs_embeds``, hidden-state / attention outputs,
 stopping criteria, streamers, more than 8 sequences, a call without ``start_pos`` -- falls through to the model's original ``forward`` / ``generate``
 (HF's own, over the fused modules).  ``state_dict`` / ``deepcopy`` / ``.to()`` are untouched: the runners live outside the module, keyed weakly by it.
@@ -57,6 +63,32 @@ _GC_PROCESSORS = ("repetition_penalty", "encoder_repetition_penalty", "no_repeat
 # ... and the warpers the runner's sampled tail does not apply (temperature, top_k and top_p it does)
 _GC_WARPERS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff", "top_h")
 MAX_BATCH = 8
+LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM = 7, 4
+# what a generate call routed to the lookup runner may carry besides the two lookup arguments
+_LOOKUP_KWARGS = ("input_ids", "max_new_tokens", "min_new_tokens", "do_sample", "num_beams", "attention_mask", "eos_token_id", "pad_token_id", "use_cache",
+                  "return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")
+
+
+def lookup_request(kwargs, batch, enabled=True):
+    """The routing predicate of prompt-lookup calls, a pure host function of the call's keyword arguments: -> (k, g) = (drafts per step, longest
+    suffix looked up) when ``generate(**kwargs)`` on ``batch`` sequences is a call the lookup runner serves, else None (HF's own generate).
+    Served: ``convert_model_to_hip(model, lookup=True)`` (``enabled``), one sequence, ``prompt_lookup_num_tokens`` = 1 .. 7 (an int),
+    ``max_matching_ngram_size`` = 1 .. 4 (HF's default 2 when absent or None), greedy (``do_sample`` false), one beam, and no argument the
+    runner does not know."""
+    if not enabled or batch != 1:
+        return None
+    k = kwargs.get("prompt_lookup_num_tokens")
+    g = kwargs.get("max_matching_ngram_size")
+    g = 2 if g is None else g
+    if isinstance(k, bool) or isinstance(g, bool) or not isinstance(k, int) or not isinstance(g, int):
+        return None
+    if not 1 <= k <= LOOKUP_MAX_DRAFTS or not 1 <= g <= LOOKUP_MAX_NGRAM:
+        return None
+    if kwargs.get("do_sample") not in (False, None) or kwargs.get("num_beams") not in (1, None):
+        return None
+    if any(key not in _LOOKUP_KWARGS + ("prompt_lookup_num_tokens", "max_matching_ngram_size") for key in kwargs):
+        return None
+    return k, g
 
 
 def _bucket(n, limit):
@@ -64,6 +96,23 @@ def _bucket(n, limit):
         if n <= b:
             return min(b, max(limit, n))
     return n
+
+
+def _lookup_runner(model, need, k, g):
+    """the lookup runner for ``k`` drafts per step with room for ``need`` positions (every call starts with a prompt pass: a rebuilt one carries
+    nothing over), looking up suffixes of up to ``g`` tokens -- one word of the runner's device block, so every g shares the runner of its k.
+    None when ``need`` (prompt + new tokens + the k draft rows) passes the model's max_position_embeddings: the caller falls through to HF."""
+    from .llama import QuantLlama
+    per = _RUNNERS.setdefault(model, {})
+    key = ("lookup", k)
+    r = per.get(key)
+    limit = int(getattr(model.config, "max_position_embeddings", 1 << 30) or (1 << 30))
+    if need > limit:
+        return None
+    if r is None or r.max_seq < need or not _same_weights(r, model):
+        r = per[key] = QuantLlama.from_hf(model, max_seq=_bucket(need, limit), lookup=k, ngram_max=g)
+    r.set_ngram_max(g)
+    return r
 
 
 def _runner(model, batch, need, ragged=False):
@@ -186,6 +235,15 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     ids = inputs if inputs is not None else kw.pop("input_ids", None)
     if inputs is not None and "input_ids" in kw:
         return fall()
+    look = None
+    if "prompt_lookup_num_tokens" in kw or "max_matching_ngram_size" in kw:
+        if kw.get("prompt_lookup_num_tokens") is None:
+            return fall()
+        look = lookup_request(kwargs, ids.shape[0] if _plain_ids(ids) else 0, self.__dict__.get("_amq_lookup", False))
+        if look is None:
+            return fall()
+        kw.pop("prompt_lookup_num_tokens", None)
+        kw.pop("max_matching_ngram_size", None)
     gc = getattr(self, "generation_config", None)
     sampling = self.__dict__.get("_amq_sampling", False)       # convert_model_to_hip(model, sampling=True): sampled and open-ended calls served too
     padded = self.__dict__.get("_amq_padded", False)           # convert_model_to_hip(model, padded=True): left-padded batches served too
@@ -212,7 +270,7 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     eos = [] if eos is None else ([int(e) for e in eos] if isinstance(eos, (list, tuple)) else [int(eos)])
     fixed = nmin == n
     if (kw or any(o is not None and (not hasattr(o, "__len__") or len(o)) for o in others) or synced_gpus or not one_beam or n is None
-            or ((do_sample or not fixed) and not sampling)
+            or ((do_sample or not fixed) and not sampling and look is None)
             or not _plain_ids(ids) or not ids.is_cuda or int(n) < 1 or len(eos) > 8):
         return fall()
     compact = None                                              # (right-padded ids, lengths) of a left-padded batch
@@ -230,6 +288,20 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
         return fall()                                           # (HF raises its own error for these)
     if nmin > n or (not fixed and pad is not None and not 0 <= int(pad) < int(self.config.vocab_size)):
         return fall()
+    if look is not None and do_sample:                          # (the model's generation_config samples: HF's own generate)
+        return fall()
+    if look is not None:
+        # prompt-lookup speculative decoding: one sequence, greedy; fixed length (the EOS ids never chosen, as above) or up to the first EOS id
+        if compact is not None:
+            return fall()
+        r = _lookup_runner(self, S + n + look[0], *look)
+        if r is None:                                           # (the draft rows would pass max_position_embeddings: HF serves the call)
+            return fall()
+        if tuple(eos if fixed else ()) != getattr(r, "_suppressed", ()):
+            r.set_suppressed(eos if fixed else ())
+        r.set_eos(() if fixed else eos)
+        new = r.generate(ids[0], n, stop_at_eos=not fixed, min_new_tokens=nmin)
+        return torch.cat([ids, new.view(1, -1).to(ids.dtype)], dim=1)
     r = _runner(self, B, S + n, ragged=compact is not None)
     if compact is not None:                                     # each row from cache row 0 at a position of its own; the caller's ids come back untouched
         prompt, gkw = compact[0], dict(lengths=compact[1].tolist())
@@ -261,18 +333,20 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     return torch.cat([ids, new.view(B, -1).to(ids.dtype)], dim=1)
 
 
-def convert_model_to_hip(model, sampling=False, padded=False):
+def convert_model_to_hip(model, sampling=False, padded=False, lookup=False):
     """convert_model_to_ft(model) + replace_generate_functions() (ftllama_modeling.py:569-580, ftllama_generate.py:613-622) for the HIP backend:
     call it on the model ``prepare_for_inference(model, backend='hip')`` returned (a Llama-family ``*ForCausalLM`` whose decoder linears are
     HIPQuantLinear modules on one GPU).  Patches THIS instance's ``forward`` and ``generate`` (see the module docstring); idempotent; returns the
     model.  ``sampling=True`` also routes ``generate(do_sample=True, temperature / top_k / top_p)`` and open-ended calls (EOS stop) to the runner;
     ``padded=True`` also routes ``generate`` calls whose ``attention_mask`` is LEFT padding (``padding_side="left"``) to a runner that decodes every
-    row at a position of its own.  Calling it again on a converted model only updates the two flags.  ``revert_model_to_hf(model)`` undoes it."""
+    row at a position of its own; ``lookup=True`` also routes ``generate(prompt_lookup_num_tokens=k, ...)`` calls for one sequence to a
+    prompt-lookup speculative runner (``lookup_request``).  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
     if "_amq_orig_forward" in model.__dict__:
         model.__dict__["_amq_sampling"] = bool(sampling)
         model.__dict__["_amq_padded"] = bool(padded)
+        model.__dict__["_amq_lookup"] = bool(lookup)
         return model
     from .llama import QuantLlama
     QuantLlama.check_hf(model)                               # refuse now, with the reason, what the runner cannot serve
@@ -280,6 +354,7 @@ def convert_model_to_hip(model, sampling=False, padded=False):
     model.__dict__["_amq_orig_generate"] = model.generate
     model.__dict__["_amq_sampling"] = bool(sampling)
     model.__dict__["_amq_padded"] = bool(padded)
+    model.__dict__["_amq_lookup"] = bool(lookup)
     model.forward = types.MethodType(_fast_forward, model)
     model.generate = types.MethodType(_fast_generate, model)
     return model
@@ -292,6 +367,7 @@ def revert_model_to_hf(model):
             model.__dict__.pop("_amq_orig_" + name)
     model.__dict__.pop("_amq_sampling", None)
     model.__dict__.pop("_amq_padded", None)
+    model.__dict__.pop("_amq_lookup", None)
     _RUNNERS.pop(model, None)
     return model
 

@@ -122,7 +122,7 @@ class QuantLlama:
     fine = False                # any layer with groups of 64 / 32 (set by __init__)
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
-                 hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False):
+                 hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2):
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
@@ -134,6 +134,10 @@ class QuantLlama:
         ragged: every sequence keeps a position of its own (prompts of unequal length: ``prefill(ids, lengths=...)``): one step-state block per
         sequence, the per-sequence forms of the attention / tail / set_token launches.  False: ONE position for the batch -- the object, graphs and
         bits the runner has always had.
+        lookup: D = 1 .. 7 -- prompt-lookup speculative decoding (greedy, batch 1): every step runs R = D + 1 rows of the ONE sequence, the current token
+        and D continuations guessed from the sequence's own history (the most recent earlier occurrence of its last ``ngram_max`` .. 1 tokens), verifies
+        them in one pass of the weights and emits 1 + (accepted drafts) tokens: ``generate`` / ``verify_step`` / ``lookup_stats``.  The output is a
+        greedy decode whatever is proposed.  0: off -- the object, graphs and bits the runner has always had.
         rope: (inv_freq fp32 [64], attention_scaling) of the rotary embedding when it is not the plain ``rope_theta`` form (from_hf hands over
         the HF module's own; otherwise derived from config["rope_scaling"]: Llama-3.1's "llama3")."""
         if isinstance(config, str):
@@ -142,6 +146,22 @@ class QuantLlama:
             raise ValueError("batch must be 1..8")
         self.B = int(batch)
         self.ragged = bool(ragged)
+        self.lookup = int(lookup or 0)
+        if self.lookup:
+            if not 1 <= self.lookup <= ops.LOOKUP_MAX_ROWS - 1:
+                raise ValueError(f"lookup: 1..{ops.LOOKUP_MAX_ROWS - 1} drafts per step (the 2 .. 8-row launches), got {lookup}")
+            if not 1 <= int(ngram_max) <= 4:
+                raise ValueError(f"ngram_max must be 1..4, got {ngram_max}")
+            if self.B != 1:
+                raise ValueError("lookup: the rows of a step are the drafts of ONE sequence (batch 1); batches are not served")
+            if self.ragged:
+                raise ValueError("lookup: a ragged runner's step-state blocks are sequences, a lookup runner's are the rows of one sequence: not offered with ragged=True")
+            if engine:
+                raise ValueError("lookup: the decode engine runs one row per launch; a verify step runs 2 .. 8")
+            if self.FUSE_QKV_ATTN:
+                raise ValueError("lookup: the fused q/k/v + attention launch runs one row; a verify step runs 2 .. 8")
+        self.ngram_max = int(ngram_max)
+        self.R = self.lookup + 1 if self.lookup else self.B      # rows of a token step
         if self.ragged and engine:
             raise ValueError("the decode engine keeps one position (batch 1): not offered with ragged=True")
         if self.ragged and self.FUSE_QKV_ATTN:
@@ -219,7 +239,7 @@ class QuantLlama:
                                      "one grouped launch, which needs one group size per sibling set")
 
         f16 = dict(dtype=torch.float16, device=dev)
-        B = self.B
+        B = self.R
         self.x = torch.zeros(B, self.H, **f16)
         self.xn = torch.zeros(B, self.H, **f16)          # normed rows (launches of more than NORM_FUSED_ROWS rows)
         self.q = torch.zeros(B, self.H, **f16)
@@ -236,8 +256,16 @@ class QuantLlama:
         self.rope_tab = ops.rope_table(max_seq, self.theta, dev, inv_freq=self.inv_freq, scale=self.rope_scale)
         # step state: cos/sin row of self.pos + the position itself in one block (set_token / the step's tail keep it)
         # (ragged: one block per sequence -- rope_cur [B, 128], pos [B], step_err [B] -- and the prompt lengths the captured prompt pass reads)
-        self.rope_cur, self.pos, self.step_err = ops.new_step_state(dev, batch=B) if self.ragged else ops.new_step_state(dev)
+        # (lookup: one block per ROW of the step -- block j at position p + j)
+        self.rope_cur, self.pos, self.step_err = ops.new_step_state(dev, batch=B) if self.ragged or self.lookup else ops.new_step_state(dev)
         self.rope_cur.copy_(self.rope_tab.view(max_seq, 128)[0])
+        self.lookup_state = self.history = None
+        if self.lookup:
+            # the device block the verify-and-propose tail reads and keeps, and the token history (prompt + everything emitted)
+            self.lookup_state, self.history = ops.new_lookup_state(dev, self.lookup, self.ngram_max, max_seq)
+            self._row_offsets = torch.arange(self.R, dtype=torch.int32, device=dev)
+            self._tok_in = torch.zeros(self.R, dtype=torch.int64, device=dev)
+            self._prompt_len = 0
         self.lengths = torch.ones(B, dtype=torch.int64, device=dev) if self.ragged else None
         self.graph = None
         self.host_pos = 0          # host mirror of self.pos (decode_step refuses to run past the cache without a device sync); ragged: of the LARGEST position
@@ -254,19 +282,19 @@ class QuantLlama:
         # down_proj's launch: the GEMV with the fused SiLU*mul prologue while the rows' x fits LDS whole; past that (7B: 7 - 8 rows of 11008) one
         # silu_mul launch + the GEMV without a prologue, x staged in two K phases (fusing the prologue there would make every workgroup take in gate
         # AND up -- 352 KB per CU at 8 rows: 23.9 us against 4.9 + ~11); past that too, the few-row MFMA kernel
-        self._down_rows_fit = self.B <= min(ops.gemv_max_rows(self.I, plain=not self.fine), self.DOWN_FUSED_ROWS)
-        self._down_rows_phased = not self._down_rows_fit and self.B <= ops.gemv_max_rows(self.I, plain=not self.fine, norm=False)
-        self.can_fuse_qkv_attn = (self.B == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
+        self._down_rows_fit = self.R <= min(ops.gemv_max_rows(self.I, plain=not self.fine), self.DOWN_FUSED_ROWS)
+        self._down_rows_phased = not self._down_rows_fit and self.R <= ops.gemv_max_rows(self.I, plain=not self.fine, norm=False)
+        self.can_fuse_qkv_attn = (self.R == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
                                   and not self.ragged)
         self.fuse_qkv_attn = self.FUSE_QKV_ATTN and self.can_fuse_qkv_attn
         self._tickets = torch.zeros(max(self.nh, 64), dtype=torch.int32, device=dev)
         # 2 .. 8 sequences: the RMSNorms ride on per-row-tile sums of squares that o_proj / down_proj leave in their epilogues (ops.gemv_grouped_sums:
         # no pass over x for the statistic -- which a fused prologue repeats in every workgroup --, no rmsnorm launch); the first norm of block 0 (its x
         # comes from the embedding) keeps the fused prologue (2 .. 4 rows) / a launch of its own (5 .. 8)
-        self._norm_sums = (self.NORM_SUMS and 2 <= self.B <= 8 and not self.fine and 2048 <= self.H <= 8192 and self.I >= 2048
-                           and self.B <= ops.gemv_max_rows(self.H, plain=True))
-        self.ss = torch.zeros(self.B, self.H // 16, dtype=torch.float32, device=dev) if self._norm_sums else None
-        eligible = self.B == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias and not self.ragged
+        self._norm_sums = (self.NORM_SUMS and 2 <= self.R <= 8 and not self.fine and 2048 <= self.H <= 8192 and self.I >= 2048
+                           and self.R <= ops.gemv_max_rows(self.H, plain=True))
+        self.ss = torch.zeros(self.R, self.H // 16, dtype=torch.float32, device=dev) if self._norm_sums else None
+        eligible = self.R == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias and not self.ragged
         if engine and not eligible:
             raise ValueError("the decode engine needs batch 1 and max_seq <= %d" % self.ENGINE_MAX_SEQ)
         self.engine = None
@@ -320,7 +348,7 @@ class QuantLlama:
         return cfg, rope
 
     @classmethod
-    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False):
+    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2):
         """The hipGraph runner over a SWAPPED HF causal LM of the Llama family (``HF_MODEL_TYPES``: Llama 2 / 3.x, Mistral, Qwen2.5) -- what
         ``prepare_for_inference(model, backend="hip")`` (or the reference's deepcopy + setattr assembly of a mixed-precision model,
         amq_speed_benchmark.py:231-256) leaves behind.  The runner shares the modules' native weight buffers and biases, the embedding, lm_head and
@@ -348,7 +376,7 @@ class QuantLlama:
         dense = {"embed": f16(model.model.embed_tokens.weight), "lm_head": f16(model.lm_head.weight), "norm": f16(model.model.norm.weight),
                  "ln1": [f16(l.input_layernorm.weight) for l in layers], "ln2": [f16(l.post_attention_layernorm.weight) for l in layers]}
         return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
-                   ragged=ragged)
+                   ragged=ragged, lookup=lookup, ngram_max=ngram_max)
 
     # ----------------------------------------------------------------- sizes
     def linear_bytes_per_token(self):
@@ -381,12 +409,15 @@ class QuantLlama:
                 qkv = [blk["self_attn.q_proj"].seg(self.q), blk["self_attn.k_proj"].seg(self.k), blk["self_attn.v_proj"].seg(self.v)]
                 if self._norm_sums and have_sums:
                     ops.gemv_grouped_sums(self.x, qkv, H, gamma=blk["ln1"], eps=self.eps, sums_in=self.ss)
-                elif self.B > self.NORM_FUSED_ROWS:
+                elif self.R > self.NORM_FUSED_ROWS:
                     ops.gemv_grouped(ops.rmsnorm(self.x, blk["ln1"], self.eps, out=self.xn), qkv, H)
                 else:
                     ops.gemv_grouped(self.x, qkv, H, prologue=ops.PRO_RMSNORM, gamma=blk["ln1"], eps=self.eps)
-                ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
-                                cur=self.rope_cur)
+                if self.lookup:                 # the R rows are consecutive positions of the one sequence: causal among them, one cache slice
+                    ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv)
+                else:
+                    ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
+                                    cur=self.rope_cur)
             if self._norm_sums:
                 ops.gemv_grouped_sums(self.att, [blk["self_attn.o_proj"].seg(self.x, residual=self.x)], H, sums_out=self.ss)
                 ops.gemv_grouped_sums(self.x, [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)], H,
@@ -395,7 +426,7 @@ class QuantLlama:
                 ops.gemv_grouped(self.att, [blk["self_attn.o_proj"].seg(self.x, residual=self.x)], H)
             if self._norm_sums:
                 pass                            # (gate / up were launched above, behind o_proj's sums)
-            elif self.B > self.NORM_FUSED_ROWS:
+            elif self.R > self.NORM_FUSED_ROWS:
                 ops.gemv_grouped(ops.rmsnorm(self.x, blk["ln2"], self.eps, out=self.xn), [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)], H)
             else:
                 ops.gemv_grouped(self.x, [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)], H,
@@ -413,13 +444,18 @@ class QuantLlama:
                 d = blk["mlp.down_proj"]
                 ops.gemm(ops.silu_mul(self.gate, self.up, out=self.gate), d.qn, d.mn, d.bits, d.mode, d.N, d.K, bias=d.bias, residual=self.x, out=self.x)
                 have_sums = False
-        ops.gemv_f16w(self.x.reshape(-1) if self.B == 1 else self.x, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
+        ops.gemv_f16w(self.x.reshape(-1) if self.R == 1 else self.x, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
         self._tail(sampled)
 
     def _tail(self, sampled):
         """the end of a token step: the next token (arg-max, or a draw with the device block's parameters + EOS bookkeeping), pos += 1,
         x = embed[token], rope_cur = cos/sin row of the new position (per sequence; the position is shared)"""
-        if sampled:
+        if self.lookup:
+            if sampled:
+                raise ValueError("lookup: speculative decoding here is greedy (the sampled tail draws one token per row)")
+            ops.decode_tail_lookup(self.logits, self.embed, self.token, self.pos, self.x, self.lookup_state, self.history, self.rope_tab, self.rope_cur,
+                                   suppress=self.suppress)
+        elif sampled:
             ops.decode_tail_sample(self.logits, self.embed, self.token, self.pos, self.x, self.sample_state, table=self.rope_tab, cur=self.rope_cur,
                                    suppress=self.suppress)
         else:
@@ -428,6 +464,7 @@ class QuantLlama:
     # ------------------------------------------------------------- sampling
     sampling, sample_state, sample_graph, eos, pad_id = None, None, None, (), 0      # (class defaults: greedy)
     ragged, lengths = False, None       # (class defaults: one position for the whole batch)
+    lookup, lookup_state, history = 0, None, None      # (class defaults: one row per sequence and step)
     EOS_POLL_STEPS = 16         # generate(stop_at_eos=True) reads the unfinished count every this many steps: fewer = less work after the last EOS, more host syncs
 
     def _write_sampling_state(self):
@@ -446,6 +483,8 @@ class QuantLlama:
         if temperature is None:
             self.sampling = None
             return
+        if self.lookup:
+            raise ValueError("lookup: speculative decoding here is greedy; sampled speculative decoding (rejection sampling) is not served")
         self.sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed))
         self._write_sampling_state()
 
@@ -502,7 +541,10 @@ class QuantLlama:
         pos = int(pos)
         if not 0 <= pos <= self.max_seq:
             raise ValueError(f"position {pos} outside the KV cache (max_seq={self.max_seq})")
-        self.pos.fill_(pos)
+        if self.lookup:                         # block j = row j of the step: position pos + j (saturating, as the tail leaves them)
+            self.pos.copy_((self._row_offsets + pos).clamp_(max=self.max_seq))
+        else:
+            self.pos.fill_(pos)
         self.host_pos = pos
 
     def check(self):
@@ -522,6 +564,8 @@ class QuantLlama:
     def set_token(self, token):
         """make ``token`` (int or 1-element tensor) the input of the next decode step; also re-derives what the step
         reads besides the token (embedding row, cos/sin row of the current position) -- set_pos() first"""
+        if self.lookup:
+            return self._lookup_set_token(token)
         if isinstance(token, torch.Tensor) and token.is_cuda and token.dtype is torch.int64 and token.numel() in (1, self.B) and token.is_contiguous():
             # one launch instead of five framework ops (a caller that feeds every token itself pays this per token: hf_fast's forward)
             return ops.set_token(token, self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur)
@@ -544,22 +588,33 @@ class QuantLlama:
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream(self.dev))
         saved = (self.token.clone(), self.pos.clone())
+        if self.lookup:                         # (the warm-up and the recorded step advance the counters and the drafts: put back below)
+            saved = saved + (self.lookup_state.clone(),)
         saved_state = self.sample_state.clone() if sampled else None       # (the warm-up and the capture's own launch-free recording must not consume a draw)
         with torch.cuda.stream(side):
             self._step(True) if sampled else self._step()                # warm-up outside capture (allocator, lazy init)
             side.synchronize()
-            self.pos.copy_(saved[1]); self.set_token(saved[0])
+            self._restore_step_inputs(saved)
             g = torch.cuda.CUDAGraph()
             with _no_gc(), torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
                 self._step(True) if sampled else self._step()
         torch.cuda.current_stream(self.dev).wait_stream(side)
         torch.cuda.synchronize(self.dev)
-        self.pos.copy_(saved[1]); self.set_token(saved[0])
+        self._restore_step_inputs(saved)
         if sampled:
             self.sample_state.copy_(saved_state)
             self.sample_graph = g
         else:
             self.graph = g
+
+    def _restore_step_inputs(self, saved):
+        """put back what a step consumed (capture's warm-up): positions, tokens and what derives from them (lookup: the state block and the draft rows too)"""
+        self.pos.copy_(saved[1])
+        if self.lookup:
+            self.lookup_state.copy_(saved[2])
+            ops.set_token(saved[0], self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur)
+        else:
+            self.set_token(saved[0])
 
     def decode_step(self, use_graph=True, sampled=None):
         # the step appends cache row host_pos: refuse on the host (the kernels also guard the device-side position:
@@ -568,9 +623,11 @@ class QuantLlama:
             raise ValueError(f"decode step at position {self.host_pos} does not fit the KV cache (max_seq={self.max_seq})")
         if sampled is None:
             sampled = self._sampled_tail()
+        if self.lookup and self.host_pos + self.lookup >= self.max_seq:
+            raise ValueError(f"a verify step at position {self.host_pos} with {self.lookup} drafts does not fit the KV cache (max_seq={self.max_seq})")
         if use_graph and (self.sample_graph if sampled else self.graph) is None:
             self.capture(sampled)
-        self.host_pos += 1
+        self.host_pos += self.R if self.lookup else 1       # (lookup: an upper bound -- a step advances by 1 + accepted drafts; lookup_sync() reads the exact value)
         if use_graph:
             (self.sample_graph if sampled else self.graph).replay()
         else:
@@ -605,6 +662,10 @@ class QuantLlama:
         start_pos = int(start_pos)
         if start_pos < 0 or start_pos + S > self.max_seq:
             raise ValueError("prompt longer than the KV cache")
+        if self.lookup and start_pos != 0:
+            raise ValueError("lookup: the history holds the whole sequence -- a prompt pass starts at position 0")
+        if self.lookup:
+            self._prompt_len = S
         if lengths is not None and not self.ragged:
             raise ValueError("lengths needs a runner built with ragged=True (this one keeps one position for the whole batch)")
         longest = S
@@ -645,6 +706,138 @@ class QuantLlama:
         if self._sampled_tail():
             self._first_token()                 # (outside the prompt graph, which ends in the arg-max: one graph per prompt length serves both)
         return self.logits
+
+    # ------------------------------------------------- prompt-lookup speculative decoding
+    def _lookup_set_token(self, token):
+        """row 0 = ``token``, no drafts (-1: rows 1 .. D run a placeholder and are never accepted); the counters are left alone"""
+        if isinstance(token, torch.Tensor):
+            self._tok_in.zero_()
+            self._tok_in[:1].copy_(token.reshape(-1)[:1])
+        else:
+            self._tok_in.zero_()
+            self._tok_in[0] = int(token)
+        self.lookup_state[ops.LOOKUP_DRAFT:ops.LOOKUP_DRAFT + 8].fill_(-1)
+        ops.set_token(self._tok_in, self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur)
+
+    def _lookup_prefill_finish(self, x, S):
+        """the end of a lookup runner's prompt pass (all device work: part of the captured prompt graph): the prompt goes into the history with a
+        device copy, and the verify-and-propose tail itself -- run on the last prompt row's logits as row 0 of a step at position S - 1 without
+        drafts -- emits the first token, proposes the first drafts and leaves the step inputs of position S"""
+        lg = self.logits.view(self.R, self.vocab)
+        if self.all_logits:
+            self.logits_rows = self._logits_of_rows(x, 1, S, lg[0])
+        else:
+            ops.gemv_f16w(x[S - 1].contiguous(), self.lm_head, gamma=self.norm, eps=self.eps, out=lg[0])
+        self.history[:S].copy_(self._lookup_ids.reshape(-1))
+        st = self.lookup_state
+        st[ops.LOOKUP_COUNT:ops.LOOKUP_TICKET + 1].zero_()                  # count, steps, accepted, ticket
+        st[ops.LOOKUP_COUNT].fill_(S)
+        st[ops.LOOKUP_DRAFT:ops.LOOKUP_DRAFT + 8].fill_(-1)
+        self.set_pos(S - 1)
+        self._tail(False)
+        st[ops.LOOKUP_STEPS].zero_()                                        # (the prompt pass is not a verify step)
+        self.host_pos = S
+        return self.logits
+
+    def set_lookup_mode(self, external):
+        """who proposes the drafts: False = the tail looks them up in the history; True = the caller (``verify_step``) -- the tail then leaves -1 drafts.
+        One word of the device block: nothing is re-captured."""
+        self.lookup_state[ops.LOOKUP_MODE].fill_(1 if external else 0)
+
+    def set_ngram_max(self, ngram_max):
+        """the longest suffix the tail looks up (1 .. 4): one word of the device block, read on every launch -- nothing is re-captured"""
+        if not self.lookup:
+            raise ValueError("set_ngram_max needs a runner built with lookup=D")
+        if not 1 <= int(ngram_max) <= 4:
+            raise ValueError(f"ngram_max must be 1..4, got {ngram_max}")
+        if int(ngram_max) != self.ngram_max:
+            self.ngram_max = int(ngram_max)
+            self.lookup_state[ops.LOOKUP_NGRAM].fill_(self.ngram_max)
+
+    def verify_step(self, drafts, use_graph=True):
+        """one verify step with the caller's drafts: a tensor (or list) of D token ids for rows 1 .. D, -1 = none.  The runner must be in external mode
+        (``set_lookup_mode(True)``) before the step that precedes this one, or the tail's own proposals are overwritten here all the same."""
+        if not self.lookup:
+            raise ValueError("verify_step needs a runner built with lookup=D")
+        d = torch.as_tensor(drafts, dtype=torch.int64).reshape(-1).to(self.dev)
+        if d.numel() != self.lookup:
+            raise ValueError(f"expected {self.lookup} draft ids (-1 = none), got {d.numel()}")
+        self._tok_in[:1].copy_(self.token[:1])
+        self._tok_in[1:].copy_(d.clamp(0, self.vocab - 1))
+        ops.set_token(self._tok_in, self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur)
+        self.lookup_state[ops.LOOKUP_DRAFT + 1:ops.LOOKUP_DRAFT + 1 + self.lookup].copy_(d.to(torch.int32))     # unclamped: what the comparison sees
+        self.decode_step(use_graph)
+
+    def lookup_sync(self):
+        """(tokens in the history, steps taken) read from the device block (synchronises); makes the host's position mirror exact again"""
+        c = self.lookup_state[ops.LOOKUP_COUNT:ops.LOOKUP_STEPS + 1].tolist()
+        self.host_pos = max(0, c[0] - 1)
+        return c[0], c[1]
+
+    def lookup_stats(self):
+        """dict(steps, tokens, mean_accepted): verify steps since the last prompt pass, tokens they emitted, accepted drafts per step"""
+        count, steps = self.lookup_sync()
+        tokens = count - self._prompt_len - 1 if steps else 0
+        return dict(steps=steps, tokens=tokens, mean_accepted=(tokens / steps - 1.0) if steps else 0.0)
+
+    def lookup_tokens(self):
+        """everything emitted since the last prompt pass (its first token included), int64 device tensor"""
+        count, _ = self.lookup_sync()
+        return self.history[self._prompt_len:count].to(torch.int64)
+
+    def _lookup_generate(self, ids, gen_len, use_graph, stop_at_eos, min_new_tokens):
+        S, D = ids.shape[-1], self.lookup
+        if S + gen_len + D > self.max_seq:
+            raise ValueError(f"prompt ({S}) + {gen_len} tokens + {D} draft rows do not fit the KV cache (max_seq={self.max_seq})")
+        if self.sampling is not None:
+            raise ValueError("lookup: speculative decoding here is greedy; call set_sampling(None)")
+        suppressed = getattr(self, "_suppressed", ())
+        eos = tuple(self.eos) if stop_at_eos else ()
+        hold = bool(eos) and min_new_tokens > 0
+        try:
+            if hold:
+                self.set_suppressed(tuple(suppressed) + tuple(e for e in eos if e not in suppressed))
+            self.set_lookup_mode(False)
+            self.prefill(ids, use_graph=use_graph)
+            count, emitted = S + 1, 1
+            while emitted < gen_len:
+                if hold and emitted >= min_new_tokens:
+                    self.set_suppressed(suppressed)
+                    hold = False
+                if hold and min_new_tokens - emitted < self.R:
+                    # the EOS ids are held back for exactly the first min_new_tokens tokens: a step that could cross that line runs without drafts
+                    # (one token)
+                    self._lookup_set_token(self.token[:1])
+                    self.decode_step(use_graph)
+                else:
+                    # a burst: at most what is still wanted (a step emits at least one token), while the EOS ids are held back only steps that stay
+                    # inside the first min_new_tokens however much is accepted, and never so far that the rows of a fully accepted step would
+                    # leave the cache
+                    k = min(self.EOS_POLL_STEPS, gen_len - emitted, max(1, (self.max_seq - D - self.host_pos) // self.R))
+                    if hold:
+                        k = min(k, (min_new_tokens - emitted) // self.R)
+                    for _ in range(k):
+                        self.decode_step(use_graph)
+                count, _ = self.lookup_sync()
+                emitted = count - S
+                if eos and self._first_eos(self.history[S:count], min_new_tokens) is not None:
+                    break
+            out = self.history[S:min(count, S + gen_len)].to(torch.int64)
+            if eos:
+                cut = self._first_eos(out, min_new_tokens)
+                if cut is not None:
+                    out = out[:cut + 1]
+            return out
+        finally:
+            if getattr(self, "_suppressed", ()) != suppressed:
+                self.set_suppressed(suppressed)
+
+    def _first_eos(self, toks, skip=0):
+        """index of the first EOS id in ``toks`` at or behind index ``skip`` (None: none)"""
+        if not self.eos or toks.numel() <= skip:
+            return None
+        hit = torch.isin(toks[skip:], torch.tensor(self.eos, dtype=toks.dtype, device=toks.device)).nonzero()
+        return None if hit.numel() == 0 else int(hit[0].item()) + skip
 
     def _ids_rows(self, ids):
         """prompt ids as [batch, S] on the device (a 1-D prompt is the batch-1 form)"""
@@ -748,6 +941,8 @@ class QuantLlama:
         if start_pos + S > self.max_seq:
             raise ValueError("prompt longer than the KV cache")
         H, nh, nkv = self.H, self.nh, self.nkv
+        if self.lookup:
+            self._lookup_ids = ids.to(self.dev)                    # (what _lookup_prefill_finish copies into the history)
         x = self.embed.index_select(0, ids.to(self.dev))           # [S, H]; the residual stream, updated in place
 
         def lin(l, inp, residual=None):
@@ -857,6 +1052,8 @@ class QuantLlama:
         if b is not None:                       # one sequence of a batch: its logits row; the caller sets position and tokens
             ops.gemv_f16w(last, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits[b])
             return self.logits[b]
+        if self.lookup:
+            return self._lookup_prefill_finish(x, S)
         if self.all_logits:
             self.logits_rows = self._logits_of_rows(x, 1, S, self.logits)
         else:
@@ -896,6 +1093,9 @@ class QuantLlama:
     def reset(self):
         self.set_pos(0)
         self.set_token(0)
+        if self.lookup:                         # an empty history; the counters start over
+            self.lookup_state[ops.LOOKUP_COUNT:ops.LOOKUP_TICKET + 1].zero_()
+            self._prompt_len = 0
 
     def generate(self, ids, gen_len, use_graph=True, stop_at_eos=False, min_new_tokens=0, lengths=None):
         """prefill + gen_len tokens (min_new_tokens = max_new_tokens = gen_len, amq/utils/speed.py:34-39): greedy, or sampled after
@@ -903,6 +1103,8 @@ class QuantLlama:
         padded with the pad id from there on, and the loop ends once every sequence has (polled every EOS_POLL_STEPS steps): returns [B, n] with
         n = the longest sequence's length, as HF does; the EOS ids stay suppressed for the first ``min_new_tokens`` tokens.
         ``lengths`` (ragged runners): see :meth:`prefill`; the longest prompt + gen_len must fit the cache."""
+        if self.lookup:
+            return self._lookup_generate(ids, gen_len, use_graph, stop_at_eos, min_new_tokens)
         S = ids.shape[-1]
         if lengths is not None:
             if not self.ragged:
@@ -964,14 +1166,16 @@ class DenseLlama(QuantLlama):
     amq_speed_benchmark.py:171-197): plain library GEMMs (torch / hipBLASLt) for the seven
     linears, the same RMSNorm / attention / lm_head kernels around them."""
 
-    def __init__(self, config, device="cuda:0", max_seq=256, seed=0, batch=1, ragged=False):
+    def __init__(self, config, device="cuda:0", max_seq=256, seed=0, batch=1, ragged=False, lookup=0):
+        if lookup:
+            raise ValueError("the fp16 baseline runs one row per sequence: lookup= is served by QuantLlama")
         if ragged:
             raise ValueError("the fp16 baseline keeps one position for the whole batch: ragged=True is served by QuantLlama")
         if isinstance(config, str):
             config = MODEL_CONFIGS[config]
         if not 1 <= int(batch) <= 8:
             raise ValueError("batch must be 1..8")
-        self.B = int(batch)
+        self.B = self.R = int(batch)
         self._dense_init(config, device, max_seq, seed)
 
     def _dense_init(self, config, device, max_seq, seed):

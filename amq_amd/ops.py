@@ -1189,6 +1189,85 @@ def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_the
     return out
 
 
+# ---- prompt-lookup speculative decoding (include/amq_hip.h: "prompt-lookup speculative decoding"; amq_decode.hip ROWS instantiations, amq_lookup.hip)
+LOOKUP_STATE_WORDS = _lib.LOOKUP_STATE_WORDS
+LOOKUP_DRAFTS, LOOKUP_NGRAM, LOOKUP_MODE, LOOKUP_COUNT, LOOKUP_STEPS, LOOKUP_ACCEPTED, LOOKUP_TICKET, LOOKUP_DRAFT, LOOKUP_ARGMAX = 0, 1, 2, 3, 4, 5, 6, 8, 16
+LOOKUP_MAX_ROWS = 8
+
+
+def new_lookup_state(device, drafts, ngram_max=2, history_cap=0):
+    """-> (state int32 [32], history int32 [history_cap]): the device block amq_decode_tail_lookup_f16 reads and keeps (word layout: include/amq_hip.h)
+    and the token history, for ``drafts`` = 1 .. 7 guessed tokens per step and suffixes of up to ``ngram_max`` = 1 .. 4 tokens; no drafts yet (-1)."""
+    drafts, ngram_max, history_cap = int(drafts), int(ngram_max), int(history_cap)
+    if not 1 <= drafts <= LOOKUP_MAX_ROWS - 1:
+        raise ValueError(f"drafts must be 1..{LOOKUP_MAX_ROWS - 1} (got {drafts})")
+    if not 1 <= ngram_max <= 4:
+        raise ValueError(f"ngram_max must be 1..4 (got {ngram_max})")
+    if not 1 <= history_cap <= 1 << 24:
+        raise ValueError(f"history_cap must be 1..2^24 (got {history_cap})")
+    host = torch.zeros(LOOKUP_STATE_WORDS, dtype=torch.int32)
+    host[LOOKUP_DRAFTS], host[LOOKUP_NGRAM] = drafts, ngram_max
+    host[LOOKUP_DRAFT:LOOKUP_DRAFT + 8] = -1
+    return host.to(device), torch.zeros(history_cap, dtype=torch.int32, device=device)
+
+
+def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads, n_splits=0):
+    """``rows`` = 2 .. 8 consecutive positions of ONE sequence (amq_attn_decode_rows_f16): q / out [rows, n_heads*128], k / v [rows, n_kv_heads*128],
+    caches [1, n_kv_heads, max_seq, 128] (or 3-D); ``cur`` [rows, 128] / ``pos`` [rows]: the views of one per-sequence step state whose block j holds
+    position p + j.  Row j appends cache row p + j and attends rows 0 .. p - 1 of the cache plus this step's rows 0 .. j.
+    ``n_splits``: 0 = by cache length, 1 = the single-workgroup kernel, >= 2 the per-head split kernel."""
+    states, R = _seq_state(cur, pos)
+    if states is None:
+        raise ValueError("cur [rows, 128] / pos [rows] must be the views of one per-sequence step state (ops.new_step_state(device, batch=rows))")
+    if not 2 <= R <= LOOKUP_MAX_ROWS:
+        raise ValueError(f"rows must be 2..{LOOKUP_MAX_ROWS} (got {R})")
+    if kcache.dim() == 4 and kcache.shape[0] != 1:
+        raise ValueError("the rows of a step belong to ONE sequence: caches [1, n_kv_heads, max_seq, 128]")
+    max_seq = kcache.shape[-2]
+    if n_splits == 0:
+        n_splits = attn_decode_splits(max_seq, n_heads, R)       # (the per-head policy also for grouped-query models: they take the per-head kernels here)
+    _need(q, torch.float16, "q", R * n_heads * 128)
+    _need(k, torch.float16, "k", R * n_kv_heads * 128)
+    _need(v, torch.float16, "v", R * n_kv_heads * 128)
+    _need(kcache, torch.float16, "kcache", n_kv_heads * max_seq * 128)
+    _need(vcache, torch.float16, "vcache", n_kv_heads * max_seq * 128)
+    _need(out, torch.float16, "out", R * n_heads * 128)
+    lib = _lib.load()
+    if n_splits > 1:
+        wsb = lib.amq_attn_decode_split_workspace_bytes(R, n_heads, n_splits)
+        ws, tk = _ATTN_WS.get(q.device, wsb // 4), _ATTN_TICKETS.get(q.device, R * n_heads)
+        _lib.check(lib.amq_attn_decode_rows_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, R,
+                                                n_heads, n_kv_heads, 128, max_seq, n_splits, _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
+    else:
+        _lib.check(lib.amq_attn_decode_rows_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, R,
+                                                n_heads, n_kv_heads, 128, max_seq, 0, None, 0, None, _lib.current_stream()))
+    return out
+
+
+def decode_tail_lookup(logits, embed, token, pos, x, state, history, table, cur, suppress=None):
+    """the verify-and-propose tail of a lookup step (amq_decode_tail_lookup_f16), one launch: logits [rows, vocab], token [rows], x [rows, hidden],
+    ``cur`` / ``pos`` the per-sequence step state of the rows, ``state`` / ``history`` from :func:`new_lookup_state`."""
+    vocab, hidden = embed.shape
+    R = token.numel()
+    if not 2 <= R <= LOOKUP_MAX_ROWS:
+        raise ValueError(f"rows must be 2..{LOOKUP_MAX_ROWS} (got {R})")
+    _need(logits, torch.float16, "logits", R * vocab)
+    _need(embed, torch.float16, "embed", vocab * hidden)
+    _need(token, torch.int64, "token", R)
+    _need(x, torch.float16, "x", R * hidden)
+    _need(state, torch.int32, "lookup state", LOOKUP_STATE_WORDS)
+    _need(history, torch.int32, "history")
+    _need(table, torch.float16, "rope table")
+    if suppress is not None:
+        _need(suppress, torch.int32, "suppress", 8)
+    states, nseq = _seq_state(cur, pos)
+    if states is None or nseq != R:
+        raise ValueError(f"cur [rows, 128] / pos [rows] must be the views of one per-sequence step state of {R} blocks")
+    _lib.check(_lib.load().amq_decode_tail_lookup_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), states, _lib.ptr(x),
+                                                      _lib.ptr(table), table.numel() // 128, R, _lib.ptr(suppress), _lib.ptr(state), _lib.ptr(history),
+                                                      history.numel(), _lib.current_stream()))
+
+
 # ---------------------------------------------------------------- the device of a launch
 # Every launch goes to the CURRENT device's stream (``_lib.current_stream()``), kernel attributes and CU counts are the current device's too.  A
 # process that keeps its weights on cuda:1 while cuda:0 is current (HF device_map, no set_device) must therefore have cuda:1 made current around
@@ -1211,7 +1290,7 @@ def _on_tensor_device(fn):
 
 for _name in ("repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "decode_tail_sample", "rope_cache",
-              "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode"):
+              "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name
 

@@ -374,6 +374,48 @@ int amq_decode_tail_sample_seq_f16(const void* logits, int vocab, const void* em
 int amq_set_token_seq_f16(const long long* token_in, int n_in, const void* embed, int vocab, int hidden, long long* token, void* step_states, void* x,
                           const void* rope_table, int rope_rows, int batch, void* stream);
 
+/* ---- prompt-lookup speculative decoding (greedy, one sequence): a step over R = D + 1 consecutive positions ------------------------------
+ * Row 0 of a step is the sequence's current token at position p, rows 1 .. D are guessed continuations (drafts) at p + 1 .. p + D.  One pass of
+ * the weights over the R rows (the 2 .. 8-row GEMV routes) verifies them all; the step emits 1 + (accepted drafts) tokens and is by construction
+ * a greedy decode.  step_states: R blocks of the amq_*_seq_f16 layout, block j holding position p + j and its cos/sin row.
+ *
+ * amq_attn_decode_rows_f16: amq_attn_decode_seq_f16 for `rows` (2 .. 8) rows of ONE sequence -- q / k / v / out have `rows` rows, there is ONE cache
+ * slice [n_kv_heads, max_seq, 128].  Row j rotates with block j, appends its K / V at cache row p + j and attends cache rows 0 .. p - 1 plus this
+ * step's rows 0 .. j (causal among the rows): every workgroup rotates the earlier rows of the step itself from k / v (they are being appended by
+ * other workgroups of the same launch and are never read from the cache).  Read from a cache that already holds rows p .. p + j - 1, row j's output
+ * is amq_attn_decode_seq_f16's at position p + j bit for bit (n_splits == 0: one workgroup per (head, row); n_splits >= 1: the per-head split kernel,
+ * chunks from each row's own position, bit-identical with one active chunk; grouped-query models take the per-head kernels here).  workspace
+ * (amq_attn_decode_split_workspace_bytes(rows, ...)) and tickets [rows * n_heads] as there.  A row whose position is outside 0 .. max_seq-1 (or whose
+ * row 0 would be below 0) is a no-op for THAT row and raises ITS block's error word.  Rows of rejected drafts stay in the cache behind the new
+ * position; no step reads them before a later step overwrites them. */
+#define AMQ_LOOKUP_MAX_ROWS 8
+int amq_attn_decode_rows_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int rows,
+                             int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
+                             void* tickets, void* stream);
+/* The verify-and-propose tail, one launch.  lookup_state: a device block of AMQ_LOOKUP_STATE_WORDS int32 words, all of them read (and the counters
+ * written) on every launch, so a captured step never needs a re-capture:
+ *   word 0      D: drafts per step (1 .. 7; the launch's rows = D + 1)
+ *   word 1      ngram_max: longest suffix looked up (1 .. 4)
+ *   word 2      mode: 0 = the tail proposes the next drafts from the history; 1 = external drafts (the tail writes -1 drafts; the host fills rows
+ *               1 .. D with amq_set_token_seq_f16 over `rows` blocks and writes the unclamped ids into words 9 .. 8 + D)
+ *   word 3      tokens in `history` (prompt + everything emitted; the sequence's current token is the last one)
+ *   word 4      steps taken (incremented by every launch)
+ *   word 5      n: drafts accepted by the last step
+ *   word 6      ticket of the last-arriver protocol: zero before and after every launch
+ *   word 7      reserved (0)
+ *   words 8+j   j = 1 .. 7: the draft row j of the NEXT step runs with, unclamped (-1 = no draft: never accepted); word 8 unused
+ *   words 16+j  j = 0 .. 7: arg-max of row j of the last step
+ *   words 24..  reserved (0)
+ * a[j] = argmax(logits[j]) (first maximum; suppress_ids -- int32 [8], -1 = unused, or NULL -- left out in every row).  n = the largest value with
+ * draft[i] == a[i - 1] for all 1 <= i <= n; a[0 .. n] are appended to history (int32 [history_cap], history_cap >= rope_rows) and the counters advance.
+ * Proposal: for g = ngram_max .. 1, the MOST RECENT earlier occurrence in history of its last g tokens that is followed by at least one token; the
+ * drafts are the up to D tokens behind it, unfilled slots -1.  Then token[0] = a[n], token[j] = draft j clamped into the vocabulary, x[j] =
+ * embed[token[j]], block j's position = (block 0's position + n + 1) + j saturating at rope_rows, and its cos/sin row. */
+#define AMQ_LOOKUP_STATE_WORDS 32
+int amq_decode_tail_lookup_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
+                               const void* rope_table, int rope_rows, int rows, const int* suppress_ids, void* lookup_state, int* history,
+                               int history_cap, void* stream);
+
 /* ---- many-row (prefill) glue --------------------------------------------------------------------------
  * The reference runs these steps as framework ops between the linears of a HF Llama block
  * (transformers LlamaAttention / LlamaMLP / LlamaDecoderLayer as driven by amq/utils/speed.py:150-200); on this path
