@@ -98,50 +98,51 @@ def _bucket(n, limit):
     return n
 
 
+def _limit(model):
+    return int(getattr(model.config, "max_position_embeddings", 1 << 30) or (1 << 30))
+
+
+def _bound(model, key, need, **build):
+    """the runner kept under ``key`` with room for ``need`` positions, built on first use (``build``: from_hf's arguments) and rebuilt when a sequence
+    outgrows it or the model's weights are no longer the ones it reads (the attention launch is chosen by the cache's size, so the cache is not
+    made larger than asked for) -> (runner, the one it replaced or None)"""
+    from .llama import QuantLlama
+    per = _RUNNERS.setdefault(model, {})
+    old = per.get(key)
+    if old is not None and old.max_seq >= need and _same_weights(old, model):
+        return old, None
+    per[key] = QuantLlama.from_hf(model, max_seq=_bucket(need, _limit(model)), **build)
+    return per[key], old
+
+
 def _lookup_runner(model, need, k, g):
     """the lookup runner for ``k`` drafts per step with room for ``need`` positions (every call starts with a prompt pass: a rebuilt one carries
     nothing over), looking up suffixes of up to ``g`` tokens -- one word of the runner's device block, so every g shares the runner of its k.
     None when ``need`` (prompt + new tokens + the k draft rows) passes the model's max_position_embeddings: the caller falls through to HF."""
-    from .llama import QuantLlama
-    per = _RUNNERS.setdefault(model, {})
-    key = ("lookup", k)
-    r = per.get(key)
-    limit = int(getattr(model.config, "max_position_embeddings", 1 << 30) or (1 << 30))
-    if need > limit:
+    if need > _limit(model):
         return None
-    if r is None or r.max_seq < need or not _same_weights(r, model):
-        r = per[key] = QuantLlama.from_hf(model, max_seq=_bucket(need, limit), lookup=k, ngram_max=g)
+    r, _ = _bound(model, ("lookup", k), need, lookup=k, ngram_max=g)
     r.set_ngram_max(g)
     return r
 
 
 def _runner(model, batch, need, ragged=False):
-    """the runner for ``batch`` sequences with room for ``need`` positions (built on first use; rebuilt larger -- cache contents carried over -- when a
-    sequence outgrows it: the attention launch is chosen by the cache's size, so the cache is not made larger than asked for).  ``ragged``: the runner
+    """the runner for ``batch`` sequences with room for ``need`` positions; a rebuilt one carries the cache contents over.  ``ragged``: the runner
     with a position per sequence (left-padded generate calls), kept under a key of its own; every call on it starts with a prompt pass, so a rebuilt
     one carries nothing over."""
-    from .llama import QuantLlama
-    per = _RUNNERS.setdefault(model, {})
-    key = ("ragged", batch) if ragged else batch
-    r = per.get(key)
-    limit = int(getattr(model.config, "max_position_embeddings", 1 << 30) or (1 << 30))
-    if need > limit:
-        raise ValueError(f"{need} positions exceed the model's max_position_embeddings ({limit})")
-    if r is not None and r.max_seq >= need and _same_weights(r, model):
-        return r
-    new = QuantLlama.from_hf(model, max_seq=_bucket(need, limit), batch=batch, ragged=ragged)
+    if need > _limit(model):
+        raise ValueError(f"{need} positions exceed the model's max_position_embeddings ({_limit(model)})")
+    r, old = _bound(model, ("ragged", batch) if ragged else batch, need, batch=batch, ragged=ragged)
     if ragged:
-        per[key] = new
-        return new
-    new.all_logits = True
-    if r is not None and _same_weights(r, model) and r.host_pos > 0:
-        for nb, ob in zip(new.blocks, r.blocks):
-            nb["kc"][:, :, :r.host_pos].copy_(ob["kc"][:, :, :r.host_pos])
-            nb["vc"][:, :, :r.host_pos].copy_(ob["vc"][:, :, :r.host_pos])
-        new.set_pos(r.host_pos)
-        new.set_token(r.token)
-    per[key] = new
-    return new
+        return r
+    r.all_logits = True
+    if old is not None and _same_weights(old, model) and old.host_pos > 0:
+        for nb, ob in zip(r.blocks, old.blocks):
+            nb["kc"][:, :, :old.host_pos].copy_(ob["kc"][:, :, :old.host_pos])
+            nb["vc"][:, :, :old.host_pos].copy_(ob["vc"][:, :, :old.host_pos])
+        r.set_pos(old.host_pos)
+        r.set_token(old.token)
+    return r
 
 
 def _same_weights(r, model):
@@ -204,7 +205,7 @@ def _fast_forward(self, input_ids=None, attention_mask=None, position_ids=None, 
     B, S = input_ids.shape
     start_pos = int(start_pos)
     # room for the tokens that usually follow (a rebuilt runner re-captures its step): twice the context, at most 1024 more, never past the model's limit
-    limit = int(getattr(self.config, "max_position_embeddings", 1 << 30) or (1 << 30))
+    limit = _limit(self)
     end = start_pos + S
     r = _runner(self, B, max(end, min(limit, max(end + 1, 2 * end if end <= 1024 else end + 1024))))
     ids = input_ids if B > 1 else input_ids[0]
@@ -297,8 +298,7 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
         r = _lookup_runner(self, S + n + look[0], *look)
         if r is None:                                           # (the draft rows would pass max_position_embeddings: HF serves the call)
             return fall()
-        if tuple(eos if fixed else ()) != getattr(r, "_suppressed", ()):
-            r.set_suppressed(eos if fixed else ())
+        r.set_suppressed(eos if fixed else ())
         r.set_eos(() if fixed else eos)
         new = r.generate(ids[0], n, stop_at_eos=not fixed, min_new_tokens=nmin)
         return torch.cat([ids, new.view(1, -1).to(ids.dtype)], dim=1)
@@ -309,8 +309,7 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
         prompt, gkw = (ids if B > 1 else ids[0]), {}
     if not do_sample and fixed:
         # min_new_tokens = max_new_tokens: HF never lets an EOS id through (MinNewTokensLengthLogitsProcessor sets their logits to -inf on every step)
-        if tuple(eos) != getattr(r, "_suppressed", ()):
-            r.set_suppressed(eos)
+        r.set_suppressed(eos)
         new = r.generate(prompt, n, **gkw)
         return torch.cat([ids, new.view(B, n).to(ids.dtype)], dim=1)
     try:
@@ -319,13 +318,11 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
             # (the tokens are not torch.multinomial's: the runner draws with its own counter-based generator)
             r.set_sampling(float(warp["temperature"]), int(warp["top_k"]), float(warp["top_p"]), seed=int(torch.randint(0, 2 ** 62, (1,)).item()))
         if fixed:
-            if tuple(eos) != getattr(r, "_suppressed", ()):
-                r.set_suppressed(eos)
+            r.set_suppressed(eos)
             new = r.generate(prompt, n, **gkw)
         else:
             # open-ended: a sequence stops at its first EOS id and is padded from there on (HF pads with eos[0] when no pad id is set)
-            if getattr(r, "_suppressed", ()) != ():
-                r.set_suppressed(())
+            r.set_suppressed(())
             r.set_eos(eos, pad_id=int(pad) if pad is not None else (eos[0] if eos else 0))
             new = r.generate(prompt, n, stop_at_eos=True, min_new_tokens=nmin, **gkw)
     finally:

@@ -19,6 +19,7 @@ synthetic native payloads of the real shapes (``synthetic=True``; there is no
 network for checkpoints -- values do not affect speed).
 """
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -97,6 +98,92 @@ def _prime_graph_state(dev):
                 keep += 1
         side.synchronize()
     _GRAPH_STATE_PRIMED.add(key)
+
+
+def capture_graph(dev, fn, restore=None):
+    """``fn()`` captured into a hipGraph on a side stream: one un-captured call first (allocator, lazy init), then ``restore()`` (puts back what that
+    call consumed), then the capture -- with no garbage collection inside it (``_no_gc``) -- and the streams joined.  Returns the graph."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        fn()
+        side.synchronize()
+        if restore is not None:
+            restore()
+        g = torch.cuda.CUDAGraph()
+        with _no_gc(), torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+            fn()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    return g
+
+
+def _ints(values, n, lo, hi, message):
+    """``n`` ints in lo .. hi from an int (taken ``n`` times), a list or a tensor; otherwise ValueError(message.format(got=...))"""
+    each = [int(values)] * n if isinstance(values, int) else [int(v) for v in (values.reshape(-1).tolist() if isinstance(values, torch.Tensor) else values)]
+    if len(each) != n or not all(lo <= v <= hi for v in each):
+        raise ValueError(message.format(got=each))
+    return each
+
+
+# how a norm of the token step runs / which form down_proj takes (StepPlan)
+NORM_FUSED, NORM_LAUNCH, NORM_FROM_SUMS = "fused", "launch", "sums"
+DOWN_FUSED, DOWN_GEMV, DOWN_GEMV_SUMS, DOWN_GEMM = "silu_mul prologue", "silu_mul + gemv", "silu_mul + gemv leaving sums", "silu_mul + gemm"
+
+
+class StepPlan(NamedTuple):
+    """the launches of a token step of R rows that depend on R"""
+    first_norm: str     # block 0's first norm (its x comes from the embedding: nothing left sums for it): NORM_FUSED | NORM_LAUNCH
+    norm: str           # every other norm: NORM_FUSED (RMSNorm prologue of the q/k/v and gate/up launches) | NORM_LAUNCH (an rmsnorm launch in front
+    #                     of them) | NORM_FROM_SUMS (from the partial sums of squares the o_proj / down_proj launch left: ops.gemv_grouped_sums)
+    down: str           # down_proj: DOWN_FUSED (the GEMV with the SiLU*mul prologue) | silu_mul and DOWN_GEMV (the plain GEMV) | DOWN_GEMV_SUMS (the
+    #                     GEMV leaving sums) | DOWN_GEMM (the few-row MFMA kernel: the rows do not fit the GEMV's LDS stage even in two K phases)
+
+    @property
+    def block_norm(self):
+        """the first norm of blocks 1 ..: rides on down_proj's sums only where down_proj leaves them"""
+        return self.first_norm if self.norm == NORM_FROM_SUMS and self.down != DOWN_GEMV_SUMS else self.norm
+
+
+def step_plan(R, H, I, fine, rows_h, rows_i, rows_i_phased, norm_sums=True, norm_fused_rows=4, down_fused_rows=1):
+    """The StepPlan of R rows at hidden size H / intermediate size I (``fine``: groups of 64 / 32).  rows_h, rows_i, rows_i_phased: the rows the
+    GEMV stages in LDS -- ops.gemv_max_rows(H, plain=True), (I, plain=not fine) and (I, plain=not fine, norm=False: in two K phases).
+    norm_sums, norm_fused_rows, down_fused_rows: QuantLlama.NORM_SUMS, NORM_FUSED_ROWS, DOWN_FUSED_ROWS.
+    A fused prologue is paid once per WORKGROUP, on R times the one-row bytes, a separate launch once per token: SiLU*mul leaves the GEMV from 2
+    rows, the norms from 5 (profiles/r05_decode_batch.txt) -- where at 2 .. 8 rows they ride on partial sums instead (no pass over x for the
+    statistic, no rmsnorm launch: profiles/r06_decode_batch.txt).  Past the whole-row LDS stage (7B: 7 - 8 rows of 11008) the plain GEMV stages x
+    in two K phases (a fused prologue there would take in gate AND up per workgroup -- 352 KB per CU at 8 rows: 23.9 us against 4.9 + ~11)."""
+    own = NORM_LAUNCH if R > norm_fused_rows else NORM_FUSED
+    sums = norm_sums and 2 <= R <= 8 and not fine and 2048 <= H <= 8192 and I >= 2048 and R <= rows_h
+    if R <= min(rows_i, down_fused_rows):
+        down = DOWN_FUSED
+    elif R <= rows_i_phased:
+        down = DOWN_GEMV_SUMS if sums else DOWN_GEMV
+    else:
+        down = DOWN_GEMM
+    return StepPlan(own, NORM_FROM_SUMS if sums else own, down)
+
+
+class _held_back:
+    """token ids (the EOS ids) held back from a runner's choice until ``release()`` -- the first ``min_new_tokens`` tokens of a generate loop --;
+    what was suppressed before is back on exit, however the loop ends"""
+
+    def __init__(self, runner, ids, hold):
+        self.runner, self.ids, self.held = runner, tuple(ids), bool(hold)
+
+    def __enter__(self):
+        self.before = self.runner.suppressed
+        if self.held:
+            self.runner.set_suppressed(self.before + tuple(e for e in self.ids if e not in self.before))
+        return self
+
+    def release(self):
+        if self.held:
+            self.runner.set_suppressed(self.before)
+            self.held = False
+
+    def __exit__(self, *exc):
+        self.runner.set_suppressed(self.before)
+        return False
 
 
 class QuantLlama:
@@ -239,61 +326,27 @@ class QuantLlama:
                                      "one grouped launch, which needs one group size per sibling set")
 
         f16 = dict(dtype=torch.float16, device=dev)
-        B = self.R
-        self.x = torch.zeros(B, self.H, **f16)
-        self.xn = torch.zeros(B, self.H, **f16)          # normed rows (launches of more than NORM_FUSED_ROWS rows)
-        self.q = torch.zeros(B, self.H, **f16)
-        self.k = torch.zeros(B, self.kvd, **f16)
-        self.v = torch.zeros(B, self.kvd, **f16)
-        self.att = torch.zeros(B, self.H, **f16)
-        self.gate = torch.zeros(B, self.I, **f16)
-        self.up = torch.zeros(B, self.I, **f16)
-        self.logits = torch.zeros(self.vocab, **f16) if B == 1 else torch.zeros(B, self.vocab, **f16)    # [vocab] | [B, vocab]
-        self.token = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
+        R = self.R
+        self.x = torch.zeros(R, self.H, **f16)
+        self.xn = torch.zeros(R, self.H, **f16)          # normed rows (NORM_LAUNCH)
+        self.q = torch.zeros(R, self.H, **f16)
+        self.k = torch.zeros(R, self.kvd, **f16)
+        self.v = torch.zeros(R, self.kvd, **f16)
+        self.att = torch.zeros(R, self.H, **f16)
+        self.gate = torch.zeros(R, self.I, **f16)
+        self.up = torch.zeros(R, self.I, **f16)
         # the cos/sin table every rotating kernel reads: plain rope_theta frequencies, or the rotary embedding's own (rope_scaling)
-        self.inv_freq, self.rope_scale = rope if rope is not None else rope_inv_freq(config)
-        self.rope_tab = ops.rope_table(max_seq, self.theta, dev, inv_freq=self.inv_freq, scale=self.rope_scale)
-        # step state: cos/sin row of self.pos + the position itself in one block (set_token / the step's tail keep it)
-        # (ragged: one block per sequence -- rope_cur [B, 128], pos [B], step_err [B] -- and the prompt lengths the captured prompt pass reads)
-        # (lookup: one block per ROW of the step -- block j at position p + j)
-        self.rope_cur, self.pos, self.step_err = ops.new_step_state(dev, batch=B) if self.ragged or self.lookup else ops.new_step_state(dev)
-        self.rope_cur.copy_(self.rope_tab.view(max_seq, 128)[0])
-        self.lookup_state = self.history = None
-        if self.lookup:
-            # the device block the verify-and-propose tail reads and keeps, and the token history (prompt + everything emitted)
-            self.lookup_state, self.history = ops.new_lookup_state(dev, self.lookup, self.ngram_max, max_seq)
-            self._row_offsets = torch.arange(self.R, dtype=torch.int32, device=dev)
-            self._tok_in = torch.zeros(self.R, dtype=torch.int64, device=dev)
-            self._prompt_len = 0
-        self.lengths = torch.ones(B, dtype=torch.int64, device=dev) if self.ragged else None
-        self.graph = None
-        self.host_pos = 0          # host mirror of self.pos (decode_step refuses to run past the cache without a device sync); ragged: of the LARGEST position
-        # token ids the greedy choice never takes (8 slots, -1 = unused; read by the step's tail kernel): what HF's min_new_tokens does to the EOS ids
-        # (set_suppressed; the values may change between replays of the captured step)
-        self.suppress = torch.full((8,), -1, dtype=torch.int32, device=dev)
-        # sampled decoding (set_sampling / set_eos): the device block the sampled tail reads on every replay, and the sampled step's own graph beside
-        # the greedy one (captured on first use; self.graph stays the greedy step)
-        self.sampling = None        # None = greedy; else dict(temperature, top_k, top_p, seed)
-        self.eos, self.pad_id = (), 0
-        self.sample_state = None
-        self.sample_graph = None
+        self._init_step_state(rope if rope is not None else rope_inv_freq(config))
         self.has_bias = any(blk[n].bias is not None for blk in self.blocks for n in config["linear"])
-        # down_proj's launch: the GEMV with the fused SiLU*mul prologue while the rows' x fits LDS whole; past that (7B: 7 - 8 rows of 11008) one
-        # silu_mul launch + the GEMV without a prologue, x staged in two K phases (fusing the prologue there would make every workgroup take in gate
-        # AND up -- 352 KB per CU at 8 rows: 23.9 us against 4.9 + ~11); past that too, the few-row MFMA kernel
-        self._down_rows_fit = self.R <= min(ops.gemv_max_rows(self.I, plain=not self.fine), self.DOWN_FUSED_ROWS)
-        self._down_rows_phased = not self._down_rows_fit and self.R <= ops.gemv_max_rows(self.I, plain=not self.fine, norm=False)
-        self.can_fuse_qkv_attn = (self.R == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
+        # which launches make up a step of R rows: decided here, once (the class switches as they stand now), walked by _step
+        self.plan = step_plan(R, self.H, self.I, self.fine, ops.gemv_max_rows(self.H, plain=True), ops.gemv_max_rows(self.I, plain=not self.fine),
+                              ops.gemv_max_rows(self.I, plain=not self.fine, norm=False), self.NORM_SUMS, self.NORM_FUSED_ROWS, self.DOWN_FUSED_ROWS)
+        # the sums of squares of self.x's rows, per 16 columns: written by the launch that produced the rows, read by the one that normalises them
+        self.ss = torch.zeros(R, self.H // 16, dtype=torch.float32, device=dev) if self.plan.norm == NORM_FROM_SUMS else None
+        self.can_fuse_qkv_attn = (R == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
                                   and not self.ragged)
         self.fuse_qkv_attn = self.FUSE_QKV_ATTN and self.can_fuse_qkv_attn
         self._tickets = torch.zeros(max(self.nh, 64), dtype=torch.int32, device=dev)
-        # 2 .. 8 sequences: the RMSNorms ride on per-row-tile sums of squares that o_proj / down_proj leave in their epilogues (ops.gemv_grouped_sums:
-        # no pass over x for the statistic -- which a fused prologue repeats in every workgroup --, no rmsnorm launch); the first norm of block 0 (its x
-        # comes from the embedding) keeps the fused prologue (2 .. 4 rows) / a launch of its own (5 .. 8)
-        self._norm_sums = (self.NORM_SUMS and 2 <= self.R <= 8 and not self.fine and 2048 <= self.H <= 8192 and self.I >= 2048
-                           and self.R <= ops.gemv_max_rows(self.H, plain=True))
-        self.ss = torch.zeros(self.R, self.H // 16, dtype=torch.float32, device=dev) if self._norm_sums else None
         eligible = self.R == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias and not self.ragged
         if engine and not eligible:
             raise ValueError("the decode engine needs batch 1 and max_seq <= %d" % self.ENGINE_MAX_SEQ)
@@ -305,6 +358,42 @@ class QuantLlama:
                 [dict({n: dict(qn=blk[n].qn, mn=blk[n].mn, bits=blk[n].bits, mode=blk[n].mode, N=blk[n].N) for n in ops.ENGINE_LINEARS},
                       ln1=blk["ln1"], ln2=blk["ln2"], kc=blk["kc"], vc=blk["vc"]) for blk in self.blocks],
                 self.H, self.I, self.nh, self.nkv, max_seq, self.eps, self.x.view(-1), self.rope_cur)
+
+    def _init_step_state(self, rope):
+        """everything a runner keeps besides weights, caches and activations (needs B, R, ragged, lookup, ngram_max, vocab, max_seq, theta, dev);
+        ``rope``: (inv_freq fp32 [64] or None = plain rope_theta, attention_scaling)"""
+        dev, R, max_seq = self.dev, self.R, self.max_seq
+        self.logits = torch.zeros(self.vocab, dtype=torch.float16, device=dev) if R == 1 else torch.zeros(R, self.vocab, dtype=torch.float16, device=dev)
+        self.logits_rows = None     # all_logits: [B, S, vocab] of the last prompt pass
+        self.token = torch.zeros(R, dtype=torch.int64, device=dev)
+        self.inv_freq, self.rope_scale = rope
+        self.rope_tab = ops.rope_table(max_seq, self.theta, dev, inv_freq=self.inv_freq, scale=self.rope_scale)
+        # step state: cos/sin row of self.pos + the position itself in one block (set_token / the step's tail keep it)
+        # (ragged: one block per sequence -- rope_cur [B, 128], pos [B], step_err [B] -- and the prompt lengths the captured prompt pass reads)
+        # (lookup: one block per ROW of the step -- block j at position p + j)
+        self.rope_cur, self.pos, self.step_err = ops.new_step_state(dev, batch=R) if self.ragged or self.lookup else ops.new_step_state(dev)
+        self.rope_cur.copy_(self.rope_tab.view(max_seq, 128)[0])
+        self.host_pos = 0          # host mirror of self.pos (decode_step refuses to run past the cache without a device sync); ragged: of the LARGEST position
+        self.lengths = torch.ones(R, dtype=torch.int64, device=dev) if self.ragged else None
+        self.lookup_state = self.history = None
+        if self.lookup:
+            # the device block the verify-and-propose tail reads and keeps, and the token history (prompt + everything emitted)
+            self.lookup_state, self.history = ops.new_lookup_state(dev, self.lookup, self.ngram_max, max_seq)
+            self._row_offsets = torch.arange(R, dtype=torch.int32, device=dev)
+            self._tok_in = torch.zeros(R, dtype=torch.int64, device=dev)
+            self._prompt_len = 0
+        # token ids the greedy choice never takes (8 slots, -1 = unused; read by the step's tail kernel): what HF's min_new_tokens does to the EOS ids
+        # (set_suppressed; the values may change between replays of the captured step)
+        self.suppress = torch.full((8,), -1, dtype=torch.int32, device=dev)
+        self.suppressed = ()        # what self.suppress holds (read-only: set_suppressed)
+        # sampled decoding (set_sampling / set_eos): the device block the sampled tail reads on every replay, and the sampled step's own graph beside
+        # the greedy one (captured on first use; self.graph stays the greedy step)
+        self.sampling = None        # None = greedy; else dict(temperature, top_k, top_p, seed)
+        self.eos, self.pad_id = (), 0
+        self.sample_state = None
+        self._greedy_eos = False    # generate() runs greedy with EOS stop: the sampled tail taking the first maximum
+        self.graph = self.sample_graph = None
+        self._prefill_graphs = {}   # (prompt length, start_pos) -> (graph, its ids buffer, its logits_rows or None)
 
     # model families whose decoder is the Llama block -- RMSNorm, rotary q / k, (grouped-query) softmax attention, SiLU-gated MLP, no extra norms --
     # and differs only in shapes, rope settings and projection biases: what the reference lists (README.md:90-92; amq/configs/{llama,mistral,qwen2}.json)
@@ -390,62 +479,57 @@ class QuantLlama:
     # ----------------------------------------------------------------- decode
     def _step(self, sampled=False):
         """one token: reads self.x (= embed[self.token], kept in step by set_token / the step's own tail) and self.pos
-        (device), writes self.logits, self.token, self.pos and the next step's self.x"""
-        H = self.H
+        (device), writes self.logits, self.token, self.pos and the next step's self.x.  The launches are self.plan's."""
+        H, plan = self.H, self.plan
         if self.engine is not None:
             self.engine.step()
             ops.gemv_f16w(self.x.reshape(-1), self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
             self._tail(sampled)
             return
-        have_sums = False                       # self.ss holds the sums of squares of self.x's rows (written by the launch that produced them)
         if self.ragged and self.fuse_qkv_attn:
             raise ValueError("the fused q/k/v + attention launch keeps one position (batch 1): not offered with ragged=True")
+        from_sums = plan.norm == NORM_FROM_SUMS
+        first = plan.first_norm
         for blk in self.blocks:
             if self.fuse_qkv_attn:
                 ops.gemv_qkv_attn(self.x, [blk["self_attn.q_proj"].seg(self.q.view(-1)), blk["self_attn.k_proj"].seg(self.k.view(-1)),
                                            blk["self_attn.v_proj"].seg(self.v.view(-1))], H, blk["ln1"], self.eps, blk["kc"], blk["vc"],
                                   self.att.view(-1), self.rope_cur, self.nh, self.nkv, self._tickets)
             else:
-                qkv = [blk["self_attn.q_proj"].seg(self.q), blk["self_attn.k_proj"].seg(self.k), blk["self_attn.v_proj"].seg(self.v)]
-                if self._norm_sums and have_sums:
-                    ops.gemv_grouped_sums(self.x, qkv, H, gamma=blk["ln1"], eps=self.eps, sums_in=self.ss)
-                elif self.R > self.NORM_FUSED_ROWS:
-                    ops.gemv_grouped(ops.rmsnorm(self.x, blk["ln1"], self.eps, out=self.xn), qkv, H)
-                else:
-                    ops.gemv_grouped(self.x, qkv, H, prologue=ops.PRO_RMSNORM, gamma=blk["ln1"], eps=self.eps)
+                self._behind_norm(first, blk["ln1"], [blk["self_attn.q_proj"].seg(self.q), blk["self_attn.k_proj"].seg(self.k),
+                                                      blk["self_attn.v_proj"].seg(self.v)])
                 if self.lookup:                 # the R rows are consecutive positions of the one sequence: causal among them, one cache slice
                     ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv)
                 else:
                     ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
                                     cur=self.rope_cur)
-            if self._norm_sums:
-                ops.gemv_grouped_sums(self.att, [blk["self_attn.o_proj"].seg(self.x, residual=self.x)], H, sums_out=self.ss)
-                ops.gemv_grouped_sums(self.x, [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)], H,
-                                      gamma=blk["ln2"], eps=self.eps, sums_in=self.ss)
+            o_proj, down = [blk["self_attn.o_proj"].seg(self.x, residual=self.x)], [blk["mlp.down_proj"].seg(self.x, residual=self.x)]
+            if from_sums:
+                ops.gemv_grouped_sums(self.att, o_proj, H, sums_out=self.ss)
             else:
-                ops.gemv_grouped(self.att, [blk["self_attn.o_proj"].seg(self.x, residual=self.x)], H)
-            if self._norm_sums:
-                pass                            # (gate / up were launched above, behind o_proj's sums)
-            elif self.R > self.NORM_FUSED_ROWS:
-                ops.gemv_grouped(ops.rmsnorm(self.x, blk["ln2"], self.eps, out=self.xn), [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)], H)
+                ops.gemv_grouped(self.att, o_proj, H)
+            self._behind_norm(plan.norm, blk["ln2"], [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)])
+            if plan.down == DOWN_FUSED:
+                ops.gemv_grouped(self.gate, down, self.I, prologue=ops.PRO_SILU_MUL, x2=self.up)
+            elif plan.down == DOWN_GEMV_SUMS:
+                ops.gemv_grouped_sums(ops.silu_mul(self.gate, self.up, out=self.gate), down, self.I, sums_out=self.ss)
+            elif plan.down == DOWN_GEMV:
+                ops.gemv_grouped(ops.silu_mul(self.gate, self.up, out=self.gate), down, self.I)
             else:
-                ops.gemv_grouped(self.x, [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)], H,
-                                 prologue=ops.PRO_RMSNORM, gamma=blk["ln2"], eps=self.eps)
-            if self._down_rows_fit:
-                ops.gemv_grouped(self.gate, [blk["mlp.down_proj"].seg(self.x, residual=self.x)], self.I,
-                                 prologue=ops.PRO_SILU_MUL, x2=self.up)
-            elif self._down_rows_phased and self._norm_sums:
-                ops.gemv_grouped_sums(ops.silu_mul(self.gate, self.up, out=self.gate), [blk["mlp.down_proj"].seg(self.x, residual=self.x)], self.I,
-                                      sums_out=self.ss)
-                have_sums = True
-            elif self._down_rows_phased:
-                ops.gemv_grouped(ops.silu_mul(self.gate, self.up, out=self.gate), [blk["mlp.down_proj"].seg(self.x, residual=self.x)], self.I)
-            else:       # batch x intermediate size past the GEMV kernel's LDS stage: few-row MFMA kernel
                 d = blk["mlp.down_proj"]
                 ops.gemm(ops.silu_mul(self.gate, self.up, out=self.gate), d.qn, d.mn, d.bits, d.mode, d.N, d.K, bias=d.bias, residual=self.x, out=self.x)
-                have_sums = False
+            first = plan.block_norm
         ops.gemv_f16w(self.x.reshape(-1) if self.R == 1 else self.x, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
         self._tail(sampled)
+
+    def _behind_norm(self, how, gamma, segments):
+        """one grouped launch (q/k/v, gate/up) over self.x behind the RMSNorm ``gamma``, which runs as the plan says"""
+        if how == NORM_FROM_SUMS:
+            ops.gemv_grouped_sums(self.x, segments, self.H, gamma=gamma, eps=self.eps, sums_in=self.ss)
+        elif how == NORM_LAUNCH:
+            ops.gemv_grouped(ops.rmsnorm(self.x, gamma, self.eps, out=self.xn), segments, self.H)
+        else:
+            ops.gemv_grouped(self.x, segments, self.H, prologue=ops.PRO_RMSNORM, gamma=gamma, eps=self.eps)
 
     def _tail(self, sampled):
         """the end of a token step: the next token (arg-max, or a draw with the device block's parameters + EOS bookkeeping), pos += 1,
@@ -462,9 +546,6 @@ class QuantLlama:
             ops.decode_tail(self.logits, self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur, suppress=self.suppress)
 
     # ------------------------------------------------------------- sampling
-    sampling, sample_state, sample_graph, eos, pad_id = None, None, None, (), 0      # (class defaults: greedy)
-    ragged, lengths = False, None       # (class defaults: one position for the whole batch)
-    lookup, lookup_state, history = 0, None, None      # (class defaults: one row per sequence and step)
     EOS_POLL_STEPS = 16         # generate(stop_at_eos=True) reads the unfinished count every this many steps: fewer = less work after the last EOS, more host syncs
 
     def _write_sampling_state(self):
@@ -500,7 +581,7 @@ class QuantLlama:
 
     def _sampled_tail(self):
         """the token steps end in the sampled tail: sampling is on, or generate() runs greedy with EOS stop (the sampled tail taking the first maximum)"""
-        return self.sampling is not None or self.__dict__.get("_greedy_eos", False)
+        return self.sampling is not None or self._greedy_eos
 
     def _first_token(self):
         """the first token after a prompt pass when the sampled tail is in use: draw 0 of every sequence from the last rows' logits"""
@@ -514,27 +595,26 @@ class QuantLlama:
     def set_suppressed(self, ids=()):
         """token ids greedy decoding must not pick (at most 8; () = none): HF's generate(min_new_tokens = max_new_tokens) never emits an EOS id.
         Takes effect from the next step / prompt pass, captured or not."""
-        ids = [int(i) for i in ids]
+        ids = tuple(int(i) for i in ids)
         if len(ids) > 8:
             raise ValueError("at most 8 suppressed token ids")
-        self.suppress.copy_(torch.tensor(ids + [-1] * (8 - len(ids)), dtype=torch.int32))
-        self._suppressed = tuple(ids)
+        if ids == self.suppressed:              # (no host-to-device copy for what is already there)
+            return
+        self.suppress.copy_(torch.tensor(ids + (-1,) * (8 - len(ids)), dtype=torch.int32))
+        self.suppressed = ids
 
-    def _argmax(self, logits, dim, keepdim=False):
+    def _argmax(self, logits):
         """arg-max over the vocabulary (the last dimension) of a prompt pass with the suppressed ids left out, as the captured step's tail kernel
         does; no host synchronisation (unused slots are pointed at a spare element behind the vocabulary)"""
-        assert dim in (-1, logits.dim() - 1)
         m = torch.zeros(self.vocab + 1, dtype=torch.float32, device=logits.device)
         m.index_fill_(0, torch.where(self.suppress >= 0, self.suppress, self.vocab).to(torch.int64), float("-inf"))
-        return torch.argmax(logits.float() + m[:self.vocab], dim=dim, keepdim=keepdim)
+        return torch.argmax(logits.float() + m[:self.vocab], dim=-1)
 
     def set_pos(self, pos):
         """set the position of the next decode step (device state + its host mirror); follow with set_token().  A ragged runner also takes one
         position per sequence (a list or tensor of B)."""
         if self.ragged and not isinstance(pos, int) and (not isinstance(pos, torch.Tensor) or pos.numel() > 1 or self.B == 1):
-            each = [int(p) for p in (pos.reshape(-1).tolist() if isinstance(pos, torch.Tensor) else pos)]
-            if len(each) != self.B or not all(0 <= p <= self.max_seq for p in each):
-                raise ValueError(f"expected {self.B} positions inside the KV cache (max_seq={self.max_seq}), got {each}")
+            each = _ints(pos, self.B, 0, self.max_seq, f"expected {self.B} positions inside the KV cache (max_seq={self.max_seq}), got {{got}}")
             self.pos.copy_(torch.tensor(each, dtype=torch.int32))
             self.host_pos = max(each)
             return
@@ -577,28 +657,22 @@ class QuantLlama:
         rows = torch.index_select(self.rope_tab.view(self.max_seq, 128), 0, self.pos.to(torch.int64).clamp_(0, self.max_seq - 1))
         self.rope_cur.copy_(rows if self.ragged else rows[0])
 
+    def _graph(self, sampled):
+        """the captured token step: the one ending in the sampled tail, or the greedy one"""
+        return self.sample_graph if sampled else self.graph
+
     def capture(self, sampled=False):
         """capture one token step into a hipGraph (replayed by decode_step); ``sampled``: the step that ends in the sampled tail, kept beside the greedy one"""
-        if (self.sample_graph if sampled else self.graph) is not None:
+        if self._graph(sampled) is not None:
             return
         if self.host_pos >= self.max_seq:
             raise ValueError(f"cannot capture a decode step at position {self.host_pos}: the KV cache holds {self.max_seq} rows")
         if sampled and self.sample_state is None:
             self._write_sampling_state()
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        saved = (self.token.clone(), self.pos.clone())
-        if self.lookup:                         # (the warm-up and the recorded step advance the counters and the drafts: put back below)
-            saved = saved + (self.lookup_state.clone(),)
+        # (the warm-up and the recorded step advance positions and tokens -- lookup: the counters and the drafts too --: put back)
+        saved = (self.token.clone(), self.pos.clone(), self.lookup_state.clone() if self.lookup else None)
         saved_state = self.sample_state.clone() if sampled else None       # (the warm-up and the capture's own launch-free recording must not consume a draw)
-        with torch.cuda.stream(side):
-            self._step(True) if sampled else self._step()                # warm-up outside capture (allocator, lazy init)
-            side.synchronize()
-            self._restore_step_inputs(saved)
-            g = torch.cuda.CUDAGraph()
-            with _no_gc(), torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                self._step(True) if sampled else self._step()
-        torch.cuda.current_stream(self.dev).wait_stream(side)
+        g = capture_graph(self.dev, lambda: self._step(sampled), lambda: self._restore_step_inputs(saved))
         torch.cuda.synchronize(self.dev)
         self._restore_step_inputs(saved)
         if sampled:
@@ -625,13 +699,13 @@ class QuantLlama:
             sampled = self._sampled_tail()
         if self.lookup and self.host_pos + self.lookup >= self.max_seq:
             raise ValueError(f"a verify step at position {self.host_pos} with {self.lookup} drafts does not fit the KV cache (max_seq={self.max_seq})")
-        if use_graph and (self.sample_graph if sampled else self.graph) is None:
+        if use_graph and self._graph(sampled) is None:
             self.capture(sampled)
         self.host_pos += self.R if self.lookup else 1       # (lookup: an upper bound -- a step advances by 1 + accepted drafts; lookup_sync() reads the exact value)
         if use_graph:
-            (self.sample_graph if sampled else self.graph).replay()
+            self._graph(sampled).replay()
         else:
-            self._step(True) if sampled else self._step()
+            self._step(sampled)
 
     # ---------------------------------------------------------------- prefill
     def _rope(self, t, positions):
@@ -672,37 +746,23 @@ class QuantLlama:
         if self.ragged:
             if start_pos != 0:
                 raise ValueError("a ragged prompt pass starts at position 0 (chunked ragged prompts are not served)")
-            each = [S] * self.B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-            if len(each) != self.B or not all(1 <= v <= S for v in each):
-                raise ValueError(f"lengths: expected {self.B} values in 1..{S}, got {each}")
+            each = _ints(S if lengths is None else lengths, self.B, 1, S, f"lengths: expected {self.B} values in 1..{S}, got {{got}}")
             self.lengths.copy_(torch.tensor(each, dtype=torch.int64))
             longest = max(each)
-        if not use_graph:
-            logits = self._prefill_rows(ids, start_pos)
-            self.host_pos = start_pos + longest
-            if self._sampled_tail():
-                self._first_token()
-            return logits
-        cache = self.__dict__.setdefault("_prefill_graphs", {})
-        ent = cache.get((S, start_pos))
-        if ent is None:
-            static_ids = ids.to(self.dev).clone()
-            side = torch.cuda.Stream(device=self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                self._prefill_rows(static_ids, start_pos)      # warm-up outside capture (allocator, lazy init)
-                side.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with _no_gc(), torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                    self._prefill_rows(static_ids, start_pos)
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            ent = cache[(S, start_pos)] = (g, static_ids, self.__dict__.get("logits_rows"))
-        g, static_ids, rows = ent
-        static_ids.copy_(ids)
-        g.replay()
-        if rows is not None:
-            self.logits_rows = rows             # (this graph's own output buffer: valid until its next replay)
-        self.host_pos = start_pos + longest     # (the replay sets the device-side position; the host mirror is not part of it)
+        if use_graph:
+            ent = self._prefill_graphs.get((S, start_pos))
+            if ent is None:
+                static_ids = ids.to(self.dev).clone()
+                g = capture_graph(self.dev, lambda: self._prefill_rows(static_ids, start_pos))
+                ent = self._prefill_graphs[(S, start_pos)] = (g, static_ids, self.logits_rows if self.all_logits else None)
+            g, static_ids, rows = ent
+            static_ids.copy_(ids)
+            g.replay()
+            if rows is not None:
+                self.logits_rows = rows         # (this graph's own output buffer: valid until its next replay)
+        else:
+            self._prefill_rows(ids, start_pos)
+        self.host_pos = start_pos + longest     # (a replay sets the device-side position; the host mirror is not part of it)
         if self._sampled_tail():
             self._first_token()                 # (outside the prompt graph, which ends in the arg-max: one graph per prompt length serves both)
         return self.logits
@@ -718,26 +778,6 @@ class QuantLlama:
             self._tok_in[0] = int(token)
         self.lookup_state[ops.LOOKUP_DRAFT:ops.LOOKUP_DRAFT + 8].fill_(-1)
         ops.set_token(self._tok_in, self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur)
-
-    def _lookup_prefill_finish(self, x, S):
-        """the end of a lookup runner's prompt pass (all device work: part of the captured prompt graph): the prompt goes into the history with a
-        device copy, and the verify-and-propose tail itself -- run on the last prompt row's logits as row 0 of a step at position S - 1 without
-        drafts -- emits the first token, proposes the first drafts and leaves the step inputs of position S"""
-        lg = self.logits.view(self.R, self.vocab)
-        if self.all_logits:
-            self.logits_rows = self._logits_of_rows(x, 1, S, lg[0])
-        else:
-            ops.gemv_f16w(x[S - 1].contiguous(), self.lm_head, gamma=self.norm, eps=self.eps, out=lg[0])
-        self.history[:S].copy_(self._lookup_ids.reshape(-1))
-        st = self.lookup_state
-        st[ops.LOOKUP_COUNT:ops.LOOKUP_TICKET + 1].zero_()                  # count, steps, accepted, ticket
-        st[ops.LOOKUP_COUNT].fill_(S)
-        st[ops.LOOKUP_DRAFT:ops.LOOKUP_DRAFT + 8].fill_(-1)
-        self.set_pos(S - 1)
-        self._tail(False)
-        st[ops.LOOKUP_STEPS].zero_()                                        # (the prompt pass is not a verify step)
-        self.host_pos = S
-        return self.logits
 
     def set_lookup_mode(self, external):
         """who proposes the drafts: False = the tail looks them up in the history; True = the caller (``verify_step``) -- the tail then leaves -1 drafts.
@@ -791,20 +831,15 @@ class QuantLlama:
             raise ValueError(f"prompt ({S}) + {gen_len} tokens + {D} draft rows do not fit the KV cache (max_seq={self.max_seq})")
         if self.sampling is not None:
             raise ValueError("lookup: speculative decoding here is greedy; call set_sampling(None)")
-        suppressed = getattr(self, "_suppressed", ())
         eos = tuple(self.eos) if stop_at_eos else ()
-        hold = bool(eos) and min_new_tokens > 0
-        try:
-            if hold:
-                self.set_suppressed(tuple(suppressed) + tuple(e for e in eos if e not in suppressed))
+        with _held_back(self, eos, bool(eos) and min_new_tokens > 0) as hold:
             self.set_lookup_mode(False)
             self.prefill(ids, use_graph=use_graph)
             count, emitted = S + 1, 1
             while emitted < gen_len:
-                if hold and emitted >= min_new_tokens:
-                    self.set_suppressed(suppressed)
-                    hold = False
-                if hold and min_new_tokens - emitted < self.R:
+                if emitted >= min_new_tokens:
+                    hold.release()
+                if hold.held and min_new_tokens - emitted < self.R:
                     # the EOS ids are held back for exactly the first min_new_tokens tokens: a step that could cross that line runs without drafts
                     # (one token)
                     self._lookup_set_token(self.token[:1])
@@ -814,7 +849,7 @@ class QuantLlama:
                     # inside the first min_new_tokens however much is accepted, and never so far that the rows of a fully accepted step would
                     # leave the cache
                     k = min(self.EOS_POLL_STEPS, gen_len - emitted, max(1, (self.max_seq - D - self.host_pos) // self.R))
-                    if hold:
+                    if hold.held:
                         k = min(k, (min_new_tokens - emitted) // self.R)
                     for _ in range(k):
                         self.decode_step(use_graph)
@@ -828,9 +863,6 @@ class QuantLlama:
                 if cut is not None:
                     out = out[:cut + 1]
             return out
-        finally:
-            if getattr(self, "_suppressed", ()) != suppressed:
-                self.set_suppressed(suppressed)
 
     def _first_eos(self, toks, skip=0):
         """index of the first EOS id in ``toks`` at or behind index ``skip`` (None: none)"""
@@ -849,45 +881,55 @@ class QuantLlama:
         return ids
 
     def _prefill_rows(self, ids, start_pos):
-        """the prompt pass of every sequence (each into its own slice of the caches), then the shared position / next tokens"""
-        if self.ragged:
-            return self._prefill_rows_ragged(ids)
-        if self.B == 1:
+        """the prompt pass of every sequence (each into its own slice of the caches), then position(s) and first token(s); all device work: what
+        the prompt graph captures"""
+        if self.B == 1 and not self.ragged:
             return self._prefill_eager(ids[0], start_pos)
         B, S = ids.shape
-        last = self._rows_pass(ids, start_pos, cache=True)
+        return self._prompt_finish(self._rows_pass(ids, start_pos, cache=True), B, S, start_pos, self.lengths)
+
+    def _prompt_finish(self, x, B, S, start_pos=0, lengths=None, prompt_ids=None):
+        """the end of a prompt pass over B prompts of S rows, x [B * S, H] its final hidden rows: the logits of every sequence's last row (all_logits:
+        of every row, in self.logits_rows), the position, the first token.  ``lengths`` (a ragged runner's, device int64 [B]): sequence b ends in
+        row lengths[b] - 1 and goes on at position lengths[b].  ``prompt_ids``: what a lookup runner copies into its history."""
+        out = self.logits.view(self.R, self.vocab)[:B]      # (lookup: row 0 of the step's R rows)
+        each = None if lengths is None else torch.arange(B, device=x.device)
         if self.all_logits:
-            self.logits_rows = self._logits_of_rows(self.__dict__.pop("_rows_x"), B, S, self.logits)
+            self.logits_rows = self._logits_of_rows(x, B, S, out)
+            if lengths is not None:
+                out.copy_(self.logits_rows[each, lengths - 1])
         else:
-            ops.gemv_f16w(last, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
-        self.set_pos(start_pos + S)
-        self.set_token(self._argmax(self.logits, 1))
+            last = (x.view(B, S, self.H)[:, S - 1] if lengths is None else x.view(B, S, self.H)[each, lengths - 1]).contiguous()
+            ops.gemv_f16w(last[0] if B == 1 else last, self.lm_head, gamma=self.norm, eps=self.eps, out=out[0] if B == 1 else out)
+        if self.lookup:
+            # the prompt goes into the history with a device copy, and the verify-and-propose tail itself -- run on the last prompt row's logits as
+            # row 0 of a step at position S - 1 without drafts -- emits the first token, proposes the first drafts and leaves the step inputs of
+            # position S
+            self.history[:S].copy_(prompt_ids.reshape(-1))
+            st = self.lookup_state
+            st[ops.LOOKUP_COUNT:ops.LOOKUP_TICKET + 1].zero_()                  # count, steps, accepted, ticket
+            st[ops.LOOKUP_COUNT].fill_(S)
+            st[ops.LOOKUP_DRAFT:ops.LOOKUP_DRAFT + 8].fill_(-1)
+            self.set_pos(S - 1)
+            self._tail(False)
+            st[ops.LOOKUP_STEPS].zero_()                                        # (the prompt pass is not a verify step)
+            self.host_pos = S
+        elif lengths is not None:
+            self.pos.copy_(lengths)             # (the host mirror: prefill())
+            self.set_token(self._argmax(out))
+        else:
+            self.set_pos(start_pos + S)
+            self.set_token(self._argmax(out))
         return self.logits
 
-    def _prefill_rows_ragged(self, ids):
-        """the prompt pass of a ragged runner: the same ONE many-row pass, then per sequence (from self.lengths, on the device: graph-capturable)
-        the last REAL row's logits, pos[b] = L_b and the first token"""
-        B, S = ids.shape
-        last = self._rows_pass(ids, 0, cache=True, lengths=self.lengths)
-        logits = self.logits.view(B, self.vocab)
-        if self.all_logits:
-            self.logits_rows = self._logits_of_rows(self.__dict__.pop("_rows_x"), B, S, self.logits)
-            logits.copy_(self.logits_rows[torch.arange(B, device=self.dev), self.lengths - 1])
-        else:
-            ops.gemv_f16w(last.reshape(-1) if B == 1 else last, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
-        self.pos.copy_(self.lengths)            # (the host mirror: prefill())
-        self.set_token(self._argmax(logits, 1))
-        return self.logits
-
-    def _rows_pass(self, ids, start_pos, cache, lengths=None):
+    def _rows_pass(self, ids, start_pos, cache):
         """ONE many-row pass over B prompts of S rows (ids [B, S]): the linears see all B * S rows at once (one pass over
         the weights), RoPE and the causal attention run as ONE launch each over all sequences.  ``cache``: the rotated keys /
         values are written into the runner's KV caches (rows start_pos .. start_pos + S - 1 of every sequence) and the
         attention reads them there (a batched decode runner's prompt); otherwise q / k are rotated in place and the
-        attention reads the projection outputs (the harness' GeMM mode, no cache).  Returns the last rows [B, H] (``lengths``, device int64 [B]:
-        row lengths[b] - 1 of sequence b)."""
+        attention reads the projection outputs (the harness' GeMM mode, no cache).  Returns the final hidden rows [B * S, H]."""
         B, S = ids.shape
-        H, nh, nkv = self.H, self.nh, self.nkv
+        nh, nkv = self.nh, self.nkv
         x = self.embed.index_select(0, ids.reshape(-1).to(self.dev))
         lin = self._rows_linear
         for blk in self.blocks:
@@ -903,11 +945,7 @@ class QuantLlama:
             h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
             act = self._rows_up_gated(blk["mlp.up_proj"], h2, lin(blk["mlp.gate_proj"], h2))
             x = lin(blk["mlp.down_proj"], act, residual=x)
-        if self.all_logits:
-            self._rows_x = x                    # (picked up by _prefill_rows)
-        if lengths is not None:
-            return x.view(B, S, H)[torch.arange(B, device=x.device), lengths - 1].contiguous()
-        return x.view(B, S, H)[:, S - 1].contiguous()
+        return x
 
     def _logits_of_rows(self, x, B, S, last_logits):
         """logits of every prompt row, [B, S, vocab] fp16: final RMSNorm + ONE pass over the lm_head for all rows (fp16 MFMA GEMM); each sequence's
@@ -932,18 +970,16 @@ class QuantLlama:
     FRAG_ROWS = (16, 384)
     FUSE_DOWN_NORM = True       # down_proj's split-K reduce also writes the next block's normed input (A/B: tools/prompt64_time.py)
 
-    def _prefill_eager(self, ids, start_pos=0, b=None):
-        """(b: sequence of a batched runner -- its slice of the caches and its logits row, position / token left to the caller)
-        Many-row pass over the prompt: per block 2 RMSNorm + 7 GEMMs (residuals fused into the o_proj / down_proj
+    def _prefill_eager(self, ids, start_pos=0):
+        """Many-row pass over the prompt: per block 2 RMSNorm + 7 GEMMs (residuals fused into the o_proj / down_proj
         epilogues) + one RoPE-and-cache-write launch + causal attention (library SDPA reading K/V straight from the
         cache) + one SiLU*up launch."""
         S = ids.numel()
         if start_pos + S > self.max_seq:
             raise ValueError("prompt longer than the KV cache")
         H, nh, nkv = self.H, self.nh, self.nkv
-        if self.lookup:
-            self._lookup_ids = ids.to(self.dev)                    # (what _lookup_prefill_finish copies into the history)
-        x = self.embed.index_select(0, ids.to(self.dev))           # [S, H]; the residual stream, updated in place
+        ids = ids.to(self.dev)
+        x = self.embed.index_select(0, ids)                        # [S, H]; the residual stream, updated in place
 
         def lin(l, inp, residual=None):
             if S > 8:
@@ -972,7 +1008,7 @@ class QuantLlama:
             else:
                 h = ops.rmsnorm(x, blk["ln1"], self.eps)
                 q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
-            kc, vc = self._cache_rows(blk, b)
+            kc, vc = blk["kc"], blk["vc"]
             ops.rope_cache(q, k, v, kc[0], vc[0], self.rope_tab, start_pos, nh, nkv)
             if frag:
                 a_xf = ops.attn_prefill(q, kc, vc, None, S, nh, nkv, batch=1, pos0=start_pos, kv_cache=True, out_xfrag=True)
@@ -981,7 +1017,7 @@ class QuantLlama:
                 g, u = lin_xf_group([blk["mlp.gate_proj"], blk["mlp.up_proj"]], h2)                            # one launch
                 act = ops.silu_mul(g, u, out=g)
             else:
-                x = lin(blk["self_attn.o_proj"], self._prefill_attention(q, blk, S, start_pos, b), residual=x)
+                x = lin(blk["self_attn.o_proj"], self._prefill_attention(q, blk, S, start_pos), residual=x)
                 h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
                 g = lin(blk["mlp.gate_proj"], h2)
                 if S > 8:
@@ -995,7 +1031,7 @@ class QuantLlama:
                                                     bias=l.bias, residual=x, out=x)
             else:
                 x = lin(blk["mlp.down_proj"], act, residual=x)
-        return self._prefill_finish(x, S, start_pos, b)
+        return self._prompt_finish(x, 1, S, start_pos, prompt_ids=ids)
 
     def _rows_linear(self, l, inp, residual=None):
         # y = inp . W^T (+ residual, in place) for many rows
@@ -1015,7 +1051,7 @@ class QuantLlama:
         B, S = ids.shape
         if S > self.max_seq:
             raise ValueError("prompt longer than the RoPE table")
-        last = self._rows_pass(ids, 0, cache=False)
+        last = self._rows_pass(ids, 0, cache=False).view(B, S, self.H)[:, S - 1].contiguous()
         logits = torch.empty(B, self.vocab, dtype=torch.float16, device=self.dev)
         for b0 in range(0, B, 8):                   # the lm_head is streamed once per 8 sequences
             rows = slice(b0, min(B, b0 + 8))
@@ -1025,16 +1061,9 @@ class QuantLlama:
                 ops.gemv_f16w(last[rows], self.lm_head, gamma=self.norm, eps=self.eps, out=logits[rows])
         return logits
 
-    def _cache_rows(self, blk, b=None):
-        """the [1, n_kv_heads, max_seq, 128] cache views of sequence b (None: the batch-1 runner's whole caches)"""
-        if b is None:
-            return blk["kc"], blk["vc"]
-        return blk["kc"][b:b + 1], blk["vc"][b:b + 1]
-
-    def _prefill_attention(self, q, blk, S, start_pos=0, b=None):
+    def _prefill_attention(self, q, blk, S, start_pos=0):
         """causal attention of the prompt rows: q [S, nh*128] rotated, K / V = cache rows 0 .. start_pos + S - 1 -> [S, nh*128]"""
-        kc, vc = self._cache_rows(blk, b)
-        return ops.attn_prefill(q, kc, vc, torch.empty_like(q), S, self.nh, self.nkv, batch=1, pos0=start_pos, kv_cache=True)
+        return ops.attn_prefill(q, blk["kc"], blk["vc"], torch.empty_like(q), S, self.nh, self.nkv, batch=1, pos0=start_pos, kv_cache=True)
 
     def _prefill_attention_sdpa(self, q, blk, S):
         """the same through the framework's SDPA (comparison point for tests / tools; not on the product path)"""
@@ -1047,21 +1076,6 @@ class QuantLlama:
         a = torch.nn.functional.scaled_dot_product_attention(qh[None], kh[None], vh[None], is_causal=True)[0]
         return a.transpose(0, 1).reshape(S, self.H).contiguous()
 
-    def _prefill_finish(self, x, S, start_pos=0, b=None):
-        last = x[S - 1].contiguous()
-        if b is not None:                       # one sequence of a batch: its logits row; the caller sets position and tokens
-            ops.gemv_f16w(last, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits[b])
-            return self.logits[b]
-        if self.lookup:
-            return self._lookup_prefill_finish(x, S)
-        if self.all_logits:
-            self.logits_rows = self._logits_of_rows(x, 1, S, self.logits)
-        else:
-            ops.gemv_f16w(last, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
-        self.set_pos(start_pos + S)
-        self.set_token(self._argmax(self.logits, 0, keepdim=True))
-        return self.logits
-
     def _prefill_unfused(self, ids):
         """The same pass with framework ops for everything but the linears and RMSNorm (HF-style RoPE in fp32 -> fp16,
         separate cache copies, residual adds, SiLU and product): kept as the comparison point of the fused pass
@@ -1070,7 +1084,8 @@ class QuantLlama:
         if S > self.max_seq:
             raise ValueError("prompt longer than the KV cache")
         H, nh, nkv = self.H, self.nh, self.nkv
-        x = self.embed.index_select(0, ids.to(self.dev))
+        ids = ids.to(self.dev)
+        x = self.embed.index_select(0, ids)
         positions = torch.arange(S, device=self.dev)
 
         def lin(l, inp):
@@ -1088,7 +1103,7 @@ class QuantLlama:
             h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
             g, u = lin(blk["mlp.gate_proj"], h2), lin(blk["mlp.up_proj"], h2)
             x = x + lin(blk["mlp.down_proj"], torch.nn.functional.silu(g) * u)
-        return self._prefill_finish(x, S)
+        return self._prompt_finish(x, 1, S, prompt_ids=ids)
 
     def reset(self):
         self.set_pos(0)
@@ -1109,8 +1124,8 @@ class QuantLlama:
         if lengths is not None:
             if not self.ragged:
                 raise ValueError("lengths needs a runner built with ragged=True (this one keeps one position for the whole batch)")
-            lengths = [int(v) for v in (lengths.reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-            S = max(lengths) if lengths else S
+            lengths = _ints(lengths, self.B, 1, S, f"lengths: expected {self.B} values in 1..{S}, got {{got}}")
+            S = max(lengths)
         if S + gen_len > self.max_seq:
             raise ValueError("sequence does not fit the KV cache")
         if not stop_at_eos and self.sampling is None:   # greedy, fixed length
@@ -1124,31 +1139,27 @@ class QuantLlama:
                 self.check()                    # a barrier time-out of the one-launch-per-token engine must not pass as tokens
             return out[0] if self.B == 1 else out
         self._greedy_eos = self.sampling is None
-        suppressed = getattr(self, "_suppressed", ())
         try:
-            self._write_sampling_state()        # draw counter 0, nobody finished: one seed fixes the whole sequence
-            if not stop_at_eos:
-                self.sample_state[8:16].fill_(-1)       # fixed length: no EOS bookkeeping
-            elif min_new_tokens > 0:
-                self.set_suppressed(tuple(suppressed) + tuple(e for e in self.eos if e not in suppressed))
-            out = torch.full((self.B, gen_len), self.pad_id, dtype=torch.int64, device=self.dev)
-            self.prefill(ids, lengths=lengths)  # (draws the first token: draw 0)
-            out[:, 0] = self.token
-            for i in range(1, gen_len):
-                if stop_at_eos and i == min_new_tokens:
-                    self.set_suppressed(suppressed)
-                if stop_at_eos and i % self.EOS_POLL_STEPS == 0 and self.unfinished() == 0:
-                    break
-                self.decode_step(use_graph, sampled=True)
-                out[:, i] = self.token
-            if self.engine is not None:
-                self.check()
-            if stop_at_eos:
-                out = self._trim_after_eos(out)
+            with _held_back(self, self.eos, stop_at_eos and min_new_tokens > 0) as hold:
+                self._write_sampling_state()    # draw counter 0, nobody finished: one seed fixes the whole sequence
+                if not stop_at_eos:
+                    self.sample_state[8:16].fill_(-1)       # fixed length: no EOS bookkeeping
+                out = torch.full((self.B, gen_len), self.pad_id, dtype=torch.int64, device=self.dev)
+                self.prefill(ids, lengths=lengths)      # (draws the first token: draw 0)
+                out[:, 0] = self.token
+                for i in range(1, gen_len):
+                    if i == min_new_tokens:
+                        hold.release()
+                    if stop_at_eos and i % self.EOS_POLL_STEPS == 0 and self.unfinished() == 0:
+                        break
+                    self.decode_step(use_graph, sampled=True)
+                    out[:, i] = self.token
+                if self.engine is not None:
+                    self.check()
+                if stop_at_eos:
+                    out = self._trim_after_eos(out)
         finally:
             self._greedy_eos = False
-            if getattr(self, "_suppressed", ()) != suppressed:
-                self.set_suppressed(suppressed)
         return out[0] if self.B == 1 else out
 
     def _trim_after_eos(self, out):
@@ -1176,9 +1187,7 @@ class DenseLlama(QuantLlama):
         if not 1 <= int(batch) <= 8:
             raise ValueError("batch must be 1..8")
         self.B = self.R = int(batch)
-        self._dense_init(config, device, max_seq, seed)
-
-    def _dense_init(self, config, device, max_seq, seed):
+        self.ragged, self.lookup, self.ngram_max = False, 0, 0     # (one position for the whole batch, one row per sequence and step)
         self.cfg = config
         self.dev = torch.device(device)
         _prime_graph_state(self.dev)
@@ -1207,16 +1216,7 @@ class DenseLlama(QuantLlama):
         self.norm = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
         self.x = torch.zeros(self.B, self.H, **f16)
         self.att = torch.zeros(self.B, self.H, **f16)
-        self.logits = torch.zeros(self.vocab, **f16) if self.B == 1 else torch.zeros(self.B, self.vocab, **f16)
-        self.token = torch.zeros(self.B, dtype=torch.int64, device=dev)
-        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.rope_tab = ops.rope_table(max_seq, self.theta, dev)
-        # step state: cos/sin row of self.pos + the position itself in one block (set_token / the step's tail keep it)
-        self.rope_cur, self.pos, self.step_err = ops.new_step_state(dev)
-        self.rope_cur.copy_(self.rope_tab.view(max_seq, 128)[0])
-        self.graph = None
-        self.host_pos = 0
-        self.suppress = torch.full((8,), -1, dtype=torch.int32, device=dev)
+        self._init_step_state((None, 1.0))      # (plain rope_theta frequencies)
         self.engine = None           # (the one-launch-per-token engine serves the quantized runner only)
 
     def linear_bytes_per_token(self):
@@ -1225,7 +1225,9 @@ class DenseLlama(QuantLlama):
     def set_sampling(self, *args, **kwargs):
         raise NotImplementedError("sampled decoding is served by QuantLlama; the fp16 baseline decodes greedily")
 
-    def _step(self):
+    def _step(self, sampled=False):
+        if sampled:
+            raise NotImplementedError("sampled decoding is served by QuantLlama; the fp16 baseline decodes greedily")
         F = torch.nn.functional
         x = self.x
         for blk in self.blocks:
@@ -1250,7 +1252,7 @@ class DenseLlama(QuantLlama):
     def _rows_up_gated(self, w, inp, gate):
         return ops.silu_mul(gate, torch.nn.functional.linear(inp, w), out=gate)
 
-    def _prefill_eager(self, ids, start_pos=0, b=None):
+    def _prefill_eager(self, ids, start_pos=0):
         F = torch.nn.functional
         S = ids.numel()
         if start_pos + S > self.max_seq:
@@ -1260,13 +1262,12 @@ class DenseLlama(QuantLlama):
         for blk in self.blocks:
             h = ops.rmsnorm(x, blk["ln1"], self.eps)
             q, k, v = F.linear(h, blk["self_attn.q_proj"]), F.linear(h, blk["self_attn.k_proj"]), F.linear(h, blk["self_attn.v_proj"])
-            kc, vc = self._cache_rows(blk, b)
-            ops.rope_cache(q, k, v, kc[0], vc[0], self.rope_tab, start_pos, nh, nkv)
-            x = torch.addmm(x, self._prefill_attention(q, blk, S, start_pos, b), blk["self_attn.o_proj"].t())
+            ops.rope_cache(q, k, v, blk["kc"][0], blk["vc"][0], self.rope_tab, start_pos, nh, nkv)
+            x = torch.addmm(x, self._prefill_attention(q, blk, S, start_pos), blk["self_attn.o_proj"].t())
             h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
             g, u = F.linear(h2, blk["mlp.gate_proj"]), F.linear(h2, blk["mlp.up_proj"])
             x = torch.addmm(x, ops.silu_mul(g, u, out=g), blk["mlp.down_proj"].t())
-        return self._prefill_finish(x, S, start_pos, b)
+        return self._prompt_finish(x, 1, S, start_pos)
 
 
 def get_memory_footprint(model, return_buffers=True):

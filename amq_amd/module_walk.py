@@ -116,21 +116,17 @@ class ModuleWalkLlama(nn.Module):
     def capture(self):
         if self.graph is not None:
             return
+        from .llama import capture_graph
         r = self.r
-        side = torch.cuda.Stream(device=r.dev)
-        side.wait_stream(torch.cuda.current_stream(r.dev))
-        saved = (r.token.clone(), r.host_pos)
-        with torch.cuda.stream(side):
-            self._step()
-            side.synchronize()
-            r.set_pos(saved[1]); r.set_token(saved[0])
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                self._step()
-        torch.cuda.current_stream(r.dev).wait_stream(side)
+        token, pos = r.token.clone(), r.host_pos
+
+        def restore():
+            r.set_pos(pos)
+            r.set_token(token)
+
+        self.graph = capture_graph(r.dev, self._step, restore)
         torch.cuda.synchronize(r.dev)
-        r.set_pos(saved[1]); r.set_token(saved[0])
-        self.graph = g
+        restore()
 
     def decode_step(self, use_graph=False):
         r = self.r
