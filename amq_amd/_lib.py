@@ -50,6 +50,13 @@ class GemvOpts(ctypes.Structure):
     _fields_ = [("math", _i), ("waves", _i), ("depth", _i), ("rpt", _i), ("dot", _i)]
 
 
+class QkNorm(ctypes.Structure):
+    """mirror of `amq_qk_norm` (include/amq_hip.h): Qwen3's per-head q / k RMSNorm weights (fp16 [128], device) and eps"""
+    _fields_ = [("q_gamma", _vp), ("k_gamma", _vp), ("eps", _f)]
+
+
+_qkn = ctypes.POINTER(QkNorm)
+
 # name -> (restype, argtypes); must list every symbol include/amq_hip.h declares
 SIGNATURES = {
     "amq_version": (_i, []),
@@ -116,6 +123,14 @@ SIGNATURES = {
     "amq_rope_cache_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "amq_rope_cache_batch_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "amq_rope_rows_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    # the rotating entry points with Qwen3's per-head q / k RMSNorm inside the kernel: the signature of the entry point without `_qkn` behind a QkNorm*
+    "amq_attn_decode_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "amq_attn_decode_cur_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "amq_attn_decode_split_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _sz, _vp, _vp]),
+    "amq_attn_decode_seq_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "amq_attn_decode_rows_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "amq_rope_cache_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "amq_rope_rows_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "amq_silu_mul_f16": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "amq_gemv_grouped_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, ctypes.POINTER(GemvOpts), _vp]),
     "amq_gemv_grouped_sums_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),

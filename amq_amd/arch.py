@@ -20,20 +20,37 @@ LINEARS = ["self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_att
            "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"]
 
 
-def _cfg(n_block, hidden, inter, heads, kv_heads, numel, vocab=32000, **extra):
-    """``extra``: rms_norm_eps, rope_theta, rope_scaling (HF's dict, "llama3"), qkv_bias (Qwen2: q / k / v projections carry a bias)"""
-    kv = hidden * kv_heads // heads
+def _cfg(n_block, hidden, inter, heads, kv_heads, numel, vocab=32000, head_dim=None, **extra):
+    """``extra``: rms_norm_eps, rope_theta, rope_scaling (HF's dict, "llama3"), qkv_bias (Qwen2: q / k / v projections carry a bias), qk_norm (Qwen3:
+    an RMSNorm over every head of q and of k in front of the rotation).
+    ``head_dim``: the config's own field where it has one (Qwen3: 128 at every size, while hidden_size is not heads * 128 at 0.6B / 4B / 32B) -- the
+    q / o projections are then heads * head_dim wide, k / v kv_heads * head_dim; None: hidden // heads, the square q / o of the Llama family."""
+    if head_dim is None:
+        head_dim = hidden // heads
+        qd, kv = hidden, hidden * kv_heads // heads
+    else:
+        qd, kv = heads * head_dim, kv_heads * head_dim
     return {
         **extra,
         "n_block": n_block, "hidden_size": hidden, "intermediate_size": inter, "num_heads": heads,
-        "num_kv_heads": kv_heads, "head_dim": hidden // heads, "vocab_size": vocab, "model_numel": numel,
+        "num_kv_heads": kv_heads, "head_dim": head_dim, "vocab_size": vocab, "model_numel": numel,
         "linear": list(LINEARS),
         "linear_shape": {
-            "self_attn.q_proj": [hidden, hidden], "self_attn.k_proj": [kv, hidden],
-            "self_attn.v_proj": [kv, hidden], "self_attn.o_proj": [hidden, hidden],
+            "self_attn.q_proj": [qd, hidden], "self_attn.k_proj": [kv, hidden],
+            "self_attn.v_proj": [kv, hidden], "self_attn.o_proj": [hidden, qd],
             "mlp.gate_proj": [inter, hidden], "mlp.up_proj": [inter, hidden], "mlp.down_proj": [hidden, inter],
         },
     }
+
+
+def linear_numel(n_block, hidden, inter, heads, kv_heads, head_dim):
+    """weights in the 7 linears of n_block blocks (what the reference's configs list as model_numel)"""
+    return n_block * (2 * hidden * heads * head_dim + 2 * hidden * kv_heads * head_dim + 3 * hidden * inter)
+
+
+def _qwen3(n_block, hidden, inter, heads, kv_heads=8):
+    return _cfg(n_block, hidden, inter, heads, kv_heads, linear_numel(n_block, hidden, inter, heads, kv_heads, 128), vocab=151936, head_dim=128,
+                rope_theta=1000000.0, rms_norm_eps=1e-6, qk_norm=True)
 
 
 _LLAMA3_SCALING = {"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0, "high_freq_factor": 4.0, "original_max_position_embeddings": 8192}
@@ -53,8 +70,17 @@ MODEL_CONFIGS = {
     "Qwen2.5-14B": _cfg(48, 5120, 13824, 40, 8, 13212057600, vocab=152064, rope_theta=1000000.0, rms_norm_eps=1e-6, qkv_bias=True),
     "Qwen2.5-32B": _cfg(64, 5120, 27648, 40, 8, 31205621760, vocab=152064, rope_theta=1000000.0, rms_norm_eps=1e-6, qkv_bias=True),
     "Qwen2.5-72B": _cfg(80, 8192, 29568, 64, 8, 70212648960, vocab=152064, rope_theta=1000000.0, rms_norm_eps=1e-6, qkv_bias=True),
+    # Qwen3 dense (not in the reference): the Llama block + per-head q / k RMSNorm, head_dim a field of its own (128 at every size; hidden_size is not
+    # heads * 128 at 0.6B / 4B / 32B), no q / k / v bias.  Dimensions as in the models' published config.json; model_numel counted from them
+    "Qwen3-0.6B": _qwen3(28, 1024, 3072, 16),
+    "Qwen3-1.7B": _qwen3(28, 2048, 6144, 16),
+    "Qwen3-4B": _qwen3(36, 2560, 9728, 32),
+    "Qwen3-8B": _qwen3(36, 4096, 12288, 32),
+    "Qwen3-14B": _qwen3(40, 5120, 17408, 40),
+    "Qwen3-32B": _qwen3(64, 5120, 25600, 64),
     # small shapes for tests / smoke (not in the reference)
     "tiny-llama-test": _cfg(2, 256, 512, 4, 4, 2 * (4 * 256 * 256 + 3 * 256 * 512), vocab=1000),
+    "tiny-qwen3-test": _cfg(2, 256, 512, 4, 2, linear_numel(2, 256, 512, 4, 2, 128), vocab=1000, head_dim=128, rms_norm_eps=1e-6, qk_norm=True),
 }
 
 # Llama-2-7B layers whose measured sensitivity exceeds 2x the median are pinned to 4 bit by the

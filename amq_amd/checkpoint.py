@@ -48,15 +48,17 @@ def load_hqq_dir(path):
 
 def runner_config(hf):
     """HF LlamaConfig json -> the dict arch.MODEL_CONFIGS uses"""
-    from .arch import _cfg
+    from .arch import _cfg, linear_numel
     hd = hf.get("head_dim") or hf["hidden_size"] // hf["num_attention_heads"]
     if hd != 128:
         raise ValueError("head_dim must be 128")
     kv = hf.get("num_key_value_heads") or hf["num_attention_heads"]
-    numel = hf["num_hidden_layers"] * (2 * hf["hidden_size"] * hf["hidden_size"] + 2 * hf["hidden_size"] * kv * 128
-                                       + 3 * hf["hidden_size"] * hf["intermediate_size"])
+    # (head_dim is the config's own field where it has one: Qwen3's q / o projections are heads * 128 wide, which is not hidden_size at every size)
+    numel = linear_numel(hf["num_hidden_layers"], hf["hidden_size"], hf["intermediate_size"], hf["num_attention_heads"], kv, hd)
     c = dict(_cfg(hf["num_hidden_layers"], hf["hidden_size"], hf["intermediate_size"], hf["num_attention_heads"], kv,
-                  numel, vocab=hf["vocab_size"]))
+                  numel, vocab=hf["vocab_size"], head_dim=hd))
+    if hf.get("model_type") == "qwen3":
+        c["qk_norm"] = True
     c["rms_norm_eps"] = float(hf.get("rms_norm_eps", 1e-5))
     c["rope_theta"] = float(hf.get("rope_theta", 10000.0) or 10000.0)
     return c

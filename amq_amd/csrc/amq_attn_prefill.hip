@@ -323,6 +323,8 @@ struct AttnGqaArgs {
     float rope_theta;
     int iters;                  // stages of AG_STAGE_KEYS keys per workgroup (chunk = AG_STAGE_KEYS * iters)
 };
+// QKN instantiations: the same block with the q / k norm's weights and eps behind it (the kernarg layout of the others is untouched)
+struct AttnGqaArgsQkn : AttnGqaArgs { QkNorm nrm; };
 constexpr int AG_WS_STRIDE = 132;       // floats per (query head, chunk) in the workspace: O[128], m, l, pad (amq_decode.hip: ATT_WS_STRIDE)
 constexpr int AG_OM_STRIDE = 132;       // floats per (wave, query row) of the cross-wave merge area
 constexpr int AG_STAGE = 512;           // bytes in front of the stage buffers: rotated new key [128], new value [128]
@@ -331,8 +333,12 @@ constexpr int AG_STAGE_KEYS = 128;      // keys per stage: two tiles of 64
 // SEQ (amq_attn_decode_seq_f16; step-state mode): a.state is block 0 of an array of gridDim.y step-state blocks STEP_STRIDE bytes apart, sequence
 // blockIdx.y reads ITS block (position, cos / sin row) and raises ITS error word; chunks and the appending workgroup follow from that position.
 // The !SEQ instantiation is the shared-position kernel as it was.
-template <bool SEQ>
-__global__ __launch_bounds__(256) void attn_decode_gqa_kernel(AttnGqaArgs a) {
+// QKN (amq_*_qkn_f16): q and the new k are normalised per head in front of the rotation (amq_common.cuh qkn_*, the shared tree order).  A query head's 128
+// values sit in the 4 lanes that share lane & 15, pair i = 32 t + 8 o + e in lane o's fragments (t, t + 2): tree levels 0 .. 2 over e in the lane, levels
+// 3 .. 4 over o across the lanes (two xor shuffles for each t), level 5 over t in the lane again.  The new key: the first 64 threads, one pair each, as in
+// the per-head kernels (wave 0's DPP reduction) -- the cache row this kernel writes has their bits.
+template <bool SEQ, bool QKN = false>
+__global__ __launch_bounds__(256) void attn_decode_gqa_kernel(std::conditional_t<QKN, AttnGqaArgsQkn, AttnGqaArgs> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -414,13 +420,38 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(AttnGqaArgs a) {
             csk = (h2){(_Float16)c_, (_Float16)sn};
         }
     }
+    h8 gqf[4];                                      // QKN: the q norm's weights in this lane's fragment order; the k norm's for the first 64 threads' pairs
+    _Float16 gk0 = 0, gk1 = 0;
+    if constexpr (QKN) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) gqf[t] = *(const h8*)((const _Float16*)a.nrm.q_gamma + 32 * t + 8 * o);
+    }
     if (tid < 64) {
         const _Float16* const kn = (const _Float16*)a.k + ((size_t)b * a.n_kv_heads + kvh) * AP_D;
         const _Float16* const vn = (const _Float16*)a.v + ((size_t)b * a.n_kv_heads + kvh) * AP_D;
         k0 = kn[tid]; k1 = kn[tid + 64];
         v0 = vn[tid]; v1 = vn[tid + 64];
+        if constexpr (QKN) { gk0 = ((const _Float16*)a.nrm.k_gamma)[tid]; gk1 = ((const _Float16*)a.nrm.k_gamma)[tid + 64]; }
     }
     AMQ_WAIT_VM("attn.gqa.landed", 0, "");          // this wave's share of stage 0 and its loads
+    if constexpr (QKN) {
+        float st[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            st[t] = qkn_tree8(qf[t], qf[t + 2]);
+            st[t] += __shfl_xor(st[t], 16);
+            st[t] += __shfl_xor(st[t], 32);
+        }
+        const float rq = qkn_rstd(st[0] + st[1], a.nrm.eps);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) qf[t][e] = qkn_apply(qf[t][e], rq, gqf[t][e]);
+        if (tid < 64) {                             // wave 0 (wave-uniform): attn_decode_kernel's reduction
+            const float rk = qkn_rstd(wave_sum_dpp(qkn_pair(k0, k1)), a.nrm.eps);
+            k0 = qkn_apply(k0, rk, gk0); k1 = qkn_apply(k1, rk, gk1);
+        }
+    }
     // rotation: q' = q * cos + rotate_half(q) * sin in fp16 (HF apply_rotary_pos_emb; the decode kernels' expression): pair (d, d + 64) = fragments t, t + 2
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -661,10 +692,20 @@ hipError_t launch_attn_decode_gqa(const AttnArgs& a, int batch, int n_splits, vo
                   (float*)ws, a.pos, a.n_heads, a.n_kv_heads, a.max_seq, n_splits, (int)cur, a.rope_theta, attn_decode_gqa_iters(a.max_seq, n_splits)};
     const size_t lds = AG_STAGE + (size_t)2 * 4 * AP_TILE;         // two stage buffers of two tiles x (K | V); the cross-wave merge reuses them
     static_assert((size_t)(4 * 16 * AG_OM_STRIDE + 4 * 16 * 2) * sizeof(float) <= (size_t)2 * 4 * AP_TILE, "merge area inside the stage buffers");
-    static unsigned long long attr_done = 0, attr_seq_done = 0;
-    if (hipError_t e = a.seq ? ensure_dyn_lds(attr_seq_done, (const void*)attn_decode_gqa_kernel<true>, (int)lds)
-                             : ensure_dyn_lds(attr_done, (const void*)attn_decode_gqa_kernel<false>, (int)lds)) return e;
-    hipLaunchKernelGGL(a.seq ? attn_decode_gqa_kernel<true> : attn_decode_gqa_kernel<false>, dim3(g.n_kv_heads, batch, g.n_splits), dim3(256), lds, st, g);
+    static unsigned long long attr_done = 0, attr_seq_done = 0, attr_qkn_done = 0, attr_seq_qkn_done = 0;
+    if (a.norm.q_gamma) {
+        AttnGqaArgsQkn gn;
+        static_cast<AttnGqaArgs&>(gn) = g;
+        gn.nrm = a.norm;
+        if (hipError_t e = a.seq ? ensure_dyn_lds(attr_seq_qkn_done, (const void*)attn_decode_gqa_kernel<true, true>, (int)lds)
+                                 : ensure_dyn_lds(attr_qkn_done, (const void*)attn_decode_gqa_kernel<false, true>, (int)lds)) return e;
+        const auto kern = a.seq ? attn_decode_gqa_kernel<true, true> : attn_decode_gqa_kernel<false, true>;
+        hipLaunchKernelGGL(kern, dim3(g.n_kv_heads, batch, g.n_splits), dim3(256), lds, st, gn);
+    } else {
+        if (hipError_t e = a.seq ? ensure_dyn_lds(attr_seq_done, (const void*)attn_decode_gqa_kernel<true>, (int)lds)
+                                 : ensure_dyn_lds(attr_done, (const void*)attn_decode_gqa_kernel<false>, (int)lds)) return e;
+        hipLaunchKernelGGL(a.seq ? attn_decode_gqa_kernel<true> : attn_decode_gqa_kernel<false>, dim3(g.n_kv_heads, batch, g.n_splits), dim3(256), lds, st, g);
+    }
     if (hipError_t e = hipGetLastError()) return e;
 #ifdef AMQ_GQA_ABL_NO_COMBINE          /* timing-only ablation: what the combine launch adds to the step (results wrong beyond one chunk) */
     return hipSuccess;

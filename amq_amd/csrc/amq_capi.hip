@@ -539,6 +539,16 @@ int amq_decode_engine_f16(const void* blocks_dev, int n_block, int hidden, int i
 }
 #endif  // AMQ_AB_ROUTES
 
+/* the q / k norm of the amq_*_qkn_f16 entry points: NULL = none (the entry point without the suffix); else both weights */
+static int qk_norm_arg(const amq_qk_norm* norm, amq::QkNorm* out) {
+    *out = amq::QkNorm{nullptr, nullptr, 0.f};
+    if (!norm) return AMQ_OK;
+    if (!norm->q_gamma || !norm->k_gamma) return fail(AMQ_EINVAL, "q / k norm: q_gamma and k_gamma go together (one of them is null)");
+    if (!(norm->eps >= 0.f)) return fail(AMQ_EINVAL, "q / k norm: eps must be >= 0");
+    *out = amq::QkNorm{norm->q_gamma, norm->k_gamma, norm->eps};
+    return AMQ_OK;
+}
+
 int amq_rope_cache_f16(void* q, const void* k, const void* v, void* kcache, void* vcache, const void* rope_table,
                        int rope_rows, int pos0, int S, int n_heads, int n_kv_heads, int head_dim, int max_seq, void* stream) {
     if (!q || !k || !v || !kcache || !vcache || !rope_table) return fail(AMQ_EINVAL, "null pointer");
@@ -553,24 +563,39 @@ int amq_rope_cache_f16(void* q, const void* k, const void* v, void* kcache, void
 int amq_rope_cache_batch_f16(void* q, const void* k, const void* v, void* kcache, void* vcache, const void* rope_table,
                              int rope_rows, int pos0, int S, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
                              void* stream) {
+    return amq_rope_cache_qkn_f16(nullptr, q, k, v, kcache, vcache, rope_table, rope_rows, pos0, S, batch, n_heads, n_kv_heads, head_dim, max_seq, stream);
+}
+
+int amq_rope_cache_qkn_f16(const amq_qk_norm* norm, void* q, const void* k, const void* v, void* kcache, void* vcache, const void* rope_table,
+                           int rope_rows, int pos0, int S, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
+                           void* stream) {
+    amq::QkNorm nrm;
+    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
     if (!q || !k || !v || !kcache || !vcache || !rope_table) return fail(AMQ_EINVAL, "null pointer");
     if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
     if (S < 1 || batch < 1 || n_heads < 1 || n_kv_heads < 1 || rope_rows < 1) return fail(AMQ_ESHAPE, "bad sizes");
     if (pos0 < 0 || pos0 + S > max_seq) return fail(AMQ_ESHAPE, "rows %d..%d do not fit the cache (max_seq %d)", pos0, pos0 + S, max_seq);
     if ((long long)S * batch * (n_heads + n_kv_heads) > (1ll << 36)) return fail(AMQ_ESHAPE, "too many rows for one launch");
     return check_hip(amq::launch_rope_cache(q, k, v, kcache, vcache, rope_table, rope_rows, pos0, S, n_heads, n_kv_heads, max_seq,
-                                            (hipStream_t)stream, batch), "rope_cache_batch");
+                                            (hipStream_t)stream, batch, norm ? &nrm : nullptr), "rope_cache_batch");
 }
 
 int amq_rope_rows_f16(void* q, void* k, const void* rope_table, int rope_rows, int pos0, int rows, int seq_len, int n_heads,
                       int n_kv_heads, int head_dim, void* stream) {
+    return amq_rope_rows_qkn_f16(nullptr, q, k, rope_table, rope_rows, pos0, rows, seq_len, n_heads, n_kv_heads, head_dim, stream);
+}
+
+int amq_rope_rows_qkn_f16(const amq_qk_norm* norm, void* q, void* k, const void* rope_table, int rope_rows, int pos0, int rows, int seq_len,
+                          int n_heads, int n_kv_heads, int head_dim, void* stream) {
+    amq::QkNorm nrm;
+    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
     if (!q || !k || !rope_table) return fail(AMQ_EINVAL, "null pointer");
     if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
     if (rows < 1 || seq_len < 1 || (rows % seq_len) != 0 || n_heads < 1 || n_kv_heads < 1 || rope_rows < 1 || pos0 < 0)
         return fail(AMQ_ESHAPE, "bad sizes (rows=%d must be a multiple of seq_len=%d)", rows, seq_len);
     if ((long long)rows * (n_heads + n_kv_heads) > (1ll << 36)) return fail(AMQ_ESHAPE, "rows=%d exceeds one launch", rows);
     return check_hip(amq::launch_rope_rows(q, k, rope_table, rope_rows, pos0, rows, seq_len, n_heads, n_kv_heads,
-                                           (hipStream_t)stream), "rope_rows");
+                                           (hipStream_t)stream, norm ? &nrm : nullptr), "rope_rows");
 }
 
 int amq_silu_mul_f16(const void* gate, const void* up, void* out, size_t n, void* stream) {
@@ -724,6 +749,14 @@ int amq_gemv_f16w_rows(const void* x, const void* W, const void* bias, void* y, 
 int amq_attn_decode_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                         const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
                         int max_seq, float rope_theta, const void* rope_table, void* stream) {
+    return amq_attn_decode_qkn_f16(nullptr, q, k, v, kcache, vcache, out, pos_dev, pos, batch, n_heads, n_kv_heads, head_dim, max_seq, rope_theta, rope_table, stream);
+}
+
+int amq_attn_decode_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                            const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
+                            int max_seq, float rope_theta, const void* rope_table, void* stream) {
+    amq::QkNorm nrm;
+    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
     if (!q || !k || !v || !kcache || !vcache || !out) return fail(AMQ_EINVAL, "null pointer");
     if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
     if (batch < 1 || n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
@@ -731,12 +764,21 @@ int amq_attn_decode_f16(const void* q, const void* k, const void* v, void* kcach
     if (max_seq < 1 || (!pos_dev && (pos < 0 || pos >= max_seq))) return fail(AMQ_ESHAPE, "position %d outside the cache (max_seq=%d)", pos, max_seq);
     if (6 * 128 + (size_t)max_seq * 4 + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
     amq::AttnArgs a{q, k, v, kcache, vcache, out, pos_dev, pos, n_heads, n_kv_heads, max_seq, rope_theta, rope_table, nullptr};
+    a.norm = nrm;
     return check_hip(amq::launch_attn_decode(a, batch, (hipStream_t)stream), "attn_decode");
 }
 
 int amq_attn_decode_cur_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                             const void* step_state, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
                             void* stream) {
+    return amq_attn_decode_cur_qkn_f16(nullptr, q, k, v, kcache, vcache, out, step_state, batch, n_heads, n_kv_heads, head_dim, max_seq, stream);
+}
+
+int amq_attn_decode_cur_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                const void* step_state, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
+                                void* stream) {
+    amq::QkNorm nrm;
+    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
     if (!q || !k || !v || !kcache || !vcache || !out || !step_state) return fail(AMQ_EINVAL, "null pointer");
     if (n_heads > 255) return fail(AMQ_ESHAPE, "at most 255 heads");
     if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
@@ -745,6 +787,7 @@ int amq_attn_decode_cur_f16(const void* q, const void* k, const void* v, void* k
     if (max_seq < 1) return fail(AMQ_ESHAPE, "bad max_seq %d", max_seq);
     if (6 * 128 + (size_t)max_seq * 4 + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
     amq::AttnArgs a{q, k, v, kcache, vcache, out, nullptr, 0, n_heads, n_kv_heads, max_seq, 10000.0f, nullptr, step_state};
+    a.norm = nrm;
     return check_hip(amq::launch_attn_decode(a, batch, (hipStream_t)stream), "attn_decode_cur");
 }
 
@@ -757,6 +800,16 @@ int amq_attn_decode_split_f16(const void* q, const void* k, const void* v, void*
                               const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads,
                               int head_dim, int max_seq, float rope_theta, const void* rope_table, int n_splits,
                               void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
+    return amq_attn_decode_split_qkn_f16(nullptr, q, k, v, kcache, vcache, out, step_state, pos_dev, pos, batch, n_heads, n_kv_heads, head_dim, max_seq, rope_theta, rope_table, n_splits,
+                                         workspace, workspace_bytes, tickets, stream);
+}
+
+int amq_attn_decode_split_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                  const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads,
+                                  int head_dim, int max_seq, float rope_theta, const void* rope_table, int n_splits,
+                                  void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
+    amq::QkNorm nrm;
+    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
     if (!q || !k || !v || !kcache || !vcache || !out || !workspace || !tickets) return fail(AMQ_EINVAL, "null pointer");
     if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
     if (batch < 1 || batch > 65535 || n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
@@ -772,6 +825,7 @@ int amq_attn_decode_split_f16(const void* q, const void* k, const void* v, void*
     if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     amq::AttnArgs a{q, k, v, kcache, vcache, out, step_state ? nullptr : pos_dev, pos, n_heads, n_kv_heads, max_seq,
                     step_state ? 10000.0f : rope_theta, step_state ? nullptr : rope_table, step_state};
+    a.norm = nrm;
     return check_hip(amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream), "attn_decode_split");
 }
 
@@ -896,6 +950,14 @@ static_assert(AMQ_STEP_STATE_STRIDE == amq::STEP_STRIDE && AMQ_STEP_STATE_STRIDE
 int amq_attn_decode_seq_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int batch,
                             int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
                             void* tickets, void* stream) {
+    return amq_attn_decode_seq_qkn_f16(nullptr, q, k, v, kcache, vcache, out, step_states, batch, n_heads, n_kv_heads, head_dim, max_seq, n_splits, workspace, workspace_bytes, tickets, stream);
+}
+
+int amq_attn_decode_seq_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                void* step_states, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
+                                void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
+    amq::QkNorm nrm;
+    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
     if (!q || !k || !v || !kcache || !vcache || !out || !step_states) return fail(AMQ_EINVAL, "null pointer");
     if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
     if (batch < 1 || batch > 65535 || n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
@@ -903,6 +965,7 @@ int amq_attn_decode_seq_f16(const void* q, const void* k, const void* v, void* k
     if (max_seq < 1) return fail(AMQ_ESHAPE, "bad max_seq %d", max_seq);
     if (n_splits < 0 || n_splits > 1024) return fail(AMQ_EINVAL, "n_splits must be 0 (one workgroup per head) or 1..1024 (got %d)", n_splits);
     amq::AttnArgs a{q, k, v, kcache, vcache, out, nullptr, 0, n_heads, n_kv_heads, max_seq, 10000.0f, nullptr, step_states, true};
+    a.norm = nrm;
     if (n_splits == 0) {
         if (6 * 128 + (size_t)max_seq * 4 + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
         return check_hip(amq::launch_attn_decode(a, batch, (hipStream_t)stream), "attn_decode_seq");
@@ -960,6 +1023,14 @@ static_assert(AMQ_LOOKUP_STATE_WORDS == amq::LK_WORDS && AMQ_LOOKUP_MAX_ROWS == 
 int amq_attn_decode_rows_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int rows,
                              int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
                              void* tickets, void* stream) {
+    return amq_attn_decode_rows_qkn_f16(nullptr, q, k, v, kcache, vcache, out, step_states, rows, n_heads, n_kv_heads, head_dim, max_seq, n_splits, workspace, workspace_bytes, tickets, stream);
+}
+
+int amq_attn_decode_rows_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                 void* step_states, int rows, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
+                                 void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
+    amq::QkNorm nrm;
+    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
     if (!q || !k || !v || !kcache || !vcache || !out || !step_states) return fail(AMQ_EINVAL, "null pointer");
     if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
     if (rows < 2 || rows > AMQ_LOOKUP_MAX_ROWS) return fail(AMQ_ESHAPE, "rows must be 2..%d (got %d)", AMQ_LOOKUP_MAX_ROWS, rows);
@@ -968,6 +1039,7 @@ int amq_attn_decode_rows_f16(const void* q, const void* k, const void* v, void* 
     if (max_seq < 1) return fail(AMQ_ESHAPE, "bad max_seq %d", max_seq);
     if (n_splits < 0 || n_splits > 1024) return fail(AMQ_EINVAL, "n_splits must be 0 (one workgroup per head) or 1..1024 (got %d)", n_splits);
     amq::AttnArgs a{q, k, v, kcache, vcache, out, nullptr, 0, n_heads, n_kv_heads, max_seq, 10000.0f, nullptr, step_states, true, true};
+    a.norm = nrm;
     const size_t rows_lds = 2 * 7 * 128 * 2 + 16;      // the earlier rows' rotated keys and values behind the score array
     if (n_splits == 0) {
         if (6 * 128 + (size_t)max_seq * 4 + rows_lds + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);

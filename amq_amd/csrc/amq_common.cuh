@@ -75,6 +75,49 @@ enum { TILE_N = 16, TILE_K = 128, GROUP = 128 };
 #define AMQ_WAIT_LGKM0(name) asm volatile("s_waitcnt lgkmcnt(0) ; AMQ_WAIT id=" name " lgkm" ::: "memory")
 #define AMQ_MARK(name) " ; AMQ_MARK id=" name
 
+// 8-lane (half of a DPP row) all-reduce: levels over lane bit 0, 1, 2
+__device__ __forceinline__ float row8_sum(float v) {
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2]
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));   // row_half_mirror
+    return v;
+}
+// 16-lane (DPP row) all-reduce: after it every lane of a row holds the row's sum
+__device__ __forceinline__ float row16_sum(float v) {
+    v = row8_sum(v);
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));   // row_mirror
+    return v;
+}
+
+// whole-wave reductions without LDS-crossbar shuffles (6 dependent ds_bpermute round trips cost ~0.35 us each):
+// DPP inside the four 16-lane rows, then four v_readlane
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+    v = row16_sum(v);
+    return (__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)) +
+            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16))) +
+           (__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)) +
+            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48)));
+}
+
+// ---- per-head q / k RMSNorm in front of the rotation (Qwen3: q_norm / k_norm over the 128 values of a head) ---------------------------
+// y = gamma * fp16(x * rstd), rstd = rsqrt(mean(x^2) + eps) in fp32: HF's Qwen3RMSNorm, the arithmetic of rmsnorm_kernel.  Every kernel that
+// rotates forms the statistic by ONE binary tree over the 64 pair sums p_i = x_i^2 + x_(i+64)^2, level by level over index bit 0, 1, .. 5 --
+// in-thread where a thread holds several pairs, across lanes (DPP / shuffle) where lanes do -- so a head normalised by any of them has the same
+// bits (what "a prefilled cache row equals the row a decode step appends" needs of the norm).
+__device__ __forceinline__ float qkn_pair(_Float16 a, _Float16 b) {
+    const float fa = (float)a, fb = (float)b;
+    return fa * fa + fb * fb;
+}
+__device__ __forceinline__ float qkn_rstd(float ss, float eps) { return rsqrtf(ss / 128.0f + eps); }
+__device__ __forceinline__ _Float16 qkn_apply(_Float16 x, float rstd, _Float16 g) { return g * (_Float16)((float)x * rstd); }
+// levels 0 .. 2 of the tree over eight pair sums a thread holds itself (pairs 8c .. 8c + 7 of its head)
+__device__ __forceinline__ float qkn_tree8(const h8& lo, const h8& hi) {
+    float p[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) p[e] = qkn_pair(lo[e], hi[e]);
+    return ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+}
+
 __device__ __forceinline__ h2 as_h2(uint32_t u) { return __builtin_bit_cast(h2, u); }
 __device__ __forceinline__ uint32_t as_u32(h2 v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ h2 bcast(_Float16 v) { return (h2){v, v}; }

@@ -11,6 +11,7 @@
 //                       with HF-Llama numerics (rotate_half RoPE, fp16 q/k/v, fp32 softmax).
 // The token position is read from device memory so a captured hipGraph can be
 // replayed for every token.
+#include <type_traits>
 #include "amq_common.cuh"
 #include "amq_kernels.h"
 
@@ -346,15 +347,6 @@ __device__ __forceinline__ void rope_cs(float theta, int pos, int i, _Float16* c
     *s16 = (_Float16)sn;
 }
 
-// 16-lane (DPP row) all-reduce: after it every lane of a row holds the row's sum
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));   // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));   // row_mirror
-    return v;
-}
-
 __device__ __forceinline__ float row16_max(float v) {
     v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false)));
     v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false)));
@@ -362,15 +354,7 @@ __device__ __forceinline__ float row16_max(float v) {
     v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false)));
     return v;
 }
-// whole-wave reductions without LDS-crossbar shuffles (6 dependent ds_bpermute round trips cost ~0.35 us each):
-// DPP inside the four 16-lane rows, then four v_readlane
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-    v = row16_sum(v);
-    return (__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)) +
-            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16))) +
-           (__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)) +
-            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48)));
-}
+// whole-wave reductions without LDS-crossbar shuffles: wave_sum_dpp (amq_common.cuh); the maximum likewise
 __device__ __forceinline__ float wave_max_dpp(float v) {
     v = row16_max(v);
     return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)),
@@ -403,6 +387,10 @@ struct AttnRest {
     unsigned long long* stamps;     // diagnostic build: [heads][16] s_memrealtime phase stamps
 #endif
 };
+// QKN instantiations (amq_*_qkn_f16: per-head RMSNorm of q and k in front of the rotation, amq_common.cuh qkn_*): the same block with the norm's two weight
+// rows and eps behind it -- the kernarg layout of the other instantiations is untouched
+struct AttnRestQkn : AttnRest { QkNorm nrm; };
+template <bool QKN> using AttnRestT = std::conditional_t<QKN, AttnRestQkn, AttnRest>;
 #ifdef AMQ_STAMP
 extern unsigned long long* g_stamp_ptr;
 #define ATT_STAMP(slot_) do { if (rest.stamps && threadIdx.x == 0) rest.stamps[(size_t)blockIdx.x * 16 + (slot_)] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -424,10 +412,13 @@ extern unsigned long long* g_stamp_ptr;
 // same order as the SEQ kernel at position p + j over a cache that already holds those rows: the same bits.
 constexpr int ATT_ROWS_MAX = 8;                              // rows of a ROWS launch (7 earlier rows at most = waves 1 .. 7)
 constexpr int ATT_ROWS_LDS = 2 * (ATT_ROWS_MAX - 1) * ATT_D * 2;   // bytes behind the score array: rotated keys and values of the earlier rows
-template <bool SEQ, bool ROWS = false>
+// QKN (amq_*_qkn_f16): q and the new k are normalised per head (rest.nrm) before rotate_and_append -- the 64 threads that hold the pairs (i, i + 64)
+// take both sums of squares within their wave (two wave reductions in the shared tree order of amq_common.cuh: qkn_*); ROWS: waves 1 .. b likewise
+// for the earlier rows' keys.  The weights are requested with the first loads of the kernel, in front of the speculative cache rows.
+template <bool SEQ, bool ROWS = false, bool QKN = false>
 __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, void* p_vc, const void* p_state, int p_heads,
                                                                    int p_max_seq, const void* p_q, const void* p_k,
-                                                                   const void* p_v, AttnRest rest) {
+                                                                   const void* p_v, AttnRestT<QKN> rest) {
     const void* const p_state0 = p_state;           // (ROWS: block 0 of the step's rows)
     if (SEQ) p_state = (const char*)p_state + (size_t)blockIdx.y * STEP_STRIDE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -468,11 +459,18 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
     // (two registers for the two possible sources of cos/sin: one variable with two defining loads makes the compiler wait
     // for the LATER one -- issued behind the speculative rows -- on both paths)
     h2 cs_cur = {(_Float16)1.f, (_Float16)0.f}, cs_tab = {(_Float16)1.f, (_Float16)0.f};
+    _Float16 gq0 = 0, gq1 = 0, gk0 = 0, gk1 = 0;    // QKN: the norm weights of this thread's pair
     if (tid < 64) {
         q0 = q[tid]; q1 = q[tid + 64];
         k0 = kn[tid]; k1 = kn[tid + 64];
         if (p_cur) cs_cur = ((const h2*)p_cur)[tid];
         v0 = vn[tid]; v1 = vn[tid + 64];
+        if constexpr (QKN) {
+            const _Float16* const gq = (const _Float16*)rest.nrm.q_gamma;
+            const _Float16* const gk = (const _Float16*)rest.nrm.k_gamma;
+            gq0 = gq[tid]; gq1 = gq[tid + 64];
+            gk0 = gk[tid]; gk1 = gk[tid + 64];
+        }
     }
     // speculative: the first ATT_SPEC * 32 key rows (clamped to the cache; rows >= pos are discarded later)
     h8 krow[ATT_PF], vrow[ATT_PF];
@@ -533,6 +531,13 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
             vc[(size_t)pos * ATT_D + i + 64] = v1;
         }
     };
+    if constexpr (QKN) {
+        if (tid < 64) {                             // wave 0: the head's statistic from its 64 pair sums, then q and k as the rotation takes them
+            const float rq = qkn_rstd(wave_sum_dpp(qkn_pair(q0, q1)), rest.nrm.eps), rk = qkn_rstd(wave_sum_dpp(qkn_pair(k0, k1)), rest.nrm.eps);
+            q0 = qkn_apply(q0, rq, gq0); q1 = qkn_apply(q1, rq, gq1);
+            k0 = qkn_apply(k0, rk, gk0); k1 = qkn_apply(k1, rk, gk1);
+        }
+    }
     if (tid < 64) {
         if (p_cur) {
             rotate_and_append(cs_cur.x, cs_cur.y);
@@ -549,7 +554,14 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(void* p_kc, vo
             const _Float16* kr = (const _Float16*)p_k + ((size_t)r * n_kv_heads + kvh) * ATT_D;
             const _Float16* vr = (const _Float16*)p_v + ((size_t)r * n_kv_heads + kvh) * ATT_D;
             const h2 cs = ((const h2*)((const char*)p_state0 + (size_t)r * STEP_STRIDE))[i];
-            const _Float16 a0 = kr[i], a1 = kr[i + 64], c16 = cs.x, s16 = cs.y;
+            _Float16 a0 = kr[i], a1 = kr[i + 64];
+            const _Float16 c16 = cs.x, s16 = cs.y;
+            if constexpr (QKN) {                    // the row's key as ITS workgroup normalises it (same tree, same bits)
+                const _Float16* const gk = (const _Float16*)rest.nrm.k_gamma;
+                const _Float16 g0 = gk[i], g1 = gk[i + 64];
+                const float rk = qkn_rstd(wave_sum_dpp(qkn_pair(a0, a1)), rest.nrm.eps);
+                a0 = qkn_apply(a0, rk, g0); a1 = qkn_apply(a1, rk, g1);
+            }
             kd[r * ATT_D + i] = a0 * c16 + (-a1) * s16;
             kd[r * ATT_D + i + 64] = a1 * c16 + a0 * s16;
             vd[r * ATT_D + i] = vr[i];
@@ -685,10 +697,11 @@ constexpr int ATT_WS_STRIDE = ATT_D + 4;       // floats per (head, chunk): O[12
 #endif
 // ROWS: attn_decode_kernel's -- every workgroup of row b (whatever its chunk) rotates rows 0 .. b - 1 of this step into LDS; the chunks follow from the row's
 // own position and the workgroup of the chunk that holds it appends it.
-template <int RING, bool SEQ, bool ROWS = false>
+// QKN: attn_decode_kernel's -- q and the new k normalised per head in front of the rotation (every chunk's workgroup rotates q; same bits in each).
+template <int RING, bool SEQ, bool ROWS = false, bool QKN = false>
 __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_kc, void* p_vc, const void* p_state, int p_heads,
                                                                          int p_max_seq, const void* p_q, const void* p_k,
-                                                                         const void* p_v, AttnRest rest, AttnSplit sp) {
+                                                                         const void* p_v, AttnRestT<QKN> rest, AttnSplit sp) {
     const void* const p_state0 = p_state;           // (ROWS: block 0 of the step's rows)
     if (SEQ) p_state = (const char*)p_state + (size_t)blockIdx.y * STEP_STRIDE;      // (attn_decode_kernel: the sequence's own step-state block)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -727,11 +740,18 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
 
     _Float16 q0 = 0, q1 = 0, k0 = 0, k1 = 0, v0 = 0, v1 = 0;
     h2 cs_cur = {(_Float16)1.f, (_Float16)0.f}, cs_tab = {(_Float16)1.f, (_Float16)0.f};
+    _Float16 gq0 = 0, gq1 = 0, gk0 = 0, gk1 = 0;    // QKN: the norm weights of this thread's pair
     if (tid < 64) {
         q0 = q[tid]; q1 = q[tid + 64];
         k0 = kn[tid]; k1 = kn[tid + 64];
         if (p_cur) cs_cur = ((const h2*)p_cur)[tid];
         v0 = vn[tid]; v1 = vn[tid + 64];
+        if constexpr (QKN) {
+            const _Float16* const gq = (const _Float16*)rest.nrm.q_gamma;
+            const _Float16* const gk = (const _Float16*)rest.nrm.k_gamma;
+            gq0 = gq[tid]; gq1 = gq[tid + 64];
+            gk0 = gk[tid]; gk1 = gk[tid + 64];
+        }
     }
     // a position outside the cache: nothing is appended or written (attn_decode_kernel's guard)
     const int p0 = ROWS ? pos - b : pos;             // ROWS: the position of row 0 = the first cache row this launch appends
@@ -778,6 +798,13 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
     static_assert(RING >= 1 && RING <= ATT_PF, "ring depth");
 #pragma unroll
     for (int i = 0; i < RING; ++i) load_k(i);
+    if constexpr (QKN) {
+        if (tid < 64) {                             // (attn_decode_kernel: the head's statistic within wave 0, q and k as the rotation takes them)
+            const float rq = qkn_rstd(wave_sum_dpp(qkn_pair(q0, q1)), rest.nrm.eps), rk = qkn_rstd(wave_sum_dpp(qkn_pair(k0, k1)), rest.nrm.eps);
+            q0 = qkn_apply(q0, rq, gq0); q1 = qkn_apply(q1, rq, gq1);
+            k0 = qkn_apply(k0, rk, gk0); k1 = qkn_apply(k1, rk, gk1);
+        }
+    }
     if (tid < 64) {
         _Float16 c16, s16;
         if (p_cur) { c16 = cs_cur.x; s16 = cs_cur.y; }
@@ -807,7 +834,14 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(void* p_
             const _Float16* kr = (const _Float16*)p_k + ((size_t)r * n_kv_heads + kvh) * ATT_D;
             const _Float16* vr = (const _Float16*)p_v + ((size_t)r * n_kv_heads + kvh) * ATT_D;
             const h2 cs = ((const h2*)((const char*)p_state0 + (size_t)r * STEP_STRIDE))[i];
-            const _Float16 a0 = kr[i], a1 = kr[i + 64], c16 = cs.x, s16 = cs.y;
+            _Float16 a0 = kr[i], a1 = kr[i + 64];
+            const _Float16 c16 = cs.x, s16 = cs.y;
+            if constexpr (QKN) {                    // the row's key as ITS workgroup normalises it (same tree, same bits)
+                const _Float16* const gk = (const _Float16*)rest.nrm.k_gamma;
+                const _Float16 g0 = gk[i], g1 = gk[i + 64];
+                const float rk = qkn_rstd(wave_sum_dpp(qkn_pair(a0, a1)), rest.nrm.eps);
+                a0 = qkn_apply(a0, rk, g0); a1 = qkn_apply(a1, rk, g1);
+            }
             kd[r * ATT_D + i] = a0 * c16 + (-a1) * s16;
             kd[r * ATT_D + i + 64] = a1 * c16 + a0 * s16;
             vd[r * ATT_D + i] = vr[i];
@@ -1037,6 +1071,16 @@ hipError_t launch_rope_table_freqs(void* tab, int max_seq, const void* inv_freq,
 // (eight threads per (row, head), 16-byte accesses: see rope_rows_kernel below)
 // Several sequences (rows = batch * seq_len, caches [batch][n_kv_heads][max_seq][128]): row s belongs to sequence s / seq_len
 // at position pos0 + s % seq_len.
+// rope_qkn_kernel (below): the head is normalised first (amq_common.cuh qkn_*) -- a thread holds the pairs 8c .. 8c + 7 of
+// its head (tree levels 0 .. 2 in the thread), the eight threads of a head are neighbouring lanes (levels 3 .. 5: three DPP steps, amq_common.cuh row8_sum).  Whole heads per
+// wave, so the early exit below leaves no lane of a live head behind.
+__device__ __forceinline__ void qkn_head8(h8& a0, h8& a1, const _Float16* gamma, int c, float eps) {
+    const h8 g0 = *(const h8*)(gamma + 8 * c), g1 = *(const h8*)(gamma + 64 + 8 * c);
+    const float rstd = qkn_rstd(row8_sum(qkn_tree8(a0, a1)), eps);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { a0[e] = qkn_apply(a0[e], rstd, g0[e]); a1[e] = qkn_apply(a1[e], rstd, g1[e]); }
+}
+
 __global__ __launch_bounds__(256) void rope_cache_kernel(_Float16* q, const _Float16* k, const _Float16* v, _Float16* kc,
                                                          _Float16* vc, const h2* tab, int rope_rows, int pos0, int nh, int nkv,
                                                          int max_seq, long units, int seq_len) {
@@ -1072,9 +1116,54 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(_Float16* q, const _Flo
     }
 }
 
+// The two kernels with the per-head q / k norm in front of the rotation (amq_rope_cache_qkn_f16 / amq_rope_rows_qkn_f16; CACHE: rope_cache_kernel's
+// destinations, else rope_rows_kernel's).  Same units, same fp16 rotation expression on the normalised head.
+template <bool CACHE>
+__global__ __launch_bounds__(256) void rope_qkn_kernel(_Float16* q, _Float16* k, const _Float16* v, _Float16* kc, _Float16* vc, const h2* tab,
+                                                       int rope_rows, int pos0, int nh, int nkv, int max_seq, long units, int seq_len,
+                                                       const _Float16* gq, const _Float16* gk, float eps) {
+    const long u = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
+    if (u >= units) return;
+    const int c = threadIdx.x & 7, nhk = nh + nkv;
+    const long s = u / nhk;
+    const int hx = (int)(u - s * nhk);
+    const int bseq = (int)(s / seq_len);
+    const int pos = pos0 + (int)(s - (long)bseq * seq_len);
+    const h2* cs = tab + (size_t)(pos < rope_rows ? pos : rope_rows - 1) * 64 + 8 * c;
+    const h8 cs0 = *(const h8*)cs, cs1 = *(const h8*)(cs + 4);
+    _Float16* const row = hx < nh ? q + ((size_t)s * nh + hx) * ATT_D : k + ((size_t)s * nkv + (hx - nh)) * ATT_D;
+    h8 a0 = *(const h8*)(row + 8 * c), a1 = *(const h8*)(row + 64 + 8 * c);
+    qkn_head8(a0, a1, hx < nh ? gq : gk, c, eps);
+    h8 r0, r1;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const _Float16 c16 = e < 4 ? cs0[2 * e] : cs1[2 * (e - 4)], s16 = e < 4 ? cs0[2 * e + 1] : cs1[2 * (e - 4) + 1];
+        r0[e] = a0[e] * c16 + (-a1[e]) * s16;
+        r1[e] = a1[e] * c16 + a0[e] * s16;
+    }
+    if (!CACHE || hx < nh) {
+        *(h8*)(row + 8 * c) = r0;
+        *(h8*)(row + 64 + 8 * c) = r1;
+    } else {
+        const int h = hx - nh;
+        const _Float16* vr = v + ((size_t)s * nkv + h) * ATT_D;
+        const size_t dst = (((size_t)bseq * nkv + h) * max_seq + pos) * ATT_D;
+        *(h8*)(kc + dst + 8 * c) = r0;
+        *(h8*)(kc + dst + 64 + 8 * c) = r1;
+        *(h8*)(vc + dst + 8 * c) = *(const h8*)(vr + 8 * c);
+        *(h8*)(vc + dst + 64 + 8 * c) = *(const h8*)(vr + 64 + 8 * c);
+    }
+}
+
 hipError_t launch_rope_cache(void* q, const void* k, const void* v, void* kcache, void* vcache, const void* rope_table,
-                             int rope_rows, int pos0, int S, int n_heads, int n_kv_heads, int max_seq, hipStream_t st, int batch) {
+                             int rope_rows, int pos0, int S, int n_heads, int n_kv_heads, int max_seq, hipStream_t st, int batch, const QkNorm* norm) {
     const long units = (long)S * batch * (n_heads + n_kv_heads);
+    if (norm) {
+        hipLaunchKernelGGL(rope_qkn_kernel<true>, dim3((unsigned)((units + 31) / 32)), dim3(256), 0, st, (_Float16*)q, (_Float16*)const_cast<void*>(k),
+                           (const _Float16*)v, (_Float16*)kcache, (_Float16*)vcache, (const h2*)rope_table, rope_rows, pos0, n_heads,
+                           n_kv_heads, max_seq, units, S, (const _Float16*)norm->q_gamma, (const _Float16*)norm->k_gamma, norm->eps);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(rope_cache_kernel, dim3((unsigned)((units + 31) / 32)), dim3(256), 0, st, (_Float16*)q, (const _Float16*)k,
                        (const _Float16*)v, (_Float16*)kcache, (_Float16*)vcache, (const h2*)rope_table, rope_rows, pos0, n_heads,
                        n_kv_heads, max_seq, units, S);
@@ -1110,8 +1199,14 @@ __global__ __launch_bounds__(256) void rope_rows_kernel(_Float16* q, _Float16* k
 }
 
 hipError_t launch_rope_rows(void* q, void* k, const void* rope_table, int rope_rows, int pos0, int rows, int seq_len, int n_heads,
-                            int n_kv_heads, hipStream_t st) {
+                            int n_kv_heads, hipStream_t st, const QkNorm* norm) {
     const long units = (long)rows * (n_heads + n_kv_heads);
+    if (norm) {
+        hipLaunchKernelGGL(rope_qkn_kernel<false>, dim3((unsigned)((units + 31) / 32)), dim3(256), 0, st, (_Float16*)q, (_Float16*)k, (const _Float16*)nullptr,
+                           (_Float16*)nullptr, (_Float16*)nullptr, (const h2*)rope_table, rope_rows, pos0, n_heads, n_kv_heads, 0, units, seq_len,
+                           (const _Float16*)norm->q_gamma, (const _Float16*)norm->k_gamma, norm->eps);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(rope_rows_kernel, dim3((unsigned)((units + 31) / 32)), dim3(256), 0, st, (_Float16*)q, (_Float16*)k,
                        (const h2*)rope_table, rope_rows, pos0, seq_len, n_heads, n_kv_heads, units);
     return hipGetLastError();
@@ -1145,18 +1240,27 @@ static int att_chunk_max(int max_seq, int n_splits) {
     return c < ATT_MIN_CHUNK ? ATT_MIN_CHUNK : c;
 }
 
-template <int RING>
+template <bool QKN>
+static AttnRestT<QKN> attn_rest(const AttnArgs& a, void* stamps) {
+    AttnRestT<QKN> rest{};
+    rest.out = a.out; rest.rope_table = a.rope_table; rest.pos = a.pos; rest.rope_theta = a.rope_theta;
+#ifdef AMQ_STAMP
+    rest.stamps = (unsigned long long*)stamps;
+#endif
+    (void)stamps;
+    if constexpr (QKN) rest.nrm = a.norm;
+    return rest;
+}
+
+template <int RING, bool QKN = false>
 static hipError_t launch_attn_decode_split_ring(const AttnArgs& a, int batch, int n_splits, void* ws, void* tickets, size_t lds, hipStream_t st) {
-    const auto kern = a.rows ? attn_decode_split_kernel<RING, true, true> : a.seq ? attn_decode_split_kernel<RING, true> : attn_decode_split_kernel<RING, false>;
+    const auto kern = a.rows ? attn_decode_split_kernel<RING, true, true, QKN> : a.seq ? attn_decode_split_kernel<RING, true, false, QKN> : attn_decode_split_kernel<RING, false, false, QKN>;
     if (a.rows) lds += ATT_ROWS_LDS;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    AttnRest rest{a.out, a.rope_table, a.pos, a.rope_theta};
-#ifdef AMQ_STAMP
-    rest.stamps = nullptr;
-#endif
+    const AttnRestT<QKN> rest = attn_rest<QKN>(a, nullptr);
     AttnSplit sp{(float*)ws, (int*)tickets, n_splits};
     const bool cur = a.rope_cur != nullptr;
     hipLaunchKernelGGL(kern, dim3(a.n_heads, batch, n_splits), dim3(ATT_THREADS), lds, st, a.kcache, a.vcache,
@@ -1177,27 +1281,38 @@ hipError_t launch_attn_decode_split(const AttnArgs& a, int batch, int n_splits, 
 #ifndef AMQ_ATT_RING_NARROW
 #define AMQ_ATT_RING_NARROW 4
 #endif
-    if ((long)a.n_heads * batch * n_splits <= 256) return launch_attn_decode_split_ring<AMQ_ATT_RING_WIDE>(a, batch, n_splits, ws, tickets, lds, st);
+    const bool wide = (long)a.n_heads * batch * n_splits <= 256;
+    if (a.norm.q_gamma) {
+        if (wide) return launch_attn_decode_split_ring<AMQ_ATT_RING_WIDE, true>(a, batch, n_splits, ws, tickets, lds, st);
+        return launch_attn_decode_split_ring<AMQ_ATT_RING_NARROW, true>(a, batch, n_splits, ws, tickets, lds, st);
+    }
+    if (wide) return launch_attn_decode_split_ring<AMQ_ATT_RING_WIDE>(a, batch, n_splits, ws, tickets, lds, st);
     return launch_attn_decode_split_ring<AMQ_ATT_RING_NARROW>(a, batch, n_splits, ws, tickets, lds, st);
 }
 
-hipError_t launch_attn_decode(const AttnArgs& a, int batch, hipStream_t st) {
+template <bool QKN>
+static hipError_t launch_attn_decode_t(const AttnArgs& a, int batch, hipStream_t st) {
     StreamDevice sd_(st);                                  // kernel attributes are per device: the stream's, not the current one
     const size_t lds = a.rows ? ((6 * ATT_D + (size_t)a.max_seq * 4 + 15) & ~(size_t)15) + ATT_ROWS_LDS : 6 * ATT_D + (size_t)a.max_seq * 4;
-    const auto kern = a.rows ? attn_decode_kernel<true, true> : a.seq ? attn_decode_kernel<true> : attn_decode_kernel<false>;
+    const auto kern = a.rows ? attn_decode_kernel<true, true, QKN> : a.seq ? attn_decode_kernel<true, false, QKN> : attn_decode_kernel<false, false, QKN>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    AttnRest rest{a.out, a.rope_table, a.pos, a.rope_theta};
 #ifdef AMQ_STAMP
-    rest.stamps = g_stamp_ptr;
+    const AttnRestT<QKN> rest = attn_rest<QKN>(a, g_stamp_ptr);
+#else
+    const AttnRestT<QKN> rest = attn_rest<QKN>(a, nullptr);
 #endif
     const bool cur = a.rope_cur != nullptr;
     hipLaunchKernelGGL(kern, dim3(a.n_heads, batch), dim3(ATT_THREADS), lds, st, a.kcache, a.vcache,
                        cur ? a.rope_cur : (const void*)a.pos_dev, a.n_heads | (a.n_kv_heads << 8) | ((int)cur << 16), a.max_seq,
                        a.q, a.k, a.v, rest);
     return hipGetLastError();
+}
+
+hipError_t launch_attn_decode(const AttnArgs& a, int batch, hipStream_t st) {
+    return a.norm.q_gamma ? launch_attn_decode_t<true>(a, batch, st) : launch_attn_decode_t<false>(a, batch, st);
 }
 
 }  // namespace amq

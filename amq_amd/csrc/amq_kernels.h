@@ -133,6 +133,10 @@ bool gemm_takes_deq(int M, int N, int K);                           // GEMM_ROUT
 hipError_t launch_gemm_f16w(const void* x, const void* w, const void* bias, const void* residual, const void* gate, void* y,
                             int M, int N, int K, int x_stride, int y_stride, hipStream_t st);
 
+// per-head q / k RMSNorm applied in front of the rotation (Qwen3; include/amq_hip.h: amq_qk_norm): fp16 [128] weights shared by all the heads of
+// a layer, y = gamma * fp16(x * rsqrt(mean(x^2) + eps)) over the 128 values of a head (amq_common.cuh: qkn_*)
+struct QkNorm { const void* q_gamma; const void* k_gamma; float eps; };
+
 // decode-step surroundings (amq_decode.hip)
 struct AttnArgs {
     const void* q;        // fp16 [B, n_heads, 128]      (un-rotated)
@@ -150,6 +154,7 @@ struct AttnArgs {
                               // maintained by launch_decode_tail, or null
     bool seq = false;         // rope_cur is block 0 of an array of `batch` step-state blocks STEP_STRIDE bytes apart: every sequence at ITS position
     bool rows = false;        // (with seq) the `batch` rows are consecutive positions of ONE sequence: one cache slice, causal among the rows (amq_attn_decode_rows_f16)
+    QkNorm norm = {};         // q_gamma / k_gamma set (both): the q/k-norm instantiations (amq_*_qkn_f16); null: the kernels as they were
 };
 // bytes between the step-state blocks of sequences decoded at positions of their own (include/amq_hip.h: AMQ_STEP_STATE_STRIDE)
 constexpr int STEP_STRIDE = 272;
@@ -188,9 +193,9 @@ hipError_t launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st);
 // prefill glue (amq_decode.hip)
 hipError_t launch_rope_cache(void* q, const void* k, const void* v, void* kcache, void* vcache, const void* rope_table,
                              int rope_rows, int pos0, int S, int n_heads, int n_kv_heads, int max_seq, hipStream_t st,
-                             int batch = 1);           // q / k / v rows = batch * S; caches [batch][n_kv_heads][max_seq][128]
+                             int batch = 1, const QkNorm* norm = nullptr);   // q / k / v rows = batch * S; caches [batch][n_kv_heads][max_seq][128]
 hipError_t launch_rope_rows(void* q, void* k, const void* rope_table, int rope_rows, int pos0, int rows, int seq_len, int n_heads,
-                            int n_kv_heads, hipStream_t st);
+                            int n_kv_heads, hipStream_t st, const QkNorm* norm = nullptr);     // norm: heads normalised before the rotation (QkNorm)
 hipError_t launch_silu_mul(const void* gate, const void* up, void* out, long n, hipStream_t st);
 hipError_t launch_decode_tail(const void* logits, int vocab, const void* embed, int hidden, void* token, void* pos, void* x,
                               const void* rope_table, void* rope_cur, int rope_rows, hipStream_t st, int batch = 1, const void* suppress = nullptr,

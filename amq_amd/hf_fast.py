@@ -6,7 +6,7 @@ With ``--use_ft`` the reference patches the model it hands to its harness: ``con
 (ftllama_generate.py:613-622); the harness then calls exactly those two things (amq/utils/speed.py:31-36, 65, 82).
 
 Here the fast step is the hipGraph runner (llama.QuantLlama).  ``convert_model_to_hip(model)`` binds one lazily over the swapped model's own
-buffers (QuantLlama.from_hf: no weight copies) and gives THIS model instance
+buffers (QuantLlama.from_hf: no weight copies; Llama 2 / 3.x, Mistral, Qwen2.5 and Qwen3 dense) and gives THIS model instance
 
   * ``model(input_ids, start_pos=p, use_cache=False)`` -- batch 1..8, any prompt length that fits the cache: the runner's prompt pass (captured per
     (length, start_pos)) or, for one new token at the runner's current position, the captured token step.  Returns a ``CausalLMOutputWithPast``
@@ -150,7 +150,12 @@ def _same_weights(r, model):
     models, amq_speed_benchmark.py:231-251 -- means a new runner)"""
     layer = model.model.layers[0]
     q = layer.self_attn.q_proj
-    return r.blocks[0]["self_attn.q_proj"].qn.data_ptr() == q.qweight.data_ptr() and r.nb == len(model.model.layers)
+    same = r.blocks[0]["self_attn.q_proj"].qn.data_ptr() == q.qweight.data_ptr() and r.nb == len(model.model.layers)
+    if same and r.qk_norm:                      # Qwen3: the per-head norm weights are the modules' own tensors too (fp16 ones: no copy was made)
+        for key, m in (("qn", getattr(layer.self_attn, "q_norm", None)), ("kn", getattr(layer.self_attn, "k_norm", None))):
+            w = getattr(m, "weight", None)
+            same = same and w is not None and (w.dtype is not torch.float16 or r.blocks[0][key].data_ptr() == w.data_ptr())
+    return same
 
 
 def _plain_ids(input_ids):

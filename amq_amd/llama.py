@@ -144,16 +144,18 @@ class StepPlan(NamedTuple):
         return self.first_norm if self.norm == NORM_FROM_SUMS and self.down != DOWN_GEMV_SUMS else self.norm
 
 
-def step_plan(R, H, I, fine, rows_h, rows_i, rows_i_phased, norm_sums=True, norm_fused_rows=4, down_fused_rows=1):
+def step_plan(R, H, I, fine, rows_h, rows_i, rows_i_phased, norm_sums=True, norm_fused_rows=4, down_fused_rows=1, rows_q=None):
     """The StepPlan of R rows at hidden size H / intermediate size I (``fine``: groups of 64 / 32).  rows_h, rows_i, rows_i_phased: the rows the
     GEMV stages in LDS -- ops.gemv_max_rows(H, plain=True), (I, plain=not fine) and (I, plain=not fine, norm=False: in two K phases).
     norm_sums, norm_fused_rows, down_fused_rows: QuantLlama.NORM_SUMS, NORM_FUSED_ROWS, DOWN_FUSED_ROWS.
+    rows_q: ops.gemv_max_rows(heads * 128, plain=True) where o_proj's input is not H wide (Qwen3: q / o widths of heads * 128) -- the launch that
+    leaves the sums stages rows of THAT width; None: H, as for every other family.
     A fused prologue is paid once per WORKGROUP, on R times the one-row bytes, a separate launch once per token: SiLU*mul leaves the GEMV from 2
     rows, the norms from 5 (profiles/r05_decode_batch.txt) -- where at 2 .. 8 rows they ride on partial sums instead (no pass over x for the
     statistic, no rmsnorm launch: profiles/r06_decode_batch.txt).  Past the whole-row LDS stage (7B: 7 - 8 rows of 11008) the plain GEMV stages x
     in two K phases (a fused prologue there would take in gate AND up per workgroup -- 352 KB per CU at 8 rows: 23.9 us against 4.9 + ~11)."""
     own = NORM_LAUNCH if R > norm_fused_rows else NORM_FUSED
-    sums = norm_sums and 2 <= R <= 8 and not fine and 2048 <= H <= 8192 and I >= 2048 and R <= rows_h
+    sums = norm_sums and 2 <= R <= 8 and not fine and 2048 <= H <= 8192 and I >= 2048 and R <= rows_h and (rows_q is None or R <= rows_q)
     if R <= min(rows_i, down_fused_rows):
         down = DOWN_FUSED
     elif R <= rows_i_phased:
@@ -213,7 +215,8 @@ class QuantLlama:
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
-        dense: {'embed','lm_head','norm','ln1'[n_block],'ln2'[n_block]} fp16 tensors (else synthetic).
+        dense: {'embed','lm_head','norm','ln1'[n_block],'ln2'[n_block]} fp16 tensors (else synthetic); a config with ``qk_norm`` (Qwen3) also
+        'qn'[n_block], 'kn'[n_block]: the per-head q / k RMSNorm weights, fp16 [128] each.
         prebuilt: {(block, name): _Lin} linears already in the native layout (from_hf: shared with the modules that own them).
         group: group size of the SYNTHETIC layers (128; 64 / 32: see ``fine``).
         batch: sequences decoded together, 1 .. 8 (same prompt length; one step = the same launches with ``batch`` rows: the
@@ -262,6 +265,8 @@ class QuantLlama:
         if config["head_dim"] != 128:
             raise ValueError("head_dim must be 128")
         self.kvd = self.nkv * 128
+        self.qd = self.nh * 128                 # width of q and of the attention output = o_proj's K (Qwen3: not H at every size)
+        self.qk_norm = bool(config.get("qk_norm"))      # Qwen3: q and k are RMS-normalised per head in front of the rotation, inside the rotating kernels
         self.nb = config["n_block"]
         self.vocab = config["vocab_size"]
         self.max_seq = max_seq
@@ -297,9 +302,14 @@ class QuantLlama:
             blk = {name: lin(b, name) for name in config["linear"]}
             if dense is not None:
                 blk["ln1"], blk["ln2"] = dense["ln1"][b].to(dev), dense["ln2"][b].to(dev)
+                if self.qk_norm:
+                    blk["qn"], blk["kn"] = dense["qn"][b].to(dev), dense["kn"][b].to(dev)
             else:
                 blk["ln1"] = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
                 blk["ln2"] = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
+                if self.qk_norm:
+                    blk["qn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
+                    blk["kn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
             blk["kc"] = torch.zeros(self.B, self.nkv, max_seq, 128, dtype=torch.float16, device=dev)
             blk["vc"] = torch.zeros(self.B, self.nkv, max_seq, 128, dtype=torch.float16, device=dev)
             self.blocks.append(blk)
@@ -329,10 +339,10 @@ class QuantLlama:
         R = self.R
         self.x = torch.zeros(R, self.H, **f16)
         self.xn = torch.zeros(R, self.H, **f16)          # normed rows (NORM_LAUNCH)
-        self.q = torch.zeros(R, self.H, **f16)
+        self.q = torch.zeros(R, self.qd, **f16)
         self.k = torch.zeros(R, self.kvd, **f16)
         self.v = torch.zeros(R, self.kvd, **f16)
-        self.att = torch.zeros(R, self.H, **f16)
+        self.att = torch.zeros(R, self.qd, **f16)
         self.gate = torch.zeros(R, self.I, **f16)
         self.up = torch.zeros(R, self.I, **f16)
         # the cos/sin table every rotating kernel reads: plain rope_theta frequencies, or the rotary embedding's own (rope_scaling)
@@ -340,14 +350,21 @@ class QuantLlama:
         self.has_bias = any(blk[n].bias is not None for blk in self.blocks for n in config["linear"])
         # which launches make up a step of R rows: decided here, once (the class switches as they stand now), walked by _step
         self.plan = step_plan(R, self.H, self.I, self.fine, ops.gemv_max_rows(self.H, plain=True), ops.gemv_max_rows(self.I, plain=not self.fine),
-                              ops.gemv_max_rows(self.I, plain=not self.fine, norm=False), self.NORM_SUMS, self.NORM_FUSED_ROWS, self.DOWN_FUSED_ROWS)
+                              ops.gemv_max_rows(self.I, plain=not self.fine, norm=False), self.NORM_SUMS, self.NORM_FUSED_ROWS, self.DOWN_FUSED_ROWS,
+                              rows_q=None if self.qd == self.H else ops.gemv_max_rows(self.qd, plain=True))
         # the sums of squares of self.x's rows, per 16 columns: written by the launch that produced the rows, read by the one that normalises them
         self.ss = torch.zeros(R, self.H // 16, dtype=torch.float32, device=dev) if self.plan.norm == NORM_FROM_SUMS else None
+        # the two A/B step forms rotate inside launches of their own, which carry no per-head norm and take q / o of hidden_size: not for Qwen3
+        qwen3_shape = self.qk_norm or self.qd != self.H
+        if qwen3_shape and (engine or self.FUSE_QKV_ATTN):
+            raise ValueError(("the decode engine" if engine else "the fused q/k/v + attention launch") + " does not serve this model: "
+                             + ("it has no per-head q / k norm" if self.qk_norm else f"q / o widths of heads * 128 = {self.qd} != hidden_size {self.H}"))
         self.can_fuse_qkv_attn = (R == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
-                                  and not self.ragged)
+                                  and not self.ragged and not qwen3_shape)
         self.fuse_qkv_attn = self.FUSE_QKV_ATTN and self.can_fuse_qkv_attn
         self._tickets = torch.zeros(max(self.nh, 64), dtype=torch.int32, device=dev)
-        eligible = self.R == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias and not self.ragged
+        eligible = (self.R == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias and not self.ragged
+                    and not self.qk_norm)
         if engine and not eligible:
             raise ValueError("the decode engine needs batch 1 and max_seq <= %d" % self.ENGINE_MAX_SEQ)
         self.engine = None
@@ -395,9 +412,14 @@ class QuantLlama:
         self.graph = self.sample_graph = None
         self._prefill_graphs = {}   # (prompt length, start_pos) -> (graph, its ids buffer, its logits_rows or None)
 
-    # model families whose decoder is the Llama block -- RMSNorm, rotary q / k, (grouped-query) softmax attention, SiLU-gated MLP, no extra norms --
-    # and differs only in shapes, rope settings and projection biases: what the reference lists (README.md:90-92; amq/configs/{llama,mistral,qwen2}.json)
-    HF_MODEL_TYPES = ("llama", "mistral", "qwen2")
+    def _qkn(self, blk):
+        """what a rotating op of block ``blk`` takes besides its own arguments: the block's per-head q / k norm weights (Qwen3), or nothing"""
+        return dict(q_norm=blk["qn"], k_norm=blk["kn"], norm_eps=self.eps) if self.qk_norm else {}
+
+    # model families whose decoder is the Llama block -- RMSNorm, rotary q / k, (grouped-query) softmax attention, SiLU-gated MLP --
+    # and differs only in shapes, rope settings, projection biases and (Qwen3) a per-head RMSNorm of q / k in front of the rotation: what the
+    # reference lists (README.md:90-92; amq/configs/{llama,mistral,qwen2}.json) and Qwen3 dense
+    HF_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")
 
     @classmethod
     def check_hf(cls, model, max_seq=None):
@@ -410,9 +432,9 @@ class QuantLlama:
             raise ValueError(f"from_hf: model_type '{mt}' is not one of {cls.HF_MODEL_TYPES} (a Llama-shaped decoder is required)")
         if hf.get("hidden_act", "silu") != "silu":
             raise ValueError("from_hf: a SiLU-gated MLP is required")
+        for li, layer in enumerate(model.model.layers):
+            cls._check_qk_norm(layer.self_attn, mt, float(hf.get("rms_norm_eps", 1e-5)), li)
         attn0 = model.model.layers[0].self_attn
-        if any(hasattr(attn0, n) for n in ("q_norm", "k_norm")):
-            raise ValueError("from_hf: per-head q / k norms are not part of the runner's block")
         from .quant_linear import HIPQuantLinear
         if not isinstance(getattr(attn0, "q_proj", None), HIPQuantLinear):
             raise ValueError("from_hf: the decoder linears are not HIPQuantLinear modules: run prepare_for_inference(model, backend='hip') first")
@@ -435,6 +457,30 @@ class QuantLlama:
             raise ValueError(f"from_hf: max_seq {max_seq} exceeds the model's sliding window ({sw}): the runner attends the whole cache")
         cfg = runner_config(hf)
         return cfg, rope
+
+    @staticmethod
+    def _check_qk_norm(attn, model_type, eps, layer):
+        """Qwen3's q_norm / k_norm: both RMSNorm modules over a head's 128 values with the model's rms_norm_eps -- what the rotating kernels apply;
+        a model of another family has neither.  Anything else is refused with its reason."""
+        qn, kn = getattr(attn, "q_norm", None), getattr(attn, "k_norm", None)
+        where = f"from_hf: model.layers.{layer}.self_attn"
+        if model_type != "qwen3":
+            if qn is not None or kn is not None:
+                raise ValueError(f"{where}: per-head q / k norms are not part of a '{model_type}' block (they are served for model_type 'qwen3')")
+            return
+        if qn is None and kn is None:
+            raise ValueError(f"{where}: a qwen3 block without q_norm / k_norm")
+        if qn is None or kn is None:
+            raise ValueError(f"{where}: a norm on only one of q / k ({'q_norm' if kn is None else 'k_norm'} alone) is not served: the kernels "
+                             "normalise both")
+        for name, m in (("q_norm", qn), ("k_norm", kn)):
+            w = getattr(m, "weight", None)
+            if "RMSNorm" not in type(m).__name__ or w is None or tuple(w.shape) != (128,):
+                raise ValueError(f"{where}.{name}: expected an RMSNorm over the 128 values of a head, got {type(m).__name__}"
+                                 f"{'' if w is None else ' of width ' + 'x'.join(str(d) for d in w.shape)}")
+            m_eps = getattr(m, "variance_epsilon", getattr(m, "eps", None))
+            if m_eps is None or float(m_eps) != eps:
+                raise ValueError(f"{where}.{name}: eps {m_eps} is not the model's rms_norm_eps {eps} (the runner keeps one eps)")
 
     @classmethod
     def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2):
@@ -464,6 +510,9 @@ class QuantLlama:
                 arch_linear[name].append(m.bits)
         dense = {"embed": f16(model.model.embed_tokens.weight), "lm_head": f16(model.lm_head.weight), "norm": f16(model.model.norm.weight),
                  "ln1": [f16(l.input_layernorm.weight) for l in layers], "ln2": [f16(l.post_attention_layernorm.weight) for l in layers]}
+        if cfg.get("qk_norm"):                  # the HF modules' own tensors (no copy when they are fp16 and contiguous)
+            dense["qn"] = [f16(l.self_attn.q_norm.weight).contiguous() for l in layers]
+            dense["kn"] = [f16(l.self_attn.k_norm.weight).contiguous() for l in layers]
         return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
                    ragged=ragged, lookup=lookup, ngram_max=ngram_max)
 
@@ -499,15 +548,16 @@ class QuantLlama:
                 self._behind_norm(first, blk["ln1"], [blk["self_attn.q_proj"].seg(self.q), blk["self_attn.k_proj"].seg(self.k),
                                                       blk["self_attn.v_proj"].seg(self.v)])
                 if self.lookup:                 # the R rows are consecutive positions of the one sequence: causal among them, one cache slice
-                    ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv)
+                    ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv,
+                                         **self._qkn(blk))
                 else:
                     ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
-                                    cur=self.rope_cur)
+                                    cur=self.rope_cur, **self._qkn(blk))
             o_proj, down = [blk["self_attn.o_proj"].seg(self.x, residual=self.x)], [blk["mlp.down_proj"].seg(self.x, residual=self.x)]
             if from_sums:
-                ops.gemv_grouped_sums(self.att, o_proj, H, sums_out=self.ss)
+                ops.gemv_grouped_sums(self.att, o_proj, self.qd, sums_out=self.ss)
             else:
-                ops.gemv_grouped(self.att, o_proj, H)
+                ops.gemv_grouped(self.att, o_proj, self.qd)
             self._behind_norm(plan.norm, blk["ln2"], [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)])
             if plan.down == DOWN_FUSED:
                 ops.gemv_grouped(self.gate, down, self.I, prologue=ops.PRO_SILU_MUL, x2=self.up)
@@ -936,10 +986,10 @@ class QuantLlama:
             h = ops.rmsnorm(x, blk["ln1"], self.eps)
             q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
             if cache:
-                ops.rope_cache(q, k, v, blk["kc"], blk["vc"], self.rope_tab, start_pos, nh, nkv)
+                ops.rope_cache(q, k, v, blk["kc"], blk["vc"], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
                 a = ops.attn_prefill(q, blk["kc"], blk["vc"], torch.empty_like(q), S, nh, nkv, batch=B, pos0=start_pos, kv_cache=True)
             else:
-                ops.rope_rows(q, k, self.rope_tab, S, nh, nkv)
+                ops.rope_rows(q, k, self.rope_tab, S, nh, nkv, **self._qkn(blk))
                 a = ops.attn_prefill(q, k, v, torch.empty_like(q), S, nh, nkv, batch=B)      # reads the projections in place
             x = lin(blk["self_attn.o_proj"], a, residual=x)
             h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
@@ -1009,7 +1059,7 @@ class QuantLlama:
                 h = ops.rmsnorm(x, blk["ln1"], self.eps)
                 q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
             kc, vc = blk["kc"], blk["vc"]
-            ops.rope_cache(q, k, v, kc[0], vc[0], self.rope_tab, start_pos, nh, nkv)
+            ops.rope_cache(q, k, v, kc[0], vc[0], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
             if frag:
                 a_xf = ops.attn_prefill(q, kc, vc, None, S, nh, nkv, batch=1, pos0=start_pos, kv_cache=True, out_xfrag=True)
                 x = lin_xf(blk["self_attn.o_proj"], a_xf, residual=x)              # attention output handed over in fragment order
@@ -1074,7 +1124,7 @@ class QuantLlama:
             kh = kh.repeat_interleave(nh // nkv, dim=0)
             vh = vh.repeat_interleave(nh // nkv, dim=0)
         a = torch.nn.functional.scaled_dot_product_attention(qh[None], kh[None], vh[None], is_causal=True)[0]
-        return a.transpose(0, 1).reshape(S, self.H).contiguous()
+        return a.transpose(0, 1).reshape(S, self.qd).contiguous()
 
     def _prefill_unfused(self, ids):
         """The same pass with framework ops for everything but the linears and RMSNorm (HF-style RoPE in fp32 -> fp16,
@@ -1083,6 +1133,8 @@ class QuantLlama:
         S = ids.numel()
         if S > self.max_seq:
             raise ValueError("prompt longer than the KV cache")
+        if self.qk_norm:
+            raise ValueError("the framework-op comparison pass has no per-head q / k norm: not offered for a qk_norm model")
         H, nh, nkv = self.H, self.nh, self.nkv
         ids = ids.to(self.dev)
         x = self.embed.index_select(0, ids)
@@ -1193,7 +1245,8 @@ class DenseLlama(QuantLlama):
         _prime_graph_state(self.dev)
         self.H, self.I = config["hidden_size"], config["intermediate_size"]
         self.nh, self.nkv = config["num_heads"], config["num_kv_heads"]
-        self.kvd = self.nkv * 128
+        self.kvd, self.qd = self.nkv * 128, self.nh * 128
+        self.qk_norm = bool(config.get("qk_norm"))
         self.nb, self.vocab, self.max_seq = config["n_block"], config["vocab_size"], max_seq
         self.eps = float(config.get("rms_norm_eps", EPS))
         self.theta = float(config.get("rope_theta", ROPE_THETA))
@@ -1208,6 +1261,9 @@ class DenseLlama(QuantLlama):
                 blk[name] = (torch.randn(n, k, device=dev, generator=gen) * (0.5 / math.sqrt(k))).to(torch.float16)
             blk["ln1"] = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
             blk["ln2"] = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
+            if self.qk_norm:
+                blk["qn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
+                blk["kn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
             blk["kc"] = torch.zeros(self.B, self.nkv, max_seq, 128, **f16)
             blk["vc"] = torch.zeros(self.B, self.nkv, max_seq, 128, **f16)
             self.blocks.append(blk)
@@ -1215,7 +1271,7 @@ class DenseLlama(QuantLlama):
         self.lm_head = (torch.randn(self.vocab, self.H, device=dev, generator=gen) / math.sqrt(self.H)).to(torch.float16)
         self.norm = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
         self.x = torch.zeros(self.B, self.H, **f16)
-        self.att = torch.zeros(self.B, self.H, **f16)
+        self.att = torch.zeros(self.B, self.qd, **f16)
         self._init_step_state((None, 1.0))      # (plain rope_theta frequencies)
         self.engine = None           # (the one-launch-per-token engine serves the quantized runner only)
 
@@ -1235,7 +1291,7 @@ class DenseLlama(QuantLlama):
             q = F.linear(h, blk["self_attn.q_proj"])
             k = F.linear(h, blk["self_attn.k_proj"])
             v = F.linear(h, blk["self_attn.v_proj"])
-            ops.attn_decode(q, k, v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta, cur=self.rope_cur)
+            ops.attn_decode(q, k, v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta, cur=self.rope_cur, **self._qkn(blk))
             x = x + F.linear(self.att, blk["self_attn.o_proj"])
             h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
             x = x + F.linear(F.silu(F.linear(h2, blk["mlp.gate_proj"])) * F.linear(h2, blk["mlp.up_proj"]),
@@ -1262,7 +1318,7 @@ class DenseLlama(QuantLlama):
         for blk in self.blocks:
             h = ops.rmsnorm(x, blk["ln1"], self.eps)
             q, k, v = F.linear(h, blk["self_attn.q_proj"]), F.linear(h, blk["self_attn.k_proj"]), F.linear(h, blk["self_attn.v_proj"])
-            ops.rope_cache(q, k, v, blk["kc"][0], blk["vc"][0], self.rope_tab, start_pos, nh, nkv)
+            ops.rope_cache(q, k, v, blk["kc"][0], blk["vc"][0], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
             x = torch.addmm(x, self._prefill_attention(q, blk, S, start_pos), blk["self_attn.o_proj"].t())
             h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
             g, u = F.linear(h2, blk["mlp.gate_proj"]), F.linear(h2, blk["mlp.up_proj"])

@@ -88,6 +88,9 @@ class ModuleWalkLlama(nn.Module):
         super().__init__()
         if getattr(runner, "B", 1) != 1:
             raise ValueError("the module walk mirrors the reference's batch-1 step")
+        if getattr(runner, "qk_norm", False):
+            raise ValueError("the module walk reaches attention through the extension's amq_attn_decode_cur_f16 binding and the fused layer "
+                             "modules, which carry no per-head q / k norm: a qk_norm (Qwen3) runner is served by QuantLlama's own step")
         self.r = runner
         self.layers = nn.ModuleList(_Block(blk, runner) for blk in runner.blocks)
         self.graph = None

@@ -806,11 +806,50 @@ def set_token(token_in, embed, token, pos, x, table=None, cur=None):
                                              _lib.current_stream()))
 
 
-def rope_cache(q, k, v, kcache, vcache, table, pos0, n_heads, n_kv_heads):
+QK_NORM_EPS = 1e-6         # Qwen3Config.rms_norm_eps: the default of the wrappers' ``norm_eps``
+
+
+def _qk_norm(q_norm, k_norm, norm_eps, device):
+    """the `amq_qk_norm` argument of the amq_*_qkn_f16 entry points (include/amq_hip.h) for Qwen3's per-head q / k RMSNorm weights, or None when
+    neither is given (the entry points without the suffix).  Both or neither; each fp16 [128], contiguous, on ``device``."""
+    if q_norm is None and k_norm is None:
+        return None
+    if q_norm is None or k_norm is None:
+        raise ValueError("q_norm and k_norm go together: the kernels normalise both q and k per head (got only "
+                         f"{'q_norm' if k_norm is None else 'k_norm'})")
+    for name, g in (("q_norm", q_norm), ("k_norm", k_norm)):
+        if not isinstance(g, torch.Tensor) or g.dtype is not torch.float16 or tuple(g.shape) != (128,) or not g.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp16 tensor of 128 elements (one weight per element of a head), got "
+                             f"{tuple(g.shape) if isinstance(g, torch.Tensor) else type(g).__name__}"
+                             f"{' ' + str(g.dtype) if isinstance(g, torch.Tensor) else ''}")
+        if not g.is_cuda:
+            raise ValueError(f"{name} must be in GPU memory, which the kernels read (it is on {g.device})")
+        if g.device != device:
+            raise ValueError(f"{name} must be on {device}, where q is (it is on {g.device})")
+    return _lib.QkNorm(q_norm.data_ptr(), k_norm.data_ptr(), float(norm_eps))
+
+
+def _qkn_fn(lib, name, norm, qkn=None):
+    """the entry point ``name`` (norm None) or its `_qkn` variant bound to ``norm``: same arguments behind it.  ``qkn``: the variant's name where
+    it is not ``name`` with the suffix"""
+    if norm is None:
+        return getattr(lib, name)
+    fn = getattr(lib, qkn or name[:-len("_f16")] + "_qkn_f16")
+    return lambda *args: fn(ctypes.byref(norm), *args)
+
+
+def rope_cache(q, k, v, kcache, vcache, table, pos0, n_heads, n_kv_heads, q_norm=None, k_norm=None, norm_eps=QK_NORM_EPS):
     """Prefill glue: rotate q [S, n_heads*128] in place, rotate k [S, n_kv_heads*128] into kcache[h, pos0+s], copy v into
     vcache (both [n_kv_heads, max_seq, 128]); ``table`` from :func:`rope_table`.
-    Caches [B, n_kv_heads, max_seq, 128] (4-D): q / k / v hold B sequences of S = rows / B rows each, one launch for all."""
-    if kcache.dim() == 4:
+    Caches [B, n_kv_heads, max_seq, 128] (4-D): q / k / v hold B sequences of S = rows / B rows each, one launch for all.
+    ``q_norm`` / ``k_norm`` (both, fp16 [128]): every head of q and k is RMS-normalised with these weights before the rotation (Qwen3), in the
+    same launch."""
+    norm = _qk_norm(q_norm, k_norm, norm_eps, q.device)
+    if kcache.dim() == 4 or norm is not None:
+        if kcache.dim() == 3:                   # with norms there is ONE entry point, the batched one: a 3-D cache goes through it as a batch of 1
+            if kcache.shape[0] != n_kv_heads:
+                raise ValueError("caches must be [n_kv_heads, max_seq, 128]")
+            kcache, vcache = kcache.unsqueeze(0), vcache.unsqueeze(0)
         B = kcache.shape[0]
         rows = q.shape[0]
         if rows % B or kcache.shape[1] != n_kv_heads or kcache.shape[3] != 128 or vcache.shape != kcache.shape:
@@ -822,9 +861,9 @@ def rope_cache(q, k, v, kcache, vcache, table, pos0, n_heads, n_kv_heads):
         _need(kcache, torch.float16, "kcache")
         _need(vcache, torch.float16, "vcache")
         _need(table, torch.float16, "rope table")
-        _lib.check(_lib.load().amq_rope_cache_batch_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
-                                                        _lib.ptr(table), table.numel() // 128, int(pos0), S, B, n_heads, n_kv_heads,
-                                                        128, kcache.shape[2], _lib.current_stream()))
+        _lib.check(_qkn_fn(_lib.load(), "amq_rope_cache_batch_f16", norm, qkn="amq_rope_cache_qkn_f16")(
+            _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(table), table.numel() // 128, int(pos0), S, B,
+            n_heads, n_kv_heads, 128, kcache.shape[2], _lib.current_stream()))
         return
     S = q.shape[0]
     _need(q, torch.float16, "q", S * n_heads * 128)
@@ -880,14 +919,16 @@ def attn_prefill(q, k, v, out, S, n_heads, n_kv_heads, batch=1, pos0=0, kv_cache
     return out
 
 
-def rope_rows(q, k, table, seq_len, n_heads, n_kv_heads, pos0=0):
-    """RoPE in place on q [rows, n_heads*128] and k [rows, n_kv_heads*128], rows = batch * seq_len (no cache)."""
+def rope_rows(q, k, table, seq_len, n_heads, n_kv_heads, pos0=0, q_norm=None, k_norm=None, norm_eps=QK_NORM_EPS):
+    """RoPE in place on q [rows, n_heads*128] and k [rows, n_kv_heads*128], rows = batch * seq_len (no cache).
+    ``q_norm`` / ``k_norm``: as :func:`rope_cache`."""
+    norm = _qk_norm(q_norm, k_norm, norm_eps, q.device)
     rows = q.shape[0]
     _need(q, torch.float16, "q", rows * n_heads * 128)
     _need(k, torch.float16, "k", rows * n_kv_heads * 128)
     _need(table, torch.float16, "rope table")
-    _lib.check(_lib.load().amq_rope_rows_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(table), table.numel() // 128, int(pos0), rows,
-                                             int(seq_len), n_heads, n_kv_heads, 128, _lib.current_stream()))
+    _lib.check(_qkn_fn(_lib.load(), "amq_rope_rows_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(table), table.numel() // 128, int(pos0), rows,
+                                                               int(seq_len), n_heads, n_kv_heads, 128, _lib.current_stream()))
 
 
 def silu_mul(gate, up, out=None):
@@ -1123,13 +1164,17 @@ def attn_decode_splits(max_seq, n_heads=32, batch=1, n_kv_heads=None):
     return s
 
 
-def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_theta=10000.0, table=None, cur=None, n_splits=0):
+def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_theta=10000.0, table=None, cur=None, n_splits=0,
+                q_norm=None, k_norm=None, norm_eps=QK_NORM_EPS):
     """One new token per sequence.  q [B, n_heads*128], k/v [B, n_kv_heads*128],
     caches [B, n_kv_heads, max_seq, 128]; ``pos`` is an int or a device int32 tensor.  ``cur``: fp16 [128] cos/sin row
     of the current position (maintained by decode_tail) -- needs ``pos`` as a device tensor.
     ``n_splits``: workgroups per head (include/amq_hip.h: amq_attn_decode_split_f16); 0 = by cache length, 1 = the
     single-workgroup kernel.
-    ``cur`` [B, 128] with ``pos`` [B] (ops.new_step_state(device, batch=B)): every sequence at its own position (amq_attn_decode_seq_f16)."""
+    ``cur`` [B, 128] with ``pos`` [B] (ops.new_step_state(device, batch=B)): every sequence at its own position (amq_attn_decode_seq_f16).
+    ``q_norm`` / ``k_norm`` (both, fp16 [128]) with ``norm_eps``: Qwen3's per-head RMSNorm of q and of the new k, applied inside the same kernels
+    in front of the rotation (the amq_*_qkn_f16 entry points); neither: the kernels as they are for every other model."""
+    norm = _qk_norm(q_norm, k_norm, norm_eps, q.device)
     B = kcache.shape[0]
     max_seq = kcache.shape[2]
     if n_splits == 0:
@@ -1148,11 +1193,11 @@ def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_the
         if n_splits > 1:
             wsb = lib.amq_attn_decode_split_workspace_bytes(B, n_heads, n_splits)
             ws, tk = _ATTN_WS.get(q.device, wsb // 4), _ATTN_TICKETS.get(q.device, B * n_heads)
-            _lib.check(lib.amq_attn_decode_seq_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, B,
-                                                   n_heads, n_kv_heads, 128, max_seq, n_splits, _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
+            _lib.check(_qkn_fn(lib, "amq_attn_decode_seq_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, B,
+                                                                     n_heads, n_kv_heads, 128, max_seq, n_splits, _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
         else:
-            _lib.check(lib.amq_attn_decode_seq_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, B,
-                                                   n_heads, n_kv_heads, 128, max_seq, 0, None, 0, None, _lib.current_stream()))
+            _lib.check(_qkn_fn(lib, "amq_attn_decode_seq_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, B,
+                                                                     n_heads, n_kv_heads, 128, max_seq, 0, None, 0, None, _lib.current_stream()))
         return out
     if isinstance(pos, torch.Tensor):
         _need(pos, torch.int32, "pos", 1)
@@ -1173,19 +1218,19 @@ def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_the
         wsb = lib.amq_attn_decode_split_workspace_bytes(B, n_heads, n_splits)
         ws = _ATTN_WS.get(q.device, wsb // 4)
         tk = _ATTN_TICKETS.get(q.device, B * n_heads)
-        _lib.check(lib.amq_attn_decode_split_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
-                                                 _lib.ptr(out), _lib.ptr(cur), pos_dev, pos_i, B, n_heads, n_kv_heads, 128,
-                                                 max_seq, ctypes.c_float(rope_theta), _lib.ptr(table), n_splits,
-                                                 _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
+        _lib.check(_qkn_fn(lib, "amq_attn_decode_split_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
+                                                                   _lib.ptr(out), _lib.ptr(cur), pos_dev, pos_i, B, n_heads, n_kv_heads, 128,
+                                                                   max_seq, ctypes.c_float(rope_theta), _lib.ptr(table), n_splits,
+                                                                   _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
         return out
     if cur is not None:
-        _lib.check(_lib.load().amq_attn_decode_cur_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
-                                                       _lib.ptr(out), _lib.ptr(cur), B, n_heads, n_kv_heads, 128, max_seq,
-                                                       _lib.current_stream()))
+        _lib.check(_qkn_fn(_lib.load(), "amq_attn_decode_cur_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
+                                                                         _lib.ptr(out), _lib.ptr(cur), B, n_heads, n_kv_heads, 128, max_seq,
+                                                                         _lib.current_stream()))
         return out
-    _lib.check(_lib.load().amq_attn_decode_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
-                                               _lib.ptr(out), pos_dev, pos_i, B, n_heads, n_kv_heads, 128, max_seq,
-                                               ctypes.c_float(rope_theta), _lib.ptr(table), _lib.current_stream()))
+    _lib.check(_qkn_fn(_lib.load(), "amq_attn_decode_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
+                                                                 _lib.ptr(out), pos_dev, pos_i, B, n_heads, n_kv_heads, 128, max_seq,
+                                                                 ctypes.c_float(rope_theta), _lib.ptr(table), _lib.current_stream()))
     return out
 
 
@@ -1211,11 +1256,13 @@ def new_lookup_state(device, drafts, ngram_max=2, history_cap=0):
     return host.to(device), torch.zeros(history_cap, dtype=torch.int32, device=device)
 
 
-def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads, n_splits=0):
+def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads, n_splits=0, q_norm=None, k_norm=None, norm_eps=QK_NORM_EPS):
     """``rows`` = 2 .. 8 consecutive positions of ONE sequence (amq_attn_decode_rows_f16): q / out [rows, n_heads*128], k / v [rows, n_kv_heads*128],
     caches [1, n_kv_heads, max_seq, 128] (or 3-D); ``cur`` [rows, 128] / ``pos`` [rows]: the views of one per-sequence step state whose block j holds
     position p + j.  Row j appends cache row p + j and attends rows 0 .. p - 1 of the cache plus this step's rows 0 .. j.
-    ``n_splits``: 0 = by cache length, 1 = the single-workgroup kernel, >= 2 the per-head split kernel."""
+    ``n_splits``: 0 = by cache length, 1 = the single-workgroup kernel, >= 2 the per-head split kernel.
+    ``q_norm`` / ``k_norm``: as :func:`attn_decode` (every workgroup normalises the earlier rows' keys it rotates for itself: the same bits)."""
+    norm = _qk_norm(q_norm, k_norm, norm_eps, q.device)
     states, R = _seq_state(cur, pos)
     if states is None:
         raise ValueError("cur [rows, 128] / pos [rows] must be the views of one per-sequence step state (ops.new_step_state(device, batch=rows))")
@@ -1236,11 +1283,11 @@ def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads
     if n_splits > 1:
         wsb = lib.amq_attn_decode_split_workspace_bytes(R, n_heads, n_splits)
         ws, tk = _ATTN_WS.get(q.device, wsb // 4), _ATTN_TICKETS.get(q.device, R * n_heads)
-        _lib.check(lib.amq_attn_decode_rows_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, R,
-                                                n_heads, n_kv_heads, 128, max_seq, n_splits, _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
+        _lib.check(_qkn_fn(lib, "amq_attn_decode_rows_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, R,
+                                                                  n_heads, n_kv_heads, 128, max_seq, n_splits, _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
     else:
-        _lib.check(lib.amq_attn_decode_rows_f16(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, R,
-                                                n_heads, n_kv_heads, 128, max_seq, 0, None, 0, None, _lib.current_stream()))
+        _lib.check(_qkn_fn(lib, "amq_attn_decode_rows_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, R,
+                                                                  n_heads, n_kv_heads, 128, max_seq, 0, None, 0, None, _lib.current_stream()))
     return out
 
 

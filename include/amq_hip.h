@@ -532,6 +532,42 @@ int amq_rope_cache_batch_f16(void* q, const void* k, const void* v, void* kcache
  * with batch_size > 1, BASELINE.json configs[3]). */
 int amq_rope_rows_f16(void* q, void* k, const void* rope_table, int rope_rows, int pos0, int rows, int seq_len, int n_heads,
                       int n_kv_heads, int head_dim, void* stream);
+/* ---- per-head q / k RMSNorm in front of the rotation (Qwen3) ------------------------------------------------------------------------
+ * Qwen3 applies an RMSNorm over the 128 values of every head of q and of k before the rotation (q_norm / k_norm: one fp16 [128] weight each,
+ * shared by all heads of a layer).  The amq_*_qkn_f16 entry points are the rotating entry points above with that norm inside the same kernel:
+ * x' = gamma * fp16(x * rsqrt(mean(x^2) + eps)) (fp32 statistic, one fp16 rounding, fp16 multiply: HF's Qwen3RMSNorm, amq_rmsnorm_f16's
+ * arithmetic), then the unchanged fp16 rotation.  The statistic is one fixed summation tree in every kernel, so the key row a prompt pass writes,
+ * the row a decode step appends (per-head, split, grouped-query kernel) and the row a `rows` workgroup rotates for itself have the same bits.
+ * `norm`: host struct, device pointers; q_gamma and k_gamma both set.  norm == NULL: the entry point without the suffix, unchanged.
+ * Every other argument, result and error as documented for the entry point of the same name. */
+typedef struct amq_qk_norm {
+    const void* q_gamma;      /* fp16 [128] */
+    const void* k_gamma;      /* fp16 [128] */
+    float eps;
+} amq_qk_norm;
+int amq_attn_decode_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                            const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
+                            int max_seq, float rope_theta, const void* rope_table, void* stream);
+int amq_attn_decode_cur_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                const void* step_state, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
+                                void* stream);
+int amq_attn_decode_split_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                  const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads,
+                                  int head_dim, int max_seq, float rope_theta, const void* rope_table, int n_splits,
+                                  void* workspace, size_t workspace_bytes, void* tickets, void* stream);
+int amq_attn_decode_seq_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                void* step_states, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
+                                void* workspace, size_t workspace_bytes, void* tickets, void* stream);
+int amq_attn_decode_rows_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                 void* step_states, int rows, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
+                                 void* workspace, size_t workspace_bytes, void* tickets, void* stream);
+/* amq_rope_cache_batch_f16 (batch 1: amq_rope_cache_f16) and amq_rope_rows_f16 with the heads of q and k normalised first */
+int amq_rope_cache_qkn_f16(const amq_qk_norm* norm, void* q, const void* k, const void* v, void* kcache, void* vcache, const void* rope_table,
+                           int rope_rows, int pos0, int S, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
+                           void* stream);
+int amq_rope_rows_qkn_f16(const amq_qk_norm* norm, void* q, void* k, const void* rope_table, int rope_rows, int pos0, int rows, int seq_len,
+                          int n_heads, int n_kv_heads, int head_dim, void* stream);
+
 /* out = fp16(silu(gate)) * up elementwise, n fp16 elements (n % 8 == 0): the LlamaMLP activation between up/gate and down */
 int amq_silu_mul_f16(const void* gate, const void* up, void* out, size_t n, void* stream);
 
