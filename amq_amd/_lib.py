@@ -110,6 +110,9 @@ SIGNATURES = {
     "amq_decode_tail_suppress_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "amq_sample_f16": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "amq_decode_tail_sample_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    # evaluation metrics over rows of logits: per-row NLL / log-sum-exp / arg-max, per-row JSD against a second model's logits
+    "amq_logit_nll_f16": (_i, [_vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "amq_logit_jsd_f16": (_i, [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _i, _i, _i, _f, _vp, _vp]),
     "amq_set_token_f16": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     # sequences at positions of their own: an array of step-state blocks STEP_STATE_STRIDE bytes apart
     "amq_attn_decode_seq_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),

@@ -918,6 +918,31 @@ int amq_sample_f16(const void* logits, int rows, int vocab, void* state, const i
     return check_hip(amq::launch_sample(a, rows, (hipStream_t)stream), "sample");
 }
 
+/* ---- evaluation metrics over rows of logits (amq_eval.hip) ---- */
+static int check_logit_rows(int M, int V, long long stride, const char* which) {
+    if (M < 1) return fail(AMQ_EINVAL, "M (rows) must be >= 1 (got %d)", M);
+    if (V < 1) return fail(AMQ_EINVAL, "V (vocabulary) must be >= 1 (got %d)", V);
+    if (stride < (long long)V) return fail(AMQ_ESHAPE, "%s: a row stride of %lld elements is shorter than a row of V = %d", which, stride, V);
+    return AMQ_OK;
+}
+
+int amq_logit_nll_f16(const void* logits, long long row_stride, const long long* labels, int M, int V, float* nll_out, float* lse_out,
+                      int* argmax_out, void* stream) {
+    if (!logits || !nll_out) return fail(AMQ_EINVAL, "null pointer (logits and nll_out are required)");
+    if (int rc = check_logit_rows(M, V, row_stride, "row_stride")) return rc;
+    return check_hip(amq::launch_logit_nll(logits, row_stride, labels, M, V, nll_out, lse_out, argmax_out, (hipStream_t)stream), "logit_nll");
+}
+
+int amq_logit_jsd_f16(const void* p, long long p_stride, const void* q, long long q_stride, int q_is_f32, int M, int V, float eps, float* jsd_out,
+                      void* stream) {
+    if (!p || !q || !jsd_out) return fail(AMQ_EINVAL, "null pointer");
+    if (q_is_f32 != 0 && q_is_f32 != 1) return fail(AMQ_EINVAL, "q_is_f32 must be 0 (fp16 q) or 1 (fp32 q), got %d", q_is_f32);
+    if (!(eps >= 0.0f)) return fail(AMQ_EINVAL, "eps must be >= 0");
+    if (int rc = check_logit_rows(M, V, p_stride, "p_stride")) return rc;
+    if (int rc = check_logit_rows(M, V, q_stride, "q_stride")) return rc;
+    return check_hip(amq::launch_logit_jsd(p, p_stride, q, q_stride, q_is_f32 != 0, M, V, eps, jsd_out, (hipStream_t)stream), "logit_jsd");
+}
+
 int amq_decode_tail_sample_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
                                const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids, void* state,
                                void* stream) {

@@ -248,6 +248,12 @@ struct LookupArgs {
 };
 hipError_t launch_decode_tail_lookup(const LookupArgs& a, int rows, hipStream_t st);
 
+// evaluation metrics over rows of logits (amq_eval.hip): one workgroup per row; strides in elements; lse_out / argmax_out / labels may be null
+hipError_t launch_logit_nll(const void* logits, long long row_stride, const void* labels, int M, int V, float* nll_out, float* lse_out,
+                            int* argmax_out, hipStream_t st);
+hipError_t launch_logit_jsd(const void* p, long long p_stride, const void* q, long long q_stride, bool q_is_f32, int M, int V, float eps,
+                            float* jsd_out, hipStream_t st);
+
 // q / k / v GEMV + decode attention in one launch (amq_gemv.hip): a's segments 0 .. 2 = q, k, v (M = 1, RMSNorm prologue, gamma / eps
 // set); t: caches, output, step-state block (rope_cur), head counts, max_seq; tickets: int32 [n_heads], zero before and after
 hipError_t launch_gemv_qkv_attn(GemvArgs& a, const AttnArgs& t, int* tickets, hipStream_t st);

@@ -39,7 +39,12 @@ on the runner (``QuantLlama(lookup=k, ngram_max=g)``, cached under ``("lookup", 
 sequence's own history in one pass of the weights.  The tokens are the greedy decode's whatever is guessed; the guesses follow the MOST RECENT earlier
 occurrence of the last g .. 1 tokens (HF takes the earliest: only the acceptance rate differs).  ``lookup_request`` is the routing predicate.
 
-Anything else -- sampling and open-ended calls without that flag, a padded mask without ``padded=True``, right padding, an all-zero mask row, ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``, beams, an attention mask with holes, ``past_key_values``, ``labels``, ``inputs_embeds``, hidden-state / attention outputs,
+With ``convert_model_to_hip(model, scoring=True)`` (opt-in as well) ``model(input_ids, start_pos=0, labels=lab, use_cache=False)`` stays on the fast
+path and returns ``loss`` as well: HF's causal-LM loss -- the mean cross-entropy of row t against ``lab[:, t + 1]``, labels of -100 ignored -- formed
+by ops.logit_nll on the runner's rows of logits (one launch; no fp32 copy of the logits goes into it).  ``logits`` is returned as without labels.
+(``amq_amd.evaluate`` scores whole windows without materialising their logits at all.)
+
+Anything else -- sampling and open-ended calls without that flag, ``labels`` without ``scoring=True`` or with ``start_pos`` other than 0, a padded mask without ``padded=True``, right padding, an all-zero mask row, ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff``, beams, an attention mask with holes, ``past_key_values``, ``labels``, ``inputs_embeds``, hidden-state / attention outputs,
 stopping criteria, streamers, more than 8 sequences, a call without ``start_pos`` -- falls through to the model's original ``forward`` / ``generate``
 (HF's own, over the fused modules).  ``state_dict`` / ``deepcopy`` / ``.to()`` are untouched: the runners live outside the module, keyed weakly by it.
 """
@@ -200,7 +205,10 @@ def _fast_forward(self, input_ids=None, attention_mask=None, position_ids=None, 
     orig = self.__dict__["_amq_orig_forward"]
     extras = {k: v for k, v in kwargs.items() if v is not None and v is not False and not (k == "return_dict" and v is True)
               and not (k == "logits_to_keep" and v == 0)}
-    if (start_pos is None or not _plain_ids(input_ids) or past_key_values is not None or inputs_embeds is not None or labels is not None
+    # convert_model_to_hip(model, scoring=True): integer labels of the ids' shape on a pass from position 0 are served (loss below)
+    scored = (labels is not None and self.__dict__.get("_amq_scoring", False) and start_pos is not None and int(start_pos) == 0
+              and _plain_ids(input_ids) and isinstance(labels, torch.Tensor) and labels.shape == input_ids.shape and not labels.dtype.is_floating_point)
+    if (start_pos is None or not _plain_ids(input_ids) or past_key_values is not None or inputs_embeds is not None or (labels is not None and not scored)
             or position_ids is not None or use_cache or extras or not input_ids.is_cuda or not _mask_is_full(attention_mask, input_ids)):
         if start_pos is not None:
             raise ValueError("model(..., start_pos=) serves input_ids [1..8, S] on the GPU with use_cache=False and nothing else "
@@ -221,9 +229,21 @@ def _fast_forward(self, input_ids=None, attention_mask=None, position_ids=None, 
     else:
         r.prefill(ids, start_pos=start_pos)
         logits = r.logits_rows.float()
-    out = CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=None, hidden_states=None, attentions=None)
+    loss = _shifted_ce(r.logits_rows, labels) if scored else None       # (scored: start_pos = 0, so the pass above was a prompt pass)
+    out = CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=None, hidden_states=None, attentions=None)
     out["start_pos"] = start_pos + S          # (the reference's output carries it: ftllama_modeling.py:486)
     return out
+
+
+def _shifted_ce(rows, labels):
+    """HF's causal-LM loss from fp16 logits ``rows`` [B, S, vocab] and ``labels`` [B, S]: mean over the rows t < S - 1 whose label labels[:, t + 1] is not
+    -100 of lse(rows[:, t]) - rows[:, t, label] (ops.logit_nll gives 0 for an ignored row); NaN when every label is ignored, as HF's is"""
+    from . import ops
+    B, S, V = rows.shape
+    lab = torch.full((B, S), -100, dtype=torch.int64, device=rows.device)
+    lab[:, :S - 1] = labels[:, 1:].to(rows.device)
+    nll, _, _ = ops.logit_nll(rows.reshape(B * S, V), lab.view(-1))
+    return nll.double().sum().div(lab.ne(-100).sum()).float()
 
 
 def _fast_generate(self, inputs=None, generation_config=None, logits_processor=None, stopping_criteria=None, prefix_allowed_tokens_fn=None,
@@ -335,20 +355,22 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     return torch.cat([ids, new.view(B, -1).to(ids.dtype)], dim=1)
 
 
-def convert_model_to_hip(model, sampling=False, padded=False, lookup=False):
+def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scoring=False):
     """convert_model_to_ft(model) + replace_generate_functions() (ftllama_modeling.py:569-580, ftllama_generate.py:613-622) for the HIP backend:
     call it on the model ``prepare_for_inference(model, backend='hip')`` returned (a Llama-family ``*ForCausalLM`` whose decoder linears are
     HIPQuantLinear modules on one GPU).  Patches THIS instance's ``forward`` and ``generate`` (see the module docstring); idempotent; returns the
     model.  ``sampling=True`` also routes ``generate(do_sample=True, temperature / top_k / top_p)`` and open-ended calls (EOS stop) to the runner;
     ``padded=True`` also routes ``generate`` calls whose ``attention_mask`` is LEFT padding (``padding_side="left"``) to a runner that decodes every
     row at a position of its own; ``lookup=True`` also routes ``generate(prompt_lookup_num_tokens=k, ...)`` calls for one sequence to a
-    prompt-lookup speculative runner (``lookup_request``).  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
+    prompt-lookup speculative runner (``lookup_request``); ``scoring=True`` keeps ``model(ids, start_pos=0, labels=..., use_cache=False)`` on the runner and
+    returns HF's shifted cross-entropy as ``loss``.  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
     if "_amq_orig_forward" in model.__dict__:
         model.__dict__["_amq_sampling"] = bool(sampling)
         model.__dict__["_amq_padded"] = bool(padded)
         model.__dict__["_amq_lookup"] = bool(lookup)
+        model.__dict__["_amq_scoring"] = bool(scoring)
         return model
     from .llama import QuantLlama
     QuantLlama.check_hf(model)                               # refuse now, with the reason, what the runner cannot serve
@@ -357,6 +379,7 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False):
     model.__dict__["_amq_sampling"] = bool(sampling)
     model.__dict__["_amq_padded"] = bool(padded)
     model.__dict__["_amq_lookup"] = bool(lookup)
+    model.__dict__["_amq_scoring"] = bool(scoring)
     model.forward = types.MethodType(_fast_forward, model)
     model.generate = types.MethodType(_fast_generate, model)
     return model
@@ -370,6 +393,7 @@ def revert_model_to_hf(model):
     model.__dict__.pop("_amq_sampling", None)
     model.__dict__.pop("_amq_padded", None)
     model.__dict__.pop("_amq_lookup", None)
+    model.__dict__.pop("_amq_scoring", None)
     _RUNNERS.pop(model, None)
     return model
 

@@ -1003,16 +1003,82 @@ class QuantLlama:
         if self.vocab % 16 == 0:
             rows = ops.gemm_f16w(ops.rmsnorm(x, self.norm, self.eps), self.lm_head).view(B, S, self.vocab)
         else:                                   # (the fp16 GEMM writes 16-column blocks; odd vocabularies -- test models -- go through the weight-streaming kernel, 8 rows a launch)
-            rows = torch.empty(B * S, self.vocab, dtype=torch.float16, device=x.device)
-            for r0 in range(0, B * S, 8):
-                r1 = min(B * S, r0 + 8)
-                if r1 - r0 == 1:
-                    ops.gemv_f16w(x[r0], self.lm_head, gamma=self.norm, eps=self.eps, out=rows[r0])
-                else:
-                    ops.gemv_f16w(x[r0:r1], self.lm_head, gamma=self.norm, eps=self.eps, out=rows[r0:r1])
-            rows = rows.view(B, S, self.vocab)
+            rows = self._lm_head_streamed(x, torch.empty(B * S, self.vocab, dtype=torch.float16, device=x.device)).view(B, S, self.vocab)
         last_logits.view(B, self.vocab).copy_(rows[:, S - 1])
         return rows
+
+    def _lm_head_streamed(self, x, out):
+        """out [n, vocab] = lm_head(final RMSNorm(x [n, H])) through the weight-streaming kernel, 8 rows a launch (any vocabulary)"""
+        n = x.shape[0]
+        for r0 in range(0, n, 8):
+            r1 = min(n, r0 + 8)
+            if r1 - r0 == 1:
+                ops.gemv_f16w(x[r0], self.lm_head, gamma=self.norm, eps=self.eps, out=out[r0])
+            else:
+                ops.gemv_f16w(x[r0:r1], self.lm_head, gamma=self.norm, eps=self.eps, out=out[r0:r1])
+        return out
+
+    # rows of logits formed at a time by score_rows: the fp16 scratch is [SCORE_ROWS, vocab] (156 MB at 512 x 152064, against the 1.87 GB of a
+    # 2048-token window's fp16 + fp32 logits)
+    SCORE_ROWS = 512
+
+    @staticmethod
+    def score_chunks(S, rows):
+        """the scored rows 0 .. S - 2 of a window of S tokens (its last row has no label) as [(first, end)] pieces of at most ``rows`` rows"""
+        if S < 2 or rows < 1:
+            raise ValueError(f"a scored window needs at least 2 tokens and a chunk at least 1 row (got S={S}, rows={rows})")
+        return [(t0, min(S - 1, t0 + rows)) for t0 in range(0, S - 1, rows)]
+
+    def score_rows(self, ids, dense_logits=None):
+        """The evaluation metrics of this model on token windows ``ids`` [B, S] (or [S]): per-row negative log-likelihood, row t scored against
+        ids[:, t + 1] -> float32 [B, S - 1] on the device; with ``dense_logits`` ([B, S, vocab] or [S, vocab], fp16 or fp32, device or host: the
+        dense model's logits on the same windows) also the per-row Jensen-Shannon divergence (ops.logit_jsd: the reference's JSD) -> (nll, jsd).
+
+        One prompt pass over all B * S rows without a KV cache (any B; S <= max_seq, the RoPE table): caches, positions and tokens of the runner
+        are untouched.  The logits of a window never exist: the final hidden rows are walked in pieces of SCORE_ROWS rows -- final RMSNorm, lm_head
+        into one reused fp16 scratch, one metric launch (two with JSD) on it; host-side dense logits are moved a piece at a time.  Nothing
+        synchronises."""
+        ids = ids.to(self.dev)
+        if ids.dim() == 1:
+            ids = ids[None, :]
+        if ids.dim() != 2 or ids.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"expected integer ids [B, S] or [S], got {ids.dtype} of shape {tuple(ids.shape)}")
+        B, S = ids.shape
+        if B < 1 or S < 2:
+            raise ValueError(f"a scored window needs at least 2 tokens (got ids of shape {tuple(ids.shape)})")
+        if S > self.max_seq:
+            raise ValueError(f"window of {S} tokens longer than the RoPE table (max_seq={self.max_seq})")
+        if dense_logits is not None:
+            if dense_logits.dim() == 2:
+                dense_logits = dense_logits[None]
+            if tuple(dense_logits.shape) != (B, S, self.vocab) or dense_logits.dtype not in (torch.float16, torch.float32):
+                raise ValueError(f"dense_logits: expected fp16 / fp32 [{B}, {S}, {self.vocab}], got {dense_logits.dtype} {tuple(dense_logits.shape)}")
+            if dense_logits.stride(2) != 1 or dense_logits.stride(1) < self.vocab:
+                dense_logits = dense_logits.contiguous()
+        R = int(self.SCORE_ROWS)
+        chunks = self.score_chunks(S, R)
+        x = self._rows_pass(ids, 0, cache=False).view(B, S, self.H)
+        labels = ids[:, 1:].to(torch.int64).contiguous()
+        buf = getattr(self, "_score_buf", None)
+        if buf is None or buf[0].shape[0] != R:
+            dev = self.dev
+            buf = self._score_buf = (torch.empty(R, self.vocab, dtype=torch.float16, device=dev), torch.empty(R, dtype=torch.float32, device=dev),
+                                     torch.empty(R, dtype=torch.int32, device=dev))
+        scratch, lse, amax = buf
+        nll = torch.empty(B, S - 1, dtype=torch.float32, device=self.dev)
+        jsd = None if dense_logits is None else torch.empty(B, S - 1, dtype=torch.float32, device=self.dev)
+        for b in range(B):
+            for t0, t1 in chunks:
+                n = t1 - t0
+                rows, lg = x[b, t0:t1], scratch[:n]
+                if self.vocab % 16 == 0:
+                    ops.gemm_f16w(ops.rmsnorm(rows, self.norm, self.eps), self.lm_head, out=lg)
+                else:
+                    self._lm_head_streamed(rows, lg)
+                ops.logit_nll(lg, labels[b, t0:t1], out=(nll[b, t0:t1], lse[:n], amax[:n]))
+                if jsd is not None:
+                    ops.logit_jsd(lg, dense_logits[b, t0:t1].to(self.dev, non_blocking=True), out=jsd[b, t0:t1])
+        return nll if jsd is None else (nll, jsd)
 
     # prompt rows (exclusive, inclusive) served by the fragment-ordered few-row kernels with q/k/v and gate/up as grouped
     # launches.  7B avg-3, ms per prompt pass, this path | the row-major / tiled kernels: 16 rows 2.91 | 2.55, 24 3.03 | 3.13,

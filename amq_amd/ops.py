@@ -750,6 +750,58 @@ def sample(logits, state, u=None, kept_out=None, suppress=None, out=None, seq0=0
     return tok
 
 
+def _need_rows(t, dtypes, name):
+    """a 2-D GPU tensor [M, V] whose rows are dense (any row stride >= V) -> (M, V, row stride in elements)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a tensor on the GPU")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{name}: expected {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name}: expected [rows, vocab] with at least one row and one column, got {tuple(t.shape)}")
+    M, V = t.shape
+    if (V > 1 and t.stride(1) != 1) or (M > 1 and t.stride(0) < V):
+        raise ValueError(f"{name}: rows must be dense and at least a row apart (strides {tuple(t.stride())})")
+    return M, V, (t.stride(0) if M > 1 else V)
+
+
+def logit_nll(logits, labels=None, out=None):
+    """(nll, lse, argmax) per row of fp16 logits [M, V] (any row stride): amq_logit_nll_f16.  ``labels``: int64 [M] on the same device; -100 (HF's
+    ignore_index) gives nll = 0, any other label outside the vocabulary NaN; None: every nll is 0.  nll / lse are float32 [M], argmax int32 [M]
+    (the first maximum).  ``out``: a (nll, lse, argmax) triple to write into.  No synchronisation."""
+    M, V, stride = _need_rows(logits, (torch.float16,), "logits")
+    if labels is not None:
+        _need(labels, torch.int64, "labels", M)
+        if labels.device != logits.device:
+            raise ValueError("labels: must be on the device of logits")
+    if out is None:
+        out = (torch.empty(M, dtype=torch.float32, device=logits.device), torch.empty(M, dtype=torch.float32, device=logits.device),
+               torch.empty(M, dtype=torch.int32, device=logits.device))
+    nll, lse, amax = out
+    for t, dt, nm in ((nll, torch.float32, "nll"), (lse, torch.float32, "lse"), (amax, torch.int32, "argmax")):
+        _need(t, dt, nm, M)
+        if t.device != logits.device:
+            raise ValueError(f"{nm}: must be on the device of logits")
+    _lib.check(_lib.load().amq_logit_nll_f16(_lib.ptr(logits), stride, _lib.ptr(labels), M, V, _lib.ptr(nll), _lib.ptr(lse), _lib.ptr(amax),
+                                             _lib.current_stream()))
+    return nll, lse, amax
+
+
+def logit_jsd(p, q, eps=1e-7, out=None):
+    """Jensen-Shannon divergence per row between fp16 logits ``p`` [M, V] and ``q`` [M, V] (fp16 or fp32), the reference's ``JSD`` (mixture clamped
+    at ``eps`` before its log: identical rows score slightly negative) -> float32 [M]: amq_logit_jsd_f16.  Any row strides.  No synchronisation."""
+    M, V, ps = _need_rows(p, (torch.float16,), "p")
+    Mq, Vq, qs = _need_rows(q, (torch.float16, torch.float32), "q")
+    if (Mq, Vq) != (M, V) or q.device != p.device:
+        raise ValueError(f"q: expected [{M}, {V}] on {p.device}, got {tuple(q.shape)} on {q.device}")
+    y = out if out is not None else torch.empty(M, dtype=torch.float32, device=p.device)
+    _need(y, torch.float32, "out", M)
+    if y.device != p.device:
+        raise ValueError("out: must be on the device of p")
+    _lib.check(_lib.load().amq_logit_jsd_f16(_lib.ptr(p), ps, _lib.ptr(q), qs, 1 if q.dtype is torch.float32 else 0, M, V, ctypes.c_float(eps),
+                                             _lib.ptr(y), _lib.current_stream()))
+    return y
+
+
 def decode_tail_sample(logits, embed, token, pos, x, state, table=None, cur=None, suppress=None):
     """:func:`decode_tail` with the token drawn by :func:`sample` (draw counter advanced, EOS bookkeeping) instead of the arg-max -- one launch"""
     vocab, hidden = embed.shape
@@ -1336,7 +1388,7 @@ def _on_tensor_device(fn):
 
 
 for _name in ("repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
-              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "decode_tail_sample", "rope_cache",
+              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name

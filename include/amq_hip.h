@@ -346,6 +346,29 @@ int amq_decode_tail_sample_f16(const void* logits, int vocab, const void* embed,
                                const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids, void* state,
                                void* stream);
 
+/* ---- evaluation metrics of the deployed model: row reductions over fp16 logits (amq_eval.hip) ----------------
+ * One workgroup per row, fp32 arithmetic, a fixed summation order (per-thread serial sums, DPP wave reduce, waves in order through LDS; no
+ * atomics): a row's result has the same bits launched alone or among others and does not depend on its index or alignment.  Rows may have any
+ * alignment of their element type; strides are in ELEMENTS and >= V.  No synchronisation.  AMQ_EINVAL: null pointer, M < 1, V < 1, bad flag;
+ * AMQ_ESHAPE: a stride shorter than a row.
+ *
+ * amq_logit_nll_f16: logits fp16 [M rows of V, row_stride apart]; labels int64 [M] on the device, or NULL (every row as if labelled -100).
+ * Per row:   lse = max + log(sum_v exp(l[v] - max)),   nll = lse - float(l[label]),   argmax = index of the first maximum (int32).
+ * label == -100 (HF's ignore_index): nll = 0, the caller counts the row out.  Any other label outside 0 .. V - 1: nll = NaN for that row; the
+ * logit is not read.  nll_out float [M]; lse_out float [M] and argmax_out int32 [M] may be NULL. */
+int amq_logit_nll_f16(const void* logits, long long row_stride, const long long* labels, int M, int V, float* nll_out, float* lse_out,
+                      int* argmax_out, void* stream);
+/* amq_logit_jsd_f16: p fp16 (this model's logits), q fp16 (q_is_f32 = 0) or fp32 (q_is_f32 = 1) (the dense model's), both [M rows of V].
+ * Per row, the reference's JSD (amq/utils/loss.py: KLDivLoss with log_target against the clamped mixture) on fp32 values:
+ *     lp = p - lse_p,   lq = q - lse_q,   m = log(max(0.5 * (e^lp + e^lq), eps)),
+ *     jsd = 0.5 * sum_v [ e^lp * (lp - m) + e^lq * (lq - m) ]
+ * Where the mixture is not clamped, lp - m and lq - m are evaluated from d = lq - lp as -log(0.5 (1 + e^d)) and d - log(0.5 (1 + e^d)): the same
+ * values, without the half-ulp-at-log-V error that forming lp and m first would put into every term.
+ * The clamp is part of the definition: identical rows score slightly NEGATIVE where entries fall below eps (about -2.4e-4 at V = 32000 with the
+ * reference's eps = 1e-7).  Inputs are finite; what -inf logits give is unspecified.  jsd_out float [M]. */
+int amq_logit_jsd_f16(const void* p, long long p_stride, const void* q, long long q_stride, int q_is_f32, int M, int V, float eps, float* jsd_out,
+                      void* stream);
+
 /* ---- sequences at positions of their OWN (batched decode over prompts of unequal length) ----------------
  * The batched entry points above keep ONE step state: every sequence is at the same position.  Here `step_states` is an ARRAY of `batch` blocks
  * with the layout of amq_attn_decode_cur_f16's block
