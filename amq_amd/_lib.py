@@ -126,14 +126,6 @@ SIGNATURES = {
     "amq_rope_cache_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "amq_rope_cache_batch_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "amq_rope_rows_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    # the rotating entry points with Qwen3's per-head q / k RMSNorm inside the kernel: the signature of the entry point without `_qkn` behind a QkNorm*
-    "amq_attn_decode_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "amq_attn_decode_cur_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "amq_attn_decode_split_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _sz, _vp, _vp]),
-    "amq_attn_decode_seq_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
-    "amq_attn_decode_rows_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
-    "amq_rope_cache_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "amq_rope_rows_qkn_f16": (_i, [_qkn, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "amq_silu_mul_f16": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "amq_gemv_grouped_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, ctypes.POINTER(GemvOpts), _vp]),
     "amq_gemv_grouped_sums_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),
@@ -143,6 +135,13 @@ SIGNATURES = {
     "amq_gemm_res_norm_xfrag_f16": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _f, _vp, _vp]),
     "amq_gemm_route_f16": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
+
+# the rotating entry points with Qwen3's per-head q / k RMSNorm inside the kernel: the signature of the entry point without `_qkn` behind a QkNorm*
+# (amq_rope_cache_qkn_f16 is the twin of the batch form)
+for _base in ("amq_attn_decode_f16", "amq_attn_decode_cur_f16", "amq_attn_decode_split_f16", "amq_attn_decode_seq_f16", "amq_attn_decode_rows_f16",
+              "amq_rope_cache_batch_f16", "amq_rope_rows_f16"):
+    SIGNATURES[_base.replace("_batch", "")[:-len("_f16")] + "_qkn_f16"] = (_i, [_qkn] + SIGNATURES[_base][1])
+del _base
 
 # name -> (restype, argtypes) of include/amq_hip_ab.h
 AB_SIGNATURES = {

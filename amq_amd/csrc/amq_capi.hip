@@ -746,6 +746,75 @@ int amq_gemv_f16w_rows(const void* x, const void* W, const void* bias, void* y, 
     return check_hip(amq::launch_gemv_f16w(x, W, bias, y, gamma, eps, N, K, (hipStream_t)stream, M), "gemv_f16w_rows");
 }
 
+/* ---- decode attention: ten entry points, one validator and dispatcher.  What differs between them is the AttnForm ("Decode-step
+   entry points: what is checked"); the checks run in the order of this function for every one of them ---- */
+enum : unsigned {           // where the position(s) of the new token(s) may come from
+    POS_HOST = 1,           // the host int `pos`: checked against max_seq when neither of the next two is given
+    POS_DEV = 2,            // the device int32 `pos_dev`
+    POS_BLOCK = 4,          // one step-state block for the whole batch
+    POS_BLOCKS = 8,         // an array of `batch` step-state blocks: every sequence at its own position
+    POS_ROWS = 16,          // ... the blocks being consecutive positions of ONE sequence
+};
+enum AttnSplits { SPLITS_NONE, SPLITS_REQUIRED, SPLITS_OPTIONAL };      // n_splits: not an argument / 1..1024 / 0 (one workgroup per head) or 1..1024
+struct AttnForm {
+    unsigned pos;           // POS_*: without POS_HOST / POS_DEV the step state is a required pointer
+    int batch_min, batch_max;
+    AttnSplits splits;      // SPLITS_REQUIRED: workspace and tickets are required pointers too
+    size_t extra_lds;       // bytes beside the score array and the kernel's own 6 * 128 + 17 KiB
+    const char* what;       // names the launch in a HIP error
+    const char* rows;       // what `batch` counts, in messages
+};
+constexpr int NO_BOUND = 0x7fffffff;
+constexpr AttnForm ATTN_POS{POS_HOST | POS_DEV, 1, NO_BOUND, SPLITS_NONE, 0, "attn_decode", "batch"};
+constexpr AttnForm ATTN_CUR{POS_BLOCK, 1, NO_BOUND, SPLITS_NONE, 0, "attn_decode_cur", "batch"};
+constexpr AttnForm ATTN_SPLIT{POS_HOST | POS_DEV | POS_BLOCK, 1, 65535, SPLITS_REQUIRED, 0, "attn_decode_split", "batch"};
+constexpr AttnForm ATTN_SEQ{POS_BLOCKS, 1, 65535, SPLITS_OPTIONAL, 0, "attn_decode_seq", "batch"};
+// (rows: the earlier rows' rotated keys and values sit behind the score array)
+constexpr AttnForm ATTN_ROWS{POS_ROWS, 2, AMQ_LOOKUP_MAX_ROWS, SPLITS_OPTIONAL, 2 * 7 * 128 * 2 + 16, "attn_decode_rows", "rows"};
+
+size_t amq_attn_decode_split_workspace_bytes(int batch, int n_heads, int n_splits) {
+    if (batch < 1 || n_heads < 1 || n_splits < 1) return 0;
+    return (size_t)batch * n_heads * n_splits * 132 * sizeof(float);
+}
+
+// An entry point passes what its signature lacks as: state / pos_dev / rope_table / workspace / tickets null, pos 0, rope_theta 10000, n_splits 0.
+static int attn_decode(const AttnForm& f, const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                       const void* state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
+                       float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
+    amq::QkNorm nrm;
+    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
+    const bool state_required = !(f.pos & (POS_HOST | POS_DEV));
+    if (!q || !k || !v || !kcache || !vcache || !out || (state_required && !state) || (f.splits == SPLITS_REQUIRED && (!workspace || !tickets)))
+        return fail(AMQ_EINVAL, "null pointer");
+    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
+    if (batch < f.batch_min || batch > f.batch_max) return fail(AMQ_ESHAPE, "%s must be %d..%d (got %d)", f.rows, f.batch_min, f.batch_max, batch);
+    if (n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
+        return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads)", n_heads, n_kv_heads);
+    if (max_seq < 1 || (!state && !pos_dev && (pos < 0 || pos >= max_seq)))
+        return fail(AMQ_ESHAPE, "position %d outside the cache (max_seq=%d)", pos, max_seq);
+    if (f.splits != SPLITS_NONE && (n_splits < (f.splits == SPLITS_REQUIRED ? 1 : 0) || n_splits > 1024))
+        return fail(AMQ_EINVAL, "n_splits must be %s1..1024 (got %d)", f.splits == SPLITS_REQUIRED ? "" : "0 (one workgroup per head) or ", n_splits);
+    if (n_splits && (!workspace || !tickets)) return fail(AMQ_EINVAL, "null pointer (workspace / tickets are required with n_splits >= 1)");
+    int keys = max_seq;             // ... one workgroup scores: the whole cache, or its chunk of it
+    if (n_splits) {
+        keys = (((max_seq + n_splits - 1) / n_splits) + 31) & ~31;
+        keys = keys < amq::ATT_MIN_CHUNK ? amq::ATT_MIN_CHUNK : keys;
+    }
+    if (6 * 128 + (size_t)keys * 4 + f.extra_lds + 17 * 1024 > LDS_LIMIT)
+        return n_splits ? fail(AMQ_ESHAPE, "max_seq=%d over %d splits leaves chunks of %d keys: too long", max_seq, n_splits, keys)
+                        : fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
+    const size_t need = amq_attn_decode_split_workspace_bytes(batch, n_heads, n_splits);
+    if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    // a step state carries the position and its cos/sin row: pos_dev, rope_theta and rope_table are then not looked at
+    amq::AttnArgs a{q, k, v, kcache, vcache, out, state ? nullptr : pos_dev, pos, n_heads, n_kv_heads, max_seq, state ? 10000.0f : rope_theta,
+                    state ? nullptr : rope_table, state, (f.pos & (POS_BLOCKS | POS_ROWS)) != 0, (f.pos & POS_ROWS) != 0};
+    a.norm = nrm;
+    const hipError_t e = n_splits ? amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream)
+                                  : amq::launch_attn_decode(a, batch, (hipStream_t)stream);
+    if (e == hipSuccess) return AMQ_OK;
+    return fail(AMQ_ELAUNCH, "%s%s: %s", f.what, n_splits && f.splits == SPLITS_OPTIONAL ? " (split)" : "", hipGetErrorString(e));
+}
+
 int amq_attn_decode_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                         const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
                         int max_seq, float rope_theta, const void* rope_table, void* stream) {
@@ -755,17 +824,8 @@ int amq_attn_decode_f16(const void* q, const void* k, const void* v, void* kcach
 int amq_attn_decode_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                             const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
                             int max_seq, float rope_theta, const void* rope_table, void* stream) {
-    amq::QkNorm nrm;
-    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
-    if (!q || !k || !v || !kcache || !vcache || !out) return fail(AMQ_EINVAL, "null pointer");
-    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
-    if (batch < 1 || n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
-        return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads)", n_heads, n_kv_heads);
-    if (max_seq < 1 || (!pos_dev && (pos < 0 || pos >= max_seq))) return fail(AMQ_ESHAPE, "position %d outside the cache (max_seq=%d)", pos, max_seq);
-    if (6 * 128 + (size_t)max_seq * 4 + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
-    amq::AttnArgs a{q, k, v, kcache, vcache, out, pos_dev, pos, n_heads, n_kv_heads, max_seq, rope_theta, rope_table, nullptr};
-    a.norm = nrm;
-    return check_hip(amq::launch_attn_decode(a, batch, (hipStream_t)stream), "attn_decode");
+    return attn_decode(ATTN_POS, norm, q, k, v, kcache, vcache, out, nullptr, pos_dev, pos, batch, n_heads, n_kv_heads, head_dim, max_seq, rope_theta, rope_table,
+                       0, nullptr, 0, nullptr, stream);
 }
 
 int amq_attn_decode_cur_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
@@ -777,23 +837,8 @@ int amq_attn_decode_cur_f16(const void* q, const void* k, const void* v, void* k
 int amq_attn_decode_cur_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                                 const void* step_state, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
                                 void* stream) {
-    amq::QkNorm nrm;
-    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
-    if (!q || !k || !v || !kcache || !vcache || !out || !step_state) return fail(AMQ_EINVAL, "null pointer");
-    if (n_heads > 255) return fail(AMQ_ESHAPE, "at most 255 heads");
-    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
-    if (batch < 1 || n_heads < 1 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
-        return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads)", n_heads, n_kv_heads);
-    if (max_seq < 1) return fail(AMQ_ESHAPE, "bad max_seq %d", max_seq);
-    if (6 * 128 + (size_t)max_seq * 4 + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
-    amq::AttnArgs a{q, k, v, kcache, vcache, out, nullptr, 0, n_heads, n_kv_heads, max_seq, 10000.0f, nullptr, step_state};
-    a.norm = nrm;
-    return check_hip(amq::launch_attn_decode(a, batch, (hipStream_t)stream), "attn_decode_cur");
-}
-
-size_t amq_attn_decode_split_workspace_bytes(int batch, int n_heads, int n_splits) {
-    if (batch < 1 || n_heads < 1 || n_splits < 1) return 0;
-    return (size_t)batch * n_heads * n_splits * 132 * sizeof(float);
+    return attn_decode(ATTN_CUR, norm, q, k, v, kcache, vcache, out, step_state, nullptr, 0, batch, n_heads, n_kv_heads, head_dim, max_seq, 10000.0f, nullptr,
+                       0, nullptr, 0, nullptr, stream);
 }
 
 int amq_attn_decode_split_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
@@ -808,25 +853,8 @@ int amq_attn_decode_split_qkn_f16(const amq_qk_norm* norm, const void* q, const 
                                   const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads,
                                   int head_dim, int max_seq, float rope_theta, const void* rope_table, int n_splits,
                                   void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
-    amq::QkNorm nrm;
-    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
-    if (!q || !k || !v || !kcache || !vcache || !out || !workspace || !tickets) return fail(AMQ_EINVAL, "null pointer");
-    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
-    if (batch < 1 || batch > 65535 || n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
-        return fail(AMQ_ESHAPE, "bad head configuration (batch %d, %d q heads, %d kv heads)", batch, n_heads, n_kv_heads);
-    if (n_splits < 1 || n_splits > 1024) return fail(AMQ_EINVAL, "n_splits must be 1..1024 (got %d)", n_splits);
-    if (max_seq < 1 || (!step_state && !pos_dev && (pos < 0 || pos >= max_seq)))
-        return fail(AMQ_ESHAPE, "position %d outside the cache (max_seq=%d)", pos, max_seq);
-    int chunk = (((max_seq + n_splits - 1) / n_splits) + 31) & ~31;
-    chunk = chunk < amq::ATT_MIN_CHUNK ? amq::ATT_MIN_CHUNK : chunk;
-    if (6 * 128 + (size_t)chunk * 4 + 17 * 1024 > LDS_LIMIT)
-        return fail(AMQ_ESHAPE, "max_seq=%d over %d splits leaves chunks of %d keys: too long", max_seq, n_splits, chunk);
-    const size_t need = amq_attn_decode_split_workspace_bytes(batch, n_heads, n_splits);
-    if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    amq::AttnArgs a{q, k, v, kcache, vcache, out, step_state ? nullptr : pos_dev, pos, n_heads, n_kv_heads, max_seq,
-                    step_state ? 10000.0f : rope_theta, step_state ? nullptr : rope_table, step_state};
-    a.norm = nrm;
-    return check_hip(amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream), "attn_decode_split");
+    return attn_decode(ATTN_SPLIT, norm, q, k, v, kcache, vcache, out, step_state, pos_dev, pos, batch, n_heads, n_kv_heads, head_dim, max_seq, rope_theta, rope_table,
+                       n_splits, workspace, workspace_bytes, tickets, stream);
 }
 
 static int amq_attn_prefill_check(const void* q, const void* k, const void* v, const void* out, int batch, int S, int pos0, int n_heads,
@@ -871,37 +899,65 @@ int amq_attn_prefill_xfrag_f16(const void* q, const void* k, const void* v, void
     return check_hip(amq::launch_attn_prefill(a, (hipStream_t)stream), "attn_prefill_xfrag");
 }
 
-int amq_decode_tail_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
-                        const void* rope_table, void* rope_cur, int rope_rows, void* stream) {
-    if (!logits || !embed || !token || !pos || !x) return fail(AMQ_EINVAL, "null pointer");
+/* ---- token tails and set_token: nine entry points, one set of shared checks.  What differs between them is the TailForm ("Decode-step
+   entry points: what is checked") and what each adds behind tail_check ---- */
+enum Vocab8 { V8_NEVER, V8_TWO_ROWS, V8_ALWAYS };       // when vocab % 8 == 0 is demanded (16-byte aligned rows of logits): never / from two rows / always
+struct TailForm {
+    int batch_min, batch_max;
+    bool blocks;            // position and cos/sin row live in an array of step-state blocks and rope_table is required;
+                            // else `pos`, and rope_table / rope_cur both or neither
+    Vocab8 vocab8;
+    int size_code;          // the answer to vocab < 1 and batch < batch_min
+    const char* rows;       // what `batch` counts, in messages
+};
+constexpr TailForm TAIL_ONE{1, 1, false, V8_TWO_ROWS, AMQ_ESHAPE, "batch"};
+constexpr TailForm TAIL_BATCH{1, 65535, false, V8_TWO_ROWS, AMQ_ESHAPE, "batch"};
+constexpr TailForm TAIL_SAMPLE{1, 8, false, V8_NEVER, AMQ_EINVAL, "rows"};          // (8: the state block holds 8 finished flags)
+constexpr TailForm SET_TOKEN{1, 65535, false, V8_NEVER, AMQ_ESHAPE, "batch"};
+constexpr TailForm TAIL_SEQ{1, 65535, true, V8_TWO_ROWS, AMQ_ESHAPE, "batch"};
+constexpr TailForm TAIL_SAMPLE_SEQ{1, 8, true, V8_NEVER, AMQ_ESHAPE, "rows"};
+constexpr TailForm SET_TOKEN_SEQ{1, 65535, true, V8_NEVER, AMQ_ESHAPE, "batch"};
+constexpr TailForm TAIL_LOOKUP{2, AMQ_LOOKUP_MAX_ROWS, true, V8_ALWAYS, AMQ_ESHAPE, "rows"};
+
+// in: logits, or set_token's token_in; state: `pos`, or the step-state blocks (then also passed as rope_cur)
+static int tail_check(const TailForm& f, const void* in, int vocab, const void* embed, int hidden, const void* token, const void* state, const void* x,
+                      const void* rope_table, const void* rope_cur, int rope_rows, int batch) {
+    if (!in || !embed || !token || !state || !x || (f.blocks && !rope_table)) return fail(AMQ_EINVAL, "null pointer");
     if ((rope_table == nullptr) != (rope_cur == nullptr)) return fail(AMQ_EINVAL, "rope_table and rope_cur go together");
     if (rope_cur && rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
-    if (vocab < 1 || hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need vocab >= 1 and hidden %% 8 == 0 (got %d, %d)", vocab, hidden);
-    return check_hip(amq::launch_decode_tail(logits, vocab, embed, hidden, token, pos, x, rope_table, rope_cur, rope_rows, (hipStream_t)stream), "decode_tail");
+    if (vocab < 1) return fail(f.size_code, "vocab must be >= 1 (got %d)", vocab);
+    if (hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need hidden >= 8 and hidden %% 8 == 0 (got %d)", hidden);
+    if (batch < f.batch_min) return fail(f.size_code, "%s must be %d..%d (got %d)", f.rows, f.batch_min, f.batch_max, batch);
+    if (batch > f.batch_max) return fail(AMQ_ESHAPE, "%s must be %d..%d (got %d)", f.rows, f.batch_min, f.batch_max, batch);
+    if ((vocab % 8) != 0 && (f.vocab8 == V8_ALWAYS || (f.vocab8 == V8_TWO_ROWS && batch > 1)))
+        return fail(AMQ_ESHAPE, "several rows need vocab %% 8 == 0 (16-byte aligned logits rows)");
+    return AMQ_OK;
+}
+// the int32 position behind `state`: of block 0 (byte 256), or `pos` itself
+static void* tail_pos(const TailForm& f, void* state) { return f.blocks ? (char*)state + 256 : state; }
+
+// the arg-max tails (suppress_ids may be null here; rope_cur: the blocks again in the per-sequence form)
+static int decode_tail(const TailForm& f, const char* what, const void* logits, int vocab, const void* embed, int hidden, long long* token, void* state,
+                       void* x, const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids, void* stream) {
+    if (int rc = tail_check(f, logits, vocab, embed, hidden, token, state, x, rope_table, rope_cur, rope_rows, batch)) return rc;
+    return check_hip(amq::launch_decode_tail(logits, vocab, embed, hidden, token, tail_pos(f, state), x, rope_table, rope_cur, rope_rows,
+                                             (hipStream_t)stream, batch, suppress_ids, f.blocks), what);
+}
+
+int amq_decode_tail_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
+                        const void* rope_table, void* rope_cur, int rope_rows, void* stream) {
+    return decode_tail(TAIL_ONE, "decode_tail", logits, vocab, embed, hidden, token, pos, x, rope_table, rope_cur, rope_rows, 1, nullptr, stream);
 }
 
 int amq_decode_tail_batch_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
                               const void* rope_table, void* rope_cur, int rope_rows, int batch, void* stream) {
-    if (!logits || !embed || !token || !pos || !x) return fail(AMQ_EINVAL, "null pointer");
-    if ((rope_table == nullptr) != (rope_cur == nullptr)) return fail(AMQ_EINVAL, "rope_table and rope_cur go together");
-    if (rope_cur && rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
-    if (vocab < 1 || hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need vocab >= 1 and hidden %% 8 == 0 (got %d, %d)", vocab, hidden);
-    if (batch < 1 || batch > 65535) return fail(AMQ_ESHAPE, "bad batch %d", batch);
-    if (batch > 1 && (vocab % 8) != 0) return fail(AMQ_ESHAPE, "batched rows need vocab %% 8 == 0 (16-byte aligned logits rows)");
-    return check_hip(amq::launch_decode_tail(logits, vocab, embed, hidden, token, pos, x, rope_table, rope_cur, rope_rows, (hipStream_t)stream, batch), "decode_tail_batch");
+    return decode_tail(TAIL_BATCH, "decode_tail_batch", logits, vocab, embed, hidden, token, pos, x, rope_table, rope_cur, rope_rows, batch, nullptr, stream);
 }
 
 int amq_decode_tail_suppress_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
                                  const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids, void* stream) {
-    if (!logits || !embed || !token || !pos || !x) return fail(AMQ_EINVAL, "null pointer");
     if (!suppress_ids) return fail(AMQ_EINVAL, "suppress_ids: a device array of 8 int32 token ids (-1 = unused slot) is required");
-    if ((rope_table == nullptr) != (rope_cur == nullptr)) return fail(AMQ_EINVAL, "rope_table and rope_cur go together");
-    if (rope_cur && rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
-    if (vocab < 1 || hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need vocab >= 1 and hidden %% 8 == 0 (got %d, %d)", vocab, hidden);
-    if (batch < 1 || batch > 65535) return fail(AMQ_ESHAPE, "bad batch %d", batch);
-    if (batch > 1 && (vocab % 8) != 0) return fail(AMQ_ESHAPE, "batched rows need vocab %% 8 == 0 (16-byte aligned logits rows)");
-    return check_hip(amq::launch_decode_tail(logits, vocab, embed, hidden, token, pos, x, rope_table, rope_cur, rope_rows, (hipStream_t)stream, batch,
-                                             suppress_ids), "decode_tail_suppress");
+    return decode_tail(TAIL_BATCH, "decode_tail_suppress", logits, vocab, embed, hidden, token, pos, x, rope_table, rope_cur, rope_rows, batch, suppress_ids, stream);
 }
 
 int amq_sample_f16(const void* logits, int rows, int vocab, void* state, const int* suppress_ids, const float* u_in, long long* token_out,
@@ -943,30 +999,35 @@ int amq_logit_jsd_f16(const void* p, long long p_stride, const void* q, long lon
     return check_hip(amq::launch_logit_jsd(p, p_stride, q, q_stride, q_is_f32 != 0, M, V, eps, jsd_out, (hipStream_t)stream), "logit_jsd");
 }
 
+// the sampled tails
+static int decode_tail_sample(const TailForm& f, const char* what, const void* logits, int vocab, const void* embed, int hidden, long long* token,
+                              void* state, void* x, const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids,
+                              void* sampling, void* stream) {
+    if (!sampling) return fail(AMQ_EINVAL, "state: the 128-byte device block of sampling parameters is required (null)");
+    if (int rc = tail_check(f, logits, vocab, embed, hidden, token, state, x, rope_table, rope_cur, rope_rows, batch)) return rc;
+    amq::SampleArgs a{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, (int*)tail_pos(f, state), (_Float16*)x,
+                      (const _Float16*)rope_table, (_Float16*)rope_cur, rope_rows, suppress_ids, (int*)sampling, nullptr, nullptr, 0,
+                      AMQ_SAMPLE_ADVANCE | AMQ_SAMPLE_EOS};
+    return check_hip(amq::launch_sample(a, batch, (hipStream_t)stream, f.blocks), what);
+}
+
 int amq_decode_tail_sample_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, int* pos, void* x,
                                const void* rope_table, void* rope_cur, int rope_rows, int batch, const int* suppress_ids, void* state,
                                void* stream) {
-    if (!state) return fail(AMQ_EINVAL, "state: the 128-byte device block of sampling parameters is required (null)");
-    if (!logits || !embed || !token || !pos || !x) return fail(AMQ_EINVAL, "null pointer");
-    if ((rope_table == nullptr) != (rope_cur == nullptr)) return fail(AMQ_EINVAL, "rope_table and rope_cur go together");
-    if (rope_cur && rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
-    if (vocab < 1) return fail(AMQ_EINVAL, "vocab must be >= 1 (got %d)", vocab);
-    if (batch < 1) return fail(AMQ_EINVAL, "rows must be >= 1 (got %d)", batch);
-    if (hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need hidden %% 8 == 0 (got %d)", hidden);
-    if (batch > 8) return fail(AMQ_ESHAPE, "at most 8 sequences (the state block holds 8 finished flags), got %d", batch);
-    amq::SampleArgs a{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, pos, (_Float16*)x, (const _Float16*)rope_table,
-                      (_Float16*)rope_cur, rope_rows, suppress_ids, (int*)state, nullptr, nullptr, 0, AMQ_SAMPLE_ADVANCE | AMQ_SAMPLE_EOS};
-    return check_hip(amq::launch_sample(a, batch, (hipStream_t)stream), "decode_tail_sample");
+    return decode_tail_sample(TAIL_SAMPLE, "decode_tail_sample", logits, vocab, embed, hidden, token, pos, x, rope_table, rope_cur, rope_rows, batch, suppress_ids, state, stream);
+}
+
+static int set_token(const TailForm& f, const char* what, const long long* token_in, int n_in, const void* embed, int vocab, int hidden, long long* token,
+                     void* state, void* x, const void* rope_table, void* rope_cur, int rope_rows, int batch, void* stream) {
+    if (int rc = tail_check(f, token_in, vocab, embed, hidden, token, state, x, rope_table, rope_cur, rope_rows, batch)) return rc;
+    if (n_in != 1 && n_in != batch) return fail(AMQ_ESHAPE, "batch %d with %d input ids (1 or one per sequence)", batch, n_in);
+    return check_hip(amq::launch_set_token(token_in, n_in, embed, vocab, hidden, token, tail_pos(f, state), x, rope_table, rope_cur, rope_rows, batch,
+                                           (hipStream_t)stream, f.blocks), what);
 }
 
 int amq_set_token_f16(const long long* token_in, int n_in, const void* embed, int vocab, int hidden, long long* token, const int* pos, void* x,
                       const void* rope_table, void* rope_cur, int rope_rows, int batch, void* stream) {
-    if (!token_in || !embed || !token || !pos || !x) return fail(AMQ_EINVAL, "null pointer");
-    if ((rope_table == nullptr) != (rope_cur == nullptr)) return fail(AMQ_EINVAL, "rope_table and rope_cur go together");
-    if (rope_cur && rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
-    if (vocab < 1 || hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need vocab >= 1 and hidden %% 8 == 0 (got %d, %d)", vocab, hidden);
-    if (batch < 1 || batch > 65535 || (n_in != 1 && n_in != batch)) return fail(AMQ_ESHAPE, "batch %d with %d input ids (1 or one per sequence)", batch, n_in);
-    return check_hip(amq::launch_set_token(token_in, n_in, embed, vocab, hidden, token, pos, x, rope_table, rope_cur, rope_rows, batch, (hipStream_t)stream), "set_token");
+    return set_token(SET_TOKEN, "set_token", token_in, n_in, embed, vocab, hidden, token, (void*)pos, x, rope_table, rope_cur, rope_rows, batch, stream);
 }
 
 /* ---- sequences at positions of their own: an array of `batch` step-state blocks AMQ_STEP_STATE_STRIDE bytes apart ---- */
@@ -981,65 +1042,24 @@ int amq_attn_decode_seq_f16(const void* q, const void* k, const void* v, void* k
 int amq_attn_decode_seq_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                                 void* step_states, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
                                 void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
-    amq::QkNorm nrm;
-    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
-    if (!q || !k || !v || !kcache || !vcache || !out || !step_states) return fail(AMQ_EINVAL, "null pointer");
-    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
-    if (batch < 1 || batch > 65535 || n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
-        return fail(AMQ_ESHAPE, "bad head configuration (batch %d, %d q heads, %d kv heads)", batch, n_heads, n_kv_heads);
-    if (max_seq < 1) return fail(AMQ_ESHAPE, "bad max_seq %d", max_seq);
-    if (n_splits < 0 || n_splits > 1024) return fail(AMQ_EINVAL, "n_splits must be 0 (one workgroup per head) or 1..1024 (got %d)", n_splits);
-    amq::AttnArgs a{q, k, v, kcache, vcache, out, nullptr, 0, n_heads, n_kv_heads, max_seq, 10000.0f, nullptr, step_states, true};
-    a.norm = nrm;
-    if (n_splits == 0) {
-        if (6 * 128 + (size_t)max_seq * 4 + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
-        return check_hip(amq::launch_attn_decode(a, batch, (hipStream_t)stream), "attn_decode_seq");
-    }
-    if (!workspace || !tickets) return fail(AMQ_EINVAL, "null pointer (workspace / tickets are required with n_splits >= 1)");
-    int chunk = (((max_seq + n_splits - 1) / n_splits) + 31) & ~31;
-    chunk = chunk < amq::ATT_MIN_CHUNK ? amq::ATT_MIN_CHUNK : chunk;
-    if (6 * 128 + (size_t)chunk * 4 + 17 * 1024 > LDS_LIMIT)
-        return fail(AMQ_ESHAPE, "max_seq=%d over %d splits leaves chunks of %d keys: too long", max_seq, n_splits, chunk);
-    const size_t need = amq_attn_decode_split_workspace_bytes(batch, n_heads, n_splits);
-    if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    return check_hip(amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream), "attn_decode_seq (split)");
-}
-
-static int tail_seq_check(const void* logits, int vocab, const void* embed, int hidden, const void* token, const void* step_states, const void* x,
-                          const void* rope_table, int rope_rows, int batch) {
-    if (!logits || !embed || !token || !step_states || !x || !rope_table) return fail(AMQ_EINVAL, "null pointer");
-    if (rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
-    if (vocab < 1 || hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need vocab >= 1 and hidden %% 8 == 0 (got %d, %d)", vocab, hidden);
-    if (batch < 1 || batch > 65535) return fail(AMQ_ESHAPE, "bad batch %d", batch);
-    return AMQ_OK;
+    return attn_decode(ATTN_SEQ, norm, q, k, v, kcache, vcache, out, step_states, nullptr, 0, batch, n_heads, n_kv_heads, head_dim, max_seq, 10000.0f, nullptr,
+                       n_splits, workspace, workspace_bytes, tickets, stream);
 }
 
 int amq_decode_tail_seq_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
                             const void* rope_table, int rope_rows, int batch, const int* suppress_ids, void* stream) {
-    if (int rc = tail_seq_check(logits, vocab, embed, hidden, token, step_states, x, rope_table, rope_rows, batch)) return rc;
-    if (batch > 1 && (vocab % 8) != 0) return fail(AMQ_ESHAPE, "batched rows need vocab %% 8 == 0 (16-byte aligned logits rows)");
-    return check_hip(amq::launch_decode_tail(logits, vocab, embed, hidden, token, (char*)step_states + 256, x, rope_table, step_states, rope_rows,
-                                             (hipStream_t)stream, batch, suppress_ids, true), "decode_tail_seq");
+    return decode_tail(TAIL_SEQ, "decode_tail_seq", logits, vocab, embed, hidden, token, step_states, x, rope_table, step_states, rope_rows, batch, suppress_ids, stream);
 }
 
 int amq_decode_tail_sample_seq_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
                                    const void* rope_table, int rope_rows, int batch, const int* suppress_ids, void* state, void* stream) {
-    if (!state) return fail(AMQ_EINVAL, "state: the 128-byte device block of sampling parameters is required (null)");
-    if (int rc = tail_seq_check(logits, vocab, embed, hidden, token, step_states, x, rope_table, rope_rows, batch)) return rc;
-    if (batch > 8) return fail(AMQ_ESHAPE, "at most 8 sequences (the state block holds 8 finished flags), got %d", batch);
-    amq::SampleArgs a{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, (int*)((char*)step_states + 256), (_Float16*)x,
-                      (const _Float16*)rope_table, (_Float16*)step_states, rope_rows, suppress_ids, (int*)state, nullptr, nullptr, 0,
-                      AMQ_SAMPLE_ADVANCE | AMQ_SAMPLE_EOS};
-    return check_hip(amq::launch_sample(a, batch, (hipStream_t)stream, true), "decode_tail_sample_seq");
+    return decode_tail_sample(TAIL_SAMPLE_SEQ, "decode_tail_sample_seq", logits, vocab, embed, hidden, token, step_states, x, rope_table, step_states, rope_rows, batch,
+                              suppress_ids, state, stream);
 }
 
 int amq_set_token_seq_f16(const long long* token_in, int n_in, const void* embed, int vocab, int hidden, long long* token, void* step_states, void* x,
                           const void* rope_table, int rope_rows, int batch, void* stream) {
-    if (!token_in) return fail(AMQ_EINVAL, "null pointer");
-    if (int rc = tail_seq_check(token_in, vocab, embed, hidden, token, step_states, x, rope_table, rope_rows, batch)) return rc;
-    if (n_in != 1 && n_in != batch) return fail(AMQ_ESHAPE, "batch %d with %d input ids (1 or one per sequence)", batch, n_in);
-    return check_hip(amq::launch_set_token(token_in, n_in, embed, vocab, hidden, token, (const char*)step_states + 256, x, rope_table, step_states,
-                                           rope_rows, batch, (hipStream_t)stream, true), "set_token_seq");
+    return set_token(SET_TOKEN_SEQ, "set_token_seq", token_in, n_in, embed, vocab, hidden, token, step_states, x, rope_table, step_states, rope_rows, batch, stream);
 }
 
 /* ---- prompt-lookup speculative decoding: `rows` consecutive positions of ONE sequence per step ---- */
@@ -1054,41 +1074,15 @@ int amq_attn_decode_rows_f16(const void* q, const void* k, const void* v, void* 
 int amq_attn_decode_rows_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                                  void* step_states, int rows, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
                                  void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
-    amq::QkNorm nrm;
-    if (int rc = qk_norm_arg(norm, &nrm)) return rc;
-    if (!q || !k || !v || !kcache || !vcache || !out || !step_states) return fail(AMQ_EINVAL, "null pointer");
-    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
-    if (rows < 2 || rows > AMQ_LOOKUP_MAX_ROWS) return fail(AMQ_ESHAPE, "rows must be 2..%d (got %d)", AMQ_LOOKUP_MAX_ROWS, rows);
-    if (n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
-        return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads)", n_heads, n_kv_heads);
-    if (max_seq < 1) return fail(AMQ_ESHAPE, "bad max_seq %d", max_seq);
-    if (n_splits < 0 || n_splits > 1024) return fail(AMQ_EINVAL, "n_splits must be 0 (one workgroup per head) or 1..1024 (got %d)", n_splits);
-    amq::AttnArgs a{q, k, v, kcache, vcache, out, nullptr, 0, n_heads, n_kv_heads, max_seq, 10000.0f, nullptr, step_states, true, true};
-    a.norm = nrm;
-    const size_t rows_lds = 2 * 7 * 128 * 2 + 16;      // the earlier rows' rotated keys and values behind the score array
-    if (n_splits == 0) {
-        if (6 * 128 + (size_t)max_seq * 4 + rows_lds + 17 * 1024 > LDS_LIMIT) return fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
-        return check_hip(amq::launch_attn_decode(a, rows, (hipStream_t)stream), "attn_decode_rows");
-    }
-    if (!workspace || !tickets) return fail(AMQ_EINVAL, "null pointer (workspace / tickets are required with n_splits >= 1)");
-    int chunk = (((max_seq + n_splits - 1) / n_splits) + 31) & ~31;
-    chunk = chunk < amq::ATT_MIN_CHUNK ? amq::ATT_MIN_CHUNK : chunk;
-    if (6 * 128 + (size_t)chunk * 4 + rows_lds + 17 * 1024 > LDS_LIMIT)
-        return fail(AMQ_ESHAPE, "max_seq=%d over %d splits leaves chunks of %d keys: too long", max_seq, n_splits, chunk);
-    const size_t need = amq_attn_decode_split_workspace_bytes(rows, n_heads, n_splits);
-    if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    return check_hip(amq::launch_attn_decode_split(a, rows, n_splits, workspace, tickets, (hipStream_t)stream), "attn_decode_rows (split)");
+    return attn_decode(ATTN_ROWS, norm, q, k, v, kcache, vcache, out, step_states, nullptr, 0, rows, n_heads, n_kv_heads, head_dim, max_seq, 10000.0f, nullptr,
+                       n_splits, workspace, workspace_bytes, tickets, stream);
 }
 
 int amq_decode_tail_lookup_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
                                const void* rope_table, int rope_rows, int rows, const int* suppress_ids, void* lookup_state, int* history,
                                int history_cap, void* stream) {
     if (!lookup_state || !history) return fail(AMQ_EINVAL, "lookup_state (the 128-byte device block) and history are required (null)");
-    if (!logits || !embed || !token || !step_states || !x || !rope_table) return fail(AMQ_EINVAL, "null pointer");
-    if (rope_rows < 1) return fail(AMQ_EINVAL, "rope_rows must be the number of rows of rope_table");
-    if (vocab < 1 || hidden < 8 || (hidden % 8) != 0) return fail(AMQ_ESHAPE, "need vocab >= 1 and hidden %% 8 == 0 (got %d, %d)", vocab, hidden);
-    if (rows < 2 || rows > AMQ_LOOKUP_MAX_ROWS) return fail(AMQ_ESHAPE, "rows must be 2..%d (got %d)", AMQ_LOOKUP_MAX_ROWS, rows);
-    if ((vocab % 8) != 0) return fail(AMQ_ESHAPE, "several rows need vocab %% 8 == 0 (16-byte aligned logits rows)");
+    if (int rc = tail_check(TAIL_LOOKUP, logits, vocab, embed, hidden, token, step_states, x, rope_table, step_states, rope_rows, rows)) return rc;
     if (history_cap < rope_rows || history_cap > (1 << 24))
         return fail(AMQ_ESHAPE, "history_cap must hold the whole cache (max_seq = rope_rows = %d) and at most 2^24 tokens, got %d", rope_rows, history_cap);
     amq::LookupArgs a{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, step_states, (_Float16*)x, (const _Float16*)rope_table,

@@ -1,4 +1,5 @@
-"""Tensor-level wrappers over the C ABI (one function per entry point).
+"""Tensor-level wrappers over the C ABI: one function per operation.  Where the ABI has several entry points for one operation (the forms of
+the decode-step attention and token tails, the `_qkn` twins), the function chooses among them by its arguments.
 
 All tensors must live on a HIP device; inputs are validated on the host before
 a kernel is launched (shape/dtype/contiguity), because an out-of-bounds access
@@ -642,13 +643,11 @@ def gemv_f16w(x, W, bias=None, gamma=None, eps=0.0, out=None):
     return y
 
 
-def decode_tail(logits, embed, token, pos, x, table=None, cur=None, suppress=None):
-    """token = argmax(logits), pos += 1, x = embed[token] (and cur = table[pos], the next step's cos/sin row) -- one
-    launch (graph-capturable).  Batched decode: logits [B, vocab], token [B], x [B, hidden]; pos / cur advance once.
-    suppress: int32 [8] device tensor of token ids never chosen (-1 = unused slot): HF's min_new_tokens treatment of the EOS ids."""
+def _tail_args(embed, token, pos, x, table, cur):
+    """the checks the token tails and set_token share, and the arguments of their C calls from ``token`` to ``rope_rows``:
+    -> (per-sequence step state?, B, (token, step states | pos, x, rope_table[, rope_cur], rope_rows))"""
     vocab, hidden = embed.shape
     B = token.numel()
-    _need(logits, torch.float16, "logits", B * vocab)
     _need(embed, torch.float16, "embed", vocab * hidden)
     _need(token, torch.int64, "token", B)
     _need(x, torch.float16, "x", B * hidden)
@@ -657,29 +656,33 @@ def decode_tail(logits, embed, token, pos, x, table=None, cur=None, suppress=Non
         if nseq != B:
             raise ValueError(f"a step state of {nseq} sequences for {B} tokens")
         _need(table, torch.float16, "rope table")
-        if suppress is not None:
-            _need(suppress, torch.int32, "suppress", 8)
-        _lib.check(_lib.load().amq_decode_tail_seq_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), states, _lib.ptr(x),
-                                                       _lib.ptr(table), table.numel() // 128, B, _lib.ptr(suppress), _lib.current_stream()))
-        return
+        return True, B, (_lib.ptr(token), states, _lib.ptr(x), _lib.ptr(table), table.numel() // 128)
     _need(pos, torch.int32, "pos", 1)
-    if cur is not None:
-        _need(cur, torch.float16, "rope_cur", 128)
-        _need(table, torch.float16, "rope table")
-    tab = _lib.ptr(table) if cur is not None else None
-    rows = table.numel() // 128 if cur is not None else 0
+    if cur is None:
+        return False, B, (_lib.ptr(token), _lib.ptr(pos), _lib.ptr(x), None, None, 0)
+    _need(cur, torch.float16, "rope_cur", 128)
+    _need(table, torch.float16, "rope table")
+    return False, B, (_lib.ptr(token), _lib.ptr(pos), _lib.ptr(x), _lib.ptr(table), _lib.ptr(cur), table.numel() // 128)
+
+
+def decode_tail(logits, embed, token, pos, x, table=None, cur=None, suppress=None):
+    """token = argmax(logits), pos += 1, x = embed[token] (and cur = table[pos], the next step's cos/sin row) -- one
+    launch (graph-capturable).  Batched decode: logits [B, vocab], token [B], x [B, hidden]; pos / cur advance once.
+    suppress: int32 [8] device tensor of token ids never chosen (-1 = unused slot): HF's min_new_tokens treatment of the EOS ids."""
+    vocab, hidden = embed.shape
+    _need(logits, torch.float16, "logits", token.numel() * vocab)
+    seq, B, mid = _tail_args(embed, token, pos, x, table, cur)
     if suppress is not None:
         _need(suppress, torch.int32, "suppress", 8)
-        _lib.check(_lib.load().amq_decode_tail_suppress_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), _lib.ptr(pos),
-                                                            _lib.ptr(x), tab, _lib.ptr(cur), rows, B, _lib.ptr(suppress), _lib.current_stream()))
-        return
-    if B == 1:
-        _lib.check(_lib.load().amq_decode_tail_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), _lib.ptr(pos),
-                                                   _lib.ptr(x), tab, _lib.ptr(cur), rows, _lib.current_stream()))
+    lib, head = _lib.load(), (_lib.ptr(logits), vocab, _lib.ptr(embed), hidden) + mid
+    if seq:
+        _lib.check(lib.amq_decode_tail_seq_f16(*head, B, _lib.ptr(suppress), _lib.current_stream()))
+    elif suppress is not None:
+        _lib.check(lib.amq_decode_tail_suppress_f16(*head, B, _lib.ptr(suppress), _lib.current_stream()))
+    elif B == 1:
+        _lib.check(lib.amq_decode_tail_f16(*head, _lib.current_stream()))
     else:
-        _lib.check(_lib.load().amq_decode_tail_batch_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token),
-                                                         _lib.ptr(pos), _lib.ptr(x), tab, _lib.ptr(cur), rows, B,
-                                                         _lib.current_stream()))
+        _lib.check(lib.amq_decode_tail_batch_f16(*head, B, _lib.current_stream()))
 
 
 # ---- sampled decoding (include/amq_hip.h: "sampled decoding"; amq_sample.hip)
@@ -805,57 +808,23 @@ def logit_jsd(p, q, eps=1e-7, out=None):
 def decode_tail_sample(logits, embed, token, pos, x, state, table=None, cur=None, suppress=None):
     """:func:`decode_tail` with the token drawn by :func:`sample` (draw counter advanced, EOS bookkeeping) instead of the arg-max -- one launch"""
     vocab, hidden = embed.shape
-    B = token.numel()
-    _need(logits, torch.float16, "logits", B * vocab)
-    _need(embed, torch.float16, "embed", vocab * hidden)
-    _need(token, torch.int64, "token", B)
-    _need(x, torch.float16, "x", B * hidden)
+    _need(logits, torch.float16, "logits", token.numel() * vocab)
     _need(state, torch.int32, "state", _SMP_WORDS)
     if suppress is not None:
         _need(suppress, torch.int32, "suppress", 8)
-    states, nseq = _seq_state(cur, pos)
-    if states is not None:
-        if nseq != B:
-            raise ValueError(f"a step state of {nseq} sequences for {B} tokens")
-        _need(table, torch.float16, "rope table")
-        _lib.check(_lib.load().amq_decode_tail_sample_seq_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), states, _lib.ptr(x),
-                                                              _lib.ptr(table), table.numel() // 128, B, _lib.ptr(suppress), _lib.ptr(state),
-                                                              _lib.current_stream()))
-        return
-    _need(pos, torch.int32, "pos", 1)
-    if cur is not None:
-        _need(cur, torch.float16, "rope_cur", 128)
-        _need(table, torch.float16, "rope table")
-    _lib.check(_lib.load().amq_decode_tail_sample_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), _lib.ptr(pos), _lib.ptr(x),
-                                                      _lib.ptr(table) if cur is not None else None, _lib.ptr(cur),
-                                                      table.numel() // 128 if cur is not None else 0, B, _lib.ptr(suppress), _lib.ptr(state),
-                                                      _lib.current_stream()))
+    seq, B, mid = _tail_args(embed, token, pos, x, table, cur)
+    fn = _lib.load().amq_decode_tail_sample_seq_f16 if seq else _lib.load().amq_decode_tail_sample_f16
+    _lib.check(fn(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, *mid, B, _lib.ptr(suppress), _lib.ptr(state), _lib.current_stream()))
 
 
 def set_token(token_in, embed, token, pos, x, table=None, cur=None):
     """token = token_in (int64 CUDA tensor: one id, or one per sequence), x = embed[token], cur = table[pos] -- one launch (amq_set_token_f16); pos unchanged"""
     vocab, hidden = embed.shape
-    B = token.numel()
     n_in = token_in.numel()
     _need(token_in, torch.int64, "token_in", n_in)
-    _need(embed, torch.float16, "embed", vocab * hidden)
-    _need(token, torch.int64, "token", B)
-    _need(x, torch.float16, "x", B * hidden)
-    states, nseq = _seq_state(cur, pos)
-    if states is not None:
-        if nseq != B:
-            raise ValueError(f"a step state of {nseq} sequences for {B} tokens")
-        _need(table, torch.float16, "rope table")
-        _lib.check(_lib.load().amq_set_token_seq_f16(_lib.ptr(token_in), n_in, _lib.ptr(embed), vocab, hidden, _lib.ptr(token), states, _lib.ptr(x),
-                                                     _lib.ptr(table), table.numel() // 128, B, _lib.current_stream()))
-        return
-    _need(pos, torch.int32, "pos", 1)
-    if cur is not None:
-        _need(cur, torch.float16, "rope_cur", 128)
-        _need(table, torch.float16, "rope table")
-    _lib.check(_lib.load().amq_set_token_f16(_lib.ptr(token_in), n_in, _lib.ptr(embed), vocab, hidden, _lib.ptr(token), _lib.ptr(pos), _lib.ptr(x),
-                                             _lib.ptr(table) if cur is not None else None, _lib.ptr(cur), table.numel() // 128 if cur is not None else 0, B,
-                                             _lib.current_stream()))
+    seq, B, mid = _tail_args(embed, token, pos, x, table, cur)
+    fn = _lib.load().amq_set_token_seq_f16 if seq else _lib.load().amq_set_token_f16
+    _lib.check(fn(_lib.ptr(token_in), n_in, _lib.ptr(embed), vocab, hidden, *mid, B, _lib.current_stream()))
 
 
 QK_NORM_EPS = 1e-6         # Qwen3Config.rms_norm_eps: the default of the wrappers' ``norm_eps``
@@ -1216,6 +1185,22 @@ def attn_decode_splits(max_seq, n_heads=32, batch=1, n_kv_heads=None):
     return s
 
 
+def _split_scratch(lib, device, rows, n_heads, n_splits):
+    """-> (workspace pointer, its bytes, tickets pointer) of a decode-attention call over ``n_splits`` > 1 workgroups per head; (None, 0, None) for one"""
+    if n_splits <= 1:
+        return None, 0, None
+    wsb = lib.amq_attn_decode_split_workspace_bytes(rows, n_heads, n_splits)
+    return _lib.ptr(_ATTN_WS.get(device, wsb // 4)), wsb, _lib.ptr(_ATTN_TICKETS.get(device, rows * n_heads))
+
+
+def _attn_call(lib, name, norm, tensors, where, heads, rest=()):
+    """one decode-attention call: entry point ``name`` (its `_qkn` twin under ``norm``) over ``tensors`` = (q, k, v, kcache, vcache, out); ``where``: its
+    position arguments; ``heads`` = (rows, n_heads, n_kv_heads, max_seq); ``rest``: what follows max_seq in front of the stream.  -> out"""
+    rows, n_heads, n_kv_heads, max_seq = heads
+    _lib.check(_qkn_fn(lib, name, norm)(*map(_lib.ptr, tensors), *where, rows, n_heads, n_kv_heads, 128, max_seq, *rest, _lib.current_stream()))
+    return tensors[5]
+
+
 def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_theta=10000.0, table=None, cur=None, n_splits=0,
                 q_norm=None, k_norm=None, norm_eps=QK_NORM_EPS):
     """One new token per sequence.  q [B, n_heads*128], k/v [B, n_kv_heads*128],
@@ -1237,20 +1222,13 @@ def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_the
     _need(kcache, torch.float16, "kcache", B * n_kv_heads * max_seq * 128)
     _need(vcache, torch.float16, "vcache", B * n_kv_heads * max_seq * 128)
     _need(out, torch.float16, "out", B * n_heads * 128)
+    lib, tensors, heads = _lib.load(), (q, k, v, kcache, vcache, out), (B, n_heads, n_kv_heads, max_seq)
     states, nseq = _seq_state(cur, pos)
     if states is not None:                      # per-sequence step state: sequence b appends at ITS pos[b] and attends rows 0 .. pos[b]
         if nseq != B:
             raise ValueError(f"a step state of {nseq} sequences for caches of {B}")
-        lib = _lib.load()
-        if n_splits > 1:
-            wsb = lib.amq_attn_decode_split_workspace_bytes(B, n_heads, n_splits)
-            ws, tk = _ATTN_WS.get(q.device, wsb // 4), _ATTN_TICKETS.get(q.device, B * n_heads)
-            _lib.check(_qkn_fn(lib, "amq_attn_decode_seq_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, B,
-                                                                     n_heads, n_kv_heads, 128, max_seq, n_splits, _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
-        else:
-            _lib.check(_qkn_fn(lib, "amq_attn_decode_seq_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, B,
-                                                                     n_heads, n_kv_heads, 128, max_seq, 0, None, 0, None, _lib.current_stream()))
-        return out
+        return _attn_call(lib, "amq_attn_decode_seq_f16", norm, tensors, (states,), heads,
+                          (n_splits if n_splits > 1 else 0,) + _split_scratch(lib, q.device, B, n_heads, n_splits))
     if isinstance(pos, torch.Tensor):
         _need(pos, torch.int32, "pos", 1)
         pos_dev, pos_i = ctypes.cast(pos.data_ptr(), ctypes.c_void_p), 0
@@ -1266,24 +1244,11 @@ def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_the
     if table is not None:
         _need(table, torch.float16, "rope table", max_seq * 128)
     if n_splits > 1:
-        lib = _lib.load()
-        wsb = lib.amq_attn_decode_split_workspace_bytes(B, n_heads, n_splits)
-        ws = _ATTN_WS.get(q.device, wsb // 4)
-        tk = _ATTN_TICKETS.get(q.device, B * n_heads)
-        _lib.check(_qkn_fn(lib, "amq_attn_decode_split_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
-                                                                   _lib.ptr(out), _lib.ptr(cur), pos_dev, pos_i, B, n_heads, n_kv_heads, 128,
-                                                                   max_seq, ctypes.c_float(rope_theta), _lib.ptr(table), n_splits,
-                                                                   _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
-        return out
+        return _attn_call(lib, "amq_attn_decode_split_f16", norm, tensors, (_lib.ptr(cur), pos_dev, pos_i), heads,
+                          (ctypes.c_float(rope_theta), _lib.ptr(table), n_splits) + _split_scratch(lib, q.device, B, n_heads, n_splits))
     if cur is not None:
-        _lib.check(_qkn_fn(_lib.load(), "amq_attn_decode_cur_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
-                                                                         _lib.ptr(out), _lib.ptr(cur), B, n_heads, n_kv_heads, 128, max_seq,
-                                                                         _lib.current_stream()))
-        return out
-    _lib.check(_qkn_fn(_lib.load(), "amq_attn_decode_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache),
-                                                                 _lib.ptr(out), pos_dev, pos_i, B, n_heads, n_kv_heads, 128, max_seq,
-                                                                 ctypes.c_float(rope_theta), _lib.ptr(table), _lib.current_stream()))
-    return out
+        return _attn_call(lib, "amq_attn_decode_cur_f16", norm, tensors, (_lib.ptr(cur),), heads)
+    return _attn_call(lib, "amq_attn_decode_f16", norm, tensors, (pos_dev, pos_i), heads, (ctypes.c_float(rope_theta), _lib.ptr(table)))
 
 
 # ---- prompt-lookup speculative decoding (include/amq_hip.h: "prompt-lookup speculative decoding"; amq_decode.hip ROWS instantiations, amq_lookup.hip)
@@ -1332,15 +1297,8 @@ def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads
     _need(vcache, torch.float16, "vcache", n_kv_heads * max_seq * 128)
     _need(out, torch.float16, "out", R * n_heads * 128)
     lib = _lib.load()
-    if n_splits > 1:
-        wsb = lib.amq_attn_decode_split_workspace_bytes(R, n_heads, n_splits)
-        ws, tk = _ATTN_WS.get(q.device, wsb // 4), _ATTN_TICKETS.get(q.device, R * n_heads)
-        _lib.check(_qkn_fn(lib, "amq_attn_decode_rows_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, R,
-                                                                  n_heads, n_kv_heads, 128, max_seq, n_splits, _lib.ptr(ws), wsb, _lib.ptr(tk), _lib.current_stream()))
-    else:
-        _lib.check(_qkn_fn(lib, "amq_attn_decode_rows_f16", norm)(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(kcache), _lib.ptr(vcache), _lib.ptr(out), states, R,
-                                                                  n_heads, n_kv_heads, 128, max_seq, 0, None, 0, None, _lib.current_stream()))
-    return out
+    return _attn_call(lib, "amq_attn_decode_rows_f16", norm, (q, k, v, kcache, vcache, out), (states,), (R, n_heads, n_kv_heads, max_seq),
+                      (n_splits if n_splits > 1 else 0,) + _split_scratch(lib, q.device, R, n_heads, n_splits))
 
 
 def decode_tail_lookup(logits, embed, token, pos, x, state, history, table, cur, suppress=None):
@@ -1351,20 +1309,15 @@ def decode_tail_lookup(logits, embed, token, pos, x, state, history, table, cur,
     if not 2 <= R <= LOOKUP_MAX_ROWS:
         raise ValueError(f"rows must be 2..{LOOKUP_MAX_ROWS} (got {R})")
     _need(logits, torch.float16, "logits", R * vocab)
-    _need(embed, torch.float16, "embed", vocab * hidden)
-    _need(token, torch.int64, "token", R)
-    _need(x, torch.float16, "x", R * hidden)
     _need(state, torch.int32, "lookup state", LOOKUP_STATE_WORDS)
     _need(history, torch.int32, "history")
-    _need(table, torch.float16, "rope table")
     if suppress is not None:
         _need(suppress, torch.int32, "suppress", 8)
-    states, nseq = _seq_state(cur, pos)
-    if states is None or nseq != R:
+    seq, _, mid = _tail_args(embed, token, pos, x, table, cur)
+    if not seq:
         raise ValueError(f"cur [rows, 128] / pos [rows] must be the views of one per-sequence step state of {R} blocks")
-    _lib.check(_lib.load().amq_decode_tail_lookup_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, _lib.ptr(token), states, _lib.ptr(x),
-                                                      _lib.ptr(table), table.numel() // 128, R, _lib.ptr(suppress), _lib.ptr(state), _lib.ptr(history),
-                                                      history.numel(), _lib.current_stream()))
+    _lib.check(_lib.load().amq_decode_tail_lookup_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, *mid, R, _lib.ptr(suppress), _lib.ptr(state),
+                                                      _lib.ptr(history), history.numel(), _lib.current_stream()))
 
 
 # ---------------------------------------------------------------- the device of a launch
