@@ -215,9 +215,9 @@ __device__ __forceinline__ void dequant_lane(const uint32_t* w, h2 meta, h2* out
 // Scaling by a power of two commutes with fp16 rounding, so w is bit-identical
 // to the reference's two-rounding dequant (quantize.py:198) as long as
 // z * 2^E and (q - z) * 2^E are normal fp16 numbers: E = -3 / -5 / -5 for
-// 4 / 3 / 2 bit, i.e. for |z|, |q - z| >= 2^-11 / 2^-9 / 2^-9; below that the
-// value involved is < 1e-3 of a quantization step and may differ by
-// <= 2^-24 * 2^-E (tests bound it).  Requires |s| * 2^-E < 65504.
+// 4 / 3 / 2 bit, i.e. for |z|, |q - z| >= T = 2^-11 / 2^-9 / 2^-9.  Below: where |q - z| < T, q - z is taken to a multiple of 2^-24 * 2^-E (w off by <= that times |s|);
+// where |z| < T <= |q - z|, z is taken to such a multiple first, which can move the FIRST rounding to the neighbouring half: one fp16 ulp of (q - z), times |s|, in w
+// (derived in tests/metadomain_ref.py, checked by tests/test_metadomain_cpu.py).  Requires |s| * 2^-E <= 65504: ops.check_scale_range refuses a layer beyond it at load time.
 // MODE_FMA: w = fma(sub * 2^B, s * 2^-E, c)   (q * 2^E is exact).
 template <int BITS> struct SdCfg;
 template <> struct SdCfg<4> { static constexpr int E = -3; };

@@ -126,6 +126,38 @@ def fma_mode_for(mn, bits):
     return MODE_FMA1 if smax <= bound else MODE_FMA
 
 
+_SD_E = {4: -3, 3: -5, 2: -5}      # csrc/amq_common.cuh SdCfg<BITS>::E
+
+
+def scale_limit(bits):
+    """largest |scale| the matmul kernels' scaled-subnormal unpack takes: it multiplies by the fp16 constant s * 2^-E (amq_common.cuh sd_meta;
+    E = -3 at 4 bit, -5 at 3 / 2 bit), which must be finite -- 8188 / 2047 / 2047"""
+    if bits not in _SD_E:
+        raise ValueError(f"bits must be 2, 3 or 4 (got {bits})")
+    return 65504.0 * 2.0 ** _SD_E[bits]
+
+
+def check_scale_range(mn, bits, mode, name=None):
+    """Refuse a native meta buffer with a scale beyond :func:`scale_limit` (ValueError naming the layer, the scale and the limit): past it the
+    matmul kernels' weights are inf / NaN while ``dequantize`` -- the other unpack -- still returns finite ones.  The limit is the same for
+    MODE_HQQ and the MODE_FMA forms (both multiply by s * 2^-E).  Pure torch (CPU or GPU tensors); one device -> host read: called where a module
+    takes its buffers (constructors, to_kernel_arithmetic, load_state_dict), never per forward.  bfloat16 meta is exempt: the bf16 kernels
+    do not use this unpack (their scale stays an fp32 factor)."""
+    limit = scale_limit(int(bits))
+    if mode not in (MODE_HQQ, MODE_FMA, MODE_FMA1):
+        raise ValueError(f"unknown dequant mode {mode}")
+    if mn.dtype == torch.bfloat16 or mn.numel() == 0 or mn.is_meta:
+        return
+    s = mn.detach().view(-1, 2)[:, 0].float().abs()
+    worst = float(s.max().item())                  # (max propagates NaN)
+    who = f"layer {name}" if name else "layer"
+    if worst != worst:
+        raise ValueError(f"{who}: a scale is NaN")
+    if worst > limit:
+        raise ValueError(f"{who}: |scale| = {worst} exceeds {limit}, the largest the {int(bits)}-bit matmul kernels' unpack takes "
+                         f"(scale * 2^{-_SD_E[int(bits)]} must be a finite fp16 number)")
+
+
 def _check_native(qn, mn, bits, N, K, fine=False):
     """validates a native (payload, meta) pair and returns its group granularity: 128, or -- where the caller serves them (``fine``) --
     64 / 32, recognised by the meta tensor's size (128 / group pairs per tile row)"""

@@ -256,6 +256,10 @@ class HIPQuantLinear(nn.Module):
 
     # ------------------------------------------------------------------ build
     def _set_native(self, qn, mn, mode):
+        """the module takes native buffers: every constructor (from_hqq, pack, from_gptq_buffers, from_ft_buffers) and to_kernel_arithmetic end
+        here.  Load time, so the one place -- with _load_from_state_dict -- that checks the scales against the matmul kernels' unpack
+        (ops.check_scale_range; bfloat16 meta is exempt there: the bf16 kernels do not use that unpack)."""
+        ops.check_scale_range(mn, self.bits, mode, name=self.name)
         self.qweight = qn
         self.meta = mn
         self.mode = mode
@@ -355,6 +359,7 @@ class HIPQuantLinear(nn.Module):
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
         self.mode = int(self.mode_flag.item())
+        ops.check_scale_range(self.meta, self.bits, self.mode, name=self.name or prefix.rstrip("."))      # (load time: one more host read beside mode_flag's)
 
     def _buffer_ptrs(self):
         """Device pointers of the module's own buffers, validated ONCE per set of buffers: the decode loop of the reference
