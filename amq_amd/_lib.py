@@ -121,6 +121,7 @@ SIGNATURES = {
     "amq_set_token_seq_f16": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     # prompt-lookup speculative decoding: `rows` consecutive positions of one sequence per step
     "amq_attn_decode_rows_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "amq_attn_decode_rows_gqa_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "amq_decode_tail_lookup_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "amq_attn_prefill_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 + [_vp]),
     "amq_rope_cache_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -139,6 +140,7 @@ SIGNATURES = {
 # the rotating entry points with Qwen3's per-head q / k RMSNorm inside the kernel: the signature of the entry point without `_qkn` behind a QkNorm*
 # (amq_rope_cache_qkn_f16 is the twin of the batch form)
 for _base in ("amq_attn_decode_f16", "amq_attn_decode_cur_f16", "amq_attn_decode_split_f16", "amq_attn_decode_seq_f16", "amq_attn_decode_rows_f16",
+              "amq_attn_decode_rows_gqa_f16",
               "amq_rope_cache_batch_f16", "amq_rope_rows_f16"):
     SIGNATURES[_base.replace("_batch", "")[:-len("_f16")] + "_qkn_f16"] = (_i, [_qkn] + SIGNATURES[_base][1])
 del _base

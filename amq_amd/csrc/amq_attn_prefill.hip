@@ -715,6 +715,365 @@ hipError_t launch_attn_decode_gqa(const AttnArgs& a, int batch, int n_splits, vo
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The verify step of prompt-lookup decoding on a GROUPED-QUERY model (amq_attn_decode_rows_gqa_f16): R = 2 .. 8 rows at consecutive positions
+// p .. p + R - 1 of ONE sequence.  attn_decode_gqa_kernel's staging, slicing, operand layouts and merge orders with R x G query rows where it has G:
+// query row (j, g) = step row j, head g of the group, in j-major order; 16 of them are one MFMA row block, NB = ceil(R G / 16) blocks in all (G need
+// not divide 16: a step row's heads may straddle two blocks).  A workgroup is (kv head, NBW row blocks, chunk): the blocks sit in the grid's y
+// dimension (free: one sequence), NBW of them per workgroup above the same staged data.  What differs from the single-token kernel:
+//   * the key limit is PER LANE: query row (j, g) sees key t iff t <= p + j.  A lane whose 32-key wave slice lies wholly past its row's position
+//     keeps its (m, l, O) untouched (all-masked would be exp2(-inf - -inf) = NaN); a chunk past a row's position writes nothing for that row;
+//   * the R new keys (normalised under QKN, rotated with their OWN block's cos / sin row: wave w takes rows w and w + 4, one pair per lane, the
+//     single-token kernel's expressions and reduction) and values sit in LDS in front of the stage buffers and are written over the LDS rows
+//     p .. p + R - 1 of whatever stage holds them -- they may cross a tile, a stage and a chunk boundary; the rows behind them up to the end of the
+//     last tile the MFMAs touch repeat the last one (masked probabilities are exact zeros, but 0 x NaN is NaN: no row the MFMAs read was never
+//     written -- at p = 0 the DMA clamp lands on a row this launch is still appending);
+//   * cache row p + j is appended by exactly one workgroup per kv head: y == 0 of the chunk that holds p + j;
+//   * row j with one active chunk is written normalised; otherwise (O, m, l) goes to slot ((j n_heads + h) n_splits + z): the per-sequence layout
+//     with batch = R, so attn_gqa_combine_kernel<true> over (n_heads, R) with the R step-state blocks finishes the rows unchanged.
+// Every term a row's result is made of is the term attn_decode_gqa_kernel<true> computes at position p + j over a cache that holds the step's
+// earlier rows, in the same order: the same bits (tests/test_gpu_rows_gqa.py).  Rows whose position is outside the cache (p + j >= max_seq, or
+// p < 0: all of them) are no-ops and raise their block's error word.
+struct AttnGqaRowsArgs {
+    const void* q; const void* k; const void* v; void* kc; void* vc; void* out;
+    const void* state;          // R step-state blocks STEP_STRIDE bytes apart, block j at position p + j
+    float* ws;
+    int rows, n_heads, n_kv_heads, max_seq, n_splits;
+    int iters;                  // stages of AG_STAGE_KEYS keys per workgroup (attn_decode_gqa_iters)
+};
+struct AttnGqaRowsArgsQkn : AttnGqaRowsArgs { QkNorm nrm; };
+constexpr int AG_ROWS_MAX = 8;                          // rows of a step (AMQ_LOOKUP_MAX_ROWS)
+constexpr int AG_ROWS_STAGE = AG_ROWS_MAX * AG_STAGE;   // bytes in front of the stage buffers: per row, rotated new key [128] | new value [128]
+// row blocks per workgroup: 1 = every block its own workgroups (grid y); 2: two blocks above one staged chunk (A/B builds; profiles/lookup_gqa.json)
+#ifndef AMQ_GQA_ROWS_NBW
+#define AMQ_GQA_ROWS_NBW 1
+#endif
+
+template <bool QKN, int NBW = AMQ_GQA_ROWS_NBW>
+__global__ __launch_bounds__(256) void attn_decode_gqa_rows_kernel(std::conditional_t<QKN, AttnGqaRowsArgsQkn, AttnGqaRowsArgs> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63, tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int r = lane & 15, o = lane >> 4;
+    const int kvh = blockIdx.x, y = blockIdx.y, z = blockIdx.z;
+    const int G = a.n_heads / a.n_kv_heads, h0 = kvh * G;
+    const int p = *(const int*)((const char*)a.state + 256);            // row 0's position; row j is at p + j
+    int Rv = p < 0 ? 0 : (a.max_seq - p < a.rows ? a.max_seq - p : a.rows);     // rows inside the cache: 0 .. Rv - 1
+    Rv = Rv < 0 ? 0 : Rv;
+    if (kvh == 0 && y == 0 && z == 0 && tid >= Rv && tid < a.rows) *(int*)((char*)const_cast<void*>(a.state) + (size_t)tid * STEP_STRIDE + 260) = 1;
+    const int nq = Rv * G, q0 = 16 * NBW * y;       // query rows of the step; this workgroup's first
+    if (q0 >= nq) return;                           // (also Rv == 0)
+    const int chunk = AG_STAGE_KEYS * a.iters;
+    const int T = p + Rv;                           // keys of the step's last row
+    const int n_act = (T + chunk - 1) / chunk;
+    if (z >= n_act) return;
+    const int t0 = z * chunk;
+    const int t1 = t0 + chunk < T ? t0 + chunk : T; // this workgroup's keys: t0 .. t1 - 1 (a lane's own limit is its row's position)
+    const int n_it = (t1 - t0 + AG_STAGE_KEYS - 1) / AG_STAGE_KEYS;
+    const unsigned last_old = p > 0 ? p - 1 : 0;    // rows >= p are never read from the cache
+    _Float16* const kc = (_Float16*)a.kc + (size_t)kvh * (size_t)a.max_seq * AP_D;
+    _Float16* const vc = (_Float16*)a.vc + (size_t)kvh * (size_t)a.max_seq * AP_D;
+
+    // ---- staging: attn_decode_gqa_kernel's
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem + AG_ROWS_STAGE;
+    const unsigned rit = 4 * wave + (lane >> 4), pp = lane & 15;
+    const unsigned kswz = (pp ^ (rit & 15)) << 4, vswz = ((((pp >> 1) ^ (rit & 7)) << 1) | (pp & 1)) << 4;
+    auto load_stage = [&](int it) {
+        const unsigned dst0 = lds0 + (it & 1) * (4 * AP_TILE) + wave * 1024;
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                unsigned key = (unsigned)(t0 + AG_STAGE_KEYS * it + 64 * ti) + rit + 16 * j;
+                key = key < last_old ? key : last_old;
+                ap_glds16(kc, __umul24(key, 256u) + kswz, dst0 + ti * (2 * AP_TILE) + j * 4096);
+                ap_glds16(vc, __umul24(key, 256u) + vswz, dst0 + ti * (2 * AP_TILE) + AP_TILE + j * 4096);
+            }
+        }
+    };
+    load_stage(0);
+    // ---- behind it: the raw query fragments of this lane's query row in each block (rows past the step's last repeat it: computed, never stored)
+    // with their step row's cos / sin pairs, and -- wave w, one pair per lane -- the new keys / values of step rows w and w + 4
+    h8 qf[NBW][4];
+    int Tj[NBW];                                    // keys this lane's query row sees: 0 .. Tj - 1
+#pragma unroll
+    for (int i = 0; i < NBW; ++i) {
+        int qr = q0 + 16 * i + r;
+        qr = qr < nq ? qr : nq - 1;
+        const int j = qr / G, g = qr - j * G;
+        Tj[i] = p + j + 1;
+        const _Float16* const qb = (const _Float16*)a.q + ((size_t)j * a.n_heads + h0 + g) * AP_D + 8 * o;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) qf[i][t] = *(const h8*)(qb + 32 * t);
+    }
+    h8 cs[NBW][2][2];                               // [block][t][half]: (cos, sin) of pairs 32 t + 8 o .. + 3 and .. + 4 .. + 7 at the row's position
+#pragma unroll
+    for (int i = 0; i < NBW; ++i) {
+        const h2* const cs_src = (const h2*)((const char*)a.state + (size_t)(Tj[i] - 1 - p) * STEP_STRIDE);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            cs[i][t][0] = *(const h8*)(cs_src + 32 * t + 8 * o);
+            cs[i][t][1] = *(const h8*)(cs_src + 32 * t + 8 * o + 4);
+        }
+    }
+    h8 gqf[4];
+    if constexpr (QKN) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) gqf[t] = *(const h8*)((const _Float16*)a.nrm.q_gamma + 32 * t + 8 * o);
+    }
+    _Float16 k0[2] = {0, 0}, k1[2] = {0, 0}, v0[2] = {0, 0}, v1[2] = {0, 0}, gk0 = 0, gk1 = 0;
+    h2 csk[2] = {{(_Float16)1.f, (_Float16)0.f}, {(_Float16)1.f, (_Float16)0.f}};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int rr = wave + 4 * u;                // (wave-uniform)
+        if (rr < Rv) {
+            const _Float16* const kn = (const _Float16*)a.k + ((size_t)rr * a.n_kv_heads + kvh) * AP_D;
+            const _Float16* const vn = (const _Float16*)a.v + ((size_t)rr * a.n_kv_heads + kvh) * AP_D;
+            k0[u] = kn[lane]; k1[u] = kn[lane + 64];
+            v0[u] = vn[lane]; v1[u] = vn[lane + 64];
+            csk[u] = ((const h2*)((const char*)a.state + (size_t)rr * STEP_STRIDE))[lane];
+        }
+    }
+    if constexpr (QKN) { gk0 = ((const _Float16*)a.nrm.k_gamma)[lane]; gk1 = ((const _Float16*)a.nrm.k_gamma)[lane + 64]; }
+    AMQ_WAIT_VM("attn.gqarows.landed", 0, "");      // this wave's share of stage 0 and its loads
+    if constexpr (QKN) {
+#pragma unroll
+        for (int i = 0; i < NBW; ++i) {
+            float st[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                st[t] = qkn_tree8(qf[i][t], qf[i][t + 2]);
+                st[t] += __shfl_xor(st[t], 16);
+                st[t] += __shfl_xor(st[t], 32);
+            }
+            const float rq = qkn_rstd(st[0] + st[1], a.nrm.eps);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) qf[i][t][e] = qkn_apply(qf[i][t][e], rq, gqf[t][e]);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+            if (wave + 4 * u < Rv) {                // a whole wave per key: attn_decode_kernel's reduction
+                const float rk = qkn_rstd(wave_sum_dpp(qkn_pair(k0[u], k1[u])), a.nrm.eps);
+                k0[u] = qkn_apply(k0[u], rk, gk0); k1[u] = qkn_apply(k1[u], rk, gk1);
+            }
+    }
+    // rotation: the decode kernels' fp16 expression
+#pragma unroll
+    for (int i = 0; i < NBW; ++i)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const h8 lo = qf[i][t], hi = qf[i][t + 2];
+            h8 nlo, nhi;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const _Float16 c16 = cs[i][t][e >> 2][2 * (e & 3)], s16 = cs[i][t][e >> 2][2 * (e & 3) + 1];
+                nlo[e] = lo[e] * c16 + (-hi[e]) * s16;
+                nhi[e] = hi[e] * c16 + lo[e] * s16;
+            }
+            qf[i][t] = nlo; qf[i][t + 2] = nhi;
+        }
+    _Float16* const knew = (_Float16*)smem;         // [row][rotated new key [128] | new value [128]]
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int rr = wave + 4 * u;
+        if (rr < Rv) {
+            const _Float16 r0 = k0[u] * csk[u].x + (-k1[u]) * csk[u].y, r1 = k1[u] * csk[u].x + k0[u] * csk[u].y;
+            _Float16* const ks = knew + rr * (2 * AP_D);
+            ks[lane] = r0; ks[lane + 64] = r1;
+            ks[AP_D + lane] = v0[u]; ks[AP_D + lane + 64] = v1[u];
+            const int pr = p + rr;
+            if (y == 0 && pr >= t0 && pr < t0 + chunk) {        // the one workgroup of this kv head that appends row rr
+                kc[(size_t)pr * AP_D + lane] = r0;
+                kc[(size_t)pr * AP_D + lane + 64] = r1;
+                vc[(size_t)pr * AP_D + lane] = v0[u];
+                vc[(size_t)pr * AP_D + lane + 64] = v1[u];
+            }
+        }
+    }
+    __syncthreads();                                // every wave's share of stage 0 has landed; the new rows are visible
+    unsigned char* const tiles = smem + AG_ROWS_STAGE;
+
+    // ---- the stages: attn_decode_gqa_kernel's, the key limit per lane
+    const float sl2 = 0.08838834764831845f * 1.4426950408889634f;           // 1 / sqrt(128) * log2(e)
+    const int tile = wave >> 1, half = wave & 1;
+    f4 oacc[NBW][8];
+    float m_run[NBW], l_run[NBW];
+#pragma unroll
+    for (int i = 0; i < NBW; ++i) {
+#pragma unroll
+        for (int d = 0; d < 8; ++d) oacc[i][d] = (f4){0.f, 0.f, 0.f, 0.f};
+        m_run[i] = -INFINITY; l_run[i] = 0.f;
+    }
+    const int t_fin = (T + 63) & ~63;               // end of the last tile the MFMAs touch
+    for (int it = 0; it < n_it; ++it) {
+        if (it + 1 < n_it) load_stage(it + 1);
+        unsigned char* const sb = tiles + (it & 1) * (4 * AP_TILE);
+        const int s0 = t0 + AG_STAGE_KEYS * it;
+        const int plo = p > s0 ? p : s0, phi = s0 + AG_STAGE_KEYS < t_fin ? s0 + AG_STAGE_KEYS : t_fin;
+        if (plo < phi) {
+            // the stage's rows at or past p: the step's new keys / values (the last one repeated behind them), 16 chunks of 16 bytes per row and operand
+            // placed where the staging's swizzles would have put them
+            for (int idx = tid; idx < (phi - plo) * 16; idx += 256) {
+                const int key = plo + (idx >> 4), c = idx & 15, lr = key - s0;
+                const _Float16* const ks = knew + (key - p < Rv ? key - p : Rv - 1) * (2 * AP_D);
+                unsigned char* const tb = sb + (lr >> 6) * (2 * AP_TILE);
+                const int row = lr & 63;
+                *(h8*)(tb + row * 256 + ((c ^ (row & 15)) << 4)) = *(const h8*)(ks + 8 * c);
+                *(h8*)(tb + AP_TILE + row * 256 + (((((c >> 1) ^ (row & 7)) << 1) | (c & 1)) << 4)) = *(const h8*)(ks + AP_D + 8 * c);
+            }
+            __syncthreads();
+        }
+        const int k0_ = s0 + 64 * tile + 32 * half;   // this wave's first key of the stage
+        if (k0_ < t1) {
+            const unsigned char* const kb_ = sb + tile * (2 * AP_TILE);
+            const unsigned char* const vb_ = kb_ + AP_TILE;
+            f4 st[NBW][2];
+#pragma unroll
+            for (int kl = 0; kl < 2; ++kl) {
+#pragma unroll
+                for (int i = 0; i < NBW; ++i) st[i][kl] = (f4){0.f, 0.f, 0.f, 0.f};
+                const int row = 32 * half + 16 * kl + r;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const h8 kf = *(const h8*)(kb_ + row * 256 + (((4 * t + o) ^ r) << 4));
+#pragma unroll
+                    for (int i = 0; i < NBW; ++i) st[i][kl] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[i][t], st[i][kl], 0, 0, 0);
+                }
+            }
+            h8 pb[NBW];
+#pragma unroll
+            for (int i = 0; i < NBW; ++i) {
+                const bool act = k0_ < Tj[i];       // the slice holds a key of this lane's row (the same for the four lanes of a row)
+                float mt = -INFINITY;
+#pragma unroll
+                for (int kl = 0; kl < 2; ++kl)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        st[i][kl][e] = (k0_ + 16 * kl + 4 * o + e) < Tj[i] ? st[i][kl][e] : -INFINITY;
+                        mt = fmaxf(mt, st[i][kl][e]);
+                    }
+                mt = fmaxf(mt, __shfl_xor(mt, 16));
+                mt = fmaxf(mt, __shfl_xor(mt, 32));
+                const float m_new = fmaxf(m_run[i], mt);
+                const bool grew = __any(m_new != m_run[i]);
+                // a slice wholly past the row's position: (m, l, O) stay as they are (alpha 1, probabilities 0) -- not exp2(-inf - -inf)
+                const float alpha = act ? __builtin_amdgcn_exp2f((m_run[i] - m_new) * sl2) : 1.f;
+                m_run[i] = m_new;
+                float ls = 0.f;
+#pragma unroll
+                for (int kl = 0; kl < 2; ++kl)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float pe = act ? __builtin_amdgcn_exp2f(st[i][kl][e] * sl2 - m_new * sl2) : 0.f;
+                        ls += pe;
+                        pb[i][4 * kl + e] = (_Float16)pe;
+                    }
+                l_run[i] = l_run[i] * alpha + ls;
+                if (grew) {
+#pragma unroll
+                    for (int d = 0; d < 8; ++d)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) oacc[i][d][e] *= alpha;
+                }
+            }
+            const int tq = r >> 2, tp = r & 3;
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+                const int row0 = 32 * half + 4 * o + tq;
+                const int seg = 2 * d + (tp >> 1);
+                const int off0 = row0 * 256 + ((((seg >> 1) ^ (row0 & 7)) << 5) | ((seg & 1) << 4)) + ((tp & 1) << 3);
+                const int row1 = row0 + 16;
+                const int off1 = row1 * 256 + ((((seg >> 1) ^ (row1 & 7)) << 5) | ((seg & 1) << 4)) + ((tp & 1) << 3);
+                h8 vf;
+                const ap_v4h t0_ = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) ap_v4h*)(vb_ + off0));
+                const ap_v4h t1_ = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) ap_v4h*)(vb_ + off1));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    vf[e] = (_Float16)t0_[e];
+                    vf[4 + e] = (_Float16)t1_[e];
+                }
+#pragma unroll
+                for (int i = 0; i < NBW; ++i) oacc[i][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb[i], oacc[i][d], 0, 0, 0);
+            }
+        }
+        AMQ_WAIT_VM("attn.gqarows.stage", 0, "");   // this wave's share of the next stage
+        __syncthreads();                            // ... every wave's; and this stage's buffer has been read
+    }
+    // ---- merge the waves' (m, l, O) in wave order, attn_decode_gqa_kernel's expressions per query row
+    constexpr int QR = 16 * NBW;                    // query rows of the workgroup
+    float* const Om = (float*)tiles;                // [4][QR][AG_OM_STRIDE]
+    float* const mlw = Om + 4 * QR * AG_OM_STRIDE;  // [4][QR][2]
+    static_assert((size_t)(4 * QR * AG_OM_STRIDE + 4 * QR * 2) * sizeof(float) <= (size_t)2 * 4 * AP_TILE, "merge area inside the stage buffers");
+#pragma unroll
+    for (int i = 0; i < NBW; ++i) {
+        l_run[i] += __shfl_xor(l_run[i], 16);
+        l_run[i] += __shfl_xor(l_run[i], 32);
+        const int row = wave * QR + 16 * i + r;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) *(f4*)(Om + (size_t)row * AG_OM_STRIDE + 16 * d + 4 * o) = oacc[i][d];
+        if (o == 0) { mlw[row * 2] = m_run[i]; mlw[row * 2 + 1] = l_run[i]; }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < QR * AP_D; idx += 256) {
+        const int lr = idx >> 7, d = idx & 127;
+        const int qr = q0 + lr;
+        if (qr >= nq) break;                        // (rows ascend with idx)
+        const int j = qr / G, qh = qr - j * G;
+        if (t0 > p + j) continue;                   // a chunk past the row's position: no keys of it here, nothing is written
+        float M = mlw[lr * 2];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) M = fmaxf(M, mlw[(w * QR + lr) * 2]);
+        float L = 0.f, O = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float f = __builtin_amdgcn_exp2f(mlw[(w * QR + lr) * 2] * sl2 - M * sl2);       // a wave that had no keys of the row: exp2(-inf) = 0
+            L += mlw[(w * QR + lr) * 2 + 1] * f;
+            O += Om[((size_t)w * QR + lr) * AG_OM_STRIDE + d] * f;
+        }
+        if (p + j < chunk) {                        // the row's one active chunk
+            ((_Float16*)a.out)[((size_t)j * a.n_heads + h0 + qh) * AP_D + d] = (_Float16)(O / L);
+        } else {
+            float* const wz = a.ws + (((size_t)j * a.n_heads + h0 + qh) * (size_t)a.n_splits + z) * AG_WS_STRIDE;
+            wz[d] = O;                              // (read by attn_gqa_combine_kernel, the next launch)
+            if (d == 0) {
+                wz[AP_D] = M * 0.08838834764831845f;
+                wz[AP_D + 1] = L;
+            }
+        }
+    }
+}
+
+int attn_decode_gqa_rows_blocks(int rows, int n_heads, int n_kv_heads) {
+    return (rows * (n_heads / n_kv_heads) + 15) / 16;
+}
+
+hipError_t launch_attn_decode_gqa_rows(const AttnArgs& a, int rows, int n_splits, void* ws, hipStream_t st) {
+    StreamDevice sd_(st);
+    AttnGqaRowsArgs g{a.q, a.k, a.v, a.kcache, a.vcache, a.out, a.rope_cur, (float*)ws, rows, a.n_heads, a.n_kv_heads, a.max_seq, n_splits,
+                      attn_decode_gqa_iters(a.max_seq, n_splits)};
+    const size_t lds = AG_ROWS_STAGE + (size_t)2 * 4 * AP_TILE;
+    const int nb = attn_decode_gqa_rows_blocks(rows, a.n_heads, a.n_kv_heads);
+    const dim3 grid(g.n_kv_heads, (nb + AMQ_GQA_ROWS_NBW - 1) / AMQ_GQA_ROWS_NBW, g.n_splits);
+    static unsigned long long attr_done = 0, attr_qkn_done = 0;
+    if (a.norm.q_gamma) {
+        AttnGqaRowsArgsQkn gn;
+        static_cast<AttnGqaRowsArgs&>(gn) = g;
+        gn.nrm = a.norm;
+        if (hipError_t e = ensure_dyn_lds(attr_qkn_done, (const void*)attn_decode_gqa_rows_kernel<true>, (int)lds)) return e;
+        hipLaunchKernelGGL(attn_decode_gqa_rows_kernel<true>, grid, dim3(256), lds, st, gn);
+    } else {
+        if (hipError_t e = ensure_dyn_lds(attr_done, (const void*)attn_decode_gqa_rows_kernel<false>, (int)lds)) return e;
+        hipLaunchKernelGGL(attn_decode_gqa_rows_kernel<false>, grid, dim3(256), lds, st, g);
+    }
+    if (hipError_t e = hipGetLastError()) return e;
+    // the rows' step-state blocks are the per-sequence blocks of the combine: row j's own position decides its number of active chunks
+    hipLaunchKernelGGL(attn_gqa_combine_kernel<true>, dim3(g.n_heads, rows), dim3(128), 0, st, (const float*)g.ws, g.out, g.state, 0, 1,
+                       g.n_heads, g.max_seq, g.n_splits, AG_STAGE_KEYS * g.iters);
+    return hipGetLastError();
+}
+
 hipError_t launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st) {
     StreamDevice sd_(st);                                  // attributes / CU counts of the stream's device
     const int lds = 2 * 2 * AP_TILE;                    // 64 KiB

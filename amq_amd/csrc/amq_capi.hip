@@ -763,6 +763,7 @@ struct AttnForm {
     size_t extra_lds;       // bytes beside the score array and the kernel's own 6 * 128 + 17 KiB
     const char* what;       // names the launch in a HIP error
     const char* rows;       // what `batch` counts, in messages
+    bool grouped = false;   // the matrix-core grouped-query kernels only: 2 <= n_heads / n_kv_heads <= 16, their fixed LDS, tickets unused
 };
 constexpr int NO_BOUND = 0x7fffffff;
 constexpr AttnForm ATTN_POS{POS_HOST | POS_DEV, 1, NO_BOUND, SPLITS_NONE, 0, "attn_decode", "batch"};
@@ -771,6 +772,7 @@ constexpr AttnForm ATTN_SPLIT{POS_HOST | POS_DEV | POS_BLOCK, 1, 65535, SPLITS_R
 constexpr AttnForm ATTN_SEQ{POS_BLOCKS, 1, 65535, SPLITS_OPTIONAL, 0, "attn_decode_seq", "batch"};
 // (rows: the earlier rows' rotated keys and values sit behind the score array)
 constexpr AttnForm ATTN_ROWS{POS_ROWS, 2, AMQ_LOOKUP_MAX_ROWS, SPLITS_OPTIONAL, 2 * 7 * 128 * 2 + 16, "attn_decode_rows", "rows"};
+constexpr AttnForm ATTN_ROWS_GQA{POS_ROWS, 2, AMQ_LOOKUP_MAX_ROWS, SPLITS_REQUIRED, 0, "attn_decode_rows_gqa", "rows", true};
 
 size_t amq_attn_decode_split_workspace_bytes(int batch, int n_heads, int n_splits) {
     if (batch < 1 || n_heads < 1 || n_splits < 1) return 0;
@@ -790,8 +792,11 @@ static int attn_decode(const AttnForm& f, const amq_qk_norm* norm, const void* q
     if (batch < f.batch_min || batch > f.batch_max) return fail(AMQ_ESHAPE, "%s must be %d..%d (got %d)", f.rows, f.batch_min, f.batch_max, batch);
     if (n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
         return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads)", n_heads, n_kv_heads);
+    if (f.grouped && (n_heads / n_kv_heads < 2 || n_heads / n_kv_heads > 16))
+        return fail(AMQ_ESHAPE, "%s serves 2..16 query heads per kv head (got %d / %d)", f.what, n_heads, n_kv_heads);
     if (max_seq < 1 || (!state && !pos_dev && (pos < 0 || pos >= max_seq)))
         return fail(AMQ_ESHAPE, "position %d outside the cache (max_seq=%d)", pos, max_seq);
+    if (f.grouped && max_seq > (1 << 24)) return fail(AMQ_ESHAPE, "%s forms a key's byte offset in 32 bits: max_seq <= 2^24 (got %d)", f.what, max_seq);
     if (f.splits != SPLITS_NONE && (n_splits < (f.splits == SPLITS_REQUIRED ? 1 : 0) || n_splits > 1024))
         return fail(AMQ_EINVAL, "n_splits must be %s1..1024 (got %d)", f.splits == SPLITS_REQUIRED ? "" : "0 (one workgroup per head) or ", n_splits);
     if (n_splits && (!workspace || !tickets)) return fail(AMQ_EINVAL, "null pointer (workspace / tickets are required with n_splits >= 1)");
@@ -800,7 +805,7 @@ static int attn_decode(const AttnForm& f, const amq_qk_norm* norm, const void* q
         keys = (((max_seq + n_splits - 1) / n_splits) + 31) & ~31;
         keys = keys < amq::ATT_MIN_CHUNK ? amq::ATT_MIN_CHUNK : keys;
     }
-    if (6 * 128 + (size_t)keys * 4 + f.extra_lds + 17 * 1024 > LDS_LIMIT)
+    if (!f.grouped && 6 * 128 + (size_t)keys * 4 + f.extra_lds + 17 * 1024 > LDS_LIMIT)
         return n_splits ? fail(AMQ_ESHAPE, "max_seq=%d over %d splits leaves chunks of %d keys: too long", max_seq, n_splits, keys)
                         : fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
     const size_t need = amq_attn_decode_split_workspace_bytes(batch, n_heads, n_splits);
@@ -809,8 +814,9 @@ static int attn_decode(const AttnForm& f, const amq_qk_norm* norm, const void* q
     amq::AttnArgs a{q, k, v, kcache, vcache, out, state ? nullptr : pos_dev, pos, n_heads, n_kv_heads, max_seq, state ? 10000.0f : rope_theta,
                     state ? nullptr : rope_table, state, (f.pos & (POS_BLOCKS | POS_ROWS)) != 0, (f.pos & POS_ROWS) != 0};
     a.norm = nrm;
-    const hipError_t e = n_splits ? amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream)
-                                  : amq::launch_attn_decode(a, batch, (hipStream_t)stream);
+    const hipError_t e = f.grouped ? amq::launch_attn_decode_gqa_rows(a, batch, n_splits, workspace, (hipStream_t)stream)
+                         : n_splits ? amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream)
+                                    : amq::launch_attn_decode(a, batch, (hipStream_t)stream);
     if (e == hipSuccess) return AMQ_OK;
     return fail(AMQ_ELAUNCH, "%s%s: %s", f.what, n_splits && f.splits == SPLITS_OPTIONAL ? " (split)" : "", hipGetErrorString(e));
 }
@@ -1075,6 +1081,19 @@ int amq_attn_decode_rows_qkn_f16(const amq_qk_norm* norm, const void* q, const v
                                  void* step_states, int rows, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
                                  void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
     return attn_decode(ATTN_ROWS, norm, q, k, v, kcache, vcache, out, step_states, nullptr, 0, rows, n_heads, n_kv_heads, head_dim, max_seq, 10000.0f, nullptr,
+                       n_splits, workspace, workspace_bytes, tickets, stream);
+}
+
+int amq_attn_decode_rows_gqa_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int rows,
+                                 int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
+                                 void* tickets, void* stream) {
+    return amq_attn_decode_rows_gqa_qkn_f16(nullptr, q, k, v, kcache, vcache, out, step_states, rows, n_heads, n_kv_heads, head_dim, max_seq, n_splits, workspace, workspace_bytes, tickets, stream);
+}
+
+int amq_attn_decode_rows_gqa_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                     void* step_states, int rows, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
+                                     void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
+    return attn_decode(ATTN_ROWS_GQA, norm, q, k, v, kcache, vcache, out, step_states, nullptr, 0, rows, n_heads, n_kv_heads, head_dim, max_seq, 10000.0f, nullptr,
                        n_splits, workspace, workspace_bytes, tickets, stream);
 }
 

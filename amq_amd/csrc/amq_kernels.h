@@ -177,6 +177,10 @@ hipError_t launch_attn_decode_split(const AttnArgs& a, int batch, int n_splits, 
 bool attn_decode_takes_gqa(int n_heads, int n_kv_heads, int max_seq, int n_splits);
 int attn_decode_gqa_iters(int max_seq, int n_splits);      // stages of 128 keys per workgroup
 hipError_t launch_attn_decode_gqa(const AttnArgs& a, int batch, int n_splits, void* ws, void* tickets, hipStream_t st);
+// the `rows` (2 .. 8) consecutive positions of a prompt-lookup verify step on such a model (attn_decode_gqa_rows_kernel): a.rope_cur = block 0 of the
+// rows' step-state blocks, one cache slice; n_splits >= 1 chunks of 128 * attn_decode_gqa_iters keys; ws = fp32 [rows][n_heads][n_splits][132]
+int attn_decode_gqa_rows_blocks(int rows, int n_heads, int n_kv_heads);       // MFMA row blocks of 16 query rows (step row, head of the group)
+hipError_t launch_attn_decode_gqa_rows(const AttnArgs& a, int rows, int n_splits, void* ws, hipStream_t st);
 hipError_t launch_rmsnorm(const void* x, const void* gamma, void* y, int M, int K, float eps, hipStream_t st);
 hipError_t launch_rmsnorm_xfrag(const void* x, const void* gamma, void* xf, int M, int K, float eps, hipStream_t st);
 // causal attention over a whole prompt (amq_attn_prefill.hip).  Element (b, s, head, d) of q / out sits at

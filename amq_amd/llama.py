@@ -204,11 +204,24 @@ class QuantLlama:
     # instead of 5.  Built, bit-identical (tests/test_gpu_qkv_attn.py) and SLOWER -- 15.7 us per fused launch against 9.2 + 5.1,
     # 755 vs 830 tokens/s (profiles/r03_qkv_attn_fused_negative.txt) -- so it is off unless a caller sets fuse_qkv_attn.
     FUSE_QKV_ATTN = False
+    # cache length (max_seq) from which a lookup runner of a grouped-query model (2 .. 16 query heads per kv head) takes the matrix-core rows attention
+    # (ops.attn_decode_rows(grouped=True)); None: never.
+    # Measured per launch (profiles/lookup_gqa.json): at 2048 / 8192 / 32768 rows of cache it wins at every measured (heads, R) -- 13.2 -> 11.1 us
+    # (32/8 heads, R = 2, 2048) up to 787 -> 63 us (64/8, R = 8, 32768) -- so the threshold is its floor; shorter caches were not measured and keep the
+    # per-head kernels (every grouped-query lookup runner of the older tests keeps its arithmetic).
+    ROWS_GQA_FROM = 2048
     ENGINE_DEFAULT = False      # what engine=None means (the engine is opt-in until it beats the five-launch step: HISTORY.md 3.2b)
     # prompt passes also leave the logits of EVERY prompt row in self.logits_rows [B, S, vocab] (HF's forward returns them all; the runner's own
     # generate loop needs the last row only): final norm + one fp16 GEMM over the prompt rows, inside the captured prompt graph (hf_fast.py sets it)
     all_logits = False
     fine = False                # any layer with groups of 64 / 32 (set by __init__)
+
+    @classmethod
+    def rows_attention_grouped(cls, n_heads, n_kv_heads, max_seq):
+        """whether a lookup runner of these heads and this cache length takes the grouped rows attention (the ``grouped=`` of ops.attn_decode_rows)"""
+        if cls.ROWS_GQA_FROM is None or n_kv_heads < 1 or n_heads % n_kv_heads:
+            return False
+        return 2 <= n_heads // n_kv_heads <= 16 and max_seq >= cls.ROWS_GQA_FROM
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
                  hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2):
@@ -549,7 +562,7 @@ class QuantLlama:
                                                       blk["self_attn.v_proj"].seg(self.v)])
                 if self.lookup:                 # the R rows are consecutive positions of the one sequence: causal among them, one cache slice
                     ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv,
-                                         **self._qkn(blk))
+                                         grouped=self.rows_attention_grouped(self.nh, self.nkv, self.max_seq), **self._qkn(blk))
                 else:
                     ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
                                     cur=self.rope_cur, **self._qkn(blk))

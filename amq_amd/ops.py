@@ -1305,13 +1305,24 @@ def new_lookup_state(device, drafts, ngram_max=2, history_cap=0):
     return host.to(device), torch.zeros(history_cap, dtype=torch.int32, device=device)
 
 
-def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads, n_splits=0, q_norm=None, k_norm=None, norm_eps=QK_NORM_EPS):
+def attn_rows_gqa_blocks(rows, n_heads, n_kv_heads):
+    """MFMA row blocks of the grouped rows launch: 16 query rows (step row, head of the group) each"""
+    return -(-rows * (n_heads // n_kv_heads) // 16)
+
+
+def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads, n_splits=0, q_norm=None, k_norm=None, norm_eps=QK_NORM_EPS,
+                     grouped=False):
     """``rows`` = 2 .. 8 consecutive positions of ONE sequence (amq_attn_decode_rows_f16): q / out [rows, n_heads*128], k / v [rows, n_kv_heads*128],
     caches [1, n_kv_heads, max_seq, 128] (or 3-D); ``cur`` [rows, 128] / ``pos`` [rows]: the views of one per-sequence step state whose block j holds
     position p + j.  Row j appends cache row p + j and attends rows 0 .. p - 1 of the cache plus this step's rows 0 .. j.
     ``n_splits``: 0 = by cache length, 1 = the single-workgroup kernel, >= 2 the per-head split kernel.
-    ``q_norm`` / ``k_norm``: as :func:`attn_decode` (every workgroup normalises the earlier rows' keys it rotates for itself: the same bits)."""
+    ``q_norm`` / ``k_norm``: as :func:`attn_decode` (every workgroup normalises the earlier rows' keys it rotates for itself: the same bits).
+    ``grouped``: the matrix-core kernel of grouped-query models (amq_attn_decode_rows_gqa_f16; 2 .. 16 query heads per kv head): row j's output has
+    the bits of :func:`attn_decode` at position p + j with the same ``n_splits`` >= 2.  ``n_splits``: chunks of the cache (>= 1); 0 = the grouped
+    policy of :func:`attn_decode_splits`."""
     norm = _qk_norm(q_norm, k_norm, norm_eps, q.device)
+    if grouped and not (n_kv_heads > 0 and n_heads % n_kv_heads == 0 and 2 <= n_heads // n_kv_heads <= 16):
+        raise ValueError(f"grouped=True serves 2..16 query heads per kv head (got {n_heads} / {n_kv_heads})")
     states, R = _seq_state(cur, pos)
     if states is None:
         raise ValueError("cur [rows, 128] / pos [rows] must be the views of one per-sequence step state (ops.new_step_state(device, batch=rows))")
@@ -1320,7 +1331,12 @@ def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads
     if kcache.dim() == 4 and kcache.shape[0] != 1:
         raise ValueError("the rows of a step belong to ONE sequence: caches [1, n_kv_heads, max_seq, 128]")
     max_seq = kcache.shape[-2]
-    if n_splits == 0:
+    if n_splits == 0 and grouped:
+        # the single-token grouped policy with the launch's row blocks standing in for sequences (workgroups = kv heads x row blocks x splits).
+        # Not tuned for this launch: measured against half and twice its split count only (tools/lookup_gqa_bench.py, profiles/lookup_gqa.json:
+        # 32/8, 28/4, 64/8 heads x 2048 / 8192 / 32768 keys x R = 2, 4, 8 -- a neighbour is never more than 2 % faster, and up to 71 % slower).
+        n_splits = attn_decode_splits(max_seq, n_heads, attn_rows_gqa_blocks(R, n_heads, n_kv_heads), n_kv_heads)
+    elif n_splits == 0:
         n_splits = attn_decode_splits(max_seq, n_heads, R)       # (the per-head policy also for grouped-query models: they take the per-head kernels here)
     _need(q, torch.float16, "q", R * n_heads * 128)
     _need(k, torch.float16, "k", R * n_kv_heads * 128)
@@ -1329,6 +1345,11 @@ def attn_decode_rows(q, k, v, kcache, vcache, out, cur, pos, n_heads, n_kv_heads
     _need(vcache, torch.float16, "vcache", n_kv_heads * max_seq * 128)
     _need(out, torch.float16, "out", R * n_heads * 128)
     lib = _lib.load()
+    if grouped:                                 # (the workspace is part of every grouped call, one chunk included)
+        wsb = lib.amq_attn_decode_split_workspace_bytes(R, n_heads, n_splits)
+        scratch = (_lib.ptr(_ATTN_WS.get(q.device, wsb // 4)), wsb, _lib.ptr(_ATTN_TICKETS.get(q.device, R * n_heads)))
+        return _attn_call(lib, "amq_attn_decode_rows_gqa_f16", norm, (q, k, v, kcache, vcache, out), (states,), (R, n_heads, n_kv_heads, max_seq),
+                          (n_splits,) + scratch)
     return _attn_call(lib, "amq_attn_decode_rows_f16", norm, (q, k, v, kcache, vcache, out), (states,), (R, n_heads, n_kv_heads, max_seq),
                       (n_splits if n_splits > 1 else 0,) + _split_scratch(lib, q.device, R, n_heads, n_splits))
 

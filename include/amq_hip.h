@@ -407,7 +407,8 @@ int amq_set_token_seq_f16(const long long* token_in, int n_in, const void* embed
  * step's rows 0 .. j (causal among the rows): every workgroup rotates the earlier rows of the step itself from k / v (they are being appended by
  * other workgroups of the same launch and are never read from the cache).  Read from a cache that already holds rows p .. p + j - 1, row j's output
  * is amq_attn_decode_seq_f16's at position p + j bit for bit (n_splits == 0: one workgroup per (head, row); n_splits >= 1: the per-head split kernel,
- * chunks from each row's own position, bit-identical with one active chunk; grouped-query models take the per-head kernels here).  workspace
+ * chunks from each row's own position, bit-identical with one active chunk; grouped-query models take the per-head kernels here too --
+ * their matrix-core form is amq_attn_decode_rows_gqa_f16 below).  workspace
  * (amq_attn_decode_split_workspace_bytes(rows, ...)) and tickets [rows * n_heads] as there.  A row whose position is outside 0 .. max_seq-1 (or whose
  * row 0 would be below 0) is a no-op for THAT row and raises ITS block's error word.  Rows of rejected drafts stay in the cache behind the new
  * position; no step reads them before a later step overwrites them. */
@@ -415,6 +416,17 @@ int amq_set_token_seq_f16(const long long* token_in, int n_in, const void* embed
 int amq_attn_decode_rows_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int rows,
                              int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
                              void* tickets, void* stream);
+/* amq_attn_decode_rows_f16 for GROUPED-QUERY models (2 <= n_heads / n_kv_heads <= 16, else AMQ_ESHAPE) on the matrix cores: the same arguments, rows,
+ * appends, causal rule among the rows and out-of-range behaviour (p < 0: every row is a no-op and raises its block's error word).  One workgroup per
+ * (kv head, block of 16 query rows, chunk) takes the chunk's K / V in once and scores it against its query rows -- query row (j, g) = step row j,
+ * head g of the group -- with amq_attn_decode_seq_f16's grouped kernel's slicing and orders, the key limit per query row: row j's output and the
+ * cache rows p .. p + rows - 1 are, bit for bit, what `rows` successive amq_attn_decode_seq_f16 calls (batch 1, the same n_splits >= 2) at positions
+ * p .. p + rows - 1 leave.  n_splits: 1 .. 1024 chunks of 128 * ceil(ceil(max_seq / n_splits) / 128) keys (0: AMQ_EINVAL); workspace (
+ * amq_attn_decode_split_workspace_bytes(rows, n_heads, n_splits)) is required; tickets must be given and is not used (the rows are finished by the
+ * grouped kernel's combine launch). */
+int amq_attn_decode_rows_gqa_f16(const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out, void* step_states, int rows,
+                                 int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits, void* workspace, size_t workspace_bytes,
+                                 void* tickets, void* stream);
 /* The verify-and-propose tail, one launch.  lookup_state: a device block of AMQ_LOOKUP_STATE_WORDS int32 words, all of them read (and the counters
  * written) on every launch, so a captured step never needs a re-capture:
  *   word 0      D: drafts per step (1 .. 7; the launch's rows = D + 1)
@@ -584,6 +596,9 @@ int amq_attn_decode_seq_qkn_f16(const amq_qk_norm* norm, const void* q, const vo
 int amq_attn_decode_rows_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                                  void* step_states, int rows, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
                                  void* workspace, size_t workspace_bytes, void* tickets, void* stream);
+int amq_attn_decode_rows_gqa_qkn_f16(const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
+                                     void* step_states, int rows, int n_heads, int n_kv_heads, int head_dim, int max_seq, int n_splits,
+                                     void* workspace, size_t workspace_bytes, void* tickets, void* stream);
 /* amq_rope_cache_batch_f16 (batch 1: amq_rope_cache_f16) and amq_rope_rows_f16 with the heads of q and k normalised first */
 int amq_rope_cache_qkn_f16(const amq_qk_norm* norm, void* q, const void* k, const void* v, void* kcache, void* vcache, const void* rope_table,
                            int rope_rows, int pos0, int S, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
