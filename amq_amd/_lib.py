@@ -18,6 +18,7 @@ AB_LIB_PATH = os.path.join(_HERE, "libamq_hip_ab.so")
 AMQ_OK = 0
 MODE_HQQ, MODE_FMA, MODE_FMA1 = 0, 1, 2
 PRO_NONE, PRO_RMSNORM, PRO_SILU_MUL = 0, 1, 2
+PRO_MUL = 4                  # x * x2 over a gate activated where it was written (GemvOpts.act_mask); 3 is internal to the library
 MAX_SEGMENTS = 4
 MATH_DEFAULT, MATH_LINEAR, MATH_GROUPSCALE, MATH_EXACT = 0, 1, 2, 3
 FEWROW_AUTO, FEWROW_TILE, FEWROW_STREAM = 0, 1, 2      # kernel form of the grouped few-row launch (amq_gemm_xfrag_grouped_form_f16)
@@ -47,7 +48,7 @@ class EngineBlock(ctypes.Structure):
 
 class GemvOpts(ctypes.Structure):
     """mirror of `amq_gemv_opts` (include/amq_hip.h): per-call launch options, all zero = defaults"""
-    _fields_ = [("math", _i), ("waves", _i), ("depth", _i), ("rpt", _i), ("dot", _i)]
+    _fields_ = [("math", _i), ("waves", _i), ("depth", _i), ("rpt", _i), ("dot", _i), ("act_mask", _i)]
 
 
 class QkNorm(ctypes.Structure):

@@ -135,9 +135,10 @@ int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const
                          void* stream) {
     if (!segs || nseg < 1 || nseg > AMQ_MAX_SEGMENTS) return fail(AMQ_EINVAL, "nseg must be 1..%d (got %d)", AMQ_MAX_SEGMENTS, nseg);
     if (!x) return fail(AMQ_EINVAL, "null x");
-    if (prologue < AMQ_PRO_NONE || prologue > AMQ_PRO_SILU_MUL) return fail(AMQ_EINVAL, "unknown prologue %d", prologue);
+    if ((prologue < AMQ_PRO_NONE || prologue > AMQ_PRO_SILU_MUL) && prologue != AMQ_PRO_MUL) return fail(AMQ_EINVAL, "unknown prologue %d", prologue);
     if (prologue == AMQ_PRO_RMSNORM && !gamma) return fail(AMQ_EINVAL, "RMSNorm prologue needs gamma");
     if (prologue == AMQ_PRO_SILU_MUL && !x2) return fail(AMQ_EINVAL, "SiLU*mul prologue needs x2");
+    if (prologue == AMQ_PRO_MUL && !x2) return fail(AMQ_EINVAL, "mul prologue needs x2");
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
     amq_gemv_opts o{};                                   // all zero = defaults
     if (opts) o = *opts;
@@ -147,6 +148,10 @@ int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const
     if (o.waves != 0 && o.waves != 4 && o.waves != 8 && o.waves != 16) return fail(AMQ_EINVAL, "opts.waves must be 0, 4, 8 or 16");
     if (o.depth != 0 && o.depth != 2 && o.depth != 4) return fail(AMQ_EINVAL, "opts.depth must be 0, 2 or 4");
     if (o.rpt < 0 || o.rpt > 64) return fail(AMQ_EINVAL, "opts.rpt (row-tiles per workgroup) must be 0..64");
+    if (o.act_mask < 0 || o.act_mask >= (1 << nseg)) return fail(AMQ_EINVAL, "opts.act_mask names segments 0..%d (got 0x%x)", nseg - 1, o.act_mask);
+    // (the activated output and the prologue that multiplies it live in the group-128 kernels; finer groups keep AMQ_PRO_SILU_MUL)
+    if ((o.act_mask || prologue == AMQ_PRO_MUL) && amq::meta_pairs(group) != 1)
+        return fail(AMQ_ESHAPE, "opts.act_mask / AMQ_PRO_MUL: groups of 128 (and multiples) only (got %d); use AMQ_PRO_SILU_MUL", group);
     const bool plain_form = !o.dot && o.math != AMQ_MATH_LINEAR && o.depth != 4 && amq::meta_pairs(group) == 1 && o.waves != 4;
     // (rows staged in two K phases -- 7 - 8 rows of K = 11008 -- need dense x rows and no full-row statistic: launch_gemv makes the same decision)
     const bool whole_rows = prologue == AMQ_PRO_RMSNORM || (x_stride != 0 && x_stride != K);
@@ -162,6 +167,8 @@ int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const
         d.qweight = s.qweight_native; d.meta = s.meta_native; d.bias = s.bias; d.residual = s.residual; d.y = s.y;
         d.N = s.N; d.bits = s.bits; d.mode = s.mode;
         d.y_stride = s.y_stride ? s.y_stride : s.N;
+        d.act = (o.act_mask >> i) & 1;
+        if (d.act && s.residual) return fail(AMQ_EINVAL, "segment %d: an activated output (opts.act_mask) takes no residual", i);
     }
     a.nseg = nseg; a.M = M; a.K = K; a.x_stride = x_stride ? x_stride : K;
     a.x = x; a.x2 = x2; a.gamma = gamma; a.eps = eps; a.prologue = prologue;

@@ -63,6 +63,7 @@ AMQ_GEMV_EXTERN(PRO_NONE)
 AMQ_GEMV_EXTERN(PRO_RMSNORM)
 AMQ_GEMV_EXTERN(PRO_SILU_MUL)
 #undef AMQ_GEMV_EXTERN
+extern template hipError_t launch_pro<PRO_MUL>(const GemvKArgs&, int, int, int, int, size_t, hipStream_t);      // (groups of 128 only: amq_gemv_pro2.hip)
 hipError_t launch_pro_sums_entry(const GemvKArgs&, int nw, int rs, int, size_t, hipStream_t);     // amq_gemv_pro3.hip
 
 // Fills the per-segment workgroup ranges and launches.  rpt = row-tiles per workgroup.
@@ -142,6 +143,10 @@ hipError_t launch_gemv(GemvArgs& a, hipStream_t st) {
     if ((a.prologue == PRO_RMSNORM_SUMS || a.sums_out) && !(rs128 || rs64)) return hipErrorInvalidValue;
     if (a.prologue == PRO_RMSNORM_SUMS && (ph2 || !a.sums_in || (a.K >> 4) > 64 * SUMS_PER_LANE || a.x_stride != a.K)) return hipErrorInvalidValue;
     if (a.sums_out && (a.nseg != 1 || a.prologue != PRO_NONE)) return hipErrorInvalidValue;
+    // an activated output is a gate, never a hidden state: no residual, no sums of squares; it and the prologue that consumes it live in the group-128 bodies
+    if (a.prologue == PRO_MUL && gp != 1) return hipErrorInvalidValue;
+    for (int i = 0; i < a.nseg; ++i)
+        if (a.seg[i].act && (gp != 1 || a.seg[i].residual || a.sums_out)) return hipErrorInvalidValue;
     GemvKArgs k{};
     k.x = a.x; k.x2 = a.prologue == PRO_RMSNORM_SUMS ? a.sums_in : a.x2; k.gamma = a.gamma;
     k.sums_out = (float*)a.sums_out; k.sums_stride = a.seg[0].n_rt;
@@ -154,6 +159,7 @@ hipError_t launch_gemv(GemvArgs& a, hipStream_t st) {
         k.wg_begin[i] = s.wg_begin; k.n_rt[i] = gemv_split(s.n_rt, s.wg_count); k.key[i] = s.bits * 4 + (s.mode == MODE_FMA1 && !has_fma1 ? (int)MODE_FMA : s.mode);
         k.qweight[i] = s.qweight; k.meta[i] = s.meta;
         k.bias[i] = s.bias; k.residual[i] = s.residual; k.y[i] = s.y; k.y_stride[i] = s.y_stride;
+        k.act_mask |= (s.act ? 1 : 0) << i;
     }
 #ifdef AMQ_STAMP
     k.stamps = g_stamp_ptr;
@@ -176,6 +182,7 @@ hipError_t launch_gemv(GemvArgs& a, hipStream_t st) {
     switch (a.prologue) {
         case PRO_NONE: return launch_pro<PRO_NONE>(k, a.flags | (rs128 ? GEMV_FLAG_RS128 : 0) | (rs64 ? GEMV_FLAG_RS64 : 0) | (ph2 ? GEMV_FLAG_PH2 : 0), a.force_depth, nw, wg, lds, st);
         case PRO_RMSNORM: return launch_pro<PRO_RMSNORM>(k, a.flags | (rs128 ? GEMV_FLAG_RS128 : 0) | (rs64 ? GEMV_FLAG_RS64 : 0) | (ph2 ? GEMV_FLAG_PH2 : 0), a.force_depth, nw, wg, lds, st);
+        case PRO_MUL: return launch_pro<PRO_MUL>(k, a.flags | (rs128 ? GEMV_FLAG_RS128 : 0) | (rs64 ? GEMV_FLAG_RS64 : 0) | (ph2 ? GEMV_FLAG_PH2 : 0), a.force_depth, nw, wg, lds, st);
         default: return launch_pro<PRO_SILU_MUL>(k, a.flags | (rs128 ? GEMV_FLAG_RS128 : 0) | (rs64 ? GEMV_FLAG_RS64 : 0) | (ph2 ? GEMV_FLAG_PH2 : 0), a.force_depth, nw, wg, lds, st);
     }
 }

@@ -67,12 +67,13 @@ struct GemvKArgs {
     int y_stride[GEMV_MAX_SEG];
     float* sums_out;                       // (5 .. 8-row kernels, one segment) per-row-tile sums of squares of the rows written: [M][sums_stride], or null
     int sums_stride;                       // = N / 16
+    int act_mask;                          // bit i: segment i stores fp16(silu(y)) (GemvSeg.act)
 #ifdef AMQ_STAMP
     unsigned long long* stamps;
 #endif
 };
 
-struct SegOut { const _Float16* bias; const _Float16* residual; _Float16* y; int y_stride; float* sums; int sums_stride; };
+struct SegOut { const _Float16* bias; const _Float16* residual; _Float16* y; int y_stride; float* sums; int sums_stride; bool act; };
 
 // sum over the 16 lanes of a DPP row (every lane of the row gets it; fixed order)
 __device__ __forceinline__ float row16_total(float v) {
@@ -123,6 +124,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 __device__ __forceinline__ float silu_f(float g) { return g / (1.0f + __expf(-g)); }
+// the prologues that take a second operand: PRO_SILU_MUL x = fp16(silu(gate)) * up; PRO_MUL x = gate * up, the gate activated by the launch that wrote
+// it (SegOut.act: the same silu_f on the same fp16 value, once per element instead of once per workgroup and element) -- the same bits
+template <int PRO> constexpr bool PRO_X2 = PRO == PRO_SILU_MUL || PRO == PRO_MUL;
+template <int PRO>
+__device__ __forceinline__ _Float16 gate_mul(_Float16 g, _Float16 u) { return (PRO == PRO_MUL ? g : (_Float16)silu_f((float)g)) * u; }
 
 // mean of squares = tot / K, as LlamaRMSNorm's .mean(): a true division -- except that for K a power of two (hidden sizes 4096, 8192) the product with
 // the exact reciprocal IS that quotient, bit for bit, at one instruction instead of ten per row (every workgroup of a fused-prologue launch pays them)
@@ -179,10 +185,10 @@ __device__ __forceinline__ void stage_x(const GemvHot& a, _Float16* xl, float* x
                     h8 r;
                     if (PRO == PRO_NONE) {
                         r = v;
-                    } else if (PRO == PRO_SILU_MUL) {
+                    } else if (PRO_X2<PRO>) {
                         const h8 u = *(const h8*)((const _Float16*)a.x2 + (size_t)m * a.x_stride + 8 * c);
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) { _Float16 s = (_Float16)silu_f((float)v[i]); r[i] = s * u[i]; }
+                        for (int i = 0; i < 8; ++i) r[i] = gate_mul<PRO>(v[i], u[i]);
                     } else {
                         const h8 gm = *(const h8*)((const _Float16*)a.gamma + 8 * c);
 #pragma unroll
@@ -221,11 +227,11 @@ __device__ __forceinline__ void stage_x(const GemvHot& a, _Float16* xl, float* x
             h8 r;
             if (PRO == PRO_NONE) {
                 r = v;
-            } else if (PRO == PRO_SILU_MUL) {
+            } else if (PRO_X2<PRO>) {
                 // x = fp16(fp16(silu(gate)) * up)  -- HF LlamaMLP: act_fn(gate) * up
                 const h8 u = *(const h8*)((const _Float16*)a.x2 + (size_t)m * a.x_stride + 8 * c);
 #pragma unroll
-                for (int i = 0; i < 8; ++i) { _Float16 s = (_Float16)silu_f((float)v[i]); r[i] = s * u[i]; }
+                for (int i = 0; i < 8; ++i) r[i] = gate_mul<PRO>(v[i], u[i]);
             } else {
                 // HF LlamaRMSNorm: weight * (x.float() * rstd).to(fp16)
                 const h8 gm = *(const h8*)((const _Float16*)a.gamma + 8 * c);
@@ -267,7 +273,7 @@ __device__ __forceinline__ void x_issue(const GemvHot& a, XRegs& xr) {
         int c = (int)threadIdx.x + i * THREADS;
         c = c < last ? c : last;                                  // clamp: every lane loads, tail lanes discard
         xr.v[i] = *(const h8*)((const _Float16*)a.x + 8 * c);
-        if (PRO == PRO_SILU_MUL) xr.w[i] = *(const h8*)((const _Float16*)a.x2 + 8 * c);
+        if (PRO_X2<PRO>) xr.w[i] = *(const h8*)((const _Float16*)a.x2 + 8 * c);
         if (PRO == PRO_RMSNORM) xr.w[i] = *(const h8*)((const _Float16*)a.gamma + 8 * c);
     }
 }
@@ -303,9 +309,9 @@ __device__ __forceinline__ void x_finish(const GemvHot& a, const XRegs& xr, _Flo
             h8 r;
             if (PRO == PRO_NONE) {
                 r = xr.v[i];
-            } else if (PRO == PRO_SILU_MUL) {
+            } else if (PRO_X2<PRO>) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { _Float16 sg = (_Float16)silu_f((float)xr.v[i][e]); r[e] = sg * xr.w[i][e]; }
+                for (int e = 0; e < 8; ++e) r[e] = gate_mul<PRO>(xr.v[i][e], xr.w[i][e]);
             } else {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { _Float16 nrm = (_Float16)((float)xr.v[i][e] * rstd); r[e] = xr.w[i][e] * nrm; }
@@ -487,7 +493,7 @@ __device__ __forceinline__ void x_finish_dma(const GemvHot& a, const XRegs& xr, 
         }
         return;
     }
-    // SiLU * mul: x = fp16(fp16(silu(gate)) * up)
+    // SiLU * mul: x = fp16(fp16(silu(gate)) * up)   (PRO_MUL: the gate rows arrive activated)
     const int last = chunks - 1;
     for (int m0 = 0; m0 < a.M; m0 += 4) {
         h8 up[4 * XCH];
@@ -512,7 +518,7 @@ __device__ __forceinline__ void x_finish_dma(const GemvHot& a, const XRegs& xr, 
                         const h8 g = *(const h8*)p;
                         h8 r;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) { _Float16 sg = (_Float16)silu_f((float)g[e]); r[e] = sg * up[j * XCH + i][e]; }
+                        for (int e = 0; e < 8; ++e) r[e] = gate_mul<PRO>(g[e], up[j * XCH + i][e]);
                         *(h8*)p = r;
                     }
                 }
@@ -523,13 +529,6 @@ __device__ __forceinline__ void x_finish_dma(const GemvHot& a, const XRegs& xr, 
 }
 
 // ---------------------------------------------------------------- epilogue
-__device__ __forceinline__ void store_out(const SegOut& s, int m, int n, float acc) {
-    _Float16 y = (_Float16)acc;                                   // fp16(matmul)
-    if (s.bias) y = y + s.bias[n];                                // out + bias      (fp16 add)
-    if (s.residual) y = s.residual[(size_t)m * s.y_stride + n] + y;  // residual + out
-    s.y[(size_t)m * s.y_stride + n] = y;
-}
-
 // shift+mask unpack for MATH_LINEAR: every pair at ONE mantissa position, out[4t+p] = packed fp16 subnormals q * 2^(SH-24)
 template <int BITS> struct LinCfg;
 template <> struct LinCfg<4> { static constexpr int SH = 6; };
@@ -667,6 +666,7 @@ __device__ __forceinline__ void gemv_body(const GemvHot& a, const GemvKArgs& blk
     so.y_stride = blk.y_stride[sidx];
     so.sums = (RS != 256 && PRO == PRO_NONE) ? blk.sums_out : nullptr;   // (the 2 .. 8-row kernels without a prologue -- o_proj, down_proj: what a PRO_RMSNORM_SUMS launch over y will read)
     so.sums_stride = blk.sums_stride;
+    so.act = GP == 1 && ((blk.act_mask >> sidx) & 1);             // (launch_gemv refuses it at groups of 64 / 32)
 #ifndef AMQ_ABL_NOSTAGE
     // xmode: 1 = one row held in registers (x_issue ran), 2 = rows on their way into LDS (x_dma_rows ran; the <= 8-row kernels, RS != 256), 0 = generic
     if (xmode == 1) x_finish<PRO, NW, XCH, MATH == MATH_LINEAR>(a, xr, lds_x, xg, red);
@@ -732,6 +732,7 @@ __device__ __forceinline__ void gemv_body(const GemvHot& a, const GemvKArgs& blk
             _Pragma("unroll") for (int w_ = 0; w_ < NW; ++w_) tot_ += rp_[w_ * RS + threadIdx.x];  \
             _Float16 y_ = (_Float16)tot_;                     /* fp16(matmul) */                 \
             if (so.bias) y_ = y_ + pf_bias;                   /* out + bias      (fp16 add) */   \
+            if constexpr (GP == 1) { if (so.act) y_ = (_Float16)silu_f((float)y_); }   /* act_fn(out): the gate a PRO_MUL launch multiplies */ \
             if (so.residual) y_ = pf_res + y_;                /* residual + out */               \
             if (SC1) __hip_atomic_store((unsigned short*)(so.y + (size_t)e_m * so.y_stride + rt_ * 16 + e_c),          \
                                         __builtin_bit_cast(unsigned short, y_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
@@ -1062,7 +1063,7 @@ inline hipError_t launch_one(const GemvKArgs& a, int total_wg, size_t lds, hipSt
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    const void* xw = PRO == PRO_SILU_MUL ? a.x2 : a.gamma;       // (PRO_RMSNORM_SUMS: gamma; the kernel reads x2 = the partial sums from the block)
+    const void* xw = PRO_X2<PRO> ? a.x2 : a.gamma;       // (PRO_RMSNORM_SUMS: gamma; the kernel reads x2 = the partial sums from the block)
     hipLaunchKernelGGL(kern, dim3(total_wg), dim3(NW * 64), lds, st, a.x, xw, a.qweight[0], a.meta[0], a.K,
                        a.M | ((a.x_stride == a.K ? 1 : 0) << 8) | (a.nseg << 16), a.rpt, a.n_rt[0], a.key[0], a.eps, a);
     return hipGetLastError();

@@ -39,7 +39,8 @@ struct StreamDevice {
 };
 
 enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_SILU_MUL = 2,
-       PRO_RMSNORM_SUMS = 3 /* internal (amq_gemv_grouped_sums_f16): RMSNorm whose sums of squares arrive as per-row-tile partials from the launch that produced x */ };
+       PRO_RMSNORM_SUMS = 3 /* internal (amq_gemv_grouped_sums_f16): RMSNorm whose sums of squares arrive as per-row-tile partials from the launch that produced x */,
+       PRO_MUL = 4 /* x <- x * x2: PRO_SILU_MUL over a gate that the launch which wrote it already activated (GemvSeg.act) */ };
 enum { FMT_HQQ = 0, FMT_GPTQ = 1, FMT_AWQ = 2 };
 constexpr int GEMV_MAX_SEG = 4;
 
@@ -56,6 +57,7 @@ struct GemvSeg {
     int wg_count;          // workgroups serving this segment          (filled by launch_gemv)
     int n_rt;              // row-tiles (N / 16)                        (filled by launch_gemv)
     int y_stride;          // elements between output rows
+    int act;               // 1: y = fp16(silu(xW^T + bias)) (gate_proj whose consumer multiplies only: PRO_MUL); not with residual or sums_out
 };
 
 struct GemvArgs {
@@ -63,8 +65,8 @@ struct GemvArgs {
     int nseg;
     int M, K;
     int x_stride;          // elements between x rows
-    const void* x;         // fp16 [M, x_stride]   (PRO_SILU_MUL: gate)
-    const void* x2;        // PRO_SILU_MUL: up
+    const void* x;         // fp16 [M, x_stride]   (PRO_SILU_MUL: gate; PRO_MUL: the activated gate)
+    const void* x2;        // PRO_SILU_MUL / PRO_MUL: up
     const void* gamma;     // PRO_RMSNORM: fp16 [K]
     float eps;
     int prologue;

@@ -21,7 +21,7 @@
 namespace {
 
 struct Segment { const void* qweight; const void* meta; const void* bias; const void* residual; void* y; int N, bits, mode, y_stride; };
-struct GemvOpts { int math, waves, depth, rpt, dot; };
+struct GemvOpts { int math, waves, depth, rpt, dot, act_mask; };
 
 using linear_fn = int (*)(int, int, const void*, const void*, const void*, const void*, void*, int, int, int, int, void*);
 using grouped_fn = int (*)(const Segment*, int, const void*, const void*, const void*, float, int, int, int, int, int, const GemvOpts*, void*);

@@ -38,8 +38,8 @@ class _Lin:
     def __init__(self, qn, mn, bits, mode, N, K, bias=None):
         self.qn, self.mn, self.bits, self.mode, self.N, self.K, self.bias = qn, mn, bits, mode, N, K, bias
 
-    def seg(self, y, residual=None):
-        return dict(qn=self.qn, mn=self.mn, bits=self.bits, mode=self.mode, N=self.N, y=y, residual=residual, bias=self.bias)
+    def seg(self, y, residual=None, act=False):
+        return dict(qn=self.qn, mn=self.mn, bits=self.bits, mode=self.mode, N=self.N, y=y, residual=residual, bias=self.bias, act=act)
 
     def nbytes(self):
         return self.qn.numel() * 4 + self.mn.numel() * 2 + (0 if self.bias is None else self.bias.numel() * 2)
@@ -199,6 +199,11 @@ class QuantLlama:
     DOWN_FUSED_ROWS = 1
     # rows up to which the two RMSNorms stay fused into the q/k/v and gate/up launches (beyond: one rmsnorm launch + the grouped GEMV without a prologue)
     NORM_FUSED_ROWS = 4
+    # one row (R == 1, plan.down == DOWN_FUSED): gate_proj's epilogue stores fp16(silu(gate)) and down_proj's prologue only multiplies by up -- SiLU once
+    # per element (16 threads of the workgroup that owns the row-tile) instead of once per element in EVERY workgroup of the down_proj launch
+    # (256 x 11008 on 7B), ahead of its first MFMA.  The same bits (tests/test_gpu_gate_act.py); profiles/silu_epilogue.txt.  False = A/B: SiLU*mul
+    # in down_proj's prologue.  Groups of 64 / 32 (``fine``) keep the old prologue: the library offers the new forms at groups of 128 only.
+    GATE_ACT = True
     NORM_SUMS = True            # (A/B switch of the partial-sum RMSNorm at 2 .. 8 rows: False = fused prologue up to NORM_FUSED_ROWS, one rmsnorm launch per norm beyond)
     # q/k/v + attention of a block as ONE launch (ops.gemv_qkv_attn; batch 1, short cache, hidden <= 8192): 4 launches per block
     # instead of 5.  Built, bit-identical (tests/test_gpu_qkv_attn.py) and SLOWER -- 15.7 us per fused launch against 9.2 + 5.1,
@@ -571,9 +576,12 @@ class QuantLlama:
                 ops.gemv_grouped_sums(self.att, o_proj, self.qd, sums_out=self.ss)
             else:
                 ops.gemv_grouped(self.att, o_proj, self.qd)
-            self._behind_norm(plan.norm, blk["ln2"], [blk["mlp.gate_proj"].seg(self.gate), blk["mlp.up_proj"].seg(self.up)])
+            # (one row only: with DOWN_FUSED_ROWS raised a step of 2 .. 8 rows keeps SiLU*mul in down_proj's prologue -- its gate/up launch may be the
+            #  partial-sum one, which takes no activated segment, and the activated gate at several rows is not measured)
+            gate_act = self.GATE_ACT and self.R == 1 and plan.down == DOWN_FUSED and not self.fine
+            self._behind_norm(plan.norm, blk["ln2"], [blk["mlp.gate_proj"].seg(self.gate, act=gate_act), blk["mlp.up_proj"].seg(self.up)])
             if plan.down == DOWN_FUSED:
-                ops.gemv_grouped(self.gate, down, self.I, prologue=ops.PRO_SILU_MUL, x2=self.up)
+                ops.gemv_grouped(self.gate, down, self.I, prologue=ops.PRO_SILU_MUL, x2=self.up, x_activated=gate_act)
             elif plan.down == DOWN_GEMV_SUMS:
                 ops.gemv_grouped_sums(ops.silu_mul(self.gate, self.up, out=self.gate), down, self.I, sums_out=self.ss)
             elif plan.down == DOWN_GEMV:

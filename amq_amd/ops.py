@@ -573,11 +573,13 @@ def gemv_max_rows(K, plain=False, norm=True):
     return int((out[4] if norm else out[5]) if plain else out[0])
 
 
-def gemv_grouped(x, segments, K, prologue=PRO_NONE, x2=None, gamma=None, eps=0.0, opts=None):
+def gemv_grouped(x, segments, K, prologue=PRO_NONE, x2=None, gamma=None, eps=0.0, opts=None, x_activated=False):
     """One launch for several linears sharing x.
 
-    segments: list of dicts {qn, mn, bits, mode, N, y, bias=None, residual=None}
-    (y / residual: fp16 [M, N] contiguous)."""
+    segments: list of dicts {qn, mn, bits, mode, N, y, bias=None, residual=None, act=False}
+    (y / residual: fp16 [M, N] contiguous).  ``act``: the segment stores fp16(silu(y)) -- a gate_proj whose down_proj launch then passes
+    ``x_activated=True`` with ``prologue=PRO_SILU_MUL``: x already holds fp16(silu(gate)), the prologue only multiplies (AMQ_PRO_MUL; the same bits
+    as SiLU*mul over the plain gate).  Groups of 128; ``act`` takes no residual."""
     xx = _prep_x(x, K)
     M = xx.shape[0]
     if not 1 <= len(segments) <= _lib.MAX_SEGMENTS:
@@ -599,12 +601,20 @@ def gemv_grouped(x, segments, K, prologue=PRO_NONE, x2=None, gamma=None, eps=0.0
                          _lib.ptr(s["y"]), s["N"], s["bits"], s["mode"], 0)
     if prologue == PRO_RMSNORM:
         _need(gamma, torch.float16, "gamma", K)
+    if x_activated and prologue != PRO_SILU_MUL:
+        raise ValueError("x_activated goes with prologue=PRO_SILU_MUL")
     if prologue == PRO_SILU_MUL:
         x2 = _prep_x(x2, K)
         if x2.shape[0] != M:
             raise ValueError("x2 rows != x rows")
+        if x_activated:
+            prologue = _lib.PRO_MUL
     if opts is None:
         opts = DEFAULT_GEMV_OPTS
+    act_mask = sum(1 << i for i, s in enumerate(segments) if s.get("act"))
+    if act_mask:                                # a per-call copy: the caller's (or the default) options stay as they are
+        o = opts
+        opts = GemvOpts(act_mask=act_mask) if o is None else GemvOpts(math=o.math, waves=o.waves, depth=o.depth, rpt=o.rpt, dot=o.dot, act_mask=act_mask)
     _lib.check(_lib.load().amq_gemv_grouped_f16(arr, len(segments), _lib.ptr(xx), _lib.ptr(x2), _lib.ptr(gamma),
                                                 ctypes.c_float(eps), prologue, M, K, group, 0,
                                                 ctypes.byref(opts) if opts is not None else None, _lib.current_stream()))
@@ -619,6 +629,8 @@ def gemv_grouped_sums(x, segments, K, gamma=None, eps=0.0, sums_in=None, sums_ou
     M = xx.shape[0]
     if not 1 <= len(segments) <= _lib.MAX_SEGMENTS:
         raise ValueError(f"1..{_lib.MAX_SEGMENTS} segments")
+    if any(s.get("act") for s in segments):
+        raise ValueError("an activated segment (act) is a gate, not a hidden state: the partial-sum launches take none (gemv_grouped)")
     arr = (Segment * len(segments))()
     for i, s in enumerate(segments):
         _check_shape(s["bits"], s["N"], K)

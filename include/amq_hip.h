@@ -46,6 +46,8 @@ extern "C" {
 #endif
 
 #define AMQ_VERSION 521            /* 0.5.2: the per-sequence step-state entry points (amq_*_seq_f16) added, nothing else changed (additions keep the number).
+                                    * LAYOUT CHANGE under the same number: amq_gemv_opts gained a trailing field, act_mask (and AMQ_PRO_MUL was added).  A caller that
+                                    * passes a non-NULL amq_gemv_opts must be rebuilt against this header -- the library reads six ints; NULL opts are unaffected.
                                     * amq_rope_table_freqs_f16 (rope_scaling) and amq_decode_tail_suppress_f16 added, nothing else changed.  0.5.1: the bfloat16 entry points
                                     * (amq_*_bf16) added.  0.5.0: amq_gemv_opts.math renumbered
                                     * (0 = the build's default), amq_default_gemv_math added; the decode-engine and fused q/k/v-attention entry points live in
@@ -68,6 +70,8 @@ extern "C" {
 #define AMQ_PRO_NONE     0
 #define AMQ_PRO_RMSNORM  1         /* x <- gamma * fp16(x * rsqrt(mean(x^2) + eps))   (LlamaRMSNorm; FT generalT5LayerNorm, layernorm.cu:25-51) */
 #define AMQ_PRO_SILU_MUL 2         /* x <- fp16(silu(x)) * x2                           (LlamaMLP act_fn(gate) * up) */
+#define AMQ_PRO_MUL      4         /* x <- x * x2: AMQ_PRO_SILU_MUL over an x that the launch which wrote it already activated (amq_gemv_opts.act_mask):
+                                    * the same bits, SiLU taken once per element instead of once per workgroup and element.  Groups of 128. */
 
 #define AMQ_MAX_SEGMENTS 4
 
@@ -94,12 +98,14 @@ int amq_default_gemv_math(void);   /* AMQ_MATH_EXACT or AMQ_MATH_GROUPSCALE */
 
 /* Per-call launch options of amq_gemv_grouped_f16 (host struct; NULL or all-zero = defaults).  There is no
  * process-wide option state in the library: what a call computes depends on its arguments only. */
-typedef struct amq_gemv_opts {
+typedef struct amq_gemv_opts {            /* (six ints since act_mask was added: see AMQ_VERSION) */
     int math;    /* AMQ_MATH_DEFAULT (0), _EXACT, _GROUPSCALE or _LINEAR */
     int waves;   /* A/B: waves per workgroup, 0 = auto, 4, 8 or 16 */
     int depth;   /* A/B: tile loads in flight per wave, 0 = auto, 2 or 4 */
     int rpt;     /* A/B: row-tiles walked by one workgroup, 0 = auto, 1..64 */
     int dot;     /* A/B: 1 = M == 1 runs the v_dot2c + wavefront-shuffle body instead of the MFMA body */
+    int act_mask; /* bit i: segment i stores y = fp16(silu(x W^T + bias)) -- gate_proj, for a consumer with AMQ_PRO_MUL.  Not with a residual on that
+                   * segment; groups of 128 */
 } amq_gemv_opts;
 
 /* kernel family of amq_gemm_route_f16 (AUTO = what every other GEMM entry point uses: chosen by shape) */
