@@ -26,6 +26,8 @@ ABI_VERSION = 521            # include/amq_hip.h AMQ_VERSION these bindings mirr
 LOOKUP_STATE_WORDS = 32     # include/amq_hip.h AMQ_LOOKUP_STATE_WORDS: int32 words of the lookup state block of amq_decode_tail_lookup_f16
 STEP_STATE_STRIDE = 272     # include/amq_hip.h AMQ_STEP_STATE_STRIDE: bytes between the step-state blocks of the amq_*_seq_f16 entry points
 GEMM_AUTO, GEMM_TILED, GEMM_SKINNY, GEMM_RING, GEMM_RING128, GEMM_WS, GEMM_DEQ = 0, 1, 2, 3, 4, 5, 6
+HQQ_ITERS = 20              # iterations of the quantizer's solver; its info block is int32 stop, int32 nonfinite, float mean_err[HQQ_ITERS]
+HQQ_INFO_BYTES = 88         # include/amq_hip.h AMQ_HQQ_INFO_BYTES
 
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
@@ -70,6 +72,9 @@ SIGNATURES = {
     "amq_repack_from_hqq": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "amq_repack_from_gptq": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "amq_repack_from_awq": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # dense fp16 -> Format A: HQQ's quantizer with its proximal solver (solve / stop / emit launches; info = {int32 stop, int32 nonfinite, float[20]})
+    "amq_hqq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
+    "amq_hqq_quantize_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amq_dequantize_f16": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "amq_dequantize_hqq_f16": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "amq_dequantize_bf16": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),

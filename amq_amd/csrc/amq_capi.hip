@@ -110,6 +110,34 @@ int amq_repack_from_awq(const void* qweight, const void* scales, const void* sca
     return check_hip(amq::launch_repack(amq::FMT_AWQ, 4, qweight, scales, scaled_zeros, N, K, qn, mn, (hipStream_t)stream, group), "repack_from_awq");
 }
 
+// the quantizer's shapes: the solve kernel is instantiated for four group sizes (other multiples of 128 are refused, not mis-run)
+static int check_hqq_quantize_shape(int bits, int N, int K, int group) {
+    if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
+    if (group != 32 && group != 64 && group != 128 && group != 256)
+        return fail(AMQ_ESHAPE, "the quantizer serves groups of 32, 64, 128 and 256 (got %d)", group);
+    if (N <= 0 || (N % 16) != 0) return fail(AMQ_ESHAPE, "need N %% 16 == 0 (got N=%d)", N);
+    if (K <= 0 || (K % group) != 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 and group %d dividing K (got K=%d)", group, K);
+    return AMQ_OK;
+}
+
+size_t amq_hqq_quantize_workspace_bytes(int N, int K, int group) {
+    if (check_hqq_quantize_shape(4, N, K, group) != AMQ_OK) return 0;
+    return amq::hqq_workspace_bytes(N, K, group);
+}
+
+int amq_hqq_quantize_f16(const void* W, int N, int K, int bits, int group, int round_zero, void* W_q, void* scale, void* zero,
+                         void* info, void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(AMQ_HQQ_INFO_BYTES == amq::HQQ_INFO_BYTES, "info block");
+    if (!W || !W_q || !scale || !zero || !info || !workspace) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)W & 7) != 0 || ((uintptr_t)workspace & 3) != 0 || ((uintptr_t)info & 3) != 0 || ((uintptr_t)W_q & 3) != 0)
+        return fail(AMQ_EINVAL, "W must be 8-byte aligned, W_q, info and workspace 4-byte aligned");
+    if (int rc = check_hqq_quantize_shape(bits, N, K, group)) return rc;
+    const size_t need = amq::hqq_workspace_bytes(N, K, group);
+    if (workspace_bytes < need) return fail(AMQ_EINVAL, "quantize workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    return check_hip(amq::launch_hqq_quantize(W, N, K, bits, group, round_zero != 0, W_q, scale, zero, info, workspace, (hipStream_t)stream),
+                     "hqq_quantize");
+}
+
 int amq_dequantize_f16(int bits, int mode, const void* qn, const void* mn, int N, int K, int group, void* W, void* stream) {
     if (int rc = check_shape(bits, N, K, group)) return rc;
     if (int rc = check_mode(mode)) return rc;

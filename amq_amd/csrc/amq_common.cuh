@@ -99,6 +99,40 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
             __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48)));
 }
 
+// the maximum twins (fmaxf: a NaN lane is dropped, not propagated)
+__device__ __forceinline__ float row16_max(float v) {
+    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false)));
+    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false)));
+    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false)));
+    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false)));
+    return v;
+}
+__device__ __forceinline__ float wave_max_dpp(float v) {
+    v = row16_max(v);
+    return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)),
+                       __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16))),
+                 fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)),
+                       __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48))));
+}
+// the two 32-lane halves of a wave reduced separately (two groups of 32 values in one wave): lanes 0 .. 31 get the lower half's result.  Same
+// tree as the whole-wave forms, one level short.
+__device__ __forceinline__ float half_sum_dpp(float v, int lane) {
+    v = row16_sum(v);
+    const float lo = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)) +
+                     __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
+    const float hi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)) +
+                     __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
+    return lane < 32 ? lo : hi;
+}
+__device__ __forceinline__ float half_max_dpp(float v, int lane) {
+    v = row16_max(v);
+    const float lo = fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)),
+                           __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16)));
+    const float hi = fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)),
+                           __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48)));
+    return lane < 32 ? lo : hi;
+}
+
 // ---- per-head q / k RMSNorm in front of the rotation (Qwen3: q_norm / k_norm over the 128 values of a head) ---------------------------
 // y = gamma * fp16(x * rstd), rstd = rsqrt(mean(x^2) + eps) in fp32: HF's Qwen3RMSNorm, the arithmetic of rmsnorm_kernel.  Every kernel that
 // rotates forms the statistic by ONE binary tree over the 64 pair sums p_i = x_i^2 + x_(i+64)^2, level by level over index bit 0, 1, .. 5 --

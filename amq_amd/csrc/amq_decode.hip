@@ -347,21 +347,7 @@ __device__ __forceinline__ void rope_cs(float theta, int pos, int i, _Float16* c
     *s16 = (_Float16)sn;
 }
 
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false)));
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false)));
-    return v;
-}
-// whole-wave reductions without LDS-crossbar shuffles: wave_sum_dpp (amq_common.cuh); the maximum likewise
-__device__ __forceinline__ float wave_max_dpp(float v) {
-    v = row16_max(v);
-    return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)),
-                       __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16))),
-                 fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)),
-                       __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48))));
-}
+// whole-wave reductions without LDS-crossbar shuffles: wave_sum_dpp and its maximum twin wave_max_dpp (amq_common.cuh)
 
 // One workgroup of 512 threads per (head, sequence) = 32 groups of 16 lanes; a group owns the cached keys / values
 // t = group + 32 i and a lane the 16-byte slice [8 lane, 8 lane + 8) of each 256-byte row, so every wave-load is four

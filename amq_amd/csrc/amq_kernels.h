@@ -307,4 +307,25 @@ hipError_t launch_gemm_bf16w(const void* x, const void* w, const void* bias, con
 hipError_t launch_dequantize_hqq(int bits, const void* wq, const void* scale, const void* zero,
                                  int N, int K, void* w_out, hipStream_t st, int group = 128);
 
+// fp16 W[N,K] -> HQQ Format A: Quantizer.quantize with its proximal solver (amq_quantize.hip).  The launch geometry is a function of the shape
+// only (what fixes the summation order of the tensor-wide error, hence the stop iteration): a wave PASS is 64 lanes' worth of groups (one group
+// of >= 64 values, two of 32), a wave takes T consecutive passes, a workgroup 4 waves, and there are at most 1024 workgroups.
+enum { HQQ_ITERS = 20, HQQ_WAVES = 4, HQQ_MAX_WGS = 1024, HQQ_INFO_BYTES = 8 + 4 * HQQ_ITERS };
+struct HqqGeom { size_t R, P; int T, wgs; };
+inline HqqGeom hqq_geometry(int N, int K, int group) {
+    HqqGeom g;
+    g.R = (size_t)N * K / group;
+    g.P = group == 32 ? g.R / 2 : g.R;
+    g.T = (int)((g.P + (size_t)HQQ_WAVES * HQQ_MAX_WGS - 1) / ((size_t)HQQ_WAVES * HQQ_MAX_WGS));
+    g.wgs = (int)((g.P + (size_t)HQQ_WAVES * g.T - 1) / ((size_t)HQQ_WAVES * g.T));
+    return g;
+}
+// workspace: fp32 s[R], Z[20][R], Epart[20][wgs], int32 nonfinite[wgs]
+inline size_t hqq_workspace_bytes(int N, int K, int group) {
+    const HqqGeom g = hqq_geometry(N, K, group);
+    return 4 * ((HQQ_ITERS + 1) * g.R + (HQQ_ITERS + 1) * (size_t)g.wgs);
+}
+hipError_t launch_hqq_quantize(const void* W, int N, int K, int bits, int group, int round_zero, void* W_q, void* scale, void* zero,
+                               void* info, void* workspace, hipStream_t st);
+
 }  // namespace amq

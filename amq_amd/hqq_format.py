@@ -6,8 +6,11 @@ This is input-format plumbing for the drop-in path (torch integer ops only):
   * ``pack_rows``   -- HQQ BitPack row-chunk packing (hqq/core/bitpack.py:24-110)
   * ``quantize_rtn``-- a plain round-to-nearest min/max quantizer emitting the
     same format (hqq/core/quantize.py:76-180 without the proximal optimizer),
-    used to make synthetic checkpoints of real shapes: there is no network, so
-    real AMQ/HQQ checkpoints are optional inputs.
+    used to make synthetic checkpoints of real shapes on any device (speed
+    work, where only the format and the value ranges matter).
+  * ``quantize_hqq``-- its sibling WITH the proximal optimizer, on the GPU
+    (ops.hqq_quantize: HIP kernels): what a model that is to be scored
+    (evaluate.eval_ppl / eval_loss) must be quantized with.
   * ``from_hqq_layer`` -- duck-typed adaptor for the reference's HQQLinear.
 """
 from dataclasses import dataclass
@@ -69,8 +72,9 @@ def pack_rows(wg: torch.Tensor, nbits: int) -> torch.Tensor:
 def quantize_rtn(W: torch.Tensor, nbits: int, group_size: int = GROUP, bias=None, name=None) -> HQQWeights:
     """Min/max round-to-nearest quantization in HQQ's format and conventions
     (axis=1 grouping, inverted scale stored, fractional fp16 zero:
-    quantize.py:106-155).  Not the HQQ optimizer -- accuracy is irrelevant to
-    the speed path, only the format and value ranges matter."""
+    quantize.py:106-155).  Not the HQQ optimizer: for synthetic layers of real
+    shapes, where only the format and the value ranges matter.  Weights whose
+    accuracy counts go through :func:`quantize_hqq`."""
     if group_size not in (64, 32) and (group_size < GROUP or group_size % GROUP):
         raise ValueError("group size must be 32, 64 or a multiple of 128")
     n, k = W.shape
@@ -85,6 +89,13 @@ def quantize_rtn(W: torch.Tensor, nbits: int, group_size: int = GROUP, bias=None
     q = (wg * scale + zero).round().clamp(0, maxv)
     return HQQWeights(pack_rows(q, nbits), (1.0 / scale).to(torch.float16), zero.to(torch.float16),
                       nbits, (n, k), group_size, bias, name)
+
+
+def quantize_hqq(W: torch.Tensor, nbits: int, group_size: int = GROUP, bias=None, name=None) -> HQQWeights:
+    """HQQ's quantizer with its proximal solver (quantize.py:76-180, optimize.py:201-255) on W's GPU: the device sibling of
+    :func:`quantize_rtn`, same conventions and return type.  Groups of 32, 64, 128 and 256."""
+    from . import ops
+    return ops.hqq_quantize(W, nbits, group_size, bias=bias, name=name)
 
 
 def random_hqq(n, k, nbits, seed=0, device="cpu", bias=False, group=GROUP) -> HQQWeights:

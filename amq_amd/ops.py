@@ -118,6 +118,74 @@ def repack_from_awq(qweight, scales, scaled_zeros, N, K, group=GROUP):
     return qn, mn
 
 
+QUANTIZE_GROUPS = (32, 64, 128, 256)      # group sizes the quantizer's solve kernel is built for
+
+
+class HQQQuantizeInfo:
+    """the info block of one ``hqq_quantize`` call, read back: ``stop`` (the iteration whose zero was kept, 0 .. 19), ``nonfinite`` and
+    ``mean_err`` (the tensor's mean |W - W_r| at the start of each of the 20 iterations, fp32)"""
+
+    def __init__(self, block):
+        self.stop = int(block[0].item())
+        self.nonfinite = int(block[1].item())
+        self.mean_err = block[2:].view(torch.float32).clone()
+
+    def __repr__(self):
+        return f"HQQQuantizeInfo(stop={self.stop}, nonfinite={self.nonfinite}, mean_err[0]={float(self.mean_err[0]):.6g})"
+
+
+def hqq_quantize_launch(W, nbits, group_size, round_zero, W_q, scale, zero, info, workspace):
+    """the bare entry point over caller-owned buffers (three launches on the current stream; no allocation, no read-back: capturable)"""
+    N, K = W.shape
+    _lib.check(_lib.load().amq_hqq_quantize_f16(_lib.ptr(W), N, K, int(nbits), int(group_size), int(bool(round_zero)), _lib.ptr(W_q), _lib.ptr(scale),
+                                                _lib.ptr(zero), _lib.ptr(info), _lib.ptr(workspace), workspace.numel() * workspace.element_size(),
+                                                _lib.current_stream()))
+
+
+def hqq_quantize_buffers(N, K, nbits, group_size, device):
+    """(W_q, scale, zero, info, workspace) of the right sizes for ``hqq_quantize_launch``"""
+    _check_shape(nbits, N, K)
+    if int(group_size) not in QUANTIZE_GROUPS or K % int(group_size):
+        raise ValueError(f"the quantizer serves groups of 32, 64, 128 and 256 that divide K={K} (got {group_size})")
+    R = N * K // int(group_size)
+    if nbits == 3:
+        W_q = torch.empty((R + 9) // 10, group_size, dtype=torch.int32, device=device)
+    else:
+        W_q = torch.empty(R * nbits // 8, group_size, dtype=torch.uint8, device=device)
+    scale = torch.empty(R, 1, dtype=torch.float16, device=device)
+    zero = torch.empty(R, 1, dtype=torch.float16, device=device)
+    info = torch.empty(_lib.HQQ_INFO_BYTES // 4, dtype=torch.int32, device=device)
+    need = int(_lib.load().amq_hqq_quantize_workspace_bytes(N, K, int(group_size)))
+    if need <= 0:
+        raise ValueError(f"the quantizer refuses N={N}, K={K}, group={group_size}")
+    return W_q, scale, zero, info, _quantize_scratch.get(device, need // 4)
+
+
+def hqq_quantize(W, nbits, group_size=GROUP, round_zero=None, return_info=False, bias=None, name=None):
+    """Dense W [N, K] on the GPU -> HQQWeights (Format A) on the same device: the reference's ``Quantizer.quantize`` with its proximal solver
+    (axis 1, lp_norm 0.7, beta 10, 20 iterations, early stop) in the fp32 arithmetic of its CPU path, as HIP kernels.  W is fp16 (bf16 / fp32 weights
+    are cast at this boundary, as the reference's ``.half()`` does before it quantizes).  ``round_zero`` defaults to ``nbits == 4`` (the reference's
+    hqq_base_quant_config).  Raises ValueError if W holds an inf or NaN.  One synchronising read of the 88-byte info block per call.
+    ``return_info``: also return the :class:`HQQQuantizeInfo`."""
+    from .hqq_format import HQQWeights
+    if not isinstance(W, torch.Tensor) or not W.is_cuda or W.dim() != 2:
+        raise ValueError("W: expected a 2-d tensor on the GPU")
+    if W.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"W: expected fp16 (or bf16 / fp32, cast to fp16), got {W.dtype}")
+    W = W.detach().to(torch.float16).contiguous()
+    N, K = W.shape
+    nbits = int(nbits)
+    if round_zero is None:
+        round_zero = nbits == 4
+    W_q, scale, zero, info, workspace = hqq_quantize_buffers(N, K, nbits, group_size, W.device)
+    hqq_quantize_launch(W, nbits, group_size, round_zero, W_q, scale, zero, info, workspace)
+    got = HQQQuantizeInfo(info.cpu())
+    if got.nonfinite:
+        raise ValueError(f"hqq_quantize: {'layer ' + name if name else 'W'} holds inf or NaN values")
+    h = HQQWeights(W_q, scale, zero, nbits, (N, K), int(group_size), bias, name)
+    return (h, got) if return_info else h
+
+
 def fma_mode_for(mn, bits):
     """AMQ_MODE_FMA1 for a native meta buffer whose scales allow the GEMV kernel's one-op unpack (|scale| <= amq_fma1_scale_bound(bits); the same
     weights bit for bit, ~5 % faster decode launches), else AMQ_MODE_FMA.  One device -> host read: call at load time, not per forward."""
@@ -264,6 +332,7 @@ class _ScratchPool:
 
 
 _SPLITK_WS = _ScratchPool(torch.float32)
+_quantize_scratch = _ScratchPool(torch.int32)      # hqq_quantize's workspace (s, the zero trace, the partial errors)
 
 
 def _splitk_workspace(device, nbytes):
@@ -1405,7 +1474,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-for _name in ("repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
+for _name in ("hqq_quantize", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup"):
     globals()[_name] = _on_tensor_device(globals()[_name])

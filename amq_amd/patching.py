@@ -274,6 +274,74 @@ def fuse_llama_layers(model):
     return n
 
 
+def _decoder_linears(model):
+    """[(block index, 'self_attn.q_proj' ..., parent module, attribute, nn.Linear)] of an HF llama / mistral / qwen2 / qwen3 causal LM: the seven
+    projections of every decoder layer (arch.LINEARS).  lm_head, the embeddings and the norms are not listed: they stay dense, as in the
+    reference's AutoHQQHFModel.quantize_model."""
+    from .arch import LINEARS
+    layers = getattr(getattr(model, "model", None), "layers", None)
+    if layers is None:
+        raise TypeError("expected an HF Llama-family causal LM (model.model.layers)")
+    out = []
+    for b, layer in enumerate(layers):
+        for full in LINEARS:
+            parent_name, attr = full.split(".")
+            parent = getattr(layer, parent_name, None)
+            lin = getattr(parent, attr, None)
+            if lin is None:
+                raise TypeError(f"layer {b}: no {full} (not a Llama-family decoder layer)")
+            if not isinstance(lin, torch.nn.Linear):
+                raise TypeError(f"layer {b}: {full} is a {type(lin).__name__}, not a dense nn.Linear (already quantized?)")
+            out.append((b, full, parent, attr, lin))
+    return out
+
+
+def _bits_of(bits, name, block):
+    """an int for every linear, or per-linear bit-widths {'self_attn.q_proj': [bits per block], ...} (an arch's 'linear' entry: arch.arch_bits)"""
+    if isinstance(bits, dict):
+        from .arch import arch_bits
+        return arch_bits(bits.get("linear", bits), name, block)
+    if int(bits) not in (2, 3, 4):
+        raise ValueError(f"bits must be 2, 3 or 4 (got {bits})")
+    return int(bits)
+
+
+@torch.no_grad()
+def quantize_model(model, bits, group_size=128, device=None):
+    """The reference's ``AutoHQQHFModel.quantize_model(model, BaseQuantizeConfig(nbits, group_size))`` (amq_quantization_proxy.py:36-37) on the GPU:
+    every decoder linear of a dense HF llama / mistral / qwen2 / qwen3 model is quantized with HQQ's solver (ops.hqq_quantize) and replaced by the
+    HIPQuantLinear holding it; lm_head, embeddings and norms stay dense and the whole model ends on ``device`` (default: the model's own GPU, else
+    cuda:0).  ``bits``: 2, 3 or 4, or per-linear bit-widths as an arch's ``'linear'`` dict holds them.  The model is then ready for
+    ``prepare_for_inference(backend='hip')`` (grouping and fusion), ``QuantLlama.from_hf`` and ``evaluate.eval_ppl`` / ``eval_loss``."""
+    todo = _decoder_linears(model)
+    if device is None:
+        p = next(model.parameters())
+        device = p.device if p.is_cuda else torch.device("cuda:0")
+    device = torch.device(device)
+    for b, full, parent, attr, lin in todo:
+        lin.name = attr
+        setattr(parent, attr, HIPQuantLinear.from_linear(lin, _bits_of(bits, full, b), group_size, device=device))
+    return model.to(device)
+
+
+@torch.no_grad()
+def quantize_bank(model, bits=(2, 3, 4), group_size=128, device=None):
+    """Every decoder linear of a dense HF model at every bit-width of ``bits``: {nbits: {(block, 'self_attn.q_proj'): HQQWeights}} on the GPU, the
+    model itself untouched -- what the reference's search holds as its per-bit model bank.  An arch picks one entry per (block, linear); the picks
+    are ``QuantLlama(hqq_layers=...)``'s input."""
+    if device is None:
+        p = next(model.parameters())
+        device = p.device if p.is_cuda else torch.device("cuda:0")
+    device = torch.device(device)
+    bank = {int(b): {} for b in bits}
+    for b, full, _, attr, lin in _decoder_linears(model):
+        w = lin.weight.detach().to(device)
+        bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
+        for nb in bank:
+            bank[nb][(b, full)] = ops.hqq_quantize(w, nb, group_size, bias=bias, name=attr)
+    return bank
+
+
 def _merge_zeros_with_lora(model):
     """``allow_merge=True`` (patching.py:210-216, patch_merge_zeros_with_lora :239-275): the reference folds the zero-point term
     of an HQQLinearLoRA into its LoRA factors -- only for layers quantized WITHOUT groups along axis 1 (":243-245: axis == 0 or a

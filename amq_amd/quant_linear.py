@@ -287,6 +287,19 @@ class HIPQuantLinear(nn.Module):
         return mod
 
     @classmethod
+    def from_linear(cls, linear, nbits, group_size=GROUP, device=None):
+        """From a dense ``nn.Linear`` (fp16 / bf16 / fp32 weights, cast to fp16): quantized on the GPU with HQQ's solver (ops.hqq_quantize), then
+        repacked -- the module ``from_hqq`` builds from the same layer quantized by the reference, scale range checked alike.  The result is an
+        fp16 module whatever the linear's dtype was."""
+        w = linear.weight.detach()
+        dev = torch.device(device) if device is not None else w.device
+        if dev.type != "cuda":
+            raise RuntimeError("HIPQuantLinear.from_linear needs a GPU device (the quantizer runs as HIP kernels)")
+        bias = None if getattr(linear, "bias", None) is None else linear.bias.detach().to(dev, torch.float16)
+        h = ops.hqq_quantize(w.to(dev), nbits, group_size, bias=bias, name=getattr(linear, "name", None))
+        return cls.from_hqq(h, device=dev)
+
+    @classmethod
     def from_gptq_buffers(cls, qweight, scales, zeros, bits, bias=None, name=None):
         """From GPTQLinear buffers (autogptq.py:55-75): qweight int32 [K/32*bits, N],
         scales / zeros fp32 [K/G, N].  Keeps the reference kernels' arithmetic

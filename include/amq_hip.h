@@ -142,6 +142,26 @@ int amq_repack_from_gptq(int bits, const void* qweight, const void* scales, cons
 int amq_repack_from_awq(const void* qweight, const void* scales, const void* scaled_zeros,
                         int N, int K, int group, void* qweight_native, void* meta_native, void* stream);
 
+/* ---- quantize: dense fp16 -> Format A -------------------------------------- */
+/* Quantizer.quantize with its proximal solver (hqq/core/quantize.py:76-180, optimize.py:96-108, 201-255: axis 1, lp_norm 0.7, beta 10,
+ * 20 iterations, early stop on the tensor's mean |W - W_r|) in the fp32 arithmetic of the reference's CPU path, as three launches on `stream`
+ * (solve: one pass over W, all 20 iterations in registers; stop: the tensor-wide decision; emit: codes packed as Format A).  No host read, no
+ * allocation, no atomics; the grid and every summation order depend on (N, K, group) only, so a layer quantizes to the same bits on every run.
+ *   W          fp16 [N, K], 8-byte aligned
+ *   W_q        Format A: uint8 [R * bits / 8, group] (4 / 2 bit) or int32 [ceil(R / 10), group] (3 bit), R = N * K / group
+ *   scale/zero fp16 [R]: the dequant multiplier 1 / s and the zero, as HQQLinear.meta holds them
+ *   info       AMQ_HQQ_INFO_BYTES: {int32 stop iteration, int32 nonfinite (!= 0: W held an inf or NaN, the outputs are meaningless),
+ *              float mean_err[20]: the tensor's mean |W - W_r| at the start of every iteration}
+ *   workspace  amq_hqq_quantize_workspace_bytes(N, K, group) = 4 * (21 * R + 21 * wgs) bytes, 4-byte aligned, where
+ *              P = R (R / 2 for group 32), T = ceil(P / 4096), wgs = ceil(P / (4 * T)); 0 for a shape the call refuses
+ *   round_zero 0 / 1: round the initial zero (the reference's default is bits == 4)
+ * Refused, in this order: a null pointer or a misaligned W (AMQ_EINVAL); bits not 2 / 3 / 4 (AMQ_EINVAL); group not 32 / 64 / 128 / 256,
+ * N % 16, K % 128 or K % group (AMQ_ESHAPE); workspace_bytes too small (AMQ_EINVAL). */
+#define AMQ_HQQ_INFO_BYTES 88
+size_t amq_hqq_quantize_workspace_bytes(int N, int K, int group);
+int amq_hqq_quantize_f16(const void* W, int N, int K, int bits, int group, int round_zero, void* W_q, void* scale, void* zero,
+                         void* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- dequantize ---------------------------------------------------------- */
 /* native -> W[N,K] fp16 (row-major, nn.Linear orientation) */
 int amq_dequantize_f16(int bits, int mode, const void* qweight_native, const void* meta_native,
