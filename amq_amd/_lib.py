@@ -28,6 +28,7 @@ STEP_STATE_STRIDE = 272     # include/amq_hip.h AMQ_STEP_STATE_STRIDE: bytes bet
 GEMM_AUTO, GEMM_TILED, GEMM_SKINNY, GEMM_RING, GEMM_RING128, GEMM_WS, GEMM_DEQ = 0, 1, 2, 3, 4, 5, 6
 HQQ_ITERS = 20              # iterations of the quantizer's solver; its info block is int32 stop, int32 nonfinite, float mean_err[HQQ_ITERS]
 HQQ_INFO_BYTES = 88         # include/amq_hip.h AMQ_HQQ_INFO_BYTES
+GPTQ_INFO_BYTES = 4         # include/amq_hip.h AMQ_GPTQ_INFO_BYTES
 
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
@@ -75,6 +76,9 @@ SIGNATURES = {
     # dense fp16 -> Format A: HQQ's quantizer with its proximal solver (solve / stop / emit launches; info = {int32 stop, int32 nonfinite, float[20]})
     "amq_hqq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
     "amq_hqq_quantize_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # dense fp16 + the inverse Hessian's Cholesky factor -> Format A: GPTQ's error-feedback solve (info = {int32 nonfinite})
+    "amq_gptq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
+    "amq_gptq_quantize_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amq_dequantize_f16": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "amq_dequantize_hqq_f16": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "amq_dequantize_bf16": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -138,6 +138,37 @@ int amq_hqq_quantize_f16(const void* W, int N, int K, int bits, int group, int r
                      "hqq_quantize");
 }
 
+// the GPTQ solve's one validator: its kernel is instantiated for the three group sizes that fit a 128-column block
+static int check_gptq_quantize_shape(int bits, int N, int K, int group) {
+    if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
+    if (group == 256)
+        return fail(AMQ_ESHAPE, "the GPTQ solve serves groups of 32, 64 and 128: a group of 256 spans two 128-column blocks and its parameters "
+                    "would need columns of the next block");
+    if (group != 32 && group != 64 && group != 128) return fail(AMQ_ESHAPE, "the GPTQ solve serves groups of 32, 64 and 128 (got %d)", group);
+    if (N <= 0 || (N % 16) != 0) return fail(AMQ_ESHAPE, "need N %% 16 == 0 (got N=%d)", N);
+    if (K <= 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 (got K=%d)", K);
+    return AMQ_OK;
+}
+
+size_t amq_gptq_quantize_workspace_bytes(int N, int K, int group) {
+    if (check_gptq_quantize_shape(4, N, K, group) != AMQ_OK) return 0;
+    return amq::gptq_workspace_bytes(N, K);
+}
+
+int amq_gptq_quantize_f16(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero, void* row_loss,
+                          void* info, void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(AMQ_GPTQ_INFO_BYTES == amq::GPTQ_INFO_BYTES, "info block");
+    if (!W || !U || !W_q || !scale || !zero || !row_loss || !info || !workspace) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)W & 15) != 0 || ((uintptr_t)U & 15) != 0 || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)W_q & 3) != 0 ||
+        ((uintptr_t)row_loss & 3) != 0 || ((uintptr_t)info & 3) != 0)
+        return fail(AMQ_EINVAL, "W, U and workspace must be 16-byte aligned, W_q, row_loss and info 4-byte aligned");
+    if (int rc = check_gptq_quantize_shape(bits, N, K, group)) return rc;
+    const size_t need = amq::gptq_workspace_bytes(N, K);
+    if (workspace_bytes < need) return fail(AMQ_EINVAL, "GPTQ workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    return check_hip(amq::launch_gptq_quantize(W, U, N, K, bits, group, W_q, scale, zero, row_loss, info, workspace, (hipStream_t)stream),
+                     "gptq_quantize");
+}
+
 int amq_dequantize_f16(int bits, int mode, const void* qn, const void* mn, int N, int K, int group, void* W, void* stream) {
     if (int rc = check_shape(bits, N, K, group)) return rc;
     if (int rc = check_mode(mode)) return rc;

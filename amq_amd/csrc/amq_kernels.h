@@ -328,4 +328,14 @@ inline size_t hqq_workspace_bytes(int N, int K, int group) {
 hipError_t launch_hqq_quantize(const void* W, int N, int K, int bits, int group, int round_zero, void* W_q, void* scale, void* zero,
                                void* info, void* workspace, hipStream_t st);
 
+// fp16 W[N,K] + fp32 U[K,K] -> HQQ Format A by GPTQ's error-feedback solve (amq_gptq.hip).  16 lanes own a row and walk K in blocks of 128 columns
+// (8 per lane); a workgroup is 4 waves = 16 rows, which share U's rows through LDS tiles of 32 rows.  workspace: fp32 E[N][K] (the columns'
+// errors), int32 nonfinite[N / 4] (one per wave), uint8 codes[N][K].
+enum { GPTQ_BLOCK = 128, GPTQ_LANES = 16, GPTQ_WAVES = 4, GPTQ_TILE = 32, GPTQ_INFO_BYTES = 4 };
+inline int gptq_workgroups(int N) { return N / (GPTQ_WAVES * 64 / GPTQ_LANES); }
+inline int gptq_flags(int N) { return N / (64 / GPTQ_LANES); }
+inline size_t gptq_workspace_bytes(int N, int K) { return 5 * (size_t)N * K + 4 * (size_t)gptq_flags(N); }
+hipError_t launch_gptq_quantize(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero,
+                                void* row_loss, void* info, void* workspace, hipStream_t st);
+
 }  // namespace amq

@@ -186,6 +186,132 @@ def hqq_quantize(W, nbits, group_size=GROUP, round_zero=None, return_info=False,
     return (h, got) if return_info else h
 
 
+GPTQ_GROUPS = (32, 64, 128)      # group sizes the GPTQ solve kernel is built for: those that fit its 128-column block
+
+
+class GPTQHessian:
+    """The running Hessian of one linear's inputs, the reference's form (amq/quantization/gptq.py:199-204) as torch fp32 ops on ``device``:
+    ``H <- H * n / (n + b); n += b; H += (sqrt(2 / n) x)^T (sqrt(2 / n) x)`` per batch of b sequences, x the batch's rows [b * seqlen, K]."""
+
+    def __init__(self, K, device):
+        self.H = torch.zeros(int(K), int(K), dtype=torch.float32, device=device)
+        self.nsamples = 0
+
+    def add_batch(self, x):
+        if x.dim() == 2:
+            x = x.unsqueeze(0)
+        b = x.shape[0]
+        x = x.reshape(-1, x.shape[-1]).t()
+        self.H *= self.nsamples / (self.nsamples + b)
+        self.nsamples += b
+        x = (2.0 / self.nsamples) ** 0.5 * x.float()
+        self.H += x.matmul(x.t())
+
+
+def gptq_hinv(H, percdamp=0.01, name=None, return_where=False):
+    """(U, dead): the upper Cholesky factor of the damped inverse of H (gptq.py:224-253: dead columns get a unit diagonal, the diagonal is damped
+    by ``percdamp`` of its mean, then cholesky, cholesky_inverse, cholesky(upper)) and the bool mask of the dead columns.  H is not modified.
+    ``torch.linalg`` runs on H's device; a build that lacks the factorisation there runs it on the host and brings U back
+    (``return_where``: also return ``'device'`` or ``'host'``).  A failed factorisation raises ValueError naming the layer."""
+    H = H.detach().to(torch.float32).clone()
+    dead = torch.diag(H) == 0
+    idx = torch.arange(H.shape[0], device=H.device)
+    H[idx, idx] = torch.where(dead, torch.ones_like(H[idx, idx]), H[idx, idx])
+    H[idx, idx] += percdamp * torch.mean(torch.diag(H))
+
+    def factor(A):
+        A = torch.linalg.cholesky(A)
+        A = torch.cholesky_inverse(A)
+        return torch.linalg.cholesky(A, upper=True)
+
+    where = "device" if H.is_cuda else "host"
+    try:
+        try:
+            U = factor(H)
+        except RuntimeError as e:
+            if isinstance(e, torch.linalg.LinAlgError) or not H.is_cuda:
+                raise
+            where = "host"                      # (a build without the device solver library)
+            U = factor(H.cpu()).to(H.device)
+    except torch.linalg.LinAlgError as e:
+        raise ValueError(f"gptq_hinv: the damped Hessian of {'layer ' + name if name else 'the layer'} is not positive definite ({e})") from None
+    U = U.contiguous()
+    return (U, dead, where) if return_where else (U, dead)
+
+
+class GPTQQuantizeInfo:
+    """what one ``gptq_quantize`` call reports: ``nonfinite`` (the info block), ``row_loss`` (fp32 [N], on the device) and ``loss``, its fp64 sum
+    (the reference's printed ``error``)"""
+
+    def __init__(self, nonfinite, row_loss):
+        self.nonfinite = int(nonfinite)
+        self.row_loss = row_loss
+        self.loss = float(row_loss.double().sum().item())
+
+    def __repr__(self):
+        return f"GPTQQuantizeInfo(nonfinite={self.nonfinite}, loss={self.loss:.6g})"
+
+
+def gptq_quantize_launch(W, U, nbits, group_size, W_q, scale, zero, row_loss, info, workspace):
+    """the bare entry point over caller-owned buffers (three launches on the current stream; no allocation, no read-back: capturable)"""
+    N, K = W.shape
+    _lib.check(_lib.load().amq_gptq_quantize_f16(_lib.ptr(W), _lib.ptr(U), N, K, int(nbits), int(group_size), _lib.ptr(W_q), _lib.ptr(scale),
+                                                 _lib.ptr(zero), _lib.ptr(row_loss), _lib.ptr(info), _lib.ptr(workspace),
+                                                 workspace.numel() * workspace.element_size(), _lib.current_stream()))
+
+
+def gptq_quantize_buffers(N, K, nbits, group_size, device):
+    """(W_q, scale, zero, row_loss, info, workspace) of the right sizes for ``gptq_quantize_launch``"""
+    _check_shape(nbits, N, K)
+    if int(group_size) == 256:
+        raise ValueError("the GPTQ solve serves groups of 32, 64 and 128: a group of 256 would span two of its 128-column blocks")
+    if int(group_size) not in GPTQ_GROUPS:
+        raise ValueError(f"the GPTQ solve serves groups of 32, 64 and 128 (got {group_size})")
+    group_size = int(group_size)
+    R = N * K // group_size
+    if nbits == 3:
+        W_q = torch.empty((R + 9) // 10, group_size, dtype=torch.int32, device=device)
+    else:
+        W_q = torch.empty(R * nbits // 8, group_size, dtype=torch.uint8, device=device)
+    scale = torch.empty(R, 1, dtype=torch.float16, device=device)
+    zero = torch.empty(R, 1, dtype=torch.float16, device=device)
+    row_loss = torch.empty(N, dtype=torch.float32, device=device)
+    info = torch.empty(_lib.GPTQ_INFO_BYTES // 4, dtype=torch.int32, device=device)
+    need = int(_lib.load().amq_gptq_quantize_workspace_bytes(N, K, group_size))
+    if need <= 0:
+        raise ValueError(f"the GPTQ solve refuses N={N}, K={K}, group={group_size}")
+    return W_q, scale, zero, row_loss, info, _gptq_scratch.get(device, (need + 3) // 4)
+
+
+def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, name=None):
+    """Dense W [N, K] and U [K, K] (``gptq_hinv``: fp32, the upper Cholesky factor of the damped inverse Hessian) on the GPU -> HQQWeights (Format
+    A) on the same device by GPTQ's error-feedback solve (gptq.py:206-311: asymmetric, grouped, blocks of 128 columns, no act-order, no static
+    groups) as HIP kernels, in the arithmetic include/amq_hip.h states: the scale is rounded to fp16 before it is used and the error feedback sees
+    the weight the packed layer will dequantize to.  W is fp16 (bf16 / fp32 weights are cast at this boundary); the caller has zeroed its dead
+    columns.  Raises ValueError if a weight, an error or U's diagonal was not finite (or the diagonal not positive).  One synchronising read of the
+    4-byte info block per call.  ``return_info``: also return the :class:`GPTQQuantizeInfo`."""
+    from .hqq_format import HQQWeights
+    if not isinstance(W, torch.Tensor) or not W.is_cuda or W.dim() != 2:
+        raise ValueError("W: expected a 2-d tensor on the GPU")
+    if W.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"W: expected fp16 (or bf16 / fp32, cast to fp16), got {W.dtype}")
+    W = W.detach().to(torch.float16).contiguous()
+    N, K = W.shape
+    if not isinstance(U, torch.Tensor) or U.device != W.device:
+        raise ValueError("U: expected a tensor on W's GPU")
+    U = U.detach().contiguous()                # (cholesky(upper=True) hands out a transposed view)
+    _need(U, torch.float32, "U", K * K)
+    nbits = int(nbits)
+    W_q, scale, zero, row_loss, info, workspace = gptq_quantize_buffers(N, K, nbits, group_size, W.device)
+    gptq_quantize_launch(W, U, nbits, group_size, W_q, scale, zero, row_loss, info, workspace)
+    got = GPTQQuantizeInfo(info.cpu()[0].item(), row_loss)
+    if got.nonfinite:
+        raise ValueError(f"gptq_quantize: {'layer ' + name if name else 'W'}: a weight, an error or U's diagonal was not finite "
+                         "(or the diagonal not positive)")
+    h = HQQWeights(W_q, scale, zero, nbits, (N, K), int(group_size), bias, name)
+    return (h, got) if return_info else h
+
+
 def fma_mode_for(mn, bits):
     """AMQ_MODE_FMA1 for a native meta buffer whose scales allow the GEMV kernel's one-op unpack (|scale| <= amq_fma1_scale_bound(bits); the same
     weights bit for bit, ~5 % faster decode launches), else AMQ_MODE_FMA.  One device -> host read: call at load time, not per forward."""
@@ -333,6 +459,7 @@ class _ScratchPool:
 
 _SPLITK_WS = _ScratchPool(torch.float32)
 _quantize_scratch = _ScratchPool(torch.int32)      # hqq_quantize's workspace (s, the zero trace, the partial errors)
+_gptq_scratch = _ScratchPool(torch.int32)          # gptq_quantize's workspace (the columns' errors, the flags, the byte codes)
 
 
 def _splitk_workspace(device, nbytes):
@@ -1474,7 +1601,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-for _name in ("hqq_quantize", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
+for _name in ("hqq_quantize", "gptq_quantize", "gptq_quantize_launch", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup"):
     globals()[_name] = _on_tensor_device(globals()[_name])

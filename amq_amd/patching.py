@@ -342,6 +342,106 @@ def quantize_bank(model, bits=(2, 3, 4), group_size=128, device=None):
     return bank
 
 
+TRUE_SEQUENTIAL = (("self_attn.k_proj", "self_attn.v_proj", "self_attn.q_proj"), ("self_attn.o_proj",), ("mlp.up_proj", "mlp.gate_proj"),
+                   ("mlp.down_proj",))      # gptq.py:100-105
+
+
+class _BlockInputCaught(Exception):
+    pass
+
+
+def _proxy_loss(W, W_hat, H):
+    """tr(dW H dW^T) in fp32 torch ops on the device"""
+    d = W.float() - W_hat.float()
+    return float(((d @ H) * d).sum().item())
+
+
+@torch.no_grad()
+def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=False, device=None):
+    """The reference's ``GPTQ.run`` (amq/quantization/gptq.py:25-161: asymmetric, grouped, act_order=False, static_groups=False) for a dense HF
+    llama / mistral / qwen2 / qwen3 model, ending in packed layers: block by block, one Hessian per linear is accumulated over ``samples`` with
+    forward hooks (ops.GPTQHessian), every linear is quantized at ``_bits_of(bits, name, block)`` by the error-feedback solve (ops.gptq_hinv,
+    ops.gptq_quantize: HIP kernels) and its dense weights are overwritten by what the packed layer dequantizes to, so that the block's second
+    forward hands the next block the quantized model's activations; then the block's linears become HIPQuantLinear modules.  ``samples``: token-id
+    tensors [1, seqlen] of one length, brought by the caller.  ``true_sequential``: the reference's four subsets per block (q/k/v, o, gate/up,
+    down), each calibrated on the outputs of the quantized ones before it.  The whole model works on ``device`` (default: the model's own GPU,
+    else cuda:0).  Returns (model, report) with ``report[(block, name)] = {"loss": tr(dW H dW^T), "rtn_loss": the same for
+    hqq_format.quantize_rtn at the same bits and group, "solver_loss": the solve's own sum of row losses (the reference's printed error), "dead":
+    the number of dead columns, "bits"}``.  The model is then ready for ``prepare_for_inference(backend='hip')``."""
+    from .arch import LINEARS
+    from .hqq_format import quantize_rtn
+    _decoder_linears(model)                                  # TypeError for a model that is not dense any more
+    samples = list(samples)
+    if not samples or any(s.dim() != 2 or s.shape != samples[0].shape for s in samples):
+        raise ValueError("samples: expected token-id tensors [1, seqlen] of one length")
+    if device is None:
+        p = next(model.parameters())
+        device = p.device if p.is_cuda else torch.device("cuda:0")
+    device = torch.device(device)
+    model.to(device)
+    layers = model.model.layers
+    use_cache = getattr(model.config, "use_cache", None)
+    model.config.use_cache = False
+    inps, kwargs = [], {}
+
+    def catch(_, args, kw):
+        inps.append((args[0] if args else kw["hidden_states"]).detach())
+        kwargs.update({k: v for k, v in kw.items() if k != "hidden_states"})
+        raise _BlockInputCaught
+
+    handle = layers[0].register_forward_pre_hook(catch, with_kwargs=True)
+    try:
+        for s in samples:
+            try:
+                model(s.to(device))
+            except _BlockInputCaught:
+                pass
+    finally:
+        handle.remove()
+
+    def run(layer, x):
+        out = layer(x, **kwargs)
+        return out[0] if isinstance(out, (tuple, list)) else out
+
+    report = {}
+    for b, layer in enumerate(layers):
+        full = {name: getattr(getattr(layer, name.split(".")[0]), name.split(".")[1]) for name in LINEARS}
+        packed = {}
+        for names in (TRUE_SEQUENTIAL if true_sequential else (tuple(LINEARS),)):
+            hess = {name: ops.GPTQHessian(full[name].in_features, device) for name in names}
+            handles = [full[name].register_forward_hook(lambda _, inp, out, acc=hess[name]: acc.add_batch(inp[0].detach())) for name in names]
+            try:
+                for x in inps:
+                    run(layer, x)
+            finally:
+                for h in handles:
+                    h.remove()
+            for name in names:
+                lin, nb = full[name], _bits_of(bits, name, b)
+                attr = name.split(".")[1]
+                H = hess[name].H
+                U, dead = ops.gptq_hinv(H, percdamp, name=f"{b}.{name}")
+                W = lin.weight.detach().to(torch.float16).clone()
+                W[:, dead] = 0
+                bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
+                h, info = ops.gptq_quantize(W, U, nb, group_size, return_info=True, bias=bias, name=attr)
+                N, K = W.shape
+                W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, N, K, group_size)
+                r = quantize_rtn(W, nb, group_size)
+                W_rtn = ops.dequantize_hqq(r.W_q.contiguous(), r.scale.reshape(-1).contiguous(), r.zero.reshape(-1).contiguous(), nb, N, K, group_size)
+                report[(b, name)] = {"loss": _proxy_loss(W, W_hat, H), "rtn_loss": _proxy_loss(W, W_rtn, H), "solver_loss": info.loss,
+                                     "dead": int(dead.sum().item()), "bits": nb}
+                lin.weight.data = W_hat.to(lin.weight.dtype)
+                packed[name] = h
+        inps = [run(layer, x).detach() for x in inps]
+        for name, h in packed.items():
+            parent_name, attr = name.split(".")
+            setattr(getattr(layer, parent_name), attr, HIPQuantLinear.from_hqq(h, device=device))
+    if use_cache is not None:
+        model.config.use_cache = use_cache
+    return model, report
+
+
 def _merge_zeros_with_lora(model):
     """``allow_merge=True`` (patching.py:210-216, patch_merge_zeros_with_lora :239-275): the reference folds the zero-point term
     of an HQQLinearLoRA into its LoRA factors -- only for layers quantized WITHOUT groups along axis 1 (":243-245: axis == 0 or a

@@ -162,6 +162,27 @@ size_t amq_hqq_quantize_workspace_bytes(int N, int K, int group);
 int amq_hqq_quantize_f16(const void* W, int N, int K, int bits, int group, int round_zero, void* W_q, void* scale, void* zero,
                          void* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* GPTQ's error-feedback solve (asymmetric, grouped, no act-order, no static groups; blocks of 128 columns) to the same Format A, as three launches on
+ * `stream` (solve, nonfinite flag, pack).  All fp32, every operation its own rounding, IEEE division, round-half-even.  Per row, columns ascending:
+ * at the start of each 128-column block every group in it takes xmin = min(min(x), 0), xmax = max(max(x), 0) of the row's CURRENT values (-1 / +1 if
+ * both are 0), s = (xmax - xmin) / maxq, s16 = max(fp16(s), 2^-24), z = rint(-xmin / s16); column i: q = clamp(rint(w / s16) + z, 0, maxq),
+ * w^ = fp16((q - z) * s16) -- the weight amq_dequantize_hqq_f16 and the matmul kernels produce --, e = (w - w^) / U[i,i],
+ * loss += ((w - w^)^2 / U[i,i]^2) / 2; then w_j -= e * U[i,j] (one multiply, one subtract) for every j > i, each element in ascending i.
+ * No host read, no allocation, no atomics; rows are independent.
+ *   W          fp16 [N, K], 16-byte aligned; the caller has zeroed the columns whose Hessian diagonal is 0
+ *   U          fp32 [K, K], 16-byte aligned: the upper Cholesky factor of the damped inverse Hessian (only its upper triangle is used)
+ *   W_q        Format A as above; scale = s16, zero = z (an integer), fp16 [R]
+ *   row_loss   fp32 [N]
+ *   info       AMQ_GPTQ_INFO_BYTES: {int32 nonfinite (!= 0: some w, e or U[i,i] was not finite, or U[i,i] <= 0: the outputs are meaningless)}
+ *   workspace  amq_gptq_quantize_workspace_bytes(N, K, group) = 5 * N * K + N bytes (fp32 errors [N, K], int32 flags [N / 4], byte codes [N, K]),
+ *              16-byte aligned; 0 for a shape the call refuses
+ * Refused, in this order: a null or misaligned pointer (AMQ_EINVAL); bits not 2 / 3 / 4 (AMQ_EINVAL); group not 32 / 64 / 128 (256 spans two
+ * blocks), N % 16, K % 128 (AMQ_ESHAPE); workspace_bytes too small (AMQ_EINVAL). */
+#define AMQ_GPTQ_INFO_BYTES 4
+size_t amq_gptq_quantize_workspace_bytes(int N, int K, int group);
+int amq_gptq_quantize_f16(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero, void* row_loss,
+                          void* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- dequantize ---------------------------------------------------------- */
 /* native -> W[N,K] fp16 (row-major, nn.Linear orientation) */
 int amq_dequantize_f16(int bits, int mode, const void* qweight_native, const void* meta_native,
