@@ -29,6 +29,8 @@ GEMM_AUTO, GEMM_TILED, GEMM_SKINNY, GEMM_RING, GEMM_RING128, GEMM_WS, GEMM_DEQ =
 HQQ_ITERS = 20              # iterations of the quantizer's solver; its info block is int32 stop, int32 nonfinite, float mean_err[HQQ_ITERS]
 HQQ_INFO_BYTES = 88         # include/amq_hip.h AMQ_HQQ_INFO_BYTES
 GPTQ_INFO_BYTES = 4         # include/amq_hip.h AMQ_GPTQ_INFO_BYTES
+AWQ_INFO_BYTES = 4          # include/amq_hip.h AMQ_AWQ_INFO_BYTES
+AWQ_STEPS = 10              # shrink steps of the AWQ clip search (err is [N, K / group, AWQ_STEPS])
 
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
@@ -79,6 +81,11 @@ SIGNATURES = {
     # dense fp16 + the inverse Hessian's Cholesky factor -> Format A: GPTQ's error-feedback solve (info = {int32 nonfinite})
     "amq_gptq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
     "amq_gptq_quantize_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # AWQ: round to nearest under a column scale / clip bounds -> Format A and / or the dense fake-quantized matrix; the clip search (info = {int32 nonfinite})
+    "amq_awq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
+    "amq_awq_quantize_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amq_awq_clip_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "amq_awq_clip_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amq_dequantize_f16": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "amq_dequantize_hqq_f16": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "amq_dequantize_bf16": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -169,6 +169,57 @@ int amq_gptq_quantize_f16(const void* W, const void* U, int N, int K, int bits, 
                      "gptq_quantize");
 }
 
+// AWQ's one validator (quantize and clip; T = 1 for the call without tokens): the kernels are instantiated for the group sizes of the GPTQ solve
+static int check_awq_shape(int bits, int N, int K, int T, int group) {
+    if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
+    if (group != 32 && group != 64 && group != 128) return fail(AMQ_ESHAPE, "the AWQ kernels serve groups of 32, 64 and 128 (got %d)", group);
+    if (N <= 0 || (N % 16) != 0) return fail(AMQ_ESHAPE, "need N %% 16 == 0 (got N=%d)", N);
+    if (K <= 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 (got K=%d)", K);
+    if (T < 1) return fail(AMQ_ESHAPE, "need at least one row of activations (got T=%d)", T);
+    return AMQ_OK;
+}
+
+size_t amq_awq_quantize_workspace_bytes(int N, int K, int group) {
+    if (check_awq_shape(4, N, K, 1, group) != AMQ_OK) return 0;
+    return amq::awq_quantize_workspace_bytes(N, K);
+}
+
+int amq_awq_quantize_f16(const void* W, const void* col_scale, const void* hi, const void* lo, int N, int K, int bits, int group, void* W_q,
+                         void* scale, void* zero, void* dense, void* info, void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(AMQ_AWQ_INFO_BYTES == amq::AWQ_INFO_BYTES, "info block");
+    if (!W || !info || !workspace) return fail(AMQ_EINVAL, "null pointer");
+    if ((hi == nullptr) != (lo == nullptr)) return fail(AMQ_EINVAL, "null pointer: hi and lo come together or not at all");
+    if ((W_q == nullptr) != (scale == nullptr) || (W_q == nullptr) != (zero == nullptr))
+        return fail(AMQ_EINVAL, "null pointer: W_q, scale and zero come together or not at all");
+    if (!W_q && !dense) return fail(AMQ_EINVAL, "null pointer: neither Format A nor the dense matrix is asked for");
+    if (((uintptr_t)W & 15) != 0 || ((uintptr_t)dense & 15) != 0 || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)col_scale & 3) != 0 ||
+        ((uintptr_t)W_q & 3) != 0 || ((uintptr_t)info & 3) != 0 || ((uintptr_t)hi & 1) != 0 || ((uintptr_t)lo & 1) != 0 ||
+        ((uintptr_t)scale & 1) != 0 || ((uintptr_t)zero & 1) != 0)
+        return fail(AMQ_EINVAL, "W, dense and workspace must be 16-byte aligned, col_scale, W_q and info 4-byte, hi, lo, scale and zero 2-byte");
+    if (int rc = check_awq_shape(bits, N, K, 1, group)) return rc;
+    const size_t need = amq::awq_quantize_workspace_bytes(N, K);
+    if (workspace_bytes < need) return fail(AMQ_EINVAL, "AWQ quantize workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    return check_hip(amq::launch_awq_quantize(W, col_scale, hi, lo, N, K, bits, group, W_q, scale, zero, dense, info, workspace,
+                                              (hipStream_t)stream), "awq_quantize");
+}
+
+size_t amq_awq_clip_workspace_bytes(int N, int K, int T, int group) {
+    if (check_awq_shape(4, N, K, T, group) != AMQ_OK) return 0;
+    return amq::awq_clip_workspace_bytes(N, K, group);
+}
+
+int amq_awq_clip_f16(const void* W, const void* X, int N, int K, int T, int bits, int group, void* hi, void* lo, void* best, void* err,
+                     void* info, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!W || !X || !hi || !lo || !best || !err || !info || !workspace) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)W & 15) != 0 || ((uintptr_t)X & 15) != 0 || ((uintptr_t)hi & 1) != 0 || ((uintptr_t)lo & 1) != 0 || ((uintptr_t)best & 3) != 0 ||
+        ((uintptr_t)err & 3) != 0 || ((uintptr_t)info & 3) != 0 || ((uintptr_t)workspace & 3) != 0)
+        return fail(AMQ_EINVAL, "W and X must be 16-byte aligned, best, err, info and workspace 4-byte, hi and lo 2-byte");
+    if (int rc = check_awq_shape(bits, N, K, T, group)) return rc;
+    const size_t need = amq::awq_clip_workspace_bytes(N, K, group);
+    if (workspace_bytes < need) return fail(AMQ_EINVAL, "AWQ clip workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    return check_hip(amq::launch_awq_clip(W, X, N, K, T, bits, group, hi, lo, best, err, info, workspace, (hipStream_t)stream), "awq_clip");
+}
+
 int amq_dequantize_f16(int bits, int mode, const void* qn, const void* mn, int N, int K, int group, void* W, void* stream) {
     if (int rc = check_shape(bits, N, K, group)) return rc;
     if (int rc = check_mode(mode)) return rc;

@@ -216,13 +216,18 @@ hipError_t launch_gptq_quantize(const void* W, const void* U, int N, int K, int 
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(gptq_flag_kernel, dim3(1), dim3(256), 0, st, NF, flags, (int*)info);
     if (hipError_t e = hipGetLastError()) return e;
-    const size_t R = (size_t)N * K / group;
+    return launch_pack_codes(Q, (size_t)N * K / group, group, bits, W_q, st);
+}
+
+hipError_t launch_pack_codes(const void* codes, size_t R, int group, int bits, void* W_q, hipStream_t st) {
+    const uint8_t* Q = (const uint8_t*)codes;
     const size_t words = (bits == 3 ? (R + 9) / 10 : R * bits / 8) * (size_t)group;
     const unsigned blocks = (unsigned)((words + 255) / 256);
 #define AMQ_PACK(B_) hipLaunchKernelGGL((gptq_pack_kernel<B_>), dim3(blocks), dim3(256), 0, st, Q, R, group, W_q)
     if (bits == 4) AMQ_PACK(4);
     else if (bits == 3) AMQ_PACK(3);
-    else AMQ_PACK(2);
+    else if (bits == 2) AMQ_PACK(2);
+    else return hipErrorInvalidValue;
 #undef AMQ_PACK
     return hipGetLastError();
 }

@@ -337,5 +337,20 @@ inline int gptq_flags(int N) { return N / (64 / GPTQ_LANES); }
 inline size_t gptq_workspace_bytes(int N, int K) { return 5 * (size_t)N * K + 4 * (size_t)gptq_flags(N); }
 hipError_t launch_gptq_quantize(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero,
                                 void* row_loss, void* info, void* workspace, hipStream_t st);
+// byte codes [R, group] -> Format A (hqq/core/bitpack.py row chunks), one thread per packed word: the pack launch of the GPTQ solve, shared
+hipError_t launch_pack_codes(const void* codes, size_t R, int group, int bits, void* W_q, hipStream_t st);
+
+// AWQ (amq_awq.hip).  quantize: 8 columns per thread, 256 threads per workgroup, round-to-nearest per group to byte codes, then the shared pack
+// launch; workspace: int32 nonfinite[N * K / 512] (one per wave), uint8 codes[N][K].  clip: one wave per (8 rows, one group): the rows' 10 clip
+// steps are 80 columns = 5 B tiles of v_mfma_f32_16x16x4_f32, X's rows go through in tiles of 16; workspace: int32 nonfinite[(N / 8) * (K / group)].
+enum { AWQ_STEPS = 10, AWQ_ROWS = 8, AWQ_TILES = AWQ_STEPS * AWQ_ROWS / 16, AWQ_INFO_BYTES = 4 };
+inline size_t awq_quantize_flags(int N, int K) { return (size_t)N * K / 512; }
+inline size_t awq_quantize_workspace_bytes(int N, int K) { return (size_t)N * K + 4 * awq_quantize_flags(N, K); }
+inline size_t awq_clip_flags(int N, int K, int group) { return (size_t)(N / AWQ_ROWS) * (K / group); }
+inline size_t awq_clip_workspace_bytes(int N, int K, int group) { return 4 * awq_clip_flags(N, K, group); }
+hipError_t launch_awq_quantize(const void* W, const void* col_scale, const void* hi, const void* lo, int N, int K, int bits, int group, void* W_q,
+                               void* scale, void* zero, void* dense, void* info, void* workspace, hipStream_t st);
+hipError_t launch_awq_clip(const void* W, const void* X, int N, int K, int T, int bits, int group, void* hi, void* lo, void* best, void* err,
+                           void* info, void* workspace, hipStream_t st);
 
 }  // namespace amq

@@ -312,6 +312,139 @@ def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, n
     return (h, got) if return_info else h
 
 
+AWQ_GROUPS = (32, 64, 128)       # group sizes the AWQ kernels are built for
+
+
+def _awq_check(N, K, nbits, group_size):
+    _check_shape(nbits, N, K)
+    if int(group_size) not in AWQ_GROUPS:
+        raise ValueError(f"the AWQ kernels serve groups of 32, 64 and 128 (got {group_size})")
+    return int(group_size)
+
+
+def _awq_weight(W, who):
+    if not isinstance(W, torch.Tensor) or not W.is_cuda or W.dim() != 2:
+        raise ValueError(f"{who}: expected a 2-d tensor on the GPU")
+    if W.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"{who}: expected fp16 (or bf16 / fp32, cast to fp16), got {W.dtype}")
+    return W.detach().to(torch.float16).contiguous()
+
+
+def awq_quantize_launch(W, nbits, group_size, col_scale, hi, lo, W_q, scale, zero, dense, info, workspace):
+    """the bare entry point over caller-owned buffers (``col_scale``, ``hi`` / ``lo``, ``W_q`` / ``scale`` / ``zero`` and ``dense`` may be None; at
+    most three launches on the current stream; no allocation, no read-back: capturable)"""
+    N, K = W.shape
+    _lib.check(_lib.load().amq_awq_quantize_f16(_lib.ptr(W), _lib.ptr(col_scale), _lib.ptr(hi), _lib.ptr(lo), N, K, int(nbits), int(group_size),
+                                                _lib.ptr(W_q), _lib.ptr(scale), _lib.ptr(zero), _lib.ptr(dense), _lib.ptr(info),
+                                                _lib.ptr(workspace), workspace.numel() * workspace.element_size(), _lib.current_stream()))
+
+
+def awq_quantize_buffers(N, K, nbits, group_size, device, dense=False):
+    """(W_q, scale, zero, dense, info, workspace) of the right sizes for ``awq_quantize_launch``: Format A buffers and ``dense`` None, or -- with
+    ``dense`` -- the fp16 [N, K] matrix and W_q / scale / zero None"""
+    group_size = _awq_check(N, K, nbits, group_size)
+    R = N * K // group_size
+    W_q = scale = zero = out = None
+    if dense:
+        out = torch.empty(N, K, dtype=torch.float16, device=device)
+    else:
+        if nbits == 3:
+            W_q = torch.empty((R + 9) // 10, group_size, dtype=torch.int32, device=device)
+        else:
+            W_q = torch.empty(R * nbits // 8, group_size, dtype=torch.uint8, device=device)
+        scale = torch.empty(R, 1, dtype=torch.float16, device=device)
+        zero = torch.empty(R, 1, dtype=torch.float16, device=device)
+    info = torch.empty(_lib.AWQ_INFO_BYTES // 4, dtype=torch.int32, device=device)
+    need = int(_lib.load().amq_awq_quantize_workspace_bytes(N, K, group_size))
+    if need <= 0:
+        raise ValueError(f"the AWQ quantizer refuses N={N}, K={K}, group={group_size}")
+    return W_q, scale, zero, out, info, _awq_scratch.get(device, (need + 3) // 4)
+
+
+def awq_quantize(W, nbits, group_size=GROUP, col_scale=None, hi=None, lo=None, dense=False, bias=None, name=None):
+    """Dense W [N, K] on the GPU -> HQQWeights (Format A) on the same device by AWQ's round-to-nearest (awq_utils/quantizer.py
+    pseudo_quantize_tensor, zero_point=True) in the arithmetic include/amq_hip.h states, as HIP kernels: ``col_scale`` (fp32 [K]) multiplies the
+    columns first, ``hi`` / ``lo`` (fp16 [N, K / group], ``awq_clip``) clamp each group before its range is taken.  ``dense``: return instead the
+    fp16 [N, K] fake-quantized matrix divided by ``col_scale`` again -- the scale search's ``w_quantize_func(W * s) / s``.  W is fp16 (bf16 / fp32
+    weights are cast at this boundary).  Raises ValueError on non-finite input.  One synchronising read of the 4-byte info block per call."""
+    from .hqq_format import HQQWeights
+    W = _awq_weight(W, "W")
+    N, K = W.shape
+    nbits = int(nbits)
+    group_size = _awq_check(N, K, nbits, group_size)
+    if (hi is None) != (lo is None):
+        raise ValueError("hi and lo come together or not at all")
+    if col_scale is not None:
+        col_scale = col_scale.detach().to(W.device, torch.float32).contiguous()
+        _need(col_scale, torch.float32, "col_scale", K)
+    if hi is not None:
+        hi, lo = hi.detach().contiguous(), lo.detach().contiguous()
+        _need(hi, torch.float16, "hi", N * K // group_size)
+        _need(lo, torch.float16, "lo", N * K // group_size)
+    W_q, scale, zero, out, info, workspace = awq_quantize_buffers(N, K, nbits, group_size, W.device, dense=dense)
+    awq_quantize_launch(W, nbits, group_size, col_scale, hi, lo, W_q, scale, zero, out, info, workspace)
+    if info.cpu()[0].item():
+        raise ValueError(f"awq_quantize: {'layer ' + name if name else 'W'}: a (scaled) weight, a bound or an output was not finite")
+    if dense:
+        return out
+    return HQQWeights(W_q, scale, zero, nbits, (N, K), group_size, bias, name)
+
+
+class AWQClipInfo:
+    """what one ``awq_clip`` call reports: ``nonfinite`` (the info block), ``best`` (int32 [N, K / group]: the chosen shrink step, 0 = none) and
+    ``err`` (fp32 [N, K / group, 10]: every step's summed squared output error over the sampled rows), both on the device"""
+
+    def __init__(self, nonfinite, best, err):
+        self.nonfinite = int(nonfinite)
+        self.best = best
+        self.err = err
+
+    def __repr__(self):
+        return f"AWQClipInfo(nonfinite={self.nonfinite}, best={tuple(self.best.shape)}, err={tuple(self.err.shape)})"
+
+
+def awq_clip_launch(W, X, nbits, group_size, hi, lo, best, err, info, workspace):
+    """the bare entry point over caller-owned buffers (two launches on the current stream; no allocation, no read-back: capturable)"""
+    N, K = W.shape
+    _lib.check(_lib.load().amq_awq_clip_f16(_lib.ptr(W), _lib.ptr(X), N, K, int(X.shape[0]), int(nbits), int(group_size), _lib.ptr(hi), _lib.ptr(lo),
+                                            _lib.ptr(best), _lib.ptr(err), _lib.ptr(info), _lib.ptr(workspace),
+                                            workspace.numel() * workspace.element_size(), _lib.current_stream()))
+
+
+def awq_clip_buffers(N, K, T, nbits, group_size, device):
+    """(hi, lo, best, err, info, workspace) of the right sizes for ``awq_clip_launch``"""
+    group_size = _awq_check(N, K, nbits, group_size)
+    kg = K // group_size
+    hi = torch.empty(N, kg, dtype=torch.float16, device=device)
+    lo = torch.empty(N, kg, dtype=torch.float16, device=device)
+    best = torch.empty(N, kg, dtype=torch.int32, device=device)
+    err = torch.empty(N, kg, _lib.AWQ_STEPS, dtype=torch.float32, device=device)
+    info = torch.empty(_lib.AWQ_INFO_BYTES // 4, dtype=torch.int32, device=device)
+    need = int(_lib.load().amq_awq_clip_workspace_bytes(N, K, int(T), group_size))
+    if need <= 0:
+        raise ValueError(f"the AWQ clip search refuses N={N}, K={K}, T={T}, group={group_size}")
+    return hi, lo, best, err, info, _awq_scratch.get(device, (need + 3) // 4)
+
+
+def awq_clip(W, X, nbits, group_size=GROUP, return_info=False):
+    """AWQ's clip search (auto_clip.py auto_clip_layer_asym: 10 shrink steps of 5 %, asymmetric) for dense W [N, K] (the layer's current, already
+    column-scaled weights) against the sampled activation rows X [T, K], on the matrix cores in the arithmetic include/amq_hip.h states: (hi, lo),
+    fp16 [N, K / group], the bounds ``awq_quantize`` takes.  W and X are fp16 (bf16 / fp32 are cast at this boundary).  Raises ValueError on
+    non-finite input.  One synchronising read of the 4-byte info block per call.  ``return_info``: also return the :class:`AWQClipInfo`."""
+    W = _awq_weight(W, "W")
+    X = _awq_weight(X, "X")
+    N, K = W.shape
+    if X.device != W.device or X.shape[1] != K or X.shape[0] < 1:
+        raise ValueError(f"X: expected at least one row of {K} values on W's GPU")
+    nbits = int(nbits)
+    hi, lo, best, err, info, workspace = awq_clip_buffers(N, K, X.shape[0], nbits, group_size, W.device)
+    awq_clip_launch(W, X, nbits, group_size, hi, lo, best, err, info, workspace)
+    got = AWQClipInfo(info.cpu()[0].item(), best, err)
+    if got.nonfinite:
+        raise ValueError("awq_clip: a weight or an error sum was not finite")
+    return (hi, lo, got) if return_info else (hi, lo)
+
+
 def fma_mode_for(mn, bits):
     """AMQ_MODE_FMA1 for a native meta buffer whose scales allow the GEMV kernel's one-op unpack (|scale| <= amq_fma1_scale_bound(bits); the same
     weights bit for bit, ~5 % faster decode launches), else AMQ_MODE_FMA.  One device -> host read: call at load time, not per forward."""
@@ -460,6 +593,7 @@ class _ScratchPool:
 _SPLITK_WS = _ScratchPool(torch.float32)
 _quantize_scratch = _ScratchPool(torch.int32)      # hqq_quantize's workspace (s, the zero trace, the partial errors)
 _gptq_scratch = _ScratchPool(torch.int32)          # gptq_quantize's workspace (the columns' errors, the flags, the byte codes)
+_awq_scratch = _ScratchPool(torch.int32)           # awq_quantize's / awq_clip's workspace (the flags, the byte codes)
 
 
 def _splitk_workspace(device, nbytes):
@@ -1601,7 +1735,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-for _name in ("hqq_quantize", "gptq_quantize", "gptq_quantize_launch", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
+for _name in ("hqq_quantize", "gptq_quantize", "gptq_quantize_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup"):
     globals()[_name] = _on_tensor_device(globals()[_name])

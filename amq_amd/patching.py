@@ -442,6 +442,201 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
     return model, report
 
 
+AWQ_GRID = 20        # ratios r / 20 of the scale search (auto_scale.py:114)
+
+
+def _awq_fake_quant(W, nbits, group_size, s):
+    return ops.awq_quantize(W, nbits, group_size, col_scale=s, dense=True)
+
+
+@torch.no_grad()
+def awq_search_scale(inspect, linears, x, bits, group_size, kwargs=None, fake_quant=None):
+    """The reference's ``_search_module_scale_per_linear`` (awq_utils/auto_scale.py:96-146): the per-input-channel scale of ``linears`` (name ->
+    nn.Linear inside ``inspect``, all fed by ``x`` [windows, seqlen, K] or [rows, K]) that loses least at ``inspect``'s output.  ``x_mean`` is the
+    mean of |x| per channel in fp32; for the ratios r / 20, r = 0 .. 19, ``s = clamp(x_mean ^ ratio, 1e-4)`` over ``sqrt(max(s) min(s))``; every
+    linear's weight data is swapped for ``fake_quant(W, bits, group_size, s)`` -- by default ops.awq_quantize(..., col_scale=s, dense=True), the HIP
+    kernel: fp16 W times s, rounded to nearest, divided by s again --; the loss is the mean of ``(org - out).float() ** 2`` over all rows, window by
+    window, summed in fp64; the first strict minimum wins.  The original weight tensors are put back by reference.  ``bits``: an int or name -> int.
+    Returns (s fp32 [K], ratio, the 20 losses)."""
+    kwargs = {} if kwargs is None else {k: v for k, v in kwargs.items() if k != "use_cache"}
+    fake_quant = _awq_fake_quant if fake_quant is None else fake_quant
+    windows = x if x.dim() == 3 else x.unsqueeze(0)
+    dtype = next(iter(linears.values())).weight.dtype
+
+    def run(xw):
+        out = inspect(xw.unsqueeze(0).to(dtype), **kwargs)
+        return out[0] if isinstance(out, (tuple, list)) else out
+
+    org = [run(xw) for xw in windows]
+    count = sum(o.numel() for o in org)
+    x_mean = x.reshape(-1, x.shape[-1]).abs().float().mean(0)
+    keep = {name: lin.weight.data for name, lin in linears.items()}
+    history, best = [], None
+    try:
+        for r in range(AWQ_GRID):
+            ratio = r / AWQ_GRID
+            s = x_mean.pow(ratio).clamp(min=1e-4)
+            s = s / (s.max() * s.min()).sqrt()
+            for name, lin in linears.items():
+                nb = bits[name] if isinstance(bits, dict) else bits
+                lin.weight.data = fake_quant(keep[name], int(nb), group_size, s).to(keep[name].dtype)
+            loss = 0.0
+            for xw, o in zip(windows, org):
+                loss += float((o - run(xw)).float().pow(2).double().sum().item())
+            loss /= count
+            history.append(loss)
+            if best is None or loss < best[0]:
+                best = (loss, ratio, s)
+    finally:
+        for name, lin in linears.items():
+            lin.weight.data = keep[name]
+    if not all(v == v for v in history) or bool(torch.isnan(best[2]).any()):
+        raise ValueError(f"awq_search_scale: a loss or a scale is NaN ({history})")
+    return best[2].detach(), best[1], history
+
+
+def _awq_searches(layer, feats, kwargs, bits, b, group_size, fake_quant=None):
+    """the four searches of one Llama-family block (auto_scale.py:166-220), each against the unmodified block: [(prev op, its kind, names, s,
+    ratio, losses)]"""
+    from .arch import LINEARS
+    attn, mlp = layer.self_attn, layer.mlp
+    nb = {name: _bits_of(bits, name, b) for name in LINEARS}
+    todo = [(layer.input_layernorm, "norm", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), attn, kwargs)]
+    if attn.v_proj.weight.shape == attn.o_proj.weight.shape:        # auto_scale.py:185 (not under GQA: v's rows are not o's columns)
+        todo.append((attn.v_proj, "linear", ("self_attn.o_proj",), attn.o_proj, None))
+    todo.append((layer.post_attention_layernorm, "norm", ("mlp.gate_proj", "mlp.up_proj"), mlp, None))
+    todo.append((mlp.up_proj, "linear", ("mlp.down_proj",), mlp.down_proj, None))
+    found = []
+    for prev, kind, names, inspect, kw in todo:
+        linears = {name: getattr(getattr(layer, name.split(".")[0]), name.split(".")[1]) for name in names}
+        s, ratio, losses = awq_search_scale(inspect, linears, feats[names[0]], nb, group_size, kwargs=kw, fake_quant=fake_quant)
+        found.append((prev, kind, names, s, ratio, losses))
+    return found
+
+
+def _awq_apply_scale(layer, found, feats=None):
+    """auto_scale.py apply_scale: a norm's weight is divided by s, a linear prev-op's last len(s) rows (and bias) are; every scaled linear becomes
+    fp16(w * s); the stored inputs are divided by s"""
+    for prev, kind, names, s, _, _ in found:
+        if kind == "norm":
+            prev.weight.data = (prev.weight.data.float() / s).to(prev.weight.dtype)
+        else:
+            w = prev.weight.data
+            w[-s.numel():] = (w[-s.numel():].float() / s.view(-1, 1)).to(w.dtype)
+            if prev.bias is not None:
+                prev.bias.data[-s.numel():] = (prev.bias.data[-s.numel():].float() / s).to(prev.bias.dtype)
+        for name in names:
+            lin = getattr(getattr(layer, name.split(".")[0]), name.split(".")[1])
+            lin.weight.data = (lin.weight.data.float() * s.view(1, -1)).to(lin.weight.dtype)
+        if feats is not None:
+            feats[names[0]] = (feats[names[0]].float() / s).to(feats[names[0]].dtype)
+
+
+_AWQ_INPUT_OF = {"self_attn.q_proj": "self_attn.q_proj", "self_attn.k_proj": "self_attn.q_proj", "self_attn.v_proj": "self_attn.q_proj",
+                 "self_attn.o_proj": "self_attn.o_proj", "mlp.gate_proj": "mlp.gate_proj", "mlp.up_proj": "mlp.gate_proj",
+                 "mlp.down_proj": "mlp.down_proj"}
+
+
+@torch.no_grad()
+def quantize_model_awq(model, bits, samples, group_size=128, clip=True, n_sample_token=512, device=None):
+    """The reference's ``run_awq`` + ``apply_awq`` (amq/quantization/awq_utils/pre_quant.py:80-234: zero_point=True, clip_asym=True, per-linear bits)
+    for a dense HF llama / mistral / qwen2 / qwen3 model, ending in packed layers -- which the reference, whose AWQ writes fake-quantized fp16
+    weights back, cannot produce.  Block by block: one pass of the dense block over ``samples`` collects the inputs of q_proj (shared by k and v),
+    o_proj, gate_proj (shared by up) and down_proj as fp16 rows on the device and hands the next block its inputs (AWQ calibrates on dense
+    activations); the four scale searches run against the unmodified block (:func:`awq_search_scale`; o_proj's only when v_proj has its shape);
+    the scales are folded into the norms / previous linears, the linears and the stored inputs; with ``clip`` every linear but q_proj and k_proj
+    gets its per-group bounds from ``ops.awq_clip`` on the rows ``x[0 :: rows // n_sample_token]`` (the reference's stride: it can yield more than
+    ``n_sample_token`` rows); ``ops.awq_quantize`` packs.  ``samples``: token-id tensors [1, seqlen] of one length, brought by the caller.
+    Returns (model, report) with ``report[(block, name)] = {"bits", "ratio": the chosen r / 20 (None for o_proj where its search is skipped),
+    "search_loss": the 20 losses of its search (None likewise), "clip_steps": the histogram of the chosen shrink steps (None without clip),
+    "loss": the mean squared output error of the packed layer on its scaled sampled inputs against the dense layer on the unscaled ones,
+    "rtn_loss": the same for hqq_format.quantize_rtn of the original weights}``.  The model is then ready for
+    ``prepare_for_inference(backend='hip')``."""
+    from .arch import LINEARS
+    from .hqq_format import quantize_rtn
+    _decoder_linears(model)                                  # TypeError for a model that is not dense any more
+    samples = list(samples)
+    if not samples or any(s.dim() != 2 or s.shape != samples[0].shape for s in samples):
+        raise ValueError("samples: expected token-id tensors [1, seqlen] of one length")
+    if device is None:
+        p = next(model.parameters())
+        device = p.device if p.is_cuda else torch.device("cuda:0")
+    device = torch.device(device)
+    model.to(device)
+    layers = model.model.layers
+    use_cache = getattr(model.config, "use_cache", None)
+    model.config.use_cache = False
+    inps, kwargs = [], {}
+
+    def catch(_, args, kw):
+        inps.append((args[0] if args else kw["hidden_states"]).detach())
+        kwargs.update({k: v for k, v in kw.items() if k != "hidden_states"})
+        raise _BlockInputCaught
+
+    handle = layers[0].register_forward_pre_hook(catch, with_kwargs=True)
+    try:
+        for s in samples:
+            try:
+                model(s.to(device))
+            except _BlockInputCaught:
+                pass
+    finally:
+        handle.remove()
+
+    def run(layer, x):
+        out = layer(x, **kwargs)
+        return out[0] if isinstance(out, (tuple, list)) else out
+
+    attn_kwargs = {k: v for k, v in kwargs.items() if k != "use_cache"}
+    report = {}
+    for b, layer in enumerate(layers):
+        full = {name: getattr(getattr(layer, name.split(".")[0]), name.split(".")[1]) for name in LINEARS}
+        caught = {name: [] for name in set(_AWQ_INPUT_OF.values())}
+        handles = [full[name].register_forward_hook(lambda _, inp, out, acc=caught[name]: acc.append(inp[0].detach().to(torch.float16)))
+                   for name in caught]
+        try:
+            inps = [run(layer, x).detach() for x in inps]
+        finally:
+            for h in handles:
+                h.remove()
+        feats = {name: torch.cat(v, dim=0) for name, v in caught.items()}        # [windows, seqlen, K]
+        found = _awq_searches(layer, feats, attn_kwargs, bits, b, group_size)
+        searched = {name: (ratio, losses) for _, _, names, _, ratio, losses in found for name in names}
+        # the sampled rows of every input, before and after the scales reach them
+        sampled = {}
+        for name in caught:
+            rows = feats[name].reshape(-1, feats[name].shape[-1])
+            sampled[name] = rows[0::max(1, rows.shape[0] // int(n_sample_token))].clone()
+        dense_w = {name: full[name].weight.detach().to(torch.float16).clone() for name in LINEARS}
+        _awq_apply_scale(layer, found, feats)
+        for name in LINEARS:
+            lin, nb = full[name], _bits_of(bits, name, b)
+            parent_name, attr = name.split(".")
+            W = lin.weight.detach().to(torch.float16).contiguous()
+            N, K = W.shape
+            rows = feats[_AWQ_INPUT_OF[name]].reshape(-1, K)
+            xs = rows[0::max(1, rows.shape[0] // int(n_sample_token))].contiguous()
+            hi = lo = steps = None
+            if clip and attr not in ("q_proj", "k_proj"):       # auto_clip.py:16: hard to clip precisely in front of the q k product
+                hi, lo, info = ops.awq_clip(W, xs, nb, group_size, return_info=True)
+                steps = torch.bincount(info.best.reshape(-1).long(), minlength=10).tolist()
+            bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
+            h = ops.awq_quantize(W, nb, group_size, hi=hi, lo=lo, bias=bias, name=attr)
+            W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, N, K, group_size)
+            r = quantize_rtn(dense_w[name], nb, group_size)
+            W_rtn = ops.dequantize_hqq(r.W_q.contiguous(), r.scale.reshape(-1).contiguous(), r.zero.reshape(-1).contiguous(), nb, N, K, group_size)
+            x0 = sampled[_AWQ_INPUT_OF[name]]
+            want = torch.nn.functional.linear(x0, dense_w[name]).float()
+            ratio, losses = searched.get(name, (None, None))
+            report[(b, name)] = {"bits": nb, "ratio": ratio, "search_loss": losses, "clip_steps": steps,
+                                 "loss": float((torch.nn.functional.linear(xs, W_hat).float() - want).pow(2).mean().item()),
+                                 "rtn_loss": float((torch.nn.functional.linear(x0, W_rtn).float() - want).pow(2).mean().item())}
+            setattr(getattr(layer, parent_name), attr, HIPQuantLinear.from_hqq(h, device=device))
+    if use_cache is not None:
+        model.config.use_cache = use_cache
+    return model, report
+
+
 def _merge_zeros_with_lora(model):
     """``allow_merge=True`` (patching.py:210-216, patch_merge_zeros_with_lora :239-275): the reference folds the zero-point term
     of an HQQLinearLoRA into its LoRA factors -- only for layers quantized WITHOUT groups along axis 1 (":243-245: axis == 0 or a

@@ -183,6 +183,48 @@ size_t amq_gptq_quantize_workspace_bytes(int N, int K, int group);
 int amq_gptq_quantize_f16(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero, void* row_loss,
                           void* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* AWQ's weight-side passes (awq_utils/quantizer.py pseudo_quantize_tensor with zero_point, auto_clip.py auto_clip_layer_asym) to the same Format A.
+ * All fp32, every operation its own IEEE rounding, IEEE division, rint = round-half-even, no contraction except the fmaf written out below.
+ * RTN of one group v[0..G) of fp16 values: maxq = 2^bits - 1, xmax = max v, xmin = min v, s = max(xmax - xmin, 1e-5f) / maxq, s16 = fp16(s) (never
+ * 0: s >= 1e-5 / 15 > 2^-24), z = clamp(rint(-xmin / s16), 0, maxq) + 0 (a -0 becomes +0), q = clamp(rint(v / s16) + z, 0, maxq), w^ = fp16((q - z) * s16) -- the weight
+ * amq_dequantize_hqq_f16 and the matmul kernels produce from scale = s16, zero = z.  (Unlike the GPTQ rule, 0 is not forced into the range and z is
+ * clamped, as AWQ does; the scale is rounded to fp16 BEFORE it is used, the deployment deviation of the GPTQ solve.)
+ *
+ * amq_awq_quantize_f16: v = col_scale ? fp16(fp32(w) * c_k) : w; with bounds v = min(max(v, lo), hi) of the element's group; RTN per group.
+ *   W          fp16 [N, K], 16-byte aligned
+ *   col_scale  fp32 [K] or NULL
+ *   hi, lo     fp16 [N, K / group], both or neither
+ *   W_q, scale, zero   Format A as above (scale = s16, zero = z), all three or none
+ *   dense      fp16 [N, K] or NULL: col_scale ? fp16(fp32(w^) / c_k) : w^ (the scale search's w_quantize_func(W s) / s); 16-byte aligned
+ *   info       AMQ_AWQ_INFO_BYTES: {int32 nonfinite (!= 0: a scaled weight, a bound or a dense output was not finite: the outputs are meaningless)}
+ *   workspace  amq_awq_quantize_workspace_bytes(N, K, group) = N * K / 128 + N * K bytes (int32 flags [N * K / 512], byte codes [N, K]), 16-byte
+ *              aligned; 0 for a shape the call refuses
+ * Three launches (round, nonfinite flag, pack; two without Format A).  No host read, no allocation, no atomics: the same bits on every run.
+ *
+ * amq_awq_clip_f16: W fp16 [N, K] (the layer's current, already column-scaled weights), X fp16 [T, K] (the sampled activation rows).  For every
+ * row n, group g and step i = 0..9: f_i = the fp32 nearest to 1 - i / 20; hi_i = fp16(fp32(max_g) * f_i), lo_i = fp16(fp32(min_g) * f_i); w^_i =
+ * RTN of the group clamped to [lo_i, hi_i] with the clamped group's own min and max; d_i[c] = fp32(w^_i[c]) - fp32(w[c]); o_i[t] = the chain
+ * acc = fmaf(fp32(x[t, c]), d_i[c], acc) over the group's columns in ascending c from acc = 0; err_i = the sum of o_i[t] * o_i[t] (one multiply per
+ * term) in THIS order: with t = 16 a + 4 h + r (h, r in 0..3; rows t >= T are zeros and add exactly 0), P_h = the running sum from 0 over a
+ * ascending, r ascending inside a; err_i = (P_0 + P_1) + (P_2 + P_3).  The order depends on T only.  The winner is the lowest i with the smallest
+ * err_i (strict <: the least shrink wins a tie; step 0 is plain RTN).
+ *   hi, lo     fp16 [N, K / group]: the winner's bounds
+ *   best       int32 [N, K / group]: the winner's step
+ *   err        fp32 [N, K / group, 10]: the sums (not divided by T)
+ *   info       AMQ_AWQ_INFO_BYTES: {int32 nonfinite (!= 0: a weight or a sum was not finite)}
+ *   workspace  amq_awq_clip_workspace_bytes(N, K, T, group) = 4 * (N / 8) * (K / group) bytes, 4-byte aligned; 0 for a shape the call refuses
+ * One wave per (8 rows, group): the chains run on v_mfma_f32_16x16x4_f32, which is bit for bit that fmaf chain.  Two launches (search, flag).
+ *
+ * Refused, in this order: a null or misaligned pointer (AMQ_EINVAL); bits not 2 / 3 / 4 (AMQ_EINVAL); group not 32 / 64 / 128, N % 16, K % 128,
+ * T < 1 (AMQ_ESHAPE); workspace_bytes too small (AMQ_EINVAL). */
+#define AMQ_AWQ_INFO_BYTES 4
+size_t amq_awq_quantize_workspace_bytes(int N, int K, int group);
+int amq_awq_quantize_f16(const void* W, const void* col_scale, const void* hi, const void* lo, int N, int K, int bits, int group, void* W_q,
+                         void* scale, void* zero, void* dense, void* info, void* workspace, size_t workspace_bytes, void* stream);
+size_t amq_awq_clip_workspace_bytes(int N, int K, int T, int group);
+int amq_awq_clip_f16(const void* W, const void* X, int N, int K, int T, int bits, int group, void* hi, void* lo, void* best, void* err,
+                     void* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- dequantize ---------------------------------------------------------- */
 /* native -> W[N,K] fp16 (row-major, nn.Linear orientation) */
 int amq_dequantize_f16(int bits, int mode, const void* qweight_native, const void* meta_native,
