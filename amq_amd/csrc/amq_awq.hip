@@ -2,8 +2,8 @@
 //
 //   awq_rtn_kernel<G, BITS>   fp16 W[N,K] (optionally times a column scale, optionally clamped to per-group bounds) -> round to nearest per group:
 //                             byte codes, (s16, z) and / or the dense fake-quantized matrix (divided by the column scale again).  A thread holds 8
-//                             consecutive columns, G / 8 lanes a group (its min and max by xor shuffles).  Then awq_flag_kernel ORs the waves'
-//                             nonfinite flags into the info block and the GPTQ solve's pack launch turns the byte codes into Format A words.
+//                             consecutive columns, G / 8 lanes a group (its min and max by xor shuffles).  Then quant_flag_kernel ORs the waves'
+//                             nonfinite flags into the info block and quant_pack_kernel turns the byte codes into Format A words (amq_quant_pack.hip).
 //   awq_clip_kernel<G, BITS>  auto_clip_layer_asym's search on the matrix cores.  One wave owns 8 rows x one group.  The rows' 10 shrink steps are 80
 //                             (row, step) pairs = 5 B tiles of v_mfma_f32_16x16x4_f32: lane (j = lane & 15, h = lane >> 4) of tile b builds, for
 //                             pair 16 b + j, d[c] = w^_step[c] - w[c] of the columns c = 4 kk + h and keeps them in registers (G / 4 per tile).  X's
@@ -12,8 +12,7 @@
 //                             four outputs and adds them to its running sum, and at the end the four lane quarters are added as (0 + 1) + (2 + 3).
 //                             The first strict minimum over the steps picks the bounds.
 // No host read, no allocation, no atomics; every summation order depends on T only.  tests/awq_search_ref.py restates both in torch, bit for bit.
-#include "amq_common.cuh"
-#include "amq_kernels.h"
+#include "amq_quant.cuh"
 
 namespace amq {
 
@@ -33,8 +32,6 @@ __device__ __forceinline__ float awq_weight(float q, float s16, float z) {
     const float t = (q - z) * s16;
     return (float)(_Float16)t;
 }
-
-__device__ __forceinline__ bool awq_finite(float v) { return fabsf(v) < __builtin_inff(); }
 
 // fp16(p) of an fp32 PRODUCT p, as two roundings (fp32, then fp16).  The empty asm makes the compiler hold p in a register as an fp32 value:
 // without it, it folds fp16(a * b) into v_fma_mixlo_f16 -- ONE rounding, which differs wherever the fp32 product lands on an fp16 midpoint
@@ -67,11 +64,11 @@ __global__ __launch_bounds__(256) void awq_rtn_kernel(const _Float16* __restrict
         } else {
             cs[c] = 1.0f;
         }
-        bad = bad || !awq_finite(v[c]);
+        bad = bad || !finite(v[c]);
     }
     if (HI) {
         const float hi = (float)HI[grp], lo = (float)LO[grp];
-        bad = bad || !awq_finite(hi) || !awq_finite(lo);
+        bad = bad || !finite(hi) || !finite(lo);
 #pragma unroll
         for (int c = 0; c < C; ++c) v[c] = fminf(fmaxf(v[c], lo), hi);
     }
@@ -92,7 +89,7 @@ __global__ __launch_bounds__(256) void awq_rtn_kernel(const _Float16* __restrict
         scale[grp] = (_Float16)s16;
         zero[grp] = (_Float16)z;
     }
-    uint32_t q0 = 0, q1 = 0;
+    Codes8 codes;
     h8 out;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -102,29 +99,14 @@ __global__ __launch_bounds__(256) void awq_rtn_kernel(const _Float16* __restrict
             const float d = wh / cs[c];
             wh = (float)(_Float16)d;
         }
-        bad = bad || !awq_finite(wh);
+        bad = bad || !finite(wh);
         out[c] = (_Float16)wh;
-        const uint32_t qi = (uint32_t)q;
-        if (c < 4) q0 |= qi << (8 * c);
-        else q1 |= qi << (8 * (c - 4));
+        codes.put(c, q);
     }
-    if (Q) *(uint2*)(Q + e0) = make_uint2(q0, q1);
+    if (Q) codes.store(Q + e0);
     if (dense) *(h8*)(dense + e0) = out;
     const bool anybad = __builtin_amdgcn_ballot_w64(bad) != 0;
     if ((threadIdx.x & 63) == 0) NF[(size_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = anybad ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void awq_flag_kernel(const int* __restrict__ NF, size_t n, int* __restrict__ info) {
-    __shared__ int sbad[256];
-    int bad = 0;
-    for (size_t w = threadIdx.x; w < n; w += 256) bad |= NF[w];
-    sbad[threadIdx.x] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int any = 0;
-        for (int j = 0; j < 256; ++j) any |= sbad[j];
-        info[0] = any != 0;
-    }
 }
 
 // the fp32 nearest to 1 - i / 20
@@ -153,7 +135,7 @@ __global__ __launch_bounds__(64) void awq_clip_kernel(const _Float16* __restrict
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) {
             wv[kk] = (float)wr[4 * kk];
-            bad = bad || !awq_finite(wv[kk]);
+            bad = bad || !finite(wv[kk]);
         }
         float mn = wv[0], mx = wv[0];
 #pragma unroll
@@ -220,7 +202,7 @@ __global__ __launch_bounds__(64) void awq_clip_kernel(const _Float16* __restrict
     for (int b = 0; b < AWQ_TILES; ++b) {
         const float a = sq[b] + __shfl_xor(sq[b], 16);       // quarters (0 + 1) and (2 + 3) ...
         const float e = a + __shfl_xor(a, 32);               // ... then their sum
-        bad = bad || !awq_finite(e);
+        bad = bad || !finite(e);
         if (h == 0) s_err[16 * b + j] = e;
     }
     __syncthreads();
@@ -246,55 +228,35 @@ __global__ __launch_bounds__(64) void awq_clip_kernel(const _Float16* __restrict
     if (lane == 0) NF[blockIdx.x] = anybad ? 1 : 0;
 }
 
-#define AMQ_AWQ_DISPATCH(LAUNCH)                 \
-    do {                                         \
-        if (group == 32) {                       \
-            if (bits == 4) LAUNCH(32, 4);        \
-            else if (bits == 3) LAUNCH(32, 3);   \
-            else LAUNCH(32, 2);                  \
-        } else if (group == 64) {                \
-            if (bits == 4) LAUNCH(64, 4);        \
-            else if (bits == 3) LAUNCH(64, 3);   \
-            else LAUNCH(64, 2);                  \
-        } else {                                 \
-            if (bits == 4) LAUNCH(128, 4);       \
-            else if (bits == 3) LAUNCH(128, 3);  \
-            else LAUNCH(128, 2);                 \
-        }                                        \
-    } while (0)
-
 hipError_t launch_awq_quantize(const void* W, const void* col_scale, const void* hi, const void* lo, int N, int K, int bits, int group, void* W_q,
                                void* scale, void* zero, void* dense, void* info, void* workspace, hipStream_t st) {
-    if ((bits != 2 && bits != 3 && bits != 4) || (group != 32 && group != 64 && group != 128)) return hipErrorInvalidValue;
     const size_t flags = awq_quantize_flags(N, K);
     int* NF = (int*)workspace;
     uint8_t* Q = W_q ? (uint8_t*)(NF + flags) : nullptr;
     const unsigned wgs = (unsigned)((size_t)N * K / 2048);
-#define AMQ_AWQ_RTN(G_, B_) hipLaunchKernelGGL((awq_rtn_kernel<G_, B_>), dim3(wgs), dim3(256), 0, st, (const _Float16*)W, (const float*)col_scale, \
-                                               (const _Float16*)hi, (const _Float16*)lo, K, Q, (_Float16*)scale, (_Float16*)zero, (_Float16*)dense, NF)
-    AMQ_AWQ_DISPATCH(AMQ_AWQ_RTN);
-#undef AMQ_AWQ_RTN
-    if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(awq_flag_kernel, dim3(1), dim3(256), 0, st, NF, flags, (int*)info);
-    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = dispatch_group_bits(group, bits, [&](auto G, auto B) {
+            hipLaunchKernelGGL((awq_rtn_kernel<G(), B()>), dim3(wgs), dim3(256), 0, st, (const _Float16*)W, (const float*)col_scale, (const _Float16*)hi,
+                               (const _Float16*)lo, K, Q, (_Float16*)scale, (_Float16*)zero, (_Float16*)dense, NF);
+            return hipGetLastError();
+        }))
+        return e;
+    if (hipError_t e = launch_quant_flags(NF, flags, (int*)info, st)) return e;
     if (!W_q) return hipSuccess;
     return launch_pack_codes(Q, (size_t)N * K / group, group, bits, W_q, st);
 }
 
 hipError_t launch_awq_clip(const void* W, const void* X, int N, int K, int T, int bits, int group, void* hi, void* lo, void* best, void* err,
                            void* info, void* workspace, hipStream_t st) {
-    if ((bits != 2 && bits != 3 && bits != 4) || (group != 32 && group != 64 && group != 128) || T < 1) return hipErrorInvalidValue;
+    if (T < 1 || group < 1) return hipErrorInvalidValue;
     const size_t waves = awq_clip_flags(N, K, group);
     int* NF = (int*)workspace;
-#define AMQ_AWQ_CLIP(G_, B_) hipLaunchKernelGGL((awq_clip_kernel<G_, B_>), dim3((unsigned)waves), dim3(64), 0, st, (const _Float16*)W, (const _Float16*)X, \
-                                                K, T, (_Float16*)hi, (_Float16*)lo, (int*)best, (float*)err, NF)
-    AMQ_AWQ_DISPATCH(AMQ_AWQ_CLIP);
-#undef AMQ_AWQ_CLIP
-    if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(awq_flag_kernel, dim3(1), dim3(256), 0, st, NF, waves, (int*)info);
-    return hipGetLastError();
+    if (hipError_t e = dispatch_group_bits(group, bits, [&](auto G, auto B) {
+            hipLaunchKernelGGL((awq_clip_kernel<G(), B()>), dim3((unsigned)waves), dim3(64), 0, st, (const _Float16*)W, (const _Float16*)X, K, T,
+                               (_Float16*)hi, (_Float16*)lo, (int*)best, (float*)err, NF);
+            return hipGetLastError();
+        }))
+        return e;
+    return launch_quant_flags(NF, waves, (int*)info, st);
 }
-
-#undef AMQ_AWQ_DISPATCH
 
 }  // namespace amq

@@ -110,18 +110,34 @@ int amq_repack_from_awq(const void* qweight, const void* scales, const void* sca
     return check_hip(amq::launch_repack(amq::FMT_AWQ, 4, qweight, scales, scaled_zeros, N, K, qn, mn, (hipStream_t)stream, group), "repack_from_awq");
 }
 
-// the quantizer's shapes: the solve kernel is instantiated for four group sizes (other multiples of 128 are refused, not mis-run)
-static int check_hqq_quantize_shape(int bits, int N, int K, int group) {
+// The quantizer family's one validator.  A family is what its kernels are instantiated for and how it words a refused group: HQQ's solve takes
+// four group sizes and wants the group to divide K; the GPTQ solve and AWQ's kernels take the three that fit a 128-column block (a multiple of
+// 128 they all divide), and the GPTQ solve says why 256 is not among them.  T: the rows of activations (1 for the calls without any).
+struct QuantFamily { const char* serves; bool has256, explains256; };
+constexpr QuantFamily QUANT_HQQ = {"the quantizer serves groups of 32, 64, 128 and 256", true, false};
+constexpr QuantFamily QUANT_GPTQ = {"the GPTQ solve serves groups of 32, 64 and 128", false, true};
+constexpr QuantFamily QUANT_AWQ = {"the AWQ kernels serve groups of 32, 64 and 128", false, false};
+
+static int check_quantize_shape(const QuantFamily& f, int bits, int N, int K, int group, int T = 1) {
     if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
-    if (group != 32 && group != 64 && group != 128 && group != 256)
-        return fail(AMQ_ESHAPE, "the quantizer serves groups of 32, 64, 128 and 256 (got %d)", group);
+    if (group == 256 && f.explains256)
+        return fail(AMQ_ESHAPE, "%s: a group of 256 spans two 128-column blocks and its parameters would need columns of the next block", f.serves);
+    if (group != 32 && group != 64 && group != 128 && !(group == 256 && f.has256)) return fail(AMQ_ESHAPE, "%s (got %d)", f.serves, group);
     if (N <= 0 || (N % 16) != 0) return fail(AMQ_ESHAPE, "need N %% 16 == 0 (got N=%d)", N);
-    if (K <= 0 || (K % group) != 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 and group %d dividing K (got K=%d)", group, K);
+    if (f.has256 && (K <= 0 || (K % group) != 0 || (K % 128) != 0))
+        return fail(AMQ_ESHAPE, "need K %% 128 == 0 and group %d dividing K (got K=%d)", group, K);
+    if (K <= 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 (got K=%d)", K);
+    if (T < 1) return fail(AMQ_ESHAPE, "need at least one row of activations (got T=%d)", T);
+    return AMQ_OK;
+}
+
+static int check_workspace(const char* what, size_t need, size_t got) {
+    if (got < need) return fail(AMQ_EINVAL, "%s workspace too small: need %zu bytes, got %zu", what, need, got);
     return AMQ_OK;
 }
 
 size_t amq_hqq_quantize_workspace_bytes(int N, int K, int group) {
-    if (check_hqq_quantize_shape(4, N, K, group) != AMQ_OK) return 0;
+    if (check_quantize_shape(QUANT_HQQ, 4, N, K, group) != AMQ_OK) return 0;
     return amq::hqq_workspace_bytes(N, K, group);
 }
 
@@ -131,27 +147,14 @@ int amq_hqq_quantize_f16(const void* W, int N, int K, int bits, int group, int r
     if (!W || !W_q || !scale || !zero || !info || !workspace) return fail(AMQ_EINVAL, "null pointer");
     if (((uintptr_t)W & 7) != 0 || ((uintptr_t)workspace & 3) != 0 || ((uintptr_t)info & 3) != 0 || ((uintptr_t)W_q & 3) != 0)
         return fail(AMQ_EINVAL, "W must be 8-byte aligned, W_q, info and workspace 4-byte aligned");
-    if (int rc = check_hqq_quantize_shape(bits, N, K, group)) return rc;
-    const size_t need = amq::hqq_workspace_bytes(N, K, group);
-    if (workspace_bytes < need) return fail(AMQ_EINVAL, "quantize workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (int rc = check_quantize_shape(QUANT_HQQ, bits, N, K, group)) return rc;
+    if (int rc = check_workspace("quantize", amq::hqq_workspace_bytes(N, K, group), workspace_bytes)) return rc;
     return check_hip(amq::launch_hqq_quantize(W, N, K, bits, group, round_zero != 0, W_q, scale, zero, info, workspace, (hipStream_t)stream),
                      "hqq_quantize");
 }
 
-// the GPTQ solve's one validator: its kernel is instantiated for the three group sizes that fit a 128-column block
-static int check_gptq_quantize_shape(int bits, int N, int K, int group) {
-    if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
-    if (group == 256)
-        return fail(AMQ_ESHAPE, "the GPTQ solve serves groups of 32, 64 and 128: a group of 256 spans two 128-column blocks and its parameters "
-                    "would need columns of the next block");
-    if (group != 32 && group != 64 && group != 128) return fail(AMQ_ESHAPE, "the GPTQ solve serves groups of 32, 64 and 128 (got %d)", group);
-    if (N <= 0 || (N % 16) != 0) return fail(AMQ_ESHAPE, "need N %% 16 == 0 (got N=%d)", N);
-    if (K <= 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 (got K=%d)", K);
-    return AMQ_OK;
-}
-
 size_t amq_gptq_quantize_workspace_bytes(int N, int K, int group) {
-    if (check_gptq_quantize_shape(4, N, K, group) != AMQ_OK) return 0;
+    if (check_quantize_shape(QUANT_GPTQ, 4, N, K, group) != AMQ_OK) return 0;
     return amq::gptq_workspace_bytes(N, K);
 }
 
@@ -162,25 +165,14 @@ int amq_gptq_quantize_f16(const void* W, const void* U, int N, int K, int bits, 
     if (((uintptr_t)W & 15) != 0 || ((uintptr_t)U & 15) != 0 || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)W_q & 3) != 0 ||
         ((uintptr_t)row_loss & 3) != 0 || ((uintptr_t)info & 3) != 0)
         return fail(AMQ_EINVAL, "W, U and workspace must be 16-byte aligned, W_q, row_loss and info 4-byte aligned");
-    if (int rc = check_gptq_quantize_shape(bits, N, K, group)) return rc;
-    const size_t need = amq::gptq_workspace_bytes(N, K);
-    if (workspace_bytes < need) return fail(AMQ_EINVAL, "GPTQ workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (int rc = check_quantize_shape(QUANT_GPTQ, bits, N, K, group)) return rc;
+    if (int rc = check_workspace("GPTQ", amq::gptq_workspace_bytes(N, K), workspace_bytes)) return rc;
     return check_hip(amq::launch_gptq_quantize(W, U, N, K, bits, group, W_q, scale, zero, row_loss, info, workspace, (hipStream_t)stream),
                      "gptq_quantize");
 }
 
-// AWQ's one validator (quantize and clip; T = 1 for the call without tokens): the kernels are instantiated for the group sizes of the GPTQ solve
-static int check_awq_shape(int bits, int N, int K, int T, int group) {
-    if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
-    if (group != 32 && group != 64 && group != 128) return fail(AMQ_ESHAPE, "the AWQ kernels serve groups of 32, 64 and 128 (got %d)", group);
-    if (N <= 0 || (N % 16) != 0) return fail(AMQ_ESHAPE, "need N %% 16 == 0 (got N=%d)", N);
-    if (K <= 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 (got K=%d)", K);
-    if (T < 1) return fail(AMQ_ESHAPE, "need at least one row of activations (got T=%d)", T);
-    return AMQ_OK;
-}
-
 size_t amq_awq_quantize_workspace_bytes(int N, int K, int group) {
-    if (check_awq_shape(4, N, K, 1, group) != AMQ_OK) return 0;
+    if (check_quantize_shape(QUANT_AWQ, 4, N, K, group) != AMQ_OK) return 0;
     return amq::awq_quantize_workspace_bytes(N, K);
 }
 
@@ -196,15 +188,14 @@ int amq_awq_quantize_f16(const void* W, const void* col_scale, const void* hi, c
         ((uintptr_t)W_q & 3) != 0 || ((uintptr_t)info & 3) != 0 || ((uintptr_t)hi & 1) != 0 || ((uintptr_t)lo & 1) != 0 ||
         ((uintptr_t)scale & 1) != 0 || ((uintptr_t)zero & 1) != 0)
         return fail(AMQ_EINVAL, "W, dense and workspace must be 16-byte aligned, col_scale, W_q and info 4-byte, hi, lo, scale and zero 2-byte");
-    if (int rc = check_awq_shape(bits, N, K, 1, group)) return rc;
-    const size_t need = amq::awq_quantize_workspace_bytes(N, K);
-    if (workspace_bytes < need) return fail(AMQ_EINVAL, "AWQ quantize workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (int rc = check_quantize_shape(QUANT_AWQ, bits, N, K, group)) return rc;
+    if (int rc = check_workspace("AWQ quantize", amq::awq_quantize_workspace_bytes(N, K), workspace_bytes)) return rc;
     return check_hip(amq::launch_awq_quantize(W, col_scale, hi, lo, N, K, bits, group, W_q, scale, zero, dense, info, workspace,
                                               (hipStream_t)stream), "awq_quantize");
 }
 
 size_t amq_awq_clip_workspace_bytes(int N, int K, int T, int group) {
-    if (check_awq_shape(4, N, K, T, group) != AMQ_OK) return 0;
+    if (check_quantize_shape(QUANT_AWQ, 4, N, K, group, T) != AMQ_OK) return 0;
     return amq::awq_clip_workspace_bytes(N, K, group);
 }
 
@@ -214,9 +205,8 @@ int amq_awq_clip_f16(const void* W, const void* X, int N, int K, int T, int bits
     if (((uintptr_t)W & 15) != 0 || ((uintptr_t)X & 15) != 0 || ((uintptr_t)hi & 1) != 0 || ((uintptr_t)lo & 1) != 0 || ((uintptr_t)best & 3) != 0 ||
         ((uintptr_t)err & 3) != 0 || ((uintptr_t)info & 3) != 0 || ((uintptr_t)workspace & 3) != 0)
         return fail(AMQ_EINVAL, "W and X must be 16-byte aligned, best, err, info and workspace 4-byte, hi and lo 2-byte");
-    if (int rc = check_awq_shape(bits, N, K, T, group)) return rc;
-    const size_t need = amq::awq_clip_workspace_bytes(N, K, group);
-    if (workspace_bytes < need) return fail(AMQ_EINVAL, "AWQ clip workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (int rc = check_quantize_shape(QUANT_AWQ, bits, N, K, group, T)) return rc;
+    if (int rc = check_workspace("AWQ clip", amq::awq_clip_workspace_bytes(N, K, group), workspace_bytes)) return rc;
     return check_hip(amq::launch_awq_clip(W, X, N, K, T, bits, group, hi, lo, best, err, info, workspace, (hipStream_t)stream), "awq_clip");
 }
 

@@ -9,12 +9,10 @@
 //                               are fixed from those values, then the 128 columns are walked: the owner lane's value goes to the row's 16 lanes,
 //                               all of them form q, w^ and e, and each subtracts e * U[i, j] from the columns j > i it holds.  Codes (one byte
 //                               each) and errors go to the workspace, (s16, z) and the row's loss to the outputs.
-//   gptq_flag_kernel            one workgroup: ORs the waves' nonfinite flags into the info block.
-//   gptq_pack_kernel<BITS>      one thread per Format A word (hqq/core/bitpack.py row chunks), from the byte codes.
+//   quant_flag_kernel, quant_pack_kernel<BITS> (amq_quant_pack.hip): the waves' nonfinite flags ORed into the info block, the byte codes packed.
 // Every operation is its own fp32 rounding (-ffp-contract=off, IEEE division, rintf) and every element receives its subtractions in ascending
 // column order, so the result does not depend on the blocking: tests/gptq_solver_ref.py restates it in torch, bit for bit.
-#include "amq_common.cuh"
-#include "amq_kernels.h"
+#include "amq_quant.cuh"
 
 namespace amq {
 
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(64 * GPTQ_WAVES) void gptq_solve_kernel(const _Floa
         for (int o = 0; o < L; ++o) {
             const float so = __shfl(s16, o, L), zo = __shfl(z, o, L);
             float ev[C];
-            uint32_t q0 = 0, q1 = 0;
+            Codes8 codes;
             const bool after = lg > o, from = lg >= o;
 #pragma unroll
             for (int c = 0; c < C; ++c) {
@@ -134,11 +132,10 @@ __global__ __launch_bounds__(64 * GPTQ_WAVES) void gptq_solve_kernel(const _Floa
                 const float e = r / d;
                 const float r2 = r * r, d2 = d * d;
                 loss = loss + (r2 / d2) / 2.0f;
+                // (spelled out, not amq_quant.cuh's finite(): through the call the compiler schedules this loop 29 instructions longer, measured 9 % slower)
                 bad = bad || !(fabsf(wi) < __builtin_inff()) || !(fabsf(e) < __builtin_inff()) || !(d > 0.0f && d < __builtin_inff());
                 ev[c] = e;
-                const uint32_t qi = (uint32_t)q;
-                if (c < 4) q0 |= qi << (8 * c);
-                else q1 |= qi << (8 * (c - 4));
+                codes.put(c, q);
 #pragma unroll
                 for (int c2 = 0; c2 < C; ++c2) {
                     const float p = e * uv[c2];
@@ -149,7 +146,7 @@ __global__ __launch_bounds__(64 * GPTQ_WAVES) void gptq_solve_kernel(const _Floa
             if (lg == o) {
                 *(float4*)(E + rowK + col0) = make_float4(ev[0], ev[1], ev[2], ev[3]);
                 *(float4*)(E + rowK + col0 + 4) = make_float4(ev[4], ev[5], ev[6], ev[7]);
-                *(uint2*)(Q + rowK + col0) = make_uint2(q0, q1);
+                codes.store(Q + rowK + col0);
             }
         }
         __syncthreads();        // the block's E is read by the row's other lanes in the next block
@@ -159,77 +156,20 @@ __global__ __launch_bounds__(64 * GPTQ_WAVES) void gptq_solve_kernel(const _Floa
     if (lane == 0) NF[blockIdx.x * GPTQ_WAVES + wave] = anybad ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void gptq_flag_kernel(const int* __restrict__ NF, int wgs, int* __restrict__ info) {
-    __shared__ int sbad[256];
-    int bad = 0;
-    for (int w = threadIdx.x; w < wgs; w += 256) bad |= NF[w];
-    sbad[threadIdx.x] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int any = 0;
-        for (int j = 0; j < 256; ++j) any |= sbad[j];
-        info[0] = any != 0;
-    }
-}
-
-template <int BITS>
-__global__ __launch_bounds__(256) void gptq_pack_kernel(const uint8_t* __restrict__ Q, size_t R, int G, void* __restrict__ Wq) {
-    constexpr int C = BITS == 4 ? 2 : BITS == 2 ? 4 : 10;
-    const size_t step = BITS == 3 ? (R + 9) / 10 : R / C;      // packed rows (3 bit: rows zero-padded to a multiple of 10)
-    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= step * (size_t)G) return;
-    const size_t row = gid / G;
-    const int col = (int)(gid % G);
-    uint32_t word = 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const size_t r = (size_t)c * step + row;
-        if (BITS == 3 && r >= R) continue;
-        const int shift = BITS == 3 ? 27 - 3 * c : 8 - BITS * (c + 1);       // chunk 0 sits in the top bits
-        word |= (uint32_t)Q[r * G + col] << shift;
-    }
-    if (BITS == 3) ((uint32_t*)Wq)[gid] = word;
-    else ((uint8_t*)Wq)[gid] = (uint8_t)word;
-}
-
 hipError_t launch_gptq_quantize(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero,
                                 void* row_loss, void* info, void* workspace, hipStream_t st) {
     const int wgs = gptq_workgroups(N), flags = gptq_flags(N);
     float* E = (float*)workspace;
     int* NF = (int*)(E + (size_t)N * K);
     uint8_t* Q = (uint8_t*)(NF + flags);
-#define AMQ_GPTQ(G_, B_) hipLaunchKernelGGL((gptq_solve_kernel<G_, B_>), dim3(wgs), dim3(64 * GPTQ_WAVES), 0, st, (const _Float16*)W, (const float*)U, K, \
-                                            E, Q, (_Float16*)scale, (_Float16*)zero, (float*)row_loss, NF)
-#define AMQ_GPTQ_G(G_)               \
-    do {                             \
-        if (bits == 4) AMQ_GPTQ(G_, 4); \
-        else if (bits == 3) AMQ_GPTQ(G_, 3); \
-        else AMQ_GPTQ(G_, 2);        \
-    } while (0)
-    if (bits != 2 && bits != 3 && bits != 4) return hipErrorInvalidValue;
-    if (group == 32) AMQ_GPTQ_G(32);
-    else if (group == 64) AMQ_GPTQ_G(64);
-    else if (group == 128) AMQ_GPTQ_G(128);
-    else return hipErrorInvalidValue;
-#undef AMQ_GPTQ_G
-#undef AMQ_GPTQ
-    if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(gptq_flag_kernel, dim3(1), dim3(256), 0, st, NF, flags, (int*)info);
-    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = dispatch_group_bits(group, bits, [&](auto G, auto B) {
+            hipLaunchKernelGGL((gptq_solve_kernel<G(), B()>), dim3(wgs), dim3(64 * GPTQ_WAVES), 0, st, (const _Float16*)W, (const float*)U, K, E, Q,
+                               (_Float16*)scale, (_Float16*)zero, (float*)row_loss, NF);
+            return hipGetLastError();
+        }))
+        return e;
+    if (hipError_t e = launch_quant_flags(NF, flags, (int*)info, st)) return e;
     return launch_pack_codes(Q, (size_t)N * K / group, group, bits, W_q, st);
-}
-
-hipError_t launch_pack_codes(const void* codes, size_t R, int group, int bits, void* W_q, hipStream_t st) {
-    const uint8_t* Q = (const uint8_t*)codes;
-    const size_t words = (bits == 3 ? (R + 9) / 10 : R * bits / 8) * (size_t)group;
-    const unsigned blocks = (unsigned)((words + 255) / 256);
-#define AMQ_PACK(B_) hipLaunchKernelGGL((gptq_pack_kernel<B_>), dim3(blocks), dim3(256), 0, st, Q, R, group, W_q)
-    if (bits == 4) AMQ_PACK(4);
-    else if (bits == 3) AMQ_PACK(3);
-    else if (bits == 2) AMQ_PACK(2);
-    else return hipErrorInvalidValue;
-#undef AMQ_PACK
-    return hipGetLastError();
 }
 
 }  // namespace amq

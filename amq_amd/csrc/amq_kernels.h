@@ -337,7 +337,9 @@ inline int gptq_flags(int N) { return N / (64 / GPTQ_LANES); }
 inline size_t gptq_workspace_bytes(int N, int K) { return 5 * (size_t)N * K + 4 * (size_t)gptq_flags(N); }
 hipError_t launch_gptq_quantize(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero,
                                 void* row_loss, void* info, void* workspace, hipStream_t st);
-// byte codes [R, group] -> Format A (hqq/core/bitpack.py row chunks), one thread per packed word: the pack launch of the GPTQ solve, shared
+// what ends the GPTQ solve and AWQ's passes (amq_quant_pack.hip): the n per-wave nonfinite flags ORed into one word of the info block, and byte
+// codes [R, group] -> Format A (hqq/core/bitpack.py row chunks), one thread per packed word
+hipError_t launch_quant_flags(const int* NF, size_t n, int* info_word, hipStream_t st);
 hipError_t launch_pack_codes(const void* codes, size_t R, int group, int bits, void* W_q, hipStream_t st);
 
 // AWQ (amq_awq.hip).  quantize: 8 columns per thread, 256 threads per workgroup, round-to-nearest per group to byte codes, then the shared pack

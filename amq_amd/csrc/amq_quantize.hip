@@ -7,11 +7,10 @@
 //                         and its sum of |W - W_r| in the wave's accumulator -- the trace that lets one pass over W replace twenty.
 //   hqq_stop_kernel       one workgroup: adds the workgroups' partial errors per iteration in index order, walks the stop rule, writes the info
 //                         block {int32 stop, int32 nonfinite, float mean_err[20]}.
-//   hqq_emit_kernel<BITS> one thread per Format A word: re-forms the codes from W, s and Z[stop] and packs them (hqq/core/bitpack.py row chunks).
+//   hqq_emit_kernel<BITS> one thread per Format A word (amq_quant.cuh format_a_store): re-forms the codes from W, s and Z[stop] and packs them.
 // Every operation is its own fp32 rounding (-ffp-contract=off, IEEE division); sums are fixed trees, so a layer quantizes to the
 // same bits on every run.  tests/hqq_solver_ref.py restates the whole of it in torch.
-#include "amq_common.cuh"
-#include "amq_kernels.h"
+#include "amq_quant.cuh"
 
 namespace amq {
 
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(64 * HQQ_WAVES) void hqq_solve_kernel(const _Float1
         float mx = w[0], mn = w[0];
 #pragma unroll
         for (int v = 0; v < V; ++v) {
-            bad = bad || !(fabsf(w[v]) <= 65504.0f);
+            bad = bad || !finite(w[v]);
             mx = fmaxf(mx, w[v]);
             mn = fminf(mn, w[v]);
         }
@@ -144,33 +143,19 @@ template <int BITS>
 __global__ __launch_bounds__(256) void hqq_emit_kernel(const _Float16* __restrict__ W, const float* __restrict__ S, const float* __restrict__ Z,
                                                        const int* __restrict__ info, size_t R, int G, void* __restrict__ Wq,
                                                        _Float16* __restrict__ scale, _Float16* __restrict__ zero) {
-    constexpr int C = BITS == 4 ? 2 : BITS == 2 ? 4 : 10;
     constexpr float maxv = (float)((1 << BITS) - 1);
-    const size_t step = BITS == 3 ? (R + 9) / 10 : R / C;      // packed rows (3 bit: rows zero-padded to a multiple of 10)
-    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= step * (size_t)G) return;
-    const size_t row = gid / G;
-    const int col = (int)(gid % G);
     int stop = info[0];
     stop = stop < 0 ? 0 : (stop >= HQQ_ITERS ? HQQ_ITERS - 1 : stop);
     const float* Zs = Z + (size_t)stop * R;
-    uint32_t word = 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const size_t r = (size_t)c * step + row;
-        if (BITS == 3 && r >= R) continue;
+    format_a_store<BITS>(Wq, R, G, [&](size_t r, int col) {
         const float s = S[r], z = Zs[r];
         const float w = (float)W[r * G + col];
-        const float q = fminf(fmaxf(rintf(w * s + z), 0.0f), maxv);
-        const int shift = BITS == 3 ? 27 - 3 * c : 8 - BITS * (c + 1);       // chunk 0 sits in the top bits
-        word |= (uint32_t)q << shift;
         if (col == 0) {
             scale[r] = (_Float16)(1.0f / s);
             zero[r] = (_Float16)z;
         }
-    }
-    if (BITS == 3) ((uint32_t*)Wq)[gid] = word;
-    else ((uint8_t*)Wq)[gid] = (uint8_t)word;
+        return fminf(fmaxf(rintf(w * s + z), 0.0f), maxv);
+    });
 }
 
 hipError_t launch_hqq_quantize(const void* W, int N, int K, int bits, int group, int round_zero, void* W_q, void* scale, void* zero,
@@ -181,27 +166,19 @@ hipError_t launch_hqq_quantize(const void* W, int N, int K, int bits, int group,
     float* Epart = Z + (size_t)HQQ_ITERS * g.R;
     int* NF = (int*)(Epart + (size_t)HQQ_ITERS * g.wgs);
     const float maxv = (float)((1 << bits) - 1);
-#define AMQ_SOLVE(G_) hipLaunchKernelGGL((hqq_solve_kernel<G_>), dim3(g.wgs), dim3(64 * HQQ_WAVES), 0, st, (const _Float16*)W, g.P, g.R, g.T, maxv, \
-                                         round_zero, S, Z, Epart, NF)
-    if (group == 32) AMQ_SOLVE(32);
-    else if (group == 64) AMQ_SOLVE(64);
-    else if (group == 128) AMQ_SOLVE(128);
-    else if (group == 256) AMQ_SOLVE(256);
-    else return hipErrorInvalidValue;
-#undef AMQ_SOLVE
-    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = dispatch<32, 64, 128, 256>(group, [&](auto G) {
+            hipLaunchKernelGGL((hqq_solve_kernel<G()>), dim3(g.wgs), dim3(64 * HQQ_WAVES), 0, st, (const _Float16*)W, g.P, g.R, g.T, maxv, round_zero, S, Z,
+                               Epart, NF);
+            return hipGetLastError();
+        }))
+        return e;
     hipLaunchKernelGGL(hqq_stop_kernel, dim3(1), dim3(256), 0, st, Epart, NF, g.wgs, (float)((size_t)N * K), (int*)info);
     if (hipError_t e = hipGetLastError()) return e;
-    const size_t words = (bits == 3 ? (g.R + 9) / 10 : g.R * bits / 8) * (size_t)group;
-    const unsigned blocks = (unsigned)((words + 255) / 256);
-#define AMQ_EMIT(B_) hipLaunchKernelGGL((hqq_emit_kernel<B_>), dim3(blocks), dim3(256), 0, st, (const _Float16*)W, S, Z, (const int*)info, g.R, group, \
-                                        W_q, (_Float16*)scale, (_Float16*)zero)
-    if (bits == 4) AMQ_EMIT(4);
-    else if (bits == 3) AMQ_EMIT(3);
-    else if (bits == 2) AMQ_EMIT(2);
-    else return hipErrorInvalidValue;
-#undef AMQ_EMIT
-    return hipGetLastError();
+    return dispatch_bits(bits, [&](auto B) {
+        hipLaunchKernelGGL((hqq_emit_kernel<B()>), dim3(format_a_blocks(g.R, group, bits)), dim3(256), 0, st, (const _Float16*)W, S, Z, (const int*)info,
+                           g.R, group, W_q, (_Float16*)scale, (_Float16*)zero);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace amq

@@ -118,7 +118,59 @@ def repack_from_awq(qweight, scales, scaled_zeros, N, K, group=GROUP):
     return qn, mn
 
 
+# ---------------------------------------------------------------------------------------------------------------- the device quantizers
 QUANTIZE_GROUPS = (32, 64, 128, 256)      # group sizes the quantizer's solve kernel is built for
+GPTQ_GROUPS = (32, 64, 128)      # group sizes the GPTQ solve kernel is built for: those that fit its 128-column block
+AWQ_GROUPS = (32, 64, 128)       # group sizes the AWQ kernels are built for
+
+
+def _format_a_buffers(N, K, nbits, group, device):
+    """(W_q, scale, zero) of Format A for a layer [N, K]: R = N K / group rows of codes as int32 [(R + 9) // 10, group] (3 bit) or uint8
+    [R nbits // 8, group], scale and zero fp16 [R, 1]"""
+    R = N * K // group
+    if nbits == 3:
+        W_q = torch.empty((R + 9) // 10, group, dtype=torch.int32, device=device)
+    else:
+        W_q = torch.empty(R * nbits // 8, group, dtype=torch.uint8, device=device)
+    return W_q, torch.empty(R, 1, dtype=torch.float16, device=device), torch.empty(R, 1, dtype=torch.float16, device=device)
+
+
+def _dense_f16(t, who):
+    """a dense 2-d operand at the boundary: on the GPU, fp16 (bf16 / fp32 are cast, as the reference's ``.half()`` does before it quantizes)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 2:
+        raise ValueError(f"{who}: expected a 2-d tensor on the GPU")
+    if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"{who}: expected fp16 (or bf16 / fp32, cast to fp16), got {t.dtype}")
+    return t.detach().to(torch.float16).contiguous()
+
+
+def _quantize_shape(N, K, nbits, group_size, groups, serves):
+    """a quantizer family's shape check: ``groups`` are what its kernels are built for, ``serves`` is how it says so; returns the group as int"""
+    _check_shape(nbits, N, K)
+    if int(group_size) not in groups or K % int(group_size):
+        raise ValueError(f"{serves} (got {group_size})")
+    return int(group_size)
+
+
+def _workspace_words(query, who, **shape):
+    """what the C ABI's workspace query answers for ``shape`` (its arguments, in order) in int32 words; 0 bytes is its refusal"""
+    need = int(getattr(_lib.load(), query)(*shape.values()))
+    if need <= 0:
+        raise ValueError(f"{who} refuses " + ", ".join(f"{k}={v}" for k, v in shape.items()))
+    return (need + 3) // 4
+
+
+def _refuse_nonfinite(nonfinite, who, name, what):
+    if nonfinite:
+        raise ValueError(f"{who}: {'layer ' + name if name else 'W'}{what}")
+
+
+def _info_block(nbytes, device):
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
 
 
 class HQQQuantizeInfo:
@@ -138,27 +190,14 @@ def hqq_quantize_launch(W, nbits, group_size, round_zero, W_q, scale, zero, info
     """the bare entry point over caller-owned buffers (three launches on the current stream; no allocation, no read-back: capturable)"""
     N, K = W.shape
     _lib.check(_lib.load().amq_hqq_quantize_f16(_lib.ptr(W), N, K, int(nbits), int(group_size), int(bool(round_zero)), _lib.ptr(W_q), _lib.ptr(scale),
-                                                _lib.ptr(zero), _lib.ptr(info), _lib.ptr(workspace), workspace.numel() * workspace.element_size(),
-                                                _lib.current_stream()))
+                                                _lib.ptr(zero), _lib.ptr(info), _lib.ptr(workspace), _nbytes(workspace), _lib.current_stream()))
 
 
 def hqq_quantize_buffers(N, K, nbits, group_size, device):
     """(W_q, scale, zero, info, workspace) of the right sizes for ``hqq_quantize_launch``"""
-    _check_shape(nbits, N, K)
-    if int(group_size) not in QUANTIZE_GROUPS or K % int(group_size):
-        raise ValueError(f"the quantizer serves groups of 32, 64, 128 and 256 that divide K={K} (got {group_size})")
-    R = N * K // int(group_size)
-    if nbits == 3:
-        W_q = torch.empty((R + 9) // 10, group_size, dtype=torch.int32, device=device)
-    else:
-        W_q = torch.empty(R * nbits // 8, group_size, dtype=torch.uint8, device=device)
-    scale = torch.empty(R, 1, dtype=torch.float16, device=device)
-    zero = torch.empty(R, 1, dtype=torch.float16, device=device)
-    info = torch.empty(_lib.HQQ_INFO_BYTES // 4, dtype=torch.int32, device=device)
-    need = int(_lib.load().amq_hqq_quantize_workspace_bytes(N, K, int(group_size)))
-    if need <= 0:
-        raise ValueError(f"the quantizer refuses N={N}, K={K}, group={group_size}")
-    return W_q, scale, zero, info, _quantize_scratch.get(device, need // 4)
+    group_size = _quantize_shape(N, K, nbits, group_size, QUANTIZE_GROUPS, f"the quantizer serves groups of 32, 64, 128 and 256 that divide K={K}")
+    words = _workspace_words("amq_hqq_quantize_workspace_bytes", "the quantizer", N=N, K=K, group=group_size)
+    return (*_format_a_buffers(N, K, nbits, group_size, device), _info_block(_lib.HQQ_INFO_BYTES, device), _quantize_scratch.get(device, words))
 
 
 def hqq_quantize(W, nbits, group_size=GROUP, round_zero=None, return_info=False, bias=None, name=None):
@@ -168,11 +207,7 @@ def hqq_quantize(W, nbits, group_size=GROUP, round_zero=None, return_info=False,
     hqq_base_quant_config).  Raises ValueError if W holds an inf or NaN.  One synchronising read of the 88-byte info block per call.
     ``return_info``: also return the :class:`HQQQuantizeInfo`."""
     from .hqq_format import HQQWeights
-    if not isinstance(W, torch.Tensor) or not W.is_cuda or W.dim() != 2:
-        raise ValueError("W: expected a 2-d tensor on the GPU")
-    if W.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise ValueError(f"W: expected fp16 (or bf16 / fp32, cast to fp16), got {W.dtype}")
-    W = W.detach().to(torch.float16).contiguous()
+    W = _dense_f16(W, "W")
     N, K = W.shape
     nbits = int(nbits)
     if round_zero is None:
@@ -180,13 +215,9 @@ def hqq_quantize(W, nbits, group_size=GROUP, round_zero=None, return_info=False,
     W_q, scale, zero, info, workspace = hqq_quantize_buffers(N, K, nbits, group_size, W.device)
     hqq_quantize_launch(W, nbits, group_size, round_zero, W_q, scale, zero, info, workspace)
     got = HQQQuantizeInfo(info.cpu())
-    if got.nonfinite:
-        raise ValueError(f"hqq_quantize: {'layer ' + name if name else 'W'} holds inf or NaN values")
+    _refuse_nonfinite(got.nonfinite, "hqq_quantize", name, " holds inf or NaN values")
     h = HQQWeights(W_q, scale, zero, nbits, (N, K), int(group_size), bias, name)
     return (h, got) if return_info else h
-
-
-GPTQ_GROUPS = (32, 64, 128)      # group sizes the GPTQ solve kernel is built for: those that fit its 128-column block
 
 
 class GPTQHessian:
@@ -256,31 +287,19 @@ def gptq_quantize_launch(W, U, nbits, group_size, W_q, scale, zero, row_loss, in
     """the bare entry point over caller-owned buffers (three launches on the current stream; no allocation, no read-back: capturable)"""
     N, K = W.shape
     _lib.check(_lib.load().amq_gptq_quantize_f16(_lib.ptr(W), _lib.ptr(U), N, K, int(nbits), int(group_size), _lib.ptr(W_q), _lib.ptr(scale),
-                                                 _lib.ptr(zero), _lib.ptr(row_loss), _lib.ptr(info), _lib.ptr(workspace),
-                                                 workspace.numel() * workspace.element_size(), _lib.current_stream()))
+                                                 _lib.ptr(zero), _lib.ptr(row_loss), _lib.ptr(info), _lib.ptr(workspace), _nbytes(workspace),
+                                                 _lib.current_stream()))
 
 
 def gptq_quantize_buffers(N, K, nbits, group_size, device):
     """(W_q, scale, zero, row_loss, info, workspace) of the right sizes for ``gptq_quantize_launch``"""
-    _check_shape(nbits, N, K)
+    serves = "the GPTQ solve serves groups of 32, 64 and 128"
     if int(group_size) == 256:
-        raise ValueError("the GPTQ solve serves groups of 32, 64 and 128: a group of 256 would span two of its 128-column blocks")
-    if int(group_size) not in GPTQ_GROUPS:
-        raise ValueError(f"the GPTQ solve serves groups of 32, 64 and 128 (got {group_size})")
-    group_size = int(group_size)
-    R = N * K // group_size
-    if nbits == 3:
-        W_q = torch.empty((R + 9) // 10, group_size, dtype=torch.int32, device=device)
-    else:
-        W_q = torch.empty(R * nbits // 8, group_size, dtype=torch.uint8, device=device)
-    scale = torch.empty(R, 1, dtype=torch.float16, device=device)
-    zero = torch.empty(R, 1, dtype=torch.float16, device=device)
-    row_loss = torch.empty(N, dtype=torch.float32, device=device)
-    info = torch.empty(_lib.GPTQ_INFO_BYTES // 4, dtype=torch.int32, device=device)
-    need = int(_lib.load().amq_gptq_quantize_workspace_bytes(N, K, group_size))
-    if need <= 0:
-        raise ValueError(f"the GPTQ solve refuses N={N}, K={K}, group={group_size}")
-    return W_q, scale, zero, row_loss, info, _gptq_scratch.get(device, (need + 3) // 4)
+        serves += ": a group of 256 would span two of its 128-column blocks"
+    group_size = _quantize_shape(N, K, nbits, group_size, GPTQ_GROUPS, serves)
+    words = _workspace_words("amq_gptq_quantize_workspace_bytes", "the GPTQ solve", N=N, K=K, group=group_size)
+    return (*_format_a_buffers(N, K, nbits, group_size, device), torch.empty(N, dtype=torch.float32, device=device),
+            _info_block(_lib.GPTQ_INFO_BYTES, device), _gptq_scratch.get(device, words))
 
 
 def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, name=None):
@@ -291,11 +310,7 @@ def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, n
     columns.  Raises ValueError if a weight, an error or U's diagonal was not finite (or the diagonal not positive).  One synchronising read of the
     4-byte info block per call.  ``return_info``: also return the :class:`GPTQQuantizeInfo`."""
     from .hqq_format import HQQWeights
-    if not isinstance(W, torch.Tensor) or not W.is_cuda or W.dim() != 2:
-        raise ValueError("W: expected a 2-d tensor on the GPU")
-    if W.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise ValueError(f"W: expected fp16 (or bf16 / fp32, cast to fp16), got {W.dtype}")
-    W = W.detach().to(torch.float16).contiguous()
+    W = _dense_f16(W, "W")
     N, K = W.shape
     if not isinstance(U, torch.Tensor) or U.device != W.device:
         raise ValueError("U: expected a tensor on W's GPU")
@@ -305,29 +320,13 @@ def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, n
     W_q, scale, zero, row_loss, info, workspace = gptq_quantize_buffers(N, K, nbits, group_size, W.device)
     gptq_quantize_launch(W, U, nbits, group_size, W_q, scale, zero, row_loss, info, workspace)
     got = GPTQQuantizeInfo(info.cpu()[0].item(), row_loss)
-    if got.nonfinite:
-        raise ValueError(f"gptq_quantize: {'layer ' + name if name else 'W'}: a weight, an error or U's diagonal was not finite "
-                         "(or the diagonal not positive)")
+    _refuse_nonfinite(got.nonfinite, "gptq_quantize", name, ": a weight, an error or U's diagonal was not finite (or the diagonal not positive)")
     h = HQQWeights(W_q, scale, zero, nbits, (N, K), int(group_size), bias, name)
     return (h, got) if return_info else h
 
 
-AWQ_GROUPS = (32, 64, 128)       # group sizes the AWQ kernels are built for
-
-
 def _awq_check(N, K, nbits, group_size):
-    _check_shape(nbits, N, K)
-    if int(group_size) not in AWQ_GROUPS:
-        raise ValueError(f"the AWQ kernels serve groups of 32, 64 and 128 (got {group_size})")
-    return int(group_size)
-
-
-def _awq_weight(W, who):
-    if not isinstance(W, torch.Tensor) or not W.is_cuda or W.dim() != 2:
-        raise ValueError(f"{who}: expected a 2-d tensor on the GPU")
-    if W.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise ValueError(f"{who}: expected fp16 (or bf16 / fp32, cast to fp16), got {W.dtype}")
-    return W.detach().to(torch.float16).contiguous()
+    return _quantize_shape(N, K, nbits, group_size, AWQ_GROUPS, "the AWQ kernels serve groups of 32, 64 and 128")
 
 
 def awq_quantize_launch(W, nbits, group_size, col_scale, hi, lo, W_q, scale, zero, dense, info, workspace):
@@ -336,29 +335,19 @@ def awq_quantize_launch(W, nbits, group_size, col_scale, hi, lo, W_q, scale, zer
     N, K = W.shape
     _lib.check(_lib.load().amq_awq_quantize_f16(_lib.ptr(W), _lib.ptr(col_scale), _lib.ptr(hi), _lib.ptr(lo), N, K, int(nbits), int(group_size),
                                                 _lib.ptr(W_q), _lib.ptr(scale), _lib.ptr(zero), _lib.ptr(dense), _lib.ptr(info),
-                                                _lib.ptr(workspace), workspace.numel() * workspace.element_size(), _lib.current_stream()))
+                                                _lib.ptr(workspace), _nbytes(workspace), _lib.current_stream()))
 
 
 def awq_quantize_buffers(N, K, nbits, group_size, device, dense=False):
     """(W_q, scale, zero, dense, info, workspace) of the right sizes for ``awq_quantize_launch``: Format A buffers and ``dense`` None, or -- with
     ``dense`` -- the fp16 [N, K] matrix and W_q / scale / zero None"""
     group_size = _awq_check(N, K, nbits, group_size)
-    R = N * K // group_size
-    W_q = scale = zero = out = None
     if dense:
-        out = torch.empty(N, K, dtype=torch.float16, device=device)
+        out = (None, None, None, torch.empty(N, K, dtype=torch.float16, device=device))
     else:
-        if nbits == 3:
-            W_q = torch.empty((R + 9) // 10, group_size, dtype=torch.int32, device=device)
-        else:
-            W_q = torch.empty(R * nbits // 8, group_size, dtype=torch.uint8, device=device)
-        scale = torch.empty(R, 1, dtype=torch.float16, device=device)
-        zero = torch.empty(R, 1, dtype=torch.float16, device=device)
-    info = torch.empty(_lib.AWQ_INFO_BYTES // 4, dtype=torch.int32, device=device)
-    need = int(_lib.load().amq_awq_quantize_workspace_bytes(N, K, group_size))
-    if need <= 0:
-        raise ValueError(f"the AWQ quantizer refuses N={N}, K={K}, group={group_size}")
-    return W_q, scale, zero, out, info, _awq_scratch.get(device, (need + 3) // 4)
+        out = (*_format_a_buffers(N, K, nbits, group_size, device), None)
+    words = _workspace_words("amq_awq_quantize_workspace_bytes", "the AWQ quantizer", N=N, K=K, group=group_size)
+    return (*out, _info_block(_lib.AWQ_INFO_BYTES, device), _awq_scratch.get(device, words))
 
 
 def awq_quantize(W, nbits, group_size=GROUP, col_scale=None, hi=None, lo=None, dense=False, bias=None, name=None):
@@ -368,7 +357,7 @@ def awq_quantize(W, nbits, group_size=GROUP, col_scale=None, hi=None, lo=None, d
     fp16 [N, K] fake-quantized matrix divided by ``col_scale`` again -- the scale search's ``w_quantize_func(W * s) / s``.  W is fp16 (bf16 / fp32
     weights are cast at this boundary).  Raises ValueError on non-finite input.  One synchronising read of the 4-byte info block per call."""
     from .hqq_format import HQQWeights
-    W = _awq_weight(W, "W")
+    W = _dense_f16(W, "W")
     N, K = W.shape
     nbits = int(nbits)
     group_size = _awq_check(N, K, nbits, group_size)
@@ -383,8 +372,7 @@ def awq_quantize(W, nbits, group_size=GROUP, col_scale=None, hi=None, lo=None, d
         _need(lo, torch.float16, "lo", N * K // group_size)
     W_q, scale, zero, out, info, workspace = awq_quantize_buffers(N, K, nbits, group_size, W.device, dense=dense)
     awq_quantize_launch(W, nbits, group_size, col_scale, hi, lo, W_q, scale, zero, out, info, workspace)
-    if info.cpu()[0].item():
-        raise ValueError(f"awq_quantize: {'layer ' + name if name else 'W'}: a (scaled) weight, a bound or an output was not finite")
+    _refuse_nonfinite(info.cpu()[0].item(), "awq_quantize", name, ": a (scaled) weight, a bound or an output was not finite")
     if dense:
         return out
     return HQQWeights(W_q, scale, zero, nbits, (N, K), group_size, bias, name)
@@ -407,8 +395,8 @@ def awq_clip_launch(W, X, nbits, group_size, hi, lo, best, err, info, workspace)
     """the bare entry point over caller-owned buffers (two launches on the current stream; no allocation, no read-back: capturable)"""
     N, K = W.shape
     _lib.check(_lib.load().amq_awq_clip_f16(_lib.ptr(W), _lib.ptr(X), N, K, int(X.shape[0]), int(nbits), int(group_size), _lib.ptr(hi), _lib.ptr(lo),
-                                            _lib.ptr(best), _lib.ptr(err), _lib.ptr(info), _lib.ptr(workspace),
-                                            workspace.numel() * workspace.element_size(), _lib.current_stream()))
+                                            _lib.ptr(best), _lib.ptr(err), _lib.ptr(info), _lib.ptr(workspace), _nbytes(workspace),
+                                            _lib.current_stream()))
 
 
 def awq_clip_buffers(N, K, T, nbits, group_size, device):
@@ -419,11 +407,8 @@ def awq_clip_buffers(N, K, T, nbits, group_size, device):
     lo = torch.empty(N, kg, dtype=torch.float16, device=device)
     best = torch.empty(N, kg, dtype=torch.int32, device=device)
     err = torch.empty(N, kg, _lib.AWQ_STEPS, dtype=torch.float32, device=device)
-    info = torch.empty(_lib.AWQ_INFO_BYTES // 4, dtype=torch.int32, device=device)
-    need = int(_lib.load().amq_awq_clip_workspace_bytes(N, K, int(T), group_size))
-    if need <= 0:
-        raise ValueError(f"the AWQ clip search refuses N={N}, K={K}, T={T}, group={group_size}")
-    return hi, lo, best, err, info, _awq_scratch.get(device, (need + 3) // 4)
+    words = _workspace_words("amq_awq_clip_workspace_bytes", "the AWQ clip search", N=N, K=K, T=int(T), group=group_size)
+    return hi, lo, best, err, _info_block(_lib.AWQ_INFO_BYTES, device), _awq_scratch.get(device, words)
 
 
 def awq_clip(W, X, nbits, group_size=GROUP, return_info=False):
@@ -431,8 +416,8 @@ def awq_clip(W, X, nbits, group_size=GROUP, return_info=False):
     column-scaled weights) against the sampled activation rows X [T, K], on the matrix cores in the arithmetic include/amq_hip.h states: (hi, lo),
     fp16 [N, K / group], the bounds ``awq_quantize`` takes.  W and X are fp16 (bf16 / fp32 are cast at this boundary).  Raises ValueError on
     non-finite input.  One synchronising read of the 4-byte info block per call.  ``return_info``: also return the :class:`AWQClipInfo`."""
-    W = _awq_weight(W, "W")
-    X = _awq_weight(X, "X")
+    W = _dense_f16(W, "W")
+    X = _dense_f16(X, "X")
     N, K = W.shape
     if X.device != W.device or X.shape[1] != K or X.shape[0] < 1:
         raise ValueError(f"X: expected at least one row of {K} values on W's GPU")
@@ -440,8 +425,7 @@ def awq_clip(W, X, nbits, group_size=GROUP, return_info=False):
     hi, lo, best, err, info, workspace = awq_clip_buffers(N, K, X.shape[0], nbits, group_size, W.device)
     awq_clip_launch(W, X, nbits, group_size, hi, lo, best, err, info, workspace)
     got = AWQClipInfo(info.cpu()[0].item(), best, err)
-    if got.nonfinite:
-        raise ValueError("awq_clip: a weight or an error sum was not finite")
+    _refuse_nonfinite(got.nonfinite, "awq_clip", None, ": a weight or an error sum was not finite")
     return (hi, lo, got) if return_info else (hi, lo)
 
 
@@ -1735,7 +1719,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-for _name in ("hqq_quantize", "gptq_quantize", "gptq_quantize_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
+for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_quantize", "gptq_quantize_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup"):
     globals()[_name] = _on_tensor_device(globals()[_name])

@@ -15,6 +15,7 @@ Reference caches written by the CUDA build (``*_GPTQLinear.pt`` / ``*_FTLinear.p
 keys ``<module>.qweight|scales|zeros`` and ``<module>.qweight|scales|scaled_zeros``)
 are imported with ``load_reference_cache``.
 """
+import contextlib
 import os
 
 import torch
@@ -306,6 +307,77 @@ def _bits_of(bits, name, block):
     return int(bits)
 
 
+def _default_device(model, device):
+    """``device``, or the model's own GPU, else cuda:0"""
+    if device is None:
+        p = next(model.parameters())
+        device = p.device if p.is_cuda else torch.device("cuda:0")
+    return torch.device(device)
+
+
+def _block_linears(layer):
+    """{'self_attn.q_proj': module, ...} over arch.LINEARS of one decoder layer"""
+    from .arch import LINEARS
+    return {name: getattr(getattr(layer, name.split(".")[0]), name.split(".")[1]) for name in LINEARS}
+
+
+def _set_linear(layer, name, module):
+    parent_name, attr = name.split(".")
+    setattr(getattr(layer, parent_name), attr, module)
+
+
+def _rtn_dequantized(W, nbits, group_size):
+    """what hqq_format.quantize_rtn of W dequantizes to on the device: the round-to-nearest column of the calibrated quantizers' reports"""
+    from .hqq_format import quantize_rtn
+    r = quantize_rtn(W, nbits, group_size)
+    return ops.dequantize_hqq(r.W_q.contiguous(), r.scale.reshape(-1).contiguous(), r.zero.reshape(-1).contiguous(), nbits, *W.shape, group_size)
+
+
+class _BlockInputCaught(Exception):
+    pass
+
+
+@contextlib.contextmanager
+def _calibrating(model, samples, device):
+    """What a block-by-block calibration walk (GPTQ, AWQ) starts and ends with: the model is dense (TypeError) and moves to ``device``; ``samples``
+    are token-id tensors [1, seqlen] of one length (ValueError); with ``use_cache`` off, a forward pre-hook catches the first block's inputs and
+    keyword arguments over the samples.  Yields (device, inps, kwargs, run) with ``run(layer, x)`` a block's output for one input;
+    ``config.use_cache`` is put back on the way out, also when the walk raises."""
+    _decoder_linears(model)
+    samples = list(samples)
+    if not samples or any(s.dim() != 2 or s.shape != samples[0].shape for s in samples):
+        raise ValueError("samples: expected token-id tensors [1, seqlen] of one length")
+    device = _default_device(model, device)
+    model.to(device)
+    use_cache = getattr(model.config, "use_cache", None)
+    model.config.use_cache = False
+    inps, kwargs = [], {}
+
+    def catch(_, args, kw):
+        inps.append((args[0] if args else kw["hidden_states"]).detach())
+        kwargs.update({k: v for k, v in kw.items() if k != "hidden_states"})
+        raise _BlockInputCaught
+
+    def run(layer, x):
+        out = layer(x, **kwargs)
+        return out[0] if isinstance(out, (tuple, list)) else out
+
+    handle = model.model.layers[0].register_forward_pre_hook(catch, with_kwargs=True)
+    try:
+        try:
+            for s in samples:
+                try:
+                    model(s.to(device))
+                except _BlockInputCaught:
+                    pass
+        finally:
+            handle.remove()
+        yield device, inps, kwargs, run
+    finally:
+        if use_cache is not None:
+            model.config.use_cache = use_cache
+
+
 @torch.no_grad()
 def quantize_model(model, bits, group_size=128, device=None):
     """The reference's ``AutoHQQHFModel.quantize_model(model, BaseQuantizeConfig(nbits, group_size))`` (amq_quantization_proxy.py:36-37) on the GPU:
@@ -314,10 +386,7 @@ def quantize_model(model, bits, group_size=128, device=None):
     cuda:0).  ``bits``: 2, 3 or 4, or per-linear bit-widths as an arch's ``'linear'`` dict holds them.  The model is then ready for
     ``prepare_for_inference(backend='hip')`` (grouping and fusion), ``QuantLlama.from_hf`` and ``evaluate.eval_ppl`` / ``eval_loss``."""
     todo = _decoder_linears(model)
-    if device is None:
-        p = next(model.parameters())
-        device = p.device if p.is_cuda else torch.device("cuda:0")
-    device = torch.device(device)
+    device = _default_device(model, device)
     for b, full, parent, attr, lin in todo:
         lin.name = attr
         setattr(parent, attr, HIPQuantLinear.from_linear(lin, _bits_of(bits, full, b), group_size, device=device))
@@ -329,10 +398,7 @@ def quantize_bank(model, bits=(2, 3, 4), group_size=128, device=None):
     """Every decoder linear of a dense HF model at every bit-width of ``bits``: {nbits: {(block, 'self_attn.q_proj'): HQQWeights}} on the GPU, the
     model itself untouched -- what the reference's search holds as its per-bit model bank.  An arch picks one entry per (block, linear); the picks
     are ``QuantLlama(hqq_layers=...)``'s input."""
-    if device is None:
-        p = next(model.parameters())
-        device = p.device if p.is_cuda else torch.device("cuda:0")
-    device = torch.device(device)
+    device = _default_device(model, device)
     bank = {int(b): {} for b in bits}
     for b, full, _, attr, lin in _decoder_linears(model):
         w = lin.weight.detach().to(device)
@@ -344,10 +410,6 @@ def quantize_bank(model, bits=(2, 3, 4), group_size=128, device=None):
 
 TRUE_SEQUENTIAL = (("self_attn.k_proj", "self_attn.v_proj", "self_attn.q_proj"), ("self_attn.o_proj",), ("mlp.up_proj", "mlp.gate_proj"),
                    ("mlp.down_proj",))      # gptq.py:100-105
-
-
-class _BlockInputCaught(Exception):
-    pass
 
 
 def _proxy_loss(W, W_hat, H):
@@ -369,76 +431,36 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
     hqq_format.quantize_rtn at the same bits and group, "solver_loss": the solve's own sum of row losses (the reference's printed error), "dead":
     the number of dead columns, "bits"}``.  The model is then ready for ``prepare_for_inference(backend='hip')``."""
     from .arch import LINEARS
-    from .hqq_format import quantize_rtn
-    _decoder_linears(model)                                  # TypeError for a model that is not dense any more
-    samples = list(samples)
-    if not samples or any(s.dim() != 2 or s.shape != samples[0].shape for s in samples):
-        raise ValueError("samples: expected token-id tensors [1, seqlen] of one length")
-    if device is None:
-        p = next(model.parameters())
-        device = p.device if p.is_cuda else torch.device("cuda:0")
-    device = torch.device(device)
-    model.to(device)
-    layers = model.model.layers
-    use_cache = getattr(model.config, "use_cache", None)
-    model.config.use_cache = False
-    inps, kwargs = [], {}
-
-    def catch(_, args, kw):
-        inps.append((args[0] if args else kw["hidden_states"]).detach())
-        kwargs.update({k: v for k, v in kw.items() if k != "hidden_states"})
-        raise _BlockInputCaught
-
-    handle = layers[0].register_forward_pre_hook(catch, with_kwargs=True)
-    try:
-        for s in samples:
-            try:
-                model(s.to(device))
-            except _BlockInputCaught:
-                pass
-    finally:
-        handle.remove()
-
-    def run(layer, x):
-        out = layer(x, **kwargs)
-        return out[0] if isinstance(out, (tuple, list)) else out
-
     report = {}
-    for b, layer in enumerate(layers):
-        full = {name: getattr(getattr(layer, name.split(".")[0]), name.split(".")[1]) for name in LINEARS}
-        packed = {}
-        for names in (TRUE_SEQUENTIAL if true_sequential else (tuple(LINEARS),)):
-            hess = {name: ops.GPTQHessian(full[name].in_features, device) for name in names}
-            handles = [full[name].register_forward_hook(lambda _, inp, out, acc=hess[name]: acc.add_batch(inp[0].detach())) for name in names]
-            try:
-                for x in inps:
-                    run(layer, x)
-            finally:
-                for h in handles:
-                    h.remove()
-            for name in names:
-                lin, nb = full[name], _bits_of(bits, name, b)
-                attr = name.split(".")[1]
-                H = hess[name].H
-                U, dead = ops.gptq_hinv(H, percdamp, name=f"{b}.{name}")
-                W = lin.weight.detach().to(torch.float16).clone()
-                W[:, dead] = 0
-                bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
-                h, info = ops.gptq_quantize(W, U, nb, group_size, return_info=True, bias=bias, name=attr)
-                N, K = W.shape
-                W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, N, K, group_size)
-                r = quantize_rtn(W, nb, group_size)
-                W_rtn = ops.dequantize_hqq(r.W_q.contiguous(), r.scale.reshape(-1).contiguous(), r.zero.reshape(-1).contiguous(), nb, N, K, group_size)
-                report[(b, name)] = {"loss": _proxy_loss(W, W_hat, H), "rtn_loss": _proxy_loss(W, W_rtn, H), "solver_loss": info.loss,
-                                     "dead": int(dead.sum().item()), "bits": nb}
-                lin.weight.data = W_hat.to(lin.weight.dtype)
-                packed[name] = h
-        inps = [run(layer, x).detach() for x in inps]
-        for name, h in packed.items():
-            parent_name, attr = name.split(".")
-            setattr(getattr(layer, parent_name), attr, HIPQuantLinear.from_hqq(h, device=device))
-    if use_cache is not None:
-        model.config.use_cache = use_cache
+    with _calibrating(model, samples, device) as (device, inps, _, run):
+        for b, layer in enumerate(model.model.layers):
+            full = _block_linears(layer)
+            packed = {}
+            for names in (TRUE_SEQUENTIAL if true_sequential else (tuple(LINEARS),)):
+                hess = {name: ops.GPTQHessian(full[name].in_features, device) for name in names}
+                handles = [full[name].register_forward_hook(lambda _, inp, out, acc=hess[name]: acc.add_batch(inp[0].detach())) for name in names]
+                try:
+                    for x in inps:
+                        run(layer, x)
+                finally:
+                    for h in handles:
+                        h.remove()
+                for name in names:
+                    lin, nb = full[name], _bits_of(bits, name, b)
+                    H = hess[name].H
+                    U, dead = ops.gptq_hinv(H, percdamp, name=f"{b}.{name}")
+                    W = lin.weight.detach().to(torch.float16).clone()
+                    W[:, dead] = 0
+                    bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
+                    h, info = ops.gptq_quantize(W, U, nb, group_size, return_info=True, bias=bias, name=name.split(".")[1])
+                    W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, *W.shape, group_size)
+                    report[(b, name)] = {"loss": _proxy_loss(W, W_hat, H), "rtn_loss": _proxy_loss(W, _rtn_dequantized(W, nb, group_size), H),
+                                         "solver_loss": info.loss, "dead": int(dead.sum().item()), "bits": nb}
+                    lin.weight.data = W_hat.to(lin.weight.dtype)
+                    packed[name] = h
+            inps = [run(layer, x).detach() for x in inps]
+            for name, h in packed.items():
+                _set_linear(layer, name, HIPQuantLinear.from_hqq(h, device=device))
     return model, report
 
 
@@ -498,9 +520,8 @@ def awq_search_scale(inspect, linears, x, bits, group_size, kwargs=None, fake_qu
 def _awq_searches(layer, feats, kwargs, bits, b, group_size, fake_quant=None):
     """the four searches of one Llama-family block (auto_scale.py:166-220), each against the unmodified block: [(prev op, its kind, names, s,
     ratio, losses)]"""
-    from .arch import LINEARS
-    attn, mlp = layer.self_attn, layer.mlp
-    nb = {name: _bits_of(bits, name, b) for name in LINEARS}
+    attn, mlp, full = layer.self_attn, layer.mlp, _block_linears(layer)
+    nb = {name: _bits_of(bits, name, b) for name in full}
     todo = [(layer.input_layernorm, "norm", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), attn, kwargs)]
     if attn.v_proj.weight.shape == attn.o_proj.weight.shape:        # auto_scale.py:185 (not under GQA: v's rows are not o's columns)
         todo.append((attn.v_proj, "linear", ("self_attn.o_proj",), attn.o_proj, None))
@@ -508,7 +529,7 @@ def _awq_searches(layer, feats, kwargs, bits, b, group_size, fake_quant=None):
     todo.append((mlp.up_proj, "linear", ("mlp.down_proj",), mlp.down_proj, None))
     found = []
     for prev, kind, names, inspect, kw in todo:
-        linears = {name: getattr(getattr(layer, name.split(".")[0]), name.split(".")[1]) for name in names}
+        linears = {name: full[name] for name in names}
         s, ratio, losses = awq_search_scale(inspect, linears, feats[names[0]], nb, group_size, kwargs=kw, fake_quant=fake_quant)
         found.append((prev, kind, names, s, ratio, losses))
     return found
@@ -526,7 +547,7 @@ def _awq_apply_scale(layer, found, feats=None):
             if prev.bias is not None:
                 prev.bias.data[-s.numel():] = (prev.bias.data[-s.numel():].float() / s).to(prev.bias.dtype)
         for name in names:
-            lin = getattr(getattr(layer, name.split(".")[0]), name.split(".")[1])
+            lin = _block_linears(layer)[name]
             lin.weight.data = (lin.weight.data.float() * s.view(1, -1)).to(lin.weight.dtype)
         if feats is not None:
             feats[names[0]] = (feats[names[0]].float() / s).to(feats[names[0]].dtype)
@@ -553,87 +574,51 @@ def quantize_model_awq(model, bits, samples, group_size=128, clip=True, n_sample
     "rtn_loss": the same for hqq_format.quantize_rtn of the original weights}``.  The model is then ready for
     ``prepare_for_inference(backend='hip')``."""
     from .arch import LINEARS
-    from .hqq_format import quantize_rtn
-    _decoder_linears(model)                                  # TypeError for a model that is not dense any more
-    samples = list(samples)
-    if not samples or any(s.dim() != 2 or s.shape != samples[0].shape for s in samples):
-        raise ValueError("samples: expected token-id tensors [1, seqlen] of one length")
-    if device is None:
-        p = next(model.parameters())
-        device = p.device if p.is_cuda else torch.device("cuda:0")
-    device = torch.device(device)
-    model.to(device)
-    layers = model.model.layers
-    use_cache = getattr(model.config, "use_cache", None)
-    model.config.use_cache = False
-    inps, kwargs = [], {}
-
-    def catch(_, args, kw):
-        inps.append((args[0] if args else kw["hidden_states"]).detach())
-        kwargs.update({k: v for k, v in kw.items() if k != "hidden_states"})
-        raise _BlockInputCaught
-
-    handle = layers[0].register_forward_pre_hook(catch, with_kwargs=True)
-    try:
-        for s in samples:
-            try:
-                model(s.to(device))
-            except _BlockInputCaught:
-                pass
-    finally:
-        handle.remove()
-
-    def run(layer, x):
-        out = layer(x, **kwargs)
-        return out[0] if isinstance(out, (tuple, list)) else out
-
-    attn_kwargs = {k: v for k, v in kwargs.items() if k != "use_cache"}
     report = {}
-    for b, layer in enumerate(layers):
-        full = {name: getattr(getattr(layer, name.split(".")[0]), name.split(".")[1]) for name in LINEARS}
-        caught = {name: [] for name in set(_AWQ_INPUT_OF.values())}
-        handles = [full[name].register_forward_hook(lambda _, inp, out, acc=caught[name]: acc.append(inp[0].detach().to(torch.float16)))
-                   for name in caught]
-        try:
-            inps = [run(layer, x).detach() for x in inps]
-        finally:
-            for h in handles:
-                h.remove()
-        feats = {name: torch.cat(v, dim=0) for name, v in caught.items()}        # [windows, seqlen, K]
-        found = _awq_searches(layer, feats, attn_kwargs, bits, b, group_size)
-        searched = {name: (ratio, losses) for _, _, names, _, ratio, losses in found for name in names}
-        # the sampled rows of every input, before and after the scales reach them
-        sampled = {}
-        for name in caught:
-            rows = feats[name].reshape(-1, feats[name].shape[-1])
-            sampled[name] = rows[0::max(1, rows.shape[0] // int(n_sample_token))].clone()
-        dense_w = {name: full[name].weight.detach().to(torch.float16).clone() for name in LINEARS}
-        _awq_apply_scale(layer, found, feats)
-        for name in LINEARS:
-            lin, nb = full[name], _bits_of(bits, name, b)
-            parent_name, attr = name.split(".")
-            W = lin.weight.detach().to(torch.float16).contiguous()
-            N, K = W.shape
-            rows = feats[_AWQ_INPUT_OF[name]].reshape(-1, K)
-            xs = rows[0::max(1, rows.shape[0] // int(n_sample_token))].contiguous()
-            hi = lo = steps = None
-            if clip and attr not in ("q_proj", "k_proj"):       # auto_clip.py:16: hard to clip precisely in front of the q k product
-                hi, lo, info = ops.awq_clip(W, xs, nb, group_size, return_info=True)
-                steps = torch.bincount(info.best.reshape(-1).long(), minlength=10).tolist()
-            bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
-            h = ops.awq_quantize(W, nb, group_size, hi=hi, lo=lo, bias=bias, name=attr)
-            W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, N, K, group_size)
-            r = quantize_rtn(dense_w[name], nb, group_size)
-            W_rtn = ops.dequantize_hqq(r.W_q.contiguous(), r.scale.reshape(-1).contiguous(), r.zero.reshape(-1).contiguous(), nb, N, K, group_size)
-            x0 = sampled[_AWQ_INPUT_OF[name]]
-            want = torch.nn.functional.linear(x0, dense_w[name]).float()
-            ratio, losses = searched.get(name, (None, None))
-            report[(b, name)] = {"bits": nb, "ratio": ratio, "search_loss": losses, "clip_steps": steps,
-                                 "loss": float((torch.nn.functional.linear(xs, W_hat).float() - want).pow(2).mean().item()),
-                                 "rtn_loss": float((torch.nn.functional.linear(x0, W_rtn).float() - want).pow(2).mean().item())}
-            setattr(getattr(layer, parent_name), attr, HIPQuantLinear.from_hqq(h, device=device))
-    if use_cache is not None:
-        model.config.use_cache = use_cache
+    with _calibrating(model, samples, device) as (device, inps, kwargs, run):
+        attn_kwargs = {k: v for k, v in kwargs.items() if k != "use_cache"}
+        for b, layer in enumerate(model.model.layers):
+            full = _block_linears(layer)
+            caught = {name: [] for name in set(_AWQ_INPUT_OF.values())}
+            handles = [full[name].register_forward_hook(lambda _, inp, out, acc=caught[name]: acc.append(inp[0].detach().to(torch.float16)))
+                       for name in caught]
+            try:
+                inps = [run(layer, x).detach() for x in inps]
+            finally:
+                for h in handles:
+                    h.remove()
+            feats = {name: torch.cat(v, dim=0) for name, v in caught.items()}        # [windows, seqlen, K]
+            found = _awq_searches(layer, feats, attn_kwargs, bits, b, group_size)
+            searched = {name: (ratio, losses) for _, _, names, _, ratio, losses in found for name in names}
+            # the sampled rows of every input, before and after the scales reach them
+            sampled = {}
+            for name in caught:
+                rows = feats[name].reshape(-1, feats[name].shape[-1])
+                sampled[name] = rows[0::max(1, rows.shape[0] // int(n_sample_token))].clone()
+            dense_w = {name: full[name].weight.detach().to(torch.float16).clone() for name in LINEARS}
+            _awq_apply_scale(layer, found, feats)
+            for name in LINEARS:
+                lin, nb = full[name], _bits_of(bits, name, b)
+                attr = name.split(".")[1]
+                W = lin.weight.detach().to(torch.float16).contiguous()
+                N, K = W.shape
+                rows = feats[_AWQ_INPUT_OF[name]].reshape(-1, K)
+                xs = rows[0::max(1, rows.shape[0] // int(n_sample_token))].contiguous()
+                hi = lo = steps = None
+                if clip and attr not in ("q_proj", "k_proj"):       # auto_clip.py:16: hard to clip precisely in front of the q k product
+                    hi, lo, info = ops.awq_clip(W, xs, nb, group_size, return_info=True)
+                    steps = torch.bincount(info.best.reshape(-1).long(), minlength=10).tolist()
+                bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
+                h = ops.awq_quantize(W, nb, group_size, hi=hi, lo=lo, bias=bias, name=attr)
+                W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, N, K, group_size)
+                W_rtn = _rtn_dequantized(dense_w[name], nb, group_size)
+                x0 = sampled[_AWQ_INPUT_OF[name]]
+                want = torch.nn.functional.linear(x0, dense_w[name]).float()
+                ratio, losses = searched.get(name, (None, None))
+                report[(b, name)] = {"bits": nb, "ratio": ratio, "search_loss": losses, "clip_steps": steps,
+                                     "loss": float((torch.nn.functional.linear(xs, W_hat).float() - want).pow(2).mean().item()),
+                                     "rtn_loss": float((torch.nn.functional.linear(x0, W_rtn).float() - want).pow(2).mean().item())}
+                _set_linear(layer, name, HIPQuantLinear.from_hqq(h, device=device))
     return model, report
 
 

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import awq_search_ref as ref
+from quantize_common import assert_codes, assert_format_a, same_bits
 from test_awq_quantize_cpu import CASES, IDS, fixture, restated
 
 pytestmark = pytest.mark.gpu
@@ -20,15 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROFILE = os.path.join(ROOT, "profiles", "awq_quantize.json")
 OBSERVED = {}
 _SEEDED = {}
-
-
-def unpack_rows(W_q, nbits, R):
-    """Format A -> [R, G] integer codes (the inverse of hqq_format.pack_rows)"""
-    if nbits == 4:
-        return torch.cat([W_q >> 4, W_q & 15]).to(torch.int32)
-    if nbits == 2:
-        return torch.cat([(W_q >> 6) & 3, (W_q >> 4) & 3, (W_q >> 2) & 3, W_q & 3]).to(torch.int32)
-    return torch.cat([(W_q >> (27 - 3 * c)) & 7 for c in range(10)])[:R].to(torch.int32)
 
 
 def seeded(N, K, group, bits, T):
@@ -44,12 +36,6 @@ def seeded(N, K, group, bits, T):
         c = (0.25 + 3.0 * torch.rand(K, generator=g)).float()
         _SEEDED[key] = (W, X, c, ref.clip(W, X, bits, group, deploy=True))
     return _SEEDED[key]
-
-
-def same_bits(a, b):
-    view = {torch.float16: torch.int16, torch.float32: torch.int32}.get(a.dtype)
-    assert a.dtype == b.dtype and a.shape == b.shape, (a.dtype, b.dtype, a.shape, b.shape)
-    return torch.equal(a.view(view), b.view(view)) if view else torch.equal(a, b)
 
 
 def clip_identical(W, X, bits, group, want):
@@ -69,17 +55,11 @@ def quantize_identical(W, bits, group, hi, lo, col_scale=None):
     """the device's packed layer and dense output equal the restatement's, bit for bit"""
     from amq_amd import ops
     N, K = W.shape
-    R = N * K // group
     want = ref.quantize(W, bits, group, col_scale=col_scale, hi=None if hi is None else hi.cpu(), lo=None if lo is None else lo.cpu(), deploy=True)
     cs = None if col_scale is None else col_scale.to(DEV)
     h = ops.awq_quantize(W.to(DEV), bits, group, col_scale=cs, hi=hi, lo=lo)
-    assert tuple(h.shape) == (N, K) and h.nbits == bits and h.group_size == group
-    if bits == 3:
-        assert h.W_q.dtype == torch.int32 and tuple(h.W_q.shape) == ((R + 9) // 10, group)
-    else:
-        assert h.W_q.dtype == torch.uint8 and tuple(h.W_q.shape) == (R * bits // 8, group)
-    q = unpack_rows(h.W_q.cpu(), bits, R)
-    assert torch.equal(q, want["q"]), f"codes: {int((q != want['q']).sum())} of {q.numel()} differ"
+    assert_format_a(h, bits, group, (N, K))
+    assert_codes(h, want["q"])
     assert same_bits(h.scale.cpu(), want["scale"]) and same_bits(h.zero.cpu(), want["zero"]), "scale / zero"
     W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), bits, N, K, group).cpu()
     assert torch.equal(W_hat.float(), want["W_hat"]), "the packed layer dequantizes to another weight than the search saw"

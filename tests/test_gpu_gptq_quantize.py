@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import gptq_solver_ref as ref
+from quantize_common import assert_codes, assert_format_a, same_bits
 from test_gptq_quantize_cpu import CASES, IDS, fixture, restated, rtn_weights
 
 pytestmark = pytest.mark.gpu
@@ -20,15 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROFILE = os.path.join(ROOT, "profiles", "gptq_quantize.json")
 OBSERVED = {}
 _SEEDED = {}
-
-
-def unpack_rows(W_q, nbits, R):
-    """Format A -> [R, G] integer codes (the inverse of hqq_format.pack_rows)"""
-    if nbits == 4:
-        return torch.cat([W_q >> 4, W_q & 15]).to(torch.int32)
-    if nbits == 2:
-        return torch.cat([(W_q >> 6) & 3, (W_q >> 4) & 3, (W_q >> 2) & 3, W_q & 3]).to(torch.int32)
-    return torch.cat([(W_q >> (27 - 3 * c)) & 7 for c in range(10)])[:R].to(torch.int32)
 
 
 def seeded(N, K, group, bits):
@@ -53,21 +45,14 @@ def seeded(N, K, group, bits):
 
 def identical(h, info, want, nbits, group, shape):
     """codes, scale, zero and row_loss of a device result equal the restatement's, bit for bit; Format A's shapes and dtypes"""
-    N, K = shape
-    R = N * K // group
-    assert tuple(h.shape) == (N, K) and h.nbits == nbits and h.group_size == group
-    if nbits == 3:
-        assert h.W_q.dtype == torch.int32 and tuple(h.W_q.shape) == ((R + 9) // 10, group)
-    else:
-        assert h.W_q.dtype == torch.uint8 and tuple(h.W_q.shape) == (R * nbits // 8, group)
-    assert h.scale.dtype == torch.float16 and h.zero.dtype == torch.float16 and tuple(h.scale.shape) == (R, 1) == tuple(h.zero.shape)
+    N = shape[0]
+    assert_format_a(h, nbits, group, shape)
     assert info.nonfinite == 0 and want["nonfinite"] == 0
-    q = unpack_rows(h.W_q.cpu(), nbits, R)
-    assert torch.equal(q, want["q"]), f"codes: {int((q != want['q']).sum())} of {q.numel()} differ"
-    assert torch.equal(h.scale.cpu().view(torch.int16), want["scale"].view(torch.int16)), "scale"
-    assert torch.equal(h.zero.cpu().view(torch.int16), want["zero"].view(torch.int16)), "zero"
+    assert_codes(h, want["q"])
+    assert same_bits(h.scale.cpu(), want["scale"]), "scale"
+    assert same_bits(h.zero.cpu(), want["zero"]), "zero"
     assert info.row_loss.dtype == torch.float32 and tuple(info.row_loss.shape) == (N,)
-    assert torch.equal(info.row_loss.cpu().view(torch.int32), want["row_loss"].view(torch.int32)), "row_loss"
+    assert same_bits(info.row_loss.cpu(), want["row_loss"]), "row_loss"
     assert info.loss == pytest.approx(want["loss"], rel=1e-12)         # (fp64 sums of the same fp32 values, in the device's and the host's order)
 
 

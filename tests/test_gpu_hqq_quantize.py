@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import hqq_solver_ref as ref
+from quantize_common import HQQ_DIGEST_CASES, assert_codes, hqq_digest, hqq_digest_key, unpack_rows
 from test_hqq_quantize_cpu import CASES
 
 pytestmark = pytest.mark.gpu
@@ -22,15 +23,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROFILE = os.path.join(ROOT, "profiles", "hqq_quantize.json")
 OBSERVED = {}
 _REF = {}
-
-
-def unpack_rows(W_q, nbits, R):
-    """Format A -> [R, G] integer codes (the inverse of hqq_format.pack_rows)"""
-    if nbits == 4:
-        return torch.cat([W_q >> 4, W_q & 15]).to(torch.int32)
-    if nbits == 2:
-        return torch.cat([(W_q >> 6) & 3, (W_q >> 4) & 3, (W_q >> 2) & 3, W_q & 3]).to(torch.int32)
-    return torch.cat([(W_q >> (27 - 3 * c)) & 7 for c in range(10)])[:R].to(torch.int32)
 
 
 def restated(key, W, nbits, group):
@@ -118,11 +110,24 @@ def test_several_workgroups_against_the_restatement(N, K, bits, group):
     compare(name, h, info, r["q"], r["scale"], r["zero"], r)
     again, info2 = ops.hqq_quantize(Wd, bits, group, return_info=True)
     assert torch.equal(again.W_q, h.W_q) and torch.equal(again.scale, h.scale) and torch.equal(again.zero, h.zero)
+    assert_codes(again, unpack_rows(h.W_q.cpu(), bits, N * K // group))
     assert info2.stop == info.stop and torch.equal(info2.mean_err, info.mean_err)
     with _lib.routed_to(_lib.open_twin()):
         twin, info3 = ops.hqq_quantize(Wd, bits, group, return_info=True)
     assert torch.equal(twin.W_q, h.W_q) and torch.equal(twin.scale, h.scale) and torch.equal(twin.zero, h.zero)
     assert info3.stop == info.stop and torch.equal(info3.mean_err, info.mean_err)
+
+
+@pytest.mark.parametrize("N,K,group,bits", HQQ_DIGEST_CASES)
+def test_bits_of_the_recorded_commit(N, K, group, bits):
+    """W_q, scale, zero and the info block are, byte for byte, what the commit recorded in tests/golden/hqq_digests.json gave (the restatement
+    holds the solver within 1 % of the groups only, which a changed rounding could pass): tests/golden/gen_hqq_digests.py wrote the file"""
+    from amq_amd import ops
+    doc = json.load(open(os.path.join(ROOT, "tests", "golden", "hqq_digests.json")))
+    h, info = ops.hqq_quantize(multi_w(N, K).to(DEV), bits, group, return_info=True)
+    got, want = hqq_digest(h, info), doc["cases"][hqq_digest_key(N, K, group, bits)]
+    assert got == want, (f"{[k for k in want if got[k] != want[k]]} differ from commit {doc['commit'][:7]}; recorded under HIP {doc['hip']}, "
+                         f"this run under HIP {torch.version.hip}")
 
 
 def test_round_zero_option_and_wider_dtypes():
