@@ -1012,7 +1012,7 @@ int amq_attn_prefill_xfrag_f16(const void* q, const void* k, const void* v, void
     return check_hip(amq::launch_attn_prefill(a, (hipStream_t)stream), "attn_prefill_xfrag");
 }
 
-/* ---- token tails and set_token: nine entry points, one set of shared checks.  What differs between them is the TailForm ("Decode-step
+/* ---- token tails and set_token: ten entry points, one set of shared checks.  What differs between them is the TailForm ("Decode-step
    entry points: what is checked") and what each adds behind tail_check ---- */
 enum Vocab8 { V8_NEVER, V8_TWO_ROWS, V8_ALWAYS };       // when vocab % 8 == 0 is demanded (16-byte aligned rows of logits): never / from two rows / always
 struct TailForm {
@@ -1214,6 +1214,20 @@ int amq_decode_tail_lookup_f16(const void* logits, int vocab, const void* embed,
     amq::LookupArgs a{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, step_states, (_Float16*)x, (const _Float16*)rope_table,
                       rope_rows, suppress_ids, (int*)lookup_state, history, history_cap};
     return check_hip(amq::launch_decode_tail_lookup(a, rows, (hipStream_t)stream), "decode_tail_lookup");
+}
+
+int amq_decode_tail_lookup_sample_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
+                                      const void* rope_table, int rope_rows, int rows, const int* suppress_ids, void* lookup_state, int* history,
+                                      int history_cap, void* sample_state, const float* u_in, unsigned char* kept_out, void* stream) {
+    if (!sample_state) return fail(AMQ_EINVAL, "sample_state: the 128-byte device block of sampling parameters is required (null)");
+    if (!lookup_state || !history) return fail(AMQ_EINVAL, "lookup_state (the 128-byte device block) and history are required (null)");
+    if (int rc = tail_check(TAIL_LOOKUP, logits, vocab, embed, hidden, token, step_states, x, rope_table, step_states, rope_rows, rows)) return rc;
+    if (history_cap < rope_rows || history_cap > (1 << 24))
+        return fail(AMQ_ESHAPE, "history_cap must hold the whole cache (max_seq = rope_rows = %d) and at most 2^24 tokens, got %d", rope_rows, history_cap);
+    amq::LookupSampleArgs a{{(const _Float16*)logits, vocab, (const _Float16*)embed, hidden, token, step_states, (_Float16*)x,
+                             (const _Float16*)rope_table, rope_rows, suppress_ids, (int*)lookup_state, history, history_cap},
+                            (int*)sample_state, u_in, kept_out};
+    return check_hip(amq::launch_decode_tail_lookup_sample(a, rows, (hipStream_t)stream), "decode_tail_lookup_sample");
 }
 
 int amq_rope_table_f16(void* table, int max_seq, float rope_theta, void* stream) {

@@ -253,6 +253,15 @@ struct LookupArgs {
     int history_cap;
 };
 hipError_t launch_decode_tail_lookup(const LookupArgs& a, int rows, hipStream_t st);
+// the same tail with every row's token DRAWN by the sampler of amq_sample.hip instead of its arg-max (row j: draw counter SMP_DRAW + j, sequence 0);
+// the last arriver advances SMP_DRAW by 1 + accepted drafts.  No EOS bookkeeping; SMP_ARRIVE is not used.
+struct LookupSampleArgs {
+    LookupArgs lk;
+    int* sample_state;          // SMP_WORDS int32
+    const float* u_in;          // [rows] uniform numbers given by the caller, or null: generated
+    unsigned char* kept;        // [rows, vocab] kept-set mask out, or null
+};
+hipError_t launch_decode_tail_lookup_sample(const LookupSampleArgs& a, int rows, hipStream_t st);
 
 // evaluation metrics over rows of logits (amq_eval.hip): one workgroup per row; strides in elements; lse_out / argmax_out / labels may be null
 hipError_t launch_logit_nll(const void* logits, long long row_stride, const void* labels, int M, int V, float* nll_out, float* lse_out,

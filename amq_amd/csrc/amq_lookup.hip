@@ -15,8 +15,12 @@
 //   * the next step's inputs: token[0] = argmax[n], token[j] = draft j (clamped into the vocabulary; the unclamped value stays in the state block for
 //     the comparison), x[j] = embed[token[j]], block j's position = new position + j (saturating at rope_rows) and its cos/sin row.
 // Everything that changes between replays lives in device memory.  Vector stores and ordinary atomics only.
-#include "amq_common.cuh"
-#include "amq_kernels.h"
+//
+// decode_tail_lookup_sample_kernel is the same tail under sampling: every workgroup DRAWS its row's token with the sampler of amq_sample_body.cuh
+// (row j: draw counter c + j, sequence 0) in the place of the arg-max, and the last arriver -- the same device function, lk_last_arriver -- also
+// advances the 64-bit draw counter by n + 1: the token emitted at index i of the sequence is drawn with counter i whichever row of whichever step
+// computes it, so the output is what one-row sampled decoding draws from the same logits.
+#include "amq_sample_body.cuh"
 
 namespace amq {
 
@@ -25,64 +29,16 @@ constexpr int LK_MAX_ROWS = 8;
 constexpr int LK_MAX_SUPPRESS = 8;
 constexpr int LK_E_BITS = 24;                   // a continuation start fits 24 bits (history_cap <= 2^24: checked by the C ABI)
 
-__global__ __launch_bounds__(LK_THREADS) void decode_tail_lookup_kernel(LookupArgs a) {
-    __shared__ float smax[LK_THREADS / 64];
-    __shared__ int sidx[LK_THREADS / 64];
+// What the last workgroup to arrive does once every row's chosen token is in LK_ARGMAX + row: acceptance, history, counters, proposal and the next
+// step's inputs.  SAMPLED: the chosen tokens are draws -- the draw counter (draw0, draw1: what this workgroup read before its ticket, as every other
+// one did) moves on by n + 1.  Every thread of the workgroup must call it.
+template <bool SAMPLED>
+__device__ __forceinline__ void lk_last_arriver(const LookupArgs& a, int R, int* smp, unsigned draw0, unsigned draw1) {
     __shared__ unsigned skey[LK_THREADS / 64];
-    __shared__ int s_last, s_n, s_len, s_len0, s_pos;
+    __shared__ int s_n, s_len, s_len0, s_pos;
     __shared__ int s_emit[LK_MAX_ROWS], s_tok[LK_MAX_ROWS], s_posj[LK_MAX_ROWS];
-    const int tid = threadIdx.x, row = blockIdx.x, R = (int)gridDim.x;
-    const _Float16* logits = a.logits + (size_t)row * a.vocab;
+    const int tid = threadIdx.x;
     int* const st = a.state;
-
-    // ---- arg-max of this row (decode_tail_kernel: first maximum, suppressed ids never chosen)
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    int sup[LK_MAX_SUPPRESS];
-#pragma unroll
-    for (int j = 0; j < LK_MAX_SUPPRESS; ++j) sup[j] = a.suppress ? a.suppress[j] : -1;
-    auto allowed = [&](int idx) {
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < LK_MAX_SUPPRESS; ++j) ok = ok && idx != sup[j];
-        return ok;
-    };
-    const int chunks = a.vocab >> 3;
-    for (int c = tid; c < chunks; c += LK_THREADS) {
-        const h8 v = *(const h8*)(logits + 8 * c);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float f = (float)v[e];
-            if (f > best && (!a.suppress || allowed(8 * c + e))) { best = f; bi = 8 * c + e; }
-        }
-    }
-    for (int i = 8 * chunks + tid; i < a.vocab; i += LK_THREADS) {
-        const float f = (float)logits[i];
-        if ((f > best || (f == best && i < bi)) && (!a.suppress || allowed(i))) { best = f; bi = i; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oi = __shfl_xor(bi, off);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if ((tid & 63) == 0) { smax[tid >> 6] = best; sidx[tid >> 6] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        float b = smax[0];
-        int ix = sidx[0];
-        for (int w = 1; w < LK_THREADS / 64; ++w)
-            if (smax[w] > b || (smax[w] == b && sidx[w] < ix)) { b = smax[w]; ix = sidx[w]; }
-        if (ix == 0x7fffffff) ix = 0;
-        // the row's result, then the ticket (release); the last arriver's ticket (acquire) sees every row's
-        __hip_atomic_store(&st[LK_ARGMAX + row], ix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int arrived = __hip_atomic_fetch_add(&st[LK_TICKET], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = arrived == R - 1;
-        if (last) __hip_atomic_store(&st[LK_TICKET], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // zero before and after every launch
-        s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return;
 
     // ---- the last arriver: acceptance, history, counters
     int D = st[LK_DRAFTS];
@@ -108,6 +64,11 @@ __global__ __launch_bounds__(LK_THREADS) void decode_tail_lookup_kernel(LookupAr
         st[LK_COUNT] = len0 + n + 1;
         st[LK_STEPS] = st[LK_STEPS] + 1;
         st[LK_ACCEPTED] = n;
+        if (SAMPLED) {
+            const unsigned long long c = (((unsigned long long)draw1 << 32) | draw0) + (unsigned)(n + 1);
+            smp[SMP_DRAW] = (int)(unsigned)c;
+            smp[SMP_DRAW + 1] = (int)(unsigned)(c >> 32);
+        }
         s_n = n;
         s_len0 = len0;
         s_len = len0 + n + 1;
@@ -185,8 +146,101 @@ __global__ __launch_bounds__(LK_THREADS) void decode_tail_lookup_kernel(LookupAr
     }
 }
 
+__global__ __launch_bounds__(LK_THREADS) void decode_tail_lookup_kernel(LookupArgs a) {
+    __shared__ float smax[LK_THREADS / 64];
+    __shared__ int sidx[LK_THREADS / 64];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, row = blockIdx.x, R = (int)gridDim.x;
+    const _Float16* logits = a.logits + (size_t)row * a.vocab;
+    int* const st = a.state;
+
+    // ---- arg-max of this row (decode_tail_kernel: first maximum, suppressed ids never chosen)
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    int sup[LK_MAX_SUPPRESS];
+#pragma unroll
+    for (int j = 0; j < LK_MAX_SUPPRESS; ++j) sup[j] = a.suppress ? a.suppress[j] : -1;
+    auto allowed = [&](int idx) {
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < LK_MAX_SUPPRESS; ++j) ok = ok && idx != sup[j];
+        return ok;
+    };
+    const int chunks = a.vocab >> 3;
+    for (int c = tid; c < chunks; c += LK_THREADS) {
+        const h8 v = *(const h8*)(logits + 8 * c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float f = (float)v[e];
+            if (f > best && (!a.suppress || allowed(8 * c + e))) { best = f; bi = 8 * c + e; }
+        }
+    }
+    for (int i = 8 * chunks + tid; i < a.vocab; i += LK_THREADS) {
+        const float f = (float)logits[i];
+        if ((f > best || (f == best && i < bi)) && (!a.suppress || allowed(i))) { best = f; bi = i; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if ((tid & 63) == 0) { smax[tid >> 6] = best; sidx[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        float b = smax[0];
+        int ix = sidx[0];
+        for (int w = 1; w < LK_THREADS / 64; ++w)
+            if (smax[w] > b || (smax[w] == b && sidx[w] < ix)) { b = smax[w]; ix = sidx[w]; }
+        if (ix == 0x7fffffff) ix = 0;
+        // the row's result, then the ticket (release); the last arriver's ticket (acquire) sees every row's
+        __hip_atomic_store(&st[LK_ARGMAX + row], ix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int arrived = __hip_atomic_fetch_add(&st[LK_TICKET], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = arrived == R - 1;
+        if (last) __hip_atomic_store(&st[LK_TICKET], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // zero before and after every launch
+        s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+
+    lk_last_arriver<false>(a, R, nullptr, 0u, 0u);
+}
+
+// one workgroup per row as above, the row's token drawn instead of its arg-max
+__global__ __launch_bounds__(LK_THREADS) void decode_tail_lookup_sample_kernel(LookupSampleArgs s) {
+    static_assert(LK_THREADS == SMP_THREADS, "the sampler's workgroup");
+    __shared__ unsigned s_draw;
+    __shared__ int s_last;
+    const LookupArgs& a = s.lk;
+    const int tid = threadIdx.x, row = blockIdx.x, R = (int)gridDim.x;
+    int* const st = a.state;
+    int* const smp = s.sample_state;
+    // the draw counter c of this step: read by every workgroup before its ticket, advanced by the last arriver behind all of them
+    const unsigned draw0 = (unsigned)smp[SMP_DRAW], draw1 = (unsigned)smp[SMP_DRAW + 1];
+    if (tid == 0) s_draw = 0;                                  // (the sampler's first barrier is behind this)
+    struct { const _Float16* logits; int vocab; const int* suppress; int* state; const float* u_in; unsigned char* kept; }
+        r{a.logits, a.vocab, a.suppress, smp, s.u_in, s.kept};
+    smp_sample_row(r, row, (unsigned)row, 0u, &s_draw);        // row j draws with counter c + j, sequence 0
+    if (tid == 0) {
+        // the row's result, then the ticket (release); the last arriver's ticket (acquire) sees every row's
+        __hip_atomic_store(&st[LK_ARGMAX + row], (int)s_draw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int arrived = __hip_atomic_fetch_add(&st[LK_TICKET], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = arrived == R - 1;
+        if (last) __hip_atomic_store(&st[LK_TICKET], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // zero before and after every launch
+        s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    lk_last_arriver<true>(a, R, smp, draw0, draw1);
+}
+
 hipError_t launch_decode_tail_lookup(const LookupArgs& a, int rows, hipStream_t st) {
     hipLaunchKernelGGL(decode_tail_lookup_kernel, dim3(rows), dim3(LK_THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_tail_lookup_sample(const LookupSampleArgs& a, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(decode_tail_lookup_sample_kernel, dim3(rows), dim3(LK_THREADS), 0, st, a);
     return hipGetLastError();
 }
 

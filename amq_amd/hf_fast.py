@@ -38,6 +38,11 @@ do_sample=False, num_beams=1, ...)`` for ONE sequence, 1 <= k <= 7 and 1 <= g <=
 on the runner (``QuantLlama(lookup=k, ngram_max=g)``, cached under ``("lookup", k)``; g is one word of its device block): every step verifies k continuations guessed from the
 sequence's own history in one pass of the weights.  The tokens are the greedy decode's whatever is guessed; the guesses follow the MOST RECENT earlier
 occurrence of the last g .. 1 tokens (HF takes the earliest: only the acceptance rate differs).  ``lookup_request`` is the routing predicate.
+With BOTH ``lookup=True`` and ``sampling=True`` the same call with ``do_sample=True`` (and ``temperature`` / ``top_k`` / ``top_p``) is served as
+well, fixed-length or up to the first EOS id: every row's token is drawn, a guess is accepted while it equals the draw of the row in front of it --
+what transformers' own prompt-lookup loop does under ``do_sample`` -- and the token at index i is always drawn with draw counter i, so the output
+is distributed as plain sampled decoding's whatever is guessed (one runner per k serves greedy and sampled calls; the seed comes from torch's
+global CPU generator as for plain sampled calls).  With either flag off such a call goes to HF.
 
 With ``convert_model_to_hip(model, scoring=True)`` (opt-in as well) ``model(input_ids, start_pos=0, labels=lab, use_cache=False)`` stays on the fast
 path and returns ``loss`` as well: HF's causal-LM loss -- the mean cross-entropy of row t against ``lab[:, t + 1]``, labels of -100 ignored -- formed
@@ -74,12 +79,13 @@ _LOOKUP_KWARGS = ("input_ids", "max_new_tokens", "min_new_tokens", "do_sample", 
                   "return_dict_in_generate", "output_scores", "output_logits", "output_attentions", "output_hidden_states")
 
 
-def lookup_request(kwargs, batch, enabled=True):
+def lookup_request(kwargs, batch, enabled=True, sampling=False):
     """The routing predicate of prompt-lookup calls, a pure host function of the call's keyword arguments: -> (k, g) = (drafts per step, longest
     suffix looked up) when ``generate(**kwargs)`` on ``batch`` sequences is a call the lookup runner serves, else None (HF's own generate).
     Served: ``convert_model_to_hip(model, lookup=True)`` (``enabled``), one sequence, ``prompt_lookup_num_tokens`` = 1 .. 7 (an int),
     ``max_matching_ngram_size`` = 1 .. 4 (HF's default 2 when absent or None), greedy (``do_sample`` false), one beam, and no argument the
-    runner does not know."""
+    runner does not know.  ``sampling`` (``convert_model_to_hip(model, lookup=True, sampling=True)``): a ``do_sample=True`` call is served as
+    well and may carry ``temperature`` / ``top_k`` / ``top_p``."""
     if not enabled or batch != 1:
         return None
     k = kwargs.get("prompt_lookup_num_tokens")
@@ -89,9 +95,10 @@ def lookup_request(kwargs, batch, enabled=True):
         return None
     if not 1 <= k <= LOOKUP_MAX_DRAFTS or not 1 <= g <= LOOKUP_MAX_NGRAM:
         return None
-    if kwargs.get("do_sample") not in (False, None) or kwargs.get("num_beams") not in (1, None):
+    if (kwargs.get("do_sample") not in (False, None) and not sampling) or kwargs.get("num_beams") not in (1, None):
         return None
-    if any(key not in _LOOKUP_KWARGS + ("prompt_lookup_num_tokens", "max_matching_ngram_size") for key in kwargs):
+    known = _LOOKUP_KWARGS + ("prompt_lookup_num_tokens", "max_matching_ngram_size") + (("temperature", "top_k", "top_p") if sampling else ())
+    if any(key not in known for key in kwargs):
         return None
     return k, g
 
@@ -126,7 +133,7 @@ def _lookup_runner(model, need, k, g):
     None when ``need`` (prompt + new tokens + the k draft rows) passes the model's max_position_embeddings: the caller falls through to HF."""
     if need > _limit(model):
         return None
-    r, _ = _bound(model, ("lookup", k), need, lookup=k, ngram_max=g)
+    r, _ = _bound(model, ("lookup", k), need, lookup=k, ngram_max=g, lookup_sampling=True)      # (one runner serves greedy and sampled calls)
     r.set_ngram_max(g)
     return r
 
@@ -265,7 +272,8 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     if "prompt_lookup_num_tokens" in kw or "max_matching_ngram_size" in kw:
         if kw.get("prompt_lookup_num_tokens") is None:
             return fall()
-        look = lookup_request(kwargs, ids.shape[0] if _plain_ids(ids) else 0, self.__dict__.get("_amq_lookup", False))
+        look = lookup_request(kwargs, ids.shape[0] if _plain_ids(ids) else 0, self.__dict__.get("_amq_lookup", False),
+                              self.__dict__.get("_amq_sampling", False))
         if look is None:
             return fall()
         kw.pop("prompt_lookup_num_tokens", None)
@@ -310,22 +318,28 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     B, S = ids.shape
     n = int(n)
     nmin = 0 if nmin is None else int(nmin)
-    if do_sample and not (float(warp["temperature"]) > 0.0 and int(warp["top_k"]) >= 0 and 0.0 < float(warp["top_p"]) <= 1.0):
+    if do_sample and warp and not (float(warp["temperature"]) > 0.0 and int(warp["top_k"]) >= 0 and 0.0 < float(warp["top_p"]) <= 1.0):
         return fall()                                           # (HF raises its own error for these)
     if nmin > n or (not fixed and pad is not None and not 0 <= int(pad) < int(self.config.vocab_size)):
         return fall()
-    if look is not None and do_sample:                          # (the model's generation_config samples: HF's own generate)
+    if look is not None and do_sample and not sampling:         # (the model's generation_config samples, sampling=True was not asked for: HF's own generate)
         return fall()
     if look is not None:
-        # prompt-lookup speculative decoding: one sequence, greedy; fixed length (the EOS ids never chosen, as above) or up to the first EOS id
+        # prompt-lookup speculative decoding: one sequence; fixed length (the EOS ids never chosen, as above) or up to the first EOS id; greedy, or
+        # -- sampling=True -- every row's token drawn and a draft accepted while it equals the draw in front of it, as HF's own loop does
         if compact is not None:
             return fall()
         r = _lookup_runner(self, S + n + look[0], *look)
         if r is None:                                           # (the draft rows would pass max_position_embeddings: HF serves the call)
             return fall()
-        r.set_suppressed(eos if fixed else ())
-        r.set_eos(() if fixed else eos)
-        new = r.generate(ids[0], n, stop_at_eos=not fixed, min_new_tokens=nmin)
+        try:
+            if do_sample:                                       # (the seed: as for plain sampled calls below)
+                r.set_sampling(float(warp["temperature"]), int(warp["top_k"]), float(warp["top_p"]), seed=int(torch.randint(0, 2 ** 62, (1,)).item()))
+            r.set_suppressed(eos if fixed else ())
+            r.set_eos(() if fixed else eos)
+            new = r.generate(ids[0], n, stop_at_eos=not fixed, min_new_tokens=nmin)
+        finally:
+            r.set_sampling(None)
         return torch.cat([ids, new.view(1, -1).to(ids.dtype)], dim=1)
     r = _runner(self, B, S + n, ragged=compact is not None)
     if compact is not None:                                     # each row from cache row 0 at a position of its own; the caller's ids come back untouched
@@ -362,7 +376,7 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
     model.  ``sampling=True`` also routes ``generate(do_sample=True, temperature / top_k / top_p)`` and open-ended calls (EOS stop) to the runner;
     ``padded=True`` also routes ``generate`` calls whose ``attention_mask`` is LEFT padding (``padding_side="left"``) to a runner that decodes every
     row at a position of its own; ``lookup=True`` also routes ``generate(prompt_lookup_num_tokens=k, ...)`` calls for one sequence to a
-    prompt-lookup speculative runner (``lookup_request``); ``scoring=True`` keeps ``model(ids, start_pos=0, labels=..., use_cache=False)`` on the runner and
+    prompt-lookup speculative runner (``lookup_request``), greedy ones -- and with ``sampling=True`` as well ``do_sample=True`` ones; ``scoring=True`` keeps ``model(ids, start_pos=0, labels=..., use_cache=False)`` on the runner and
     returns HF's shifted cross-entropy as ``loss``.  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")

@@ -229,7 +229,8 @@ class QuantLlama:
         return 2 <= n_heads // n_kv_heads <= 16 and max_seq >= cls.ROWS_GQA_FROM
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
-                 hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2):
+                 hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2,
+                 lookup_sampling=False):
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
@@ -246,6 +247,10 @@ class QuantLlama:
         and D continuations guessed from the sequence's own history (the most recent earlier occurrence of its last ``ngram_max`` .. 1 tokens), verifies
         them in one pass of the weights and emits 1 + (accepted drafts) tokens: ``generate`` / ``verify_step`` / ``lookup_stats``.  The output is a
         greedy decode whatever is proposed.  0: off -- the object, graphs and bits the runner has always had.
+        lookup_sampling: a lookup runner that also serves ``set_sampling``: the verify step then ends in the sampled lookup tail (every row's token is
+        DRAWN, a draft is accepted while it equals the draw of the row in front of it, and the token emitted at index i is always drawn with draw
+        counter i), so the output is what one-row sampled decoding draws from the same logits, whatever is proposed.  False: ``set_sampling`` is
+        refused, as lookup runners always have.
         rope: (inv_freq fp32 [64], attention_scaling) of the rotary embedding when it is not the plain ``rope_theta`` form (from_hf hands over
         the HF module's own; otherwise derived from config["rope_scaling"]: Llama-3.1's "llama3")."""
         if isinstance(config, str):
@@ -255,6 +260,9 @@ class QuantLlama:
         self.B = int(batch)
         self.ragged = bool(ragged)
         self.lookup = int(lookup or 0)
+        self.lookup_sampling = bool(lookup_sampling)
+        if self.lookup_sampling and not self.lookup:
+            raise ValueError("lookup_sampling: sampled verify steps need a runner built with lookup=D (a plain runner samples after set_sampling)")
         if self.lookup:
             if not 1 <= self.lookup <= ops.LOOKUP_MAX_ROWS - 1:
                 raise ValueError(f"lookup: 1..{ops.LOOKUP_MAX_ROWS - 1} drafts per step (the 2 .. 8-row launches), got {lookup}")
@@ -501,7 +509,7 @@ class QuantLlama:
                 raise ValueError(f"{where}.{name}: eps {m_eps} is not the model's rms_norm_eps {eps} (the runner keeps one eps)")
 
     @classmethod
-    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2):
+    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False):
         """The hipGraph runner over a SWAPPED HF causal LM of the Llama family (``HF_MODEL_TYPES``: Llama 2 / 3.x, Mistral, Qwen2.5) -- what
         ``prepare_for_inference(model, backend="hip")`` (or the reference's deepcopy + setattr assembly of a mixed-precision model,
         amq_speed_benchmark.py:231-256) leaves behind.  The runner shares the modules' native weight buffers and biases, the embedding, lm_head and
@@ -532,7 +540,7 @@ class QuantLlama:
             dense["qn"] = [f16(l.self_attn.q_norm.weight).contiguous() for l in layers]
             dense["kn"] = [f16(l.self_attn.k_norm.weight).contiguous() for l in layers]
         return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
-                   ragged=ragged, lookup=lookup, ngram_max=ngram_max)
+                   ragged=ragged, lookup=lookup, ngram_max=ngram_max, lookup_sampling=lookup_sampling)
 
     # ----------------------------------------------------------------- sizes
     def linear_bytes_per_token(self):
@@ -604,10 +612,14 @@ class QuantLlama:
 
     def _tail(self, sampled):
         """the end of a token step: the next token (arg-max, or a draw with the device block's parameters + EOS bookkeeping), pos += 1,
-        x = embed[token], rope_cur = cos/sin row of the new position (per sequence; the position is shared)"""
-        if self.lookup:
-            if sampled:
+        x = embed[token], rope_cur = cos/sin row of the new position (per sequence; the position is shared).  A lookup runner: the
+        verify-and-propose tail over the R rows, greedy or -- ``lookup_sampling=True`` -- with every row's token drawn"""
+        if self.lookup and sampled:
+            if not self.lookup_sampling:
                 raise ValueError("lookup: speculative decoding here is greedy (the sampled tail draws one token per row)")
+            ops.decode_tail_lookup_sample(self.logits, self.embed, self.token, self.pos, self.x, self.lookup_state, self.history, self.rope_tab,
+                                          self.rope_cur, self.sample_state, suppress=self.suppress)
+        elif self.lookup:
             ops.decode_tail_lookup(self.logits, self.embed, self.token, self.pos, self.x, self.lookup_state, self.history, self.rope_tab, self.rope_cur,
                                    suppress=self.suppress)
         elif sampled:
@@ -631,11 +643,12 @@ class QuantLlama:
         """Sampled decoding from the next prompt pass on: temperature, then top-k (0 = off), then top-p (1 = off), HF's order; ``seed`` fixes the
         whole sequence (counter-based generator: draw i of sequence b is a function of (seed, i, b) -- not torch.multinomial's stream).
         ``set_sampling(None)``: back to greedy.  Writes the device block only: the greedy step (self.graph) and the sampled step (self.sample_graph)
-        are two graphs, each captured once, and switching re-captures neither."""
+        are two graphs, each captured once, and switching re-captures neither.  A lookup runner serves this only when built with
+        ``lookup_sampling=True`` (its sampled step ends in the sampled verify-and-propose tail); a default one refuses."""
         if temperature is None:
             self.sampling = None
             return
-        if self.lookup:
+        if self.lookup and not self.lookup_sampling:
             raise ValueError("lookup: speculative decoding here is greedy; sampled speculative decoding (rejection sampling) is not served")
         self.sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed))
         self._write_sampling_state()
@@ -656,6 +669,8 @@ class QuantLlama:
 
     def _first_token(self):
         """the first token after a prompt pass when the sampled tail is in use: draw 0 of every sequence from the last rows' logits"""
+        if self.lookup:                         # (the prompt graph ended in the greedy lookup tail: the same again with the token drawn)
+            return self._lookup_first_token(self._prompt_len, sampled=True)
         tok = ops.sample(self.logits, self.sample_state, suppress=self.suppress, flags=ops.SAMPLE_ADVANCE | ops.SAMPLE_EOS)
         self.set_token(tok)
 
@@ -743,7 +758,7 @@ class QuantLlama:
         # (the warm-up and the recorded step advance positions and tokens -- lookup: the counters and the drafts too --: put back)
         saved = (self.token.clone(), self.pos.clone(), self.lookup_state.clone() if self.lookup else None)
         saved_state = self.sample_state.clone() if sampled else None       # (the warm-up and the capture's own launch-free recording must not consume a draw)
-        g = capture_graph(self.dev, lambda: self._step(sampled), lambda: self._restore_step_inputs(saved))
+        g = capture_graph(self.dev, lambda: self._step(sampled), lambda: self._restore_step_inputs(saved, saved_state))
         torch.cuda.synchronize(self.dev)
         self._restore_step_inputs(saved)
         if sampled:
@@ -752,9 +767,12 @@ class QuantLlama:
         else:
             self.graph = g
 
-    def _restore_step_inputs(self, saved):
-        """put back what a step consumed (capture's warm-up): positions, tokens and what derives from them (lookup: the state block and the draft rows too)"""
+    def _restore_step_inputs(self, saved, saved_state=None):
+        """put back what a step consumed (capture's warm-up): positions, tokens and what derives from them (lookup: the state block and the draft rows
+        too; ``saved_state``: the sampling block -- a sampled lookup step advances its draw counter by what it accepted)"""
         self.pos.copy_(saved[1])
+        if saved_state is not None:
+            self.sample_state.copy_(saved_state)
         if self.lookup:
             self.lookup_state.copy_(saved[2])
             ops.set_token(saved[0], self.embed, self.token, self.pos, self.x, table=self.rope_tab, cur=self.rope_cur)
@@ -839,6 +857,20 @@ class QuantLlama:
         return self.logits
 
     # ------------------------------------------------- prompt-lookup speculative decoding
+    def _lookup_first_token(self, S, sampled):
+        """the first token of a lookup run, with the prompt's S tokens in the history: the lookup block is armed -- S tokens, no steps, no drafts, row
+        j at position S - 1 + j -- and the verify-and-propose tail runs on the last prompt row's logits as row 0 of a step without drafts: it
+        emits the first token, proposes the first drafts and leaves the step inputs of position S.  ``sampled``: outside the prompt graph (which
+        ends in the greedy tail: one graph per length serves both), the sampled tail -- it draws with counter 0 and leaves the counter at 1."""
+        st = self.lookup_state
+        st[ops.LOOKUP_COUNT:ops.LOOKUP_TICKET + 1].zero_()                      # count, steps, accepted, ticket
+        st[ops.LOOKUP_COUNT].fill_(S)
+        st[ops.LOOKUP_DRAFT:ops.LOOKUP_DRAFT + 8].fill_(-1)
+        self.set_pos(S - 1)
+        self._tail(sampled)
+        st[ops.LOOKUP_STEPS].zero_()                                            # (the prompt pass is not a verify step)
+        self.host_pos = S
+
     def _lookup_set_token(self, token):
         """row 0 = ``token``, no drafts (-1: rows 1 .. D run a placeholder and are never accepted); the counters are left alone"""
         if isinstance(token, torch.Tensor):
@@ -900,8 +932,10 @@ class QuantLlama:
         S, D = ids.shape[-1], self.lookup
         if S + gen_len + D > self.max_seq:
             raise ValueError(f"prompt ({S}) + {gen_len} tokens + {D} draft rows do not fit the KV cache (max_seq={self.max_seq})")
-        if self.sampling is not None:
+        if self.sampling is not None and not self.lookup_sampling:
             raise ValueError("lookup: speculative decoding here is greedy; call set_sampling(None)")
+        if self.sampling is not None:
+            self._write_sampling_state()        # draw counter 0: one seed fixes the whole sequence
         eos = tuple(self.eos) if stop_at_eos else ()
         with _held_back(self, eos, bool(eos) and min_new_tokens > 0) as hold:
             self.set_lookup_mode(False)
@@ -977,14 +1011,7 @@ class QuantLlama:
             # row 0 of a step at position S - 1 without drafts -- emits the first token, proposes the first drafts and leaves the step inputs of
             # position S
             self.history[:S].copy_(prompt_ids.reshape(-1))
-            st = self.lookup_state
-            st[ops.LOOKUP_COUNT:ops.LOOKUP_TICKET + 1].zero_()                  # count, steps, accepted, ticket
-            st[ops.LOOKUP_COUNT].fill_(S)
-            st[ops.LOOKUP_DRAFT:ops.LOOKUP_DRAFT + 8].fill_(-1)
-            self.set_pos(S - 1)
-            self._tail(False)
-            st[ops.LOOKUP_STEPS].zero_()                                        # (the prompt pass is not a verify step)
-            self.host_pos = S
+            self._lookup_first_token(S, sampled=False)
         elif lengths is not None:
             self.pos.copy_(lengths)             # (the host mirror: prefill())
             self.set_token(self._argmax(out))

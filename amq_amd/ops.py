@@ -1699,6 +1699,33 @@ def decode_tail_lookup(logits, embed, token, pos, x, state, history, table, cur,
                                                       _lib.ptr(history), history.numel(), _lib.current_stream()))
 
 
+def decode_tail_lookup_sample(logits, embed, token, pos, x, state, history, table, cur, sample_state, suppress=None, u=None, kept_out=None):
+    """:func:`decode_tail_lookup` with every row's token drawn by :func:`sample` instead of its arg-max (amq_decode_tail_lookup_sample_f16), one
+    launch: row j draws with the parameters of ``sample_state`` (:func:`new_sampling_state`) and draw counter c + j, sequence 0; the counter moves on
+    by 1 + accepted drafts; no EOS bookkeeping.  ``u``: float32 [rows] uniform numbers used instead of the generator (tests); ``kept_out``: uint8
+    [rows, vocab] receives the kept-set masks."""
+    vocab, hidden = embed.shape
+    R = token.numel()
+    if not 2 <= R <= LOOKUP_MAX_ROWS:
+        raise ValueError(f"rows must be 2..{LOOKUP_MAX_ROWS} (got {R})")
+    _need(logits, torch.float16, "logits", R * vocab)
+    _need(state, torch.int32, "lookup state", LOOKUP_STATE_WORDS)
+    _need(history, torch.int32, "history")
+    _need(sample_state, torch.int32, "sample_state", _SMP_WORDS)
+    if suppress is not None:
+        _need(suppress, torch.int32, "suppress", 8)
+    if u is not None:
+        _need(u, torch.float32, "u", R)
+    if kept_out is not None:
+        _need(kept_out, torch.uint8, "kept_out", R * vocab)
+    seq, _, mid = _tail_args(embed, token, pos, x, table, cur)
+    if not seq:
+        raise ValueError(f"cur [rows, 128] / pos [rows] must be the views of one per-sequence step state of {R} blocks")
+    _lib.check(_lib.load().amq_decode_tail_lookup_sample_f16(_lib.ptr(logits), vocab, _lib.ptr(embed), hidden, *mid, R, _lib.ptr(suppress),
+                                                             _lib.ptr(state), _lib.ptr(history), history.numel(), _lib.ptr(sample_state), _lib.ptr(u),
+                                                             _lib.ptr(kept_out), _lib.current_stream()))
+
+
 # ---------------------------------------------------------------- the device of a launch
 # Every launch goes to the CURRENT device's stream (``_lib.current_stream()``), kernel attributes and CU counts are the current device's too.  A
 # process that keeps its weights on cuda:1 while cuda:0 is current (HF device_map, no set_device) must therefore have cuda:1 made current around
@@ -1721,7 +1748,7 @@ def _on_tensor_device(fn):
 
 for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_quantize", "gptq_quantize_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
-              "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup"):
+              "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup", "decode_tail_lookup_sample"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name
 

@@ -539,6 +539,22 @@ int amq_attn_decode_rows_gqa_f16(const void* q, const void* k, const void* v, vo
 int amq_decode_tail_lookup_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
                                const void* rope_table, int rope_rows, int rows, const int* suppress_ids, void* lookup_state, int* history,
                                int history_cap, void* stream);
+/* The SAMPLED verify-and-propose tail, one launch: amq_decode_tail_lookup_f16 with a[j] DRAWN from row j instead of its arg-max.  Row j runs
+ * amq_sample_f16's sampler (the same kept set, weights and ascending-index draw; suppress_ids are never drawn; a row without a candidate gives
+ * token 0) with the parameters of sample_state, the 128-byte block of amq_sample_f16:
+ *   read      words 0 .. 2 (temperature, top_k, top_p), words 4 .. 5 (seed), words 6 .. 7 (the 64-bit draw counter c), word 26 (first_kept)
+ *   advanced  words 6 .. 7: c + n + 1 (64-bit), by the last workgroup to arrive -- every workgroup has read c before it takes its ticket
+ *   untouched the pad id, the EOS ids, the finished flags, the unfinished count and the arrival word (25: stays 0): there is NO EOS bookkeeping
+ *             here -- the host finds the first EOS id in `history`
+ * Row j's uniform number is Philox(seed; draw = c + j (64-bit add), sequence 0): the token emitted at index i of the sequence (0 = the first one
+ * after the prompt) is drawn with counter i whichever row of whichever step computes it -- the numbers amq_decode_tail_sample_f16 uses for a
+ * single sequence.  Acceptance, history, counters, proposal and the next step's inputs are amq_decode_tail_lookup_f16's with the drawn tokens in
+ * the place of the arg-maxes; words 16 + j of lookup_state hold the DRAWN token of row j.
+ * u_in (float32 [rows] or NULL): uniform numbers used instead of the generator; kept_out (uint8 [rows, vocab] or NULL): the kept-set masks.
+ * The checks of amq_decode_tail_lookup_f16; sample_state NULL: AMQ_EINVAL. */
+int amq_decode_tail_lookup_sample_f16(const void* logits, int vocab, const void* embed, int hidden, long long* token, void* step_states, void* x,
+                                      const void* rope_table, int rope_rows, int rows, const int* suppress_ids, void* lookup_state, int* history,
+                                      int history_cap, void* sample_state, const float* u_in, unsigned char* kept_out, void* stream);
 
 /* ---- many-row (prefill) glue --------------------------------------------------------------------------
  * The reference runs these steps as framework ops between the linears of a HF Llama block

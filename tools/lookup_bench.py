@@ -13,7 +13,14 @@ of the figure; the "lookup" leg, where the tail proposes on the device, has neit
 legs alternate over ``--repeats`` rounds and the spread is recorded.  break_even_acceptance = t_R / t_1 - 1: the mean number of accepted drafts
 per step from which the verify step wins.  The batched step at B = R is measured by tools/decode_batch.py in a child process.
 ``--parent DIR``: a built checkout of the parent commit; its plain step (bench.py --gpus 1 --steps 256 --warmup 16) and its batched steps
-(tools/decode_batch.py) are run there as child processes, in the same session on the same box, and recorded under "parent"."""
+(tools/decode_batch.py) are run there as child processes, in the same session on the same box, and recorded under "parent".
+
+    python tools/lookup_bench.py --sampled [--drafts 3,7] [--steps 128] [--repeats 5] [--out profiles/lookup_sample.json]
+
+The SAMPLED verify step (QuantLlama(lookup=D, lookup_sampling=True) after set_sampling: the tail draws every row's token) against the greedy verify
+step of the same runner -- two captured graphs of one process, replayed alternately, the tail proposing on the device in both -- on the 7B avg-3
+synthetic models with vocabulary 32000 (Llama-2-7b-hf) and 152064 (Qwen2.5-7B), and, per model, the plain one-row sampled step against the plain
+one-row greedy step in that process (the surcharge tools/sampling_bench.py measures).  The greedy verify step's launches are the parent commit's."""
 import argparse
 import json
 import os
@@ -146,6 +153,73 @@ def verify_rows(dev, R, plain, ids, steps, repeats):
     return res, plain_ts
 
 
+SAMPLED_MODELS = ("Llama-2-7b-hf", "Qwen2.5-7B")      # vocabulary 32000 / 152064
+SAMPLER = dict(temperature=0.8, top_k=50, top_p=0.9, seed=1)
+
+
+def _build_model(dev, model, max_seq, **kw):
+    import bench
+    from amq_amd import arch
+    from amq_amd.llama import QuantLlama
+    cfg = arch.MODEL_CONFIGS[model]
+    a, _ = arch.synthesize_arch(cfg, bench.TARGET_BITS, seed=0, pinned=arch.PINNED_7B if model == bench.MODEL else ())
+    return QuantLlama(cfg, a["linear"], device=dev, max_seq=max_seq, seed=0, **kw)
+
+
+def _alternate(m, ids, steps, repeats):
+    """greedy and sampled captured steps of runner ``m`` replayed alternately: -> {leg: median / runs / spread}, sampled_over_greedy_pct"""
+    legs = {"greedy": [], "sampled": []}
+    per_step = {}
+    for rep in range(repeats + 1):                      # (the first round captures and warms up: not kept)
+        for leg in legs:
+            m.set_sampling(**SAMPLER) if leg == "sampled" else m.set_sampling(None)
+            m.reset()
+            m.prefill(ids)
+            m.capture(leg == "sampled")
+            g = m.sample_graph if leg == "sampled" else m.graph
+            t = _timed(lambda i: g.replay(), steps)
+            if m.lookup:
+                count, st = m.lookup_sync()
+                per_step[leg] = (count - ids.numel() - 1) / st
+            if rep:
+                legs[leg].append(t)
+    m.set_sampling(None)
+    m.check()
+    res = {leg: _med(ts) for leg, ts in legs.items()}
+    for leg, v in per_step.items():
+        res[leg]["tokens_per_step"] = v
+    res["sampled_over_greedy_pct"] = 100.0 * (res["sampled"]["ms"] / res["greedy"]["ms"] - 1.0)
+    return res
+
+
+def sampled_main(a):
+    dev = torch.device("cuda:0")
+    drafts = [int(d) for d in a.drafts.split(",") if d]
+    res = {"sampler": SAMPLER, "prompt": PROMPT, "steps": a.steps, "repeats": a.repeats, "models": {}}
+    for model in SAMPLED_MODELS:
+        plain = _build_model(dev, model, PROMPT + 16 + a.steps)
+        ids = torch.randint(8, plain.vocab, (PROMPT,), generator=torch.Generator().manual_seed(0)).to(dev)
+        entry = {"vocab": plain.vocab, "plain_step": _alternate(plain, ids, a.steps, a.repeats), "verify": {}}
+        del plain
+        torch.cuda.empty_cache()
+        for D in drafts:
+            R = D + 1
+            m = _build_model(dev, model, PROMPT + 16 + a.steps * R + R, lookup=D, lookup_sampling=True)
+            v = _alternate(m, ids, a.steps, a.repeats)
+            # the same sampler on R rows side by side instead of one: what the tail adds, beside what the one-row sampled step adds
+            v["sampled_minus_greedy_us"] = 1e3 * (v["sampled"]["ms"] - v["greedy"]["ms"])
+            v["plain_sampled_minus_greedy_us"] = 1e3 * (entry["plain_step"]["sampled"]["ms"] - entry["plain_step"]["greedy"]["ms"])
+            entry["verify"][str(D)] = v
+            del m
+            torch.cuda.empty_cache()
+        res["models"][model] = entry
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="2,3,4,5,6,7,8")
@@ -153,8 +227,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--parent", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sampled", action="store_true", help="the sampled verify step against the greedy one (see the module docstring)")
+    ap.add_argument("--drafts", default="3,7")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
+    if a.sampled:
+        return sampled_main(a)
     dev = torch.device("cuda:0")
     rows = [int(r) for r in a.rows.split(",") if r]
     ids = torch.randint(8, 32000, (PROMPT,), generator=torch.Generator().manual_seed(0)).to(dev)
