@@ -30,6 +30,7 @@ HQQ_ITERS = 20              # iterations of the quantizer's solver; its info blo
 HQQ_INFO_BYTES = 88         # include/amq_hip.h AMQ_HQQ_INFO_BYTES
 GPTQ_INFO_BYTES = 4         # include/amq_hip.h AMQ_GPTQ_INFO_BYTES
 AWQ_INFO_BYTES = 4          # include/amq_hip.h AMQ_AWQ_INFO_BYTES
+OWQ_INFO_BYTES = 4          # include/amq_hip.h AMQ_OWQ_INFO_BYTES
 AWQ_STEPS = 10              # shrink steps of the AWQ clip search (err is [N, K / group, AWQ_STEPS])
 
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -81,6 +82,12 @@ SIGNATURES = {
     # dense fp16 + the inverse Hessian's Cholesky factor -> Format A: GPTQ's error-feedback solve (info = {int32 nonfinite})
     "amq_gptq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
     "amq_gptq_quantize_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # OWQ: the range search of row segments, the solve that leaves n_out columns fp16, the layer's gather and outlier add (info = {int32 nonfinite})
+    "amq_owq_range_f16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amq_owq_quantize_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "amq_owq_quantize_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amq_owq_gather_f16": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "amq_owq_outlier_add_f16": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
     # AWQ: round to nearest under a column scale / clip bounds -> Format A and / or the dense fake-quantized matrix; the clip search (info = {int32 nonfinite})
     "amq_awq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
     "amq_awq_quantize_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

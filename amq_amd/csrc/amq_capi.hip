@@ -171,6 +171,72 @@ int amq_gptq_quantize_f16(const void* W, const void* U, int N, int K, int bits, 
                      "gptq_quantize");
 }
 
+// OWQ: groups of 128 only (AMQ's); the shape rules of the range search and of the solve, in the order the header documents
+static int check_owq_shape(int bits, int N, int K, int group, int num) {
+    if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
+    if (group != 128) return fail(AMQ_ESHAPE, "the OWQ kernels serve groups of 128 only (got %d)", group);
+    if (N <= 0 || (N % 16) != 0) return fail(AMQ_ESHAPE, "need N %% 16 == 0 (got N=%d)", N);
+    if (K <= 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 (got K=%d)", K);
+    if (num < 1 || num > amq::OWQ_MAX_NUM) return fail(AMQ_ESHAPE, "num (range candidates) must be 1..%d (got %d)", (int)amq::OWQ_MAX_NUM, num);
+    return AMQ_OK;
+}
+static int check_owq_outliers(int K, int n_out) {
+    if (n_out < 0 || (n_out % 2) != 0 || n_out >= K) return fail(AMQ_ESHAPE, "n_out must be even and in 0 .. K - 2 (got n_out=%d, K=%d)", n_out, K);
+    return AMQ_OK;
+}
+
+int amq_owq_range_f16(const void* W, int N, int K, int col0, int L, int bits, int num, void* scale, void* zero, void* choice, void* score,
+                      void* wq_err, void* info, void* stream) {
+    static_assert(AMQ_OWQ_INFO_BYTES == amq::OWQ_INFO_BYTES, "info block");
+    if (!W || !scale || !zero || !choice || !score || !info) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)W & 1) != 0 || ((uintptr_t)scale & 1) != 0 || ((uintptr_t)zero & 1) != 0 || ((uintptr_t)choice & 3) != 0 ||
+        ((uintptr_t)score & 3) != 0 || ((uintptr_t)wq_err & 3) != 0 || ((uintptr_t)info & 3) != 0)
+        return fail(AMQ_EINVAL, "W, scale and zero must be 2-byte aligned, choice, score, wq_err and info 4-byte aligned");
+    if (int rc = check_owq_shape(bits, N, K, 128, num)) return rc;
+    if (col0 < 0 || L < 1 || col0 > K - L) return fail(AMQ_ESHAPE, "the segment col0=%d, L=%d does not lie inside K=%d", col0, L, K);
+    if (L > amq::OWQ_RANGE_MAX_L) return fail(AMQ_ESHAPE, "a segment of L=%d does not fit LDS (at most %d)", L, (int)amq::OWQ_RANGE_MAX_L);
+    if (wq_err && (col0 != 0 || L != K)) return fail(AMQ_ESHAPE, "wq_err goes with the whole-row search (col0 = 0, L = K)");
+    return check_hip(amq::launch_owq_range(W, N, K, col0, L, bits, num, scale, zero, choice, score, wq_err, info, (hipStream_t)stream), "owq_range");
+}
+
+size_t amq_owq_quantize_workspace_bytes(int N, int K, int n_out, int group) {
+    if (check_owq_shape(4, N, K, group, 1) != AMQ_OK || check_owq_outliers(K, n_out) != AMQ_OK) return 0;
+    return amq::owq_workspace_bytes(N, K, n_out);
+}
+
+int amq_owq_quantize_f16(const void* W_p, const void* U_p, int N, int K, int n_out, int bits, int group, int num, void* W_q, void* scale,
+                         void* zero, void* W_out, void* choice, void* row_loss, void* info, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    if (!W_p || !U_p || !W_q || !scale || !zero || !choice || !row_loss || !info || !workspace || (!W_out && n_out != 0))
+        return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)W_p & 15) != 0 || ((uintptr_t)U_p & 15) != 0 || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)W_q & 3) != 0 ||
+        ((uintptr_t)W_out & 1) != 0 || ((uintptr_t)choice & 3) != 0 || ((uintptr_t)row_loss & 3) != 0 || ((uintptr_t)info & 3) != 0)
+        return fail(AMQ_EINVAL, "W_p, U_p and workspace must be 16-byte aligned, W_q, choice, row_loss and info 4-byte, W_out 2-byte aligned");
+    if (int rc = check_owq_shape(bits, N, K, group, num)) return rc;
+    if (int rc = check_owq_outliers(K, n_out)) return rc;
+    if (int rc = check_workspace("OWQ", amq::owq_workspace_bytes(N, K, n_out), workspace_bytes)) return rc;
+    return check_hip(amq::launch_owq_quantize(W_p, U_p, N, K, n_out, bits, num, W_q, scale, zero, W_out, choice, row_loss, info, workspace,
+                                              (hipStream_t)stream), "owq_quantize");
+}
+
+int amq_owq_gather_f16(const void* x, int M, int K, const void* perm, int Kp, void* xg, void* stream) {
+    if (!x || !perm || !xg) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)x & 1) != 0 || ((uintptr_t)perm & 3) != 0 || ((uintptr_t)xg & 3) != 0)
+        return fail(AMQ_EINVAL, "x must be 2-byte aligned, perm and xg 4-byte aligned");
+    if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
+    if (K <= 0 || Kp <= 0 || (Kp % 128) != 0) return fail(AMQ_ESHAPE, "need K > 0 and Kp %% 128 == 0 (got K=%d Kp=%d)", K, Kp);
+    return check_hip(amq::launch_owq_gather(x, M, K, perm, Kp, xg, (hipStream_t)stream), "owq_gather");
+}
+
+int amq_owq_outlier_add_f16(const void* x, int M, int K, const void* out_ids, int n_out, const void* W_out, void* y, int N, void* stream) {
+    if (!x || !out_ids || !W_out || !y) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)x & 1) != 0 || ((uintptr_t)out_ids & 3) != 0 || ((uintptr_t)W_out & 1) != 0 || ((uintptr_t)y & 1) != 0)
+        return fail(AMQ_EINVAL, "x, W_out and y must be 2-byte aligned, out_ids 4-byte aligned");
+    if (M < 1 || M > 65535) return fail(AMQ_ESHAPE, "M must be 1..65535 (got %d)", M);
+    if (N <= 0 || K <= 0 || n_out < 1 || n_out >= K) return fail(AMQ_ESHAPE, "need N > 0 and 1 <= n_out < K (got N=%d K=%d n_out=%d)", N, K, n_out);
+    return check_hip(amq::launch_owq_outlier_add(x, M, K, out_ids, n_out, W_out, y, N, (hipStream_t)stream), "owq_outlier_add");
+}
+
 size_t amq_awq_quantize_workspace_bytes(int N, int K, int group) {
     if (check_quantize_shape(QUANT_AWQ, 4, N, K, group) != AMQ_OK) return 0;
     return amq::awq_quantize_workspace_bytes(N, K);

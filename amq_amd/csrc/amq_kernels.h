@@ -351,6 +351,19 @@ hipError_t launch_gptq_quantize(const void* W, const void* U, int N, int K, int 
 hipError_t launch_quant_flags(const int* NF, size_t n, int* info_word, hipStream_t st);
 hipError_t launch_pack_codes(const void* codes, size_t R, int group, int bits, void* W_q, hipStream_t st);
 
+// OWQ (amq_owq.hip): the range search of row segments (one workgroup per row, the segment staged in LDS as fp16: L <= OWQ_RANGE_MAX_L = 60 KiB),
+// the solve in the GPTQ solve's shape over the permuted columns, of which the last n_out stay fp16 (workspace: fp32 E[N][Kp], int32
+// nonfinite[N / 4], uint8 codes[N][Kp], Kp = the quantized columns padded to whole groups of 128), and the layer's gather and outlier add.
+enum { OWQ_RANGE_WAVES = 4, OWQ_RANGE_MAX_L = 30720, OWQ_MAX_NUM = 100, OWQ_INFO_BYTES = 4, OWQ_ADD_ROWS = 16, OWQ_ADD_J = 64 };
+inline int owq_packed_columns(int K, int n_out) { return (K - n_out + GPTQ_BLOCK - 1) / GPTQ_BLOCK * GPTQ_BLOCK; }
+inline size_t owq_workspace_bytes(int N, int K, int n_out) { return 5 * (size_t)N * owq_packed_columns(K, n_out) + 4 * (size_t)gptq_flags(N); }
+hipError_t launch_owq_range(const void* W, int N, int K, int col0, int L, int bits, int num, void* scale, void* zero, void* choice, void* score,
+                            void* wq_err, void* info, hipStream_t st);
+hipError_t launch_owq_quantize(const void* W, const void* U, int N, int K, int n_out, int bits, int num, void* W_q, void* scale, void* zero,
+                               void* W_out, void* choice, void* row_loss, void* info, void* workspace, hipStream_t st);
+hipError_t launch_owq_gather(const void* x, int M, int K, const void* perm, int Kp, void* xg, hipStream_t st);
+hipError_t launch_owq_outlier_add(const void* x, int M, int K, const void* out_ids, int n_out, const void* W_out, void* y, int N, hipStream_t st);
+
 // AWQ (amq_awq.hip).  quantize: 8 columns per thread, 256 threads per workgroup, round-to-nearest per group to byte codes, then the shared pack
 // launch; workspace: int32 nonfinite[N * K / 512] (one per wave), uint8 codes[N][K].  clip: one wave per (8 rows, one group): the rows' 10 clip
 // steps are 80 columns = 5 B tiles of v_mfma_f32_16x16x4_f32, X's rows go through in tiles of 16; workspace: int32 nonfinite[(N / 8) * (K / group)].

@@ -325,6 +325,162 @@ def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, n
     return (h, got) if return_info else h
 
 
+OWQ_NUM = 40                     # delta candidates of OWQ's range search (owq.py:202, 364)
+_OWQ_SERVES = "the OWQ kernels serve groups of 128 only"
+
+
+class OWQRangeInfo:
+    """what one ``owq_range`` call reports: ``choice`` (int32 [N, 2]: the winner's (i, zp) per row), ``score`` (fp32 [N]), ``wq_err`` (fp32 [K]: the
+    column sums of (w - w^)^2, whole-row calls only, else None) and ``nonfinite`` (some row ended without a winner)"""
+
+    def __init__(self, nonfinite, choice, score, wq_err):
+        self.nonfinite, self.choice, self.score, self.wq_err = int(nonfinite), choice, score, wq_err
+
+    def __repr__(self):
+        return f"OWQRangeInfo(nonfinite={self.nonfinite}, rows={self.score.numel()})"
+
+
+def owq_range_launch(W, col0, L, nbits, num, scale, zero, choice, score, wq_err, info):
+    """the bare entry point over caller-owned buffers (``wq_err`` may be None; up to three launches on the current stream; no allocation, no
+    read-back: capturable)"""
+    N, K = W.shape
+    _lib.check(_lib.load().amq_owq_range_f16(_lib.ptr(W), N, K, int(col0), int(L), int(nbits), int(num), _lib.ptr(scale), _lib.ptr(zero),
+                                             _lib.ptr(choice), _lib.ptr(score), _lib.ptr(wq_err), _lib.ptr(info), _lib.current_stream()))
+
+
+def owq_range_buffers(N, K, device, wq_err=False):
+    """(scale, zero, choice, score, wq_err, info) of the right sizes for ``owq_range_launch``"""
+    return (torch.empty(N, dtype=torch.float16, device=device), torch.empty(N, dtype=torch.float16, device=device),
+            torch.empty(N, 2, dtype=torch.int32, device=device), torch.empty(N, dtype=torch.float32, device=device),
+            torch.empty(K, dtype=torch.float32, device=device) if wq_err else None, _info_block(_lib.OWQ_INFO_BYTES, device))
+
+
+def owq_range(W, nbits, col0=0, L=None, num=OWQ_NUM, return_info=False):
+    """OWQ's range search (owq.py Quantizer.find_params with mse, asymmetric, per channel) of the segment ``W[n, col0 : col0 + L]`` of every row of
+    the dense W [N, K] on the GPU, as a HIP kernel in the arithmetic include/amq_hip.h states: ``num`` x 2^nbits (delta, zero-point) candidates
+    under the lp-2.4 loss of the deployed weight.  Returns (scale, zero) fp16 [N] -- with ``return_info`` also the :class:`OWQRangeInfo`, whose
+    ``wq_err`` a whole-row call (col0 = 0, L = K) fills.  Raises ValueError if a row holds an inf or NaN.  One synchronising read per call."""
+    W = _dense_f16(W, "W")
+    N, K = W.shape
+    _check_shape(int(nbits), N, K)
+    L = K - int(col0) if L is None else int(L)
+    if not 1 <= int(num) <= 100:
+        raise ValueError(f"owq_range: num must be 1..100 (got {num})")
+    if col0 < 0 or L < 1 or col0 + L > K:
+        raise ValueError(f"owq_range: the segment col0={col0}, L={L} does not lie inside K={K}")
+    scale, zero, choice, score, wq_err, info = owq_range_buffers(N, K, W.device, wq_err=(col0 == 0 and L == K))
+    owq_range_launch(W, col0, L, nbits, num, scale, zero, choice, score, wq_err, info)
+    got = OWQRangeInfo(info.cpu()[0].item(), choice, score, wq_err)
+    _refuse_nonfinite(got.nonfinite, "owq_range", None, " holds inf or NaN values")
+    return (scale, zero, got) if return_info else (scale, zero)
+
+
+def owq_select(W, H, n_out, nbits, num=OWQ_NUM):
+    """OWQ's column choice (owq.py:197-207, hessian_sorting with frob_norm, actorder=False): the whole-row range pass gives frob_c = the column sums
+    of (w - w^)^2, sens_c = diag(H)_c * frob_c, the ``n_out`` columns of largest sens are the outliers.  Returns (ids int64 [K]: the kept columns
+    ascending, then the outliers in descending sens; out_ids int32 [n_out]: the outliers ascending), on W's device."""
+    W = _dense_f16(W, "W")
+    N, K = W.shape
+    n_out = int(n_out)
+    if n_out < 0 or n_out % 2 or n_out >= K:
+        raise ValueError(f"owq_select: n_out must be even and in 0 .. K - 2 (got {n_out}, K={K})")
+    if not isinstance(H, torch.Tensor) or H.device != W.device or tuple(H.shape) != (K, K):
+        raise ValueError("H: expected a [K, K] tensor on W's GPU")
+    every = torch.arange(K, device=W.device)
+    if n_out == 0:
+        return every, torch.empty(0, dtype=torch.int32, device=W.device)
+    _, _, info = owq_range(W, nbits, num=num, return_info=True)
+    sens = torch.diag(H).to(torch.float32) * info.wq_err
+    desc = torch.argsort(sens, descending=True, stable=True)
+    keep = torch.ones(K, dtype=torch.bool, device=W.device)
+    keep[desc[:n_out]] = False
+    return torch.cat([every[keep], desc[:n_out]]), torch.sort(desc[:n_out])[0].to(torch.int32)
+
+
+class OWQQuantizeInfo:
+    """what one ``owq_quantize`` call reports: ``nonfinite`` (the info block), ``choice`` (int32 [N, Kp / 128, 2]: the winner's (i, zp) per row and
+    group), ``row_loss`` (fp32 [N], on the device) and ``loss``, its fp64 sum"""
+
+    def __init__(self, nonfinite, choice, row_loss):
+        self.nonfinite, self.choice, self.row_loss = int(nonfinite), choice, row_loss
+        self.loss = float(row_loss.double().sum().item())
+
+    def __repr__(self):
+        return f"OWQQuantizeInfo(nonfinite={self.nonfinite}, loss={self.loss:.6g})"
+
+
+def owq_packed_columns(K, n_out):
+    """Kp: the quantized columns K - n_out padded to whole groups of 128"""
+    return -(-(K - n_out) // GROUP) * GROUP
+
+
+def owq_quantize_launch(W_p, U_p, n_out, nbits, group_size, num, W_q, scale, zero, W_out, choice, row_loss, info, workspace):
+    """the bare entry point over caller-owned buffers (three launches on the current stream; no allocation, no read-back: capturable)"""
+    N, K = W_p.shape
+    _lib.check(_lib.load().amq_owq_quantize_f16(_lib.ptr(W_p), _lib.ptr(U_p), N, K, int(n_out), int(nbits), int(group_size), int(num),
+                                                _lib.ptr(W_q), _lib.ptr(scale), _lib.ptr(zero), _lib.ptr(W_out) if n_out else None,
+                                                _lib.ptr(choice), _lib.ptr(row_loss), _lib.ptr(info), _lib.ptr(workspace), _nbytes(workspace),
+                                                _lib.current_stream()))
+
+
+def owq_quantize_buffers(N, K, n_out, nbits, group_size, device):
+    """(W_q, scale, zero, W_out, choice, row_loss, info, workspace) of the right sizes for ``owq_quantize_launch``"""
+    group_size = _quantize_shape(N, K, nbits, group_size, (GROUP,), _OWQ_SERVES)
+    n_out = int(n_out)
+    if n_out < 0 or n_out % 2 or n_out >= K:
+        raise ValueError(f"owq_quantize: n_out must be even and in 0 .. K - 2 (got {n_out}, K={K})")
+    Kp = owq_packed_columns(K, n_out)
+    words = _workspace_words("amq_owq_quantize_workspace_bytes", "the OWQ solve", N=N, K=K, n_out=n_out, group=group_size)
+    return (*_format_a_buffers(N, Kp, nbits, group_size, device), torch.empty(N, n_out, dtype=torch.float16, device=device),
+            torch.empty(N, Kp // GROUP, 2, dtype=torch.int32, device=device), torch.empty(N, dtype=torch.float32, device=device),
+            _info_block(_lib.OWQ_INFO_BYTES, device), _owq_scratch.get(device, words))
+
+
+def owq_quantize(W_p, U_p, n_out, nbits, group_size=GROUP, num=OWQ_NUM, return_info=False, bias=None, name=None):
+    """OWQ's solve (owq.py:312-391 with grouping, actorder=False) as HIP kernels in the arithmetic include/amq_hip.h states.  ``W_p`` [N, K] is the
+    dense matrix with its columns permuted (``owq_select``'s ids: the ``n_out`` outliers last) and its dead columns zeroed, ``U_p`` [K, K] is
+    ``gptq_hinv`` of the equally permuted Hessian, both on the GPU.  Returns (HQQWeights of shape (N, Kp) -- the first K - n_out columns quantized
+    in groups of 128 with searched ranges, padded with columns that dequantize to 0 --, W_out fp16 [N, n_out]: the outlier columns after the error
+    feedback, in W_p's order); with ``return_info`` also the :class:`OWQQuantizeInfo`.  Raises ValueError on non-finite values.  One
+    synchronising read of the 4-byte info block per call."""
+    from .hqq_format import HQQWeights
+    W_p = _dense_f16(W_p, "W_p")
+    N, K = W_p.shape
+    if not isinstance(U_p, torch.Tensor) or U_p.device != W_p.device:
+        raise ValueError("U_p: expected a tensor on W_p's GPU")
+    U_p = U_p.detach().contiguous()
+    _need(U_p, torch.float32, "U_p", K * K)
+    nbits, n_out = int(nbits), int(n_out)
+    if not 1 <= int(num) <= 100:
+        raise ValueError(f"owq_quantize: num must be 1..100 (got {num})")
+    W_q, scale, zero, W_out, choice, row_loss, info, workspace = owq_quantize_buffers(N, K, n_out, nbits, group_size, W_p.device)
+    owq_quantize_launch(W_p, U_p, n_out, nbits, group_size, num, W_q, scale, zero, W_out, choice, row_loss, info, workspace)
+    got = OWQQuantizeInfo(info.cpu()[0].item(), choice, row_loss)
+    _refuse_nonfinite(got.nonfinite, "owq_quantize", name, ": a weight, an error or U's diagonal was not finite (or the diagonal not positive)")
+    h = HQQWeights(W_q, scale, zero, nbits, (N, owq_packed_columns(K, n_out)), int(group_size), bias, name)
+    return (h, W_out, got) if return_info else (h, W_out)
+
+
+def owq_gather(x, perm):
+    """xg [M, Kp] = x[:, perm] with 0 where perm < 0 (HIPOWQLinear's first launch); x fp16 [M, K] contiguous, perm int32 [Kp]"""
+    M, K = x.shape
+    Kp = perm.numel()
+    xg = torch.empty(M, Kp, dtype=torch.float16, device=x.device)
+    _lib.check(_lib.load().amq_owq_gather_f16(_lib.ptr(x), M, K, _lib.ptr(perm), Kp, _lib.ptr(xg), _lib.current_stream()))
+    return xg
+
+
+def owq_outlier_add(x, out_ids, W_out, y):
+    """y [M, N] += x[:, out_ids] . W_out^T in place (HIPOWQLinear's last launch: an fp32 fmaf chain per output, one rounding back to fp16)"""
+    M, K = x.shape
+    N, n_out = W_out.shape
+    for lo in range(0, M, 65535):           # (the entry point takes 65535 rows a call: its grid's second dimension)
+        rows = min(65535, M - lo)
+        _lib.check(_lib.load().amq_owq_outlier_add_f16(_lib.ptr(x[lo:]), rows, K, _lib.ptr(out_ids), n_out, _lib.ptr(W_out), _lib.ptr(y[lo:]), N,
+                                                       _lib.current_stream()))
+    return y
+
+
 def _awq_check(N, K, nbits, group_size):
     return _quantize_shape(N, K, nbits, group_size, AWQ_GROUPS, "the AWQ kernels serve groups of 32, 64 and 128")
 
@@ -578,6 +734,7 @@ _SPLITK_WS = _ScratchPool(torch.float32)
 _quantize_scratch = _ScratchPool(torch.int32)      # hqq_quantize's workspace (s, the zero trace, the partial errors)
 _gptq_scratch = _ScratchPool(torch.int32)          # gptq_quantize's workspace (the columns' errors, the flags, the byte codes)
 _awq_scratch = _ScratchPool(torch.int32)           # awq_quantize's / awq_clip's workspace (the flags, the byte codes)
+_owq_scratch = _ScratchPool(torch.int32)           # owq_quantize's workspace (the quantized columns' errors, the flags, the byte codes)
 
 
 def _splitk_workspace(device, nbytes):
@@ -1746,7 +1903,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_quantize", "gptq_quantize_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
+for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_quantize", "gptq_quantize_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup", "decode_tail_lookup_sample"):
     globals()[_name] = _on_tensor_device(globals()[_name])

@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from .hqq_format import HQQWeights, from_hqq_layer
-from .quant_linear import HIPLlamaMLP, HIPQuantLinear, HIPRMSNorm, LinearGroup
+from .quant_linear import HIPLlamaMLP, HIPOWQLinear, HIPQuantLinear, HIPRMSNorm, LinearGroup
 
 # sibling linears of one parent module that read the same input (HF LlamaAttention / LlamaMLP attribute names)
 SIBLING_GROUPS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))
@@ -105,15 +105,15 @@ def patch_hqq_to_hip_load(layer, patch_params=None):
 
 def patch_add_weight_param(layer, patch_param):
     """patching.py:76-91: dummy ``.weight`` so HF code can query dtype/device."""
-    if isinstance(layer, HIPQuantLinear) and not hasattr(layer, "weight"):
-        layer.weight = torch.nn.Parameter(torch.zeros((1,), device=layer.qweight.device, dtype=torch.float16),
-                                          requires_grad=False)
+    if isinstance(layer, (HIPQuantLinear, HIPOWQLinear)) and not hasattr(layer, "weight"):
+        device = layer.W_out.device if isinstance(layer, HIPOWQLinear) else layer.qweight.device
+        layer.weight = torch.nn.Parameter(torch.zeros((1,), device=device, dtype=torch.float16), requires_grad=False)
     return layer
 
 
 def _walk_hip(model, fct):
     for name, layer in model.named_children():
-        if isinstance(layer, HIPQuantLinear):
+        if isinstance(layer, (HIPQuantLinear, HIPOWQLinear)):      # (an OWQ layer is one module: its inner packed layer is not walked)
             setattr(model, name, fct(layer, None))
         else:
             _walk_hip(layer, fct)
@@ -464,6 +464,107 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
     return model, report
 
 
+OWQ_RATIOS = {"self_attn.q_proj": 1, "self_attn.k_proj": 1, "self_attn.v_proj": 1, "self_attn.o_proj": 1, "mlp.up_proj": 0.375,
+              "mlp.gate_proj": 0.375, "mlp.down_proj": 0.375}      # the reference's model_config.json "ratios" for the Llama family
+
+
+def owq_n_out(K, avg_bits, name, group_size=128):
+    """The reference's number of fp16 columns of a linear with K input columns (owq.py:69-70, 146-153): ``avg_bits`` is the arch's
+    ``get_bits_usage`` (the group's 32 / group_size bits of scale and zero included, which the rule takes off again),
+    r = 12 / (16 - (avg_bits - 32 / group_size)) * 0.1 / 7 over the seven linears, n_out = round(K * r * ratio), made even."""
+    r = (12 / (16 - (avg_bits - (32 / group_size if group_size > 0 else 0)))) * 0.1
+    r /= len(OWQ_RATIOS)
+    n_out = round(K * r * OWQ_RATIOS[name])
+    return n_out + n_out % 2
+
+
+def _owq_avg_bits(model, bits, group_size):
+    """arch.get_bits_usage over the model's own decoder linears: the mean of bits + 32 / group_size, weighted by the linears' sizes"""
+    mem = numel = 0.0
+    for b, full, _, _, lin in _decoder_linears(model):
+        n = lin.weight.numel()
+        mem += n * (_bits_of(bits, full, b) + 32 / group_size)
+        numel += n
+    return mem / numel
+
+
+@torch.no_grad()
+def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=True, frob_norm=True, n_out=None, device=None):
+    """The reference's ``OWQ.run`` (amq/quantization/owq.py:50-237: asymmetric, grouped, act_order=False) for a dense HF llama / mistral / qwen2 /
+    qwen3 model, ending in deployable layers (the reference only writes fake-quantized fp16 weights): block by block and subset by subset (the
+    four ``TRUE_SEQUENTIAL`` subsets by default, as the reference's), one Hessian per linear is accumulated over ``samples`` with forward hooks
+    (ops.GPTQHessian); per linear the outlier columns are chosen (ops.owq_select: the whole-row range pass, sens = diag(H) * the columns'
+    round-off; ``frob_norm=False``: diag(H) alone), W and H are permuted, and the solve (ops.gptq_hinv, ops.owq_quantize: HIP kernels) leaves a
+    packed layer over the kept columns and the fp16 outlier columns that absorbed the error feedback.  The dense weights are overwritten by what
+    the new layer dequantizes to for the block's second forward; at the block's end the linears become HIPOWQLinear modules (HIPQuantLinear where
+    n_out is 0).  ``n_out``: None = the reference's rule (``owq_n_out`` at the assignment's average bits), an int for every linear, or a dict
+    name -> int (names as in arch.LINEARS; a missing name takes the rule).  Groups of 128 only.  Returns (model, report) with
+    ``report[(block, name)] = {"loss", "rtn_loss", "solver_loss", "dead", "bits", "n_out", "out_ids"}`` -- loss = tr(dW H dW^T) over all K
+    columns, the outliers' change included.  An OWQ model runs under HF's own forward; ``prepare_for_inference(backend='hip')`` leaves its
+    layers as they are, and the hipGraph runner does not take them."""
+    from .arch import LINEARS
+    if int(group_size) != 128:
+        raise ValueError(f"the OWQ kernels serve groups of 128 only (got {group_size})")
+    report = {}
+    avg_bits = _owq_avg_bits(model, bits, group_size)
+
+    def outliers(name, K):
+        want = n_out.get(name) if isinstance(n_out, dict) else n_out
+        return owq_n_out(K, avg_bits, name, group_size) if want is None else int(want)
+
+    with _calibrating(model, samples, device) as (device, inps, _, run):
+        for b, layer in enumerate(model.model.layers):
+            full = _block_linears(layer)
+            made = {}
+            for names in (TRUE_SEQUENTIAL if true_sequential else (tuple(LINEARS),)):
+                hess = {name: ops.GPTQHessian(full[name].in_features, device) for name in names}
+                handles = [full[name].register_forward_hook(lambda _, inp, out, acc=hess[name]: acc.add_batch(inp[0].detach())) for name in names]
+                try:
+                    for x in inps:
+                        run(layer, x)
+                finally:
+                    for h in handles:
+                        h.remove()
+                for name in names:
+                    lin, nb = full[name], _bits_of(bits, name, b)
+                    H = hess[name].H
+                    W = lin.weight.detach().to(torch.float16).clone()
+                    K = W.shape[1]
+                    no = outliers(name, K)
+                    if frob_norm:
+                        ids, out_ids = ops.owq_select(W, H, no, nb)
+                    else:
+                        ids, out_ids = ops.owq_select(W, H, 0, nb) if no == 0 else _owq_select_by_hessian(H, no)
+                    Hp = H[ids][:, ids]
+                    U, dead = ops.gptq_hinv(Hp, percdamp, name=f"{b}.{name}")
+                    Wp = W[:, ids].contiguous()
+                    Wp[:, dead] = 0
+                    bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
+                    h, W_out, info = ops.owq_quantize(Wp, U, no, nb, group_size, return_info=True, bias=bias, name=name.split(".")[1])
+                    mod = HIPOWQLinear.from_owq(h, W_out, ids, device=device)
+                    W_hat = mod.dequantize()
+                    W0 = W.clone()
+                    W0[:, ids[dead]] = 0
+                    report[(b, name)] = {"loss": _proxy_loss(W0, W_hat, H), "rtn_loss": _proxy_loss(W0, _rtn_dequantized(W0, nb, group_size), H),
+                                         "solver_loss": info.loss, "dead": int(dead.sum().item()), "bits": nb, "n_out": no,
+                                         "out_ids": out_ids.cpu()}
+                    lin.weight.data = W_hat.to(lin.weight.dtype)
+                    made[name] = mod
+            inps = [run(layer, x).detach() for x in inps]
+            for name, mod in made.items():
+                _set_linear(layer, name, mod)
+    return model, report
+
+
+def _owq_select_by_hessian(H, n_out):
+    """owq.py hessian_sorting without frob_norm: the columns of largest diag(H)"""
+    K = H.shape[0]
+    desc = torch.argsort(torch.diag(H), descending=True, stable=True)
+    keep = torch.ones(K, dtype=torch.bool, device=H.device)
+    keep[desc[:n_out]] = False
+    return torch.cat([torch.arange(K, device=H.device)[keep], desc[:n_out]]), torch.sort(desc[:n_out])[0].to(torch.int32)
+
+
 AWQ_GRID = 20        # ratios r / 20 of the scale search (auto_scale.py:114)
 
 
@@ -669,8 +770,9 @@ def prepare_for_inference(model, allow_merge=False, backend="hip", verbose=False
         print("No load_path provided, using the model as is")
     _walk_hip(model, patch_add_weight_param)
     if kernel_arithmetic:
+        owq_inner = {id(m.inner) for m in model.modules() if isinstance(m, HIPOWQLinear)}      # OWQ layers keep the arithmetic their solve saw
         for mod in model.modules():
-            if isinstance(mod, HIPQuantLinear):
+            if isinstance(mod, HIPQuantLinear) and id(mod) not in owq_inner:
                 mod.to_kernel_arithmetic()
     if group_siblings:
         group_sibling_linears(model)
@@ -690,7 +792,13 @@ def _warn_unfused(model, group_siblings, fuse_mlp, fuse_norms, fuse_layers):
     signature), so a transformers refactor would otherwise fall back to 13 launches per block without a word.  Correctness is not
     affected either way."""
     import warnings
-    lins = [(n.rsplit(".", 1)[-1], m) for n, m in model.named_modules() if isinstance(m, HIPQuantLinear)]
+    owq = [n for n, m in model.named_modules() if isinstance(m, HIPOWQLinear)]
+    if owq:
+        warnings.warn(f"prepare_for_inference: {len(owq)} OWQ layers ({', '.join(owq[:3])}{', ...' if len(owq) > 3 else ''}) stay as they are: "
+                      "a HIPOWQLinear is not grouped with its siblings and not fused (its gather has no place in those launches)",
+                      RuntimeWarning, stacklevel=3)
+    owq_inner = {id(m.inner) for m in model.modules() if isinstance(m, HIPOWQLinear)}
+    lins = [(n.rsplit(".", 1)[-1], m) for n, m in model.named_modules() if isinstance(m, HIPQuantLinear) and id(m) not in owq_inner]
     names = {n for n, _ in lins}
     if not lins:
         return
@@ -702,7 +810,7 @@ def _warn_unfused(model, group_siblings, fuse_mlp, fuse_norms, fuse_layers):
         warnings.warn("prepare_for_inference: gate/up/down projections found but no MLP was fused (fuse_llama_mlps matched nothing: "
                       "no SiLU-gated, bias-free MLP of three HIPQuantLinear children)", RuntimeWarning, stacklevel=3)
     layers = [m for m in model.modules() if all(hasattr(m, k) for k in ("input_layernorm", "self_attn", "post_attention_layernorm", "mlp"))
-              and any(isinstance(c, HIPQuantLinear) for c in m.modules())]
+              and any(isinstance(c, HIPQuantLinear) and id(c) not in owq_inner for c in m.modules())]
     if fuse_norms and layers and not any(isinstance(m, HIPRMSNorm) for m in model.modules()):
         warnings.warn("prepare_for_inference: decoder layers found but no RMSNorm was fused into its consumer (fuse_llama_norms matched "
                       "nothing: needs a grouped q/k/v, a fused MLP and a LlamaRMSNorm-class norm)", RuntimeWarning, stacklevel=3)

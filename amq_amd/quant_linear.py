@@ -463,6 +463,96 @@ class HIPQuantLinear(nn.Module):
                 f"group_size={self.group_size}, bias={self.bias is not None}, mode={self.mode}")
 
 
+class HIPOWQLinear(nn.Module):
+    """An OWQ layer (owq.py): ``n_out`` input columns stay fp16, the others are a packed layer over the permuted, padded columns.
+    ``y = inner(x[:, perm]) + x[:, out_ids] . W_out^T`` as three steps: the gather kernel, the inner HIPQuantLinear's forward (any of its matmul
+    routes), the outlier-add kernel (an fp32 fmaf chain per output, added to the fp16 result and rounded once).  Holds ``inner`` (HIPQuantLinear
+    [N, Kp], Kp = the K - n_out quantized columns padded to whole groups of 128; it also holds the bias) and the buffers ``perm`` int32 [Kp]
+    (the original column of every packed column, -1 for the padding), ``out_ids`` int32 [n_out] ascending and ``W_out`` fp16 [N, n_out] in that
+    order.  The drop-in surface of HIPQuantLinear: ``bits, group_size, infeatures, outfeatures, bias, name``; any leading dims; fp16 in and out
+    (other dtypes are cast); state_dict / deepcopy / ``.to``.  Not grouped with siblings and not fused: the gather has no place in those launches."""
+    QUANT_TYPE = "hip-amq-owq"
+
+    def __init__(self, bits, group_size, infeatures, outfeatures, n_out, bias=False, name=None):
+        super().__init__()
+        if group_size != GROUP:
+            raise NotImplementedError("HIPOWQLinear: groups of 128 only")
+        n_out = int(n_out)
+        if n_out < 2 or n_out % 2 or n_out >= infeatures:
+            raise ValueError(f"HIPOWQLinear: n_out must be even and in 2 .. K - 2 (got {n_out}); a layer without outliers is a HIPQuantLinear")
+        self.bits, self.group_size, self.infeatures, self.outfeatures, self.n_out, self.name = bits, group_size, infeatures, outfeatures, n_out, name
+        self.packed_features = ops.owq_packed_columns(infeatures, n_out)
+        self.inner = HIPQuantLinear(bits, group_size, self.packed_features, outfeatures, bias=bias, name=name)
+        self.register_buffer("perm", torch.full((self.packed_features,), -1, dtype=torch.int32))
+        self.register_buffer("out_ids", torch.zeros(n_out, dtype=torch.int32))
+        self.register_buffer("W_out", torch.zeros(outfeatures, n_out, dtype=torch.float16))
+
+    @property
+    def bias(self):
+        return self.inner.bias
+
+    @classmethod
+    def from_owq(cls, h, W_out, ids, device=None):
+        """From ``ops.owq_quantize``'s result (HQQWeights of shape (N, Kp) and W_out fp16 [N, n_out] in the permuted order) and ``ops.owq_select``'s
+        ids [K].  With n_out == 0 the result is a plain HIPQuantLinear."""
+        n_out = int(W_out.shape[1]) if W_out is not None else 0
+        if n_out == 0:
+            return HIPQuantLinear.from_hqq(h, device=device)
+        dev = torch.device(device) if device is not None else h.W_q.device
+        N, Kp = h.shape
+        K = int(ids.numel())
+        nq = K - n_out
+        if Kp != ops.owq_packed_columns(K, n_out) or tuple(W_out.shape) != (N, n_out):
+            raise ValueError(f"from_owq: a packed layer {tuple(h.shape)}, W_out {tuple(W_out.shape)} and {K} ids do not belong together")
+        ids = ids.to(dev)
+        if int(ids.min()) < 0 or int(ids.max()) >= K or int(torch.unique(ids).numel()) != K:
+            raise ValueError("from_owq: ids is not a permutation of the input columns")
+        mod = cls(h.nbits, h.group_size, K, N, n_out, name=h.name)
+        mod.inner = HIPQuantLinear.from_hqq(h, device=dev)
+        out, order = torch.sort(ids[nq:])
+        perm = torch.full((Kp,), -1, dtype=torch.int32, device=dev)
+        perm[:nq] = ids[:nq].to(torch.int32)
+        mod.perm, mod.out_ids = perm, out.to(torch.int32).contiguous()
+        mod.W_out = W_out.to(dev, torch.float16)[:, order].contiguous()
+        return mod
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        K = self.infeatures                 # (load time: the gather and the add skip a column outside x, but such a module computes nonsense)
+        if int(self.perm.max()) >= K or int(self.out_ids.max()) >= K or int(self.out_ids.min()) < 0:
+            raise ValueError(f"HIPOWQLinear {self.name or prefix.rstrip('.')}: perm / out_ids name columns outside 0 .. {K - 1}")
+
+    def forward(self, x):
+        x_dtype = x.dtype
+        if x_dtype != torch.float16:
+            x = x.to(torch.float16)
+        K, N = self.infeatures, self.outfeatures
+        if x.shape[-1] != K:
+            raise ValueError(f"x: last dim {x.shape[-1]} != K={K}")
+        if not x.is_cuda or x.device != self.W_out.device:
+            raise ValueError(f"x is on {x.device} but the module's weights are on {self.W_out.device}")
+        x2 = x.reshape(-1, K)
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        if x2.shape[0] == 0:
+            return torch.empty(*x.shape[:-1], N, dtype=x_dtype, device=x.device)
+        y = self.inner(ops.owq_gather(x2, self.perm))
+        ops.owq_outlier_add(x2, self.out_ids, self.W_out, y)
+        y = y.reshape(*x.shape[:-1], N)
+        return y if x_dtype == torch.float16 else y.to(x_dtype)
+
+    def dequantize(self):
+        """the dense W [N, K] fp16 in the ORIGINAL column order: the packed columns as the inner layer dequantizes them, the outliers as held"""
+        nq = self.infeatures - self.n_out
+        W = torch.empty(self.outfeatures, self.infeatures, dtype=torch.float16, device=self.W_out.device)
+        W[:, self.perm[:nq].long()] = self.inner.dequantize()[:, :nq]
+        W[:, self.out_ids.long()] = self.W_out
+        return W
+
+    def extra_repr(self):
+        return (f"in_features={self.infeatures}, out_features={self.outfeatures}, bits={self.bits}, group_size={self.group_size}, "
+                f"n_out={self.n_out}, bias={self.bias is not None}")
+
+
 # HIPLlamaMLP / HIPQuantLinear -> C++ launch handles (kept OUTSIDE the modules: deepcopy / pickling of a model never meets a handle)
 _MLP_HANDLES = weakref.WeakKeyDictionary()
 _LIN_HANDLES = weakref.WeakKeyDictionary()

@@ -225,6 +225,65 @@ size_t amq_awq_clip_workspace_bytes(int N, int K, int T, int group);
 int amq_awq_clip_f16(const void* W, const void* X, int N, int K, int T, int bits, int group, void* hi, void* lo, void* best, void* err,
                      void* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* OWQ (amq/quantization/owq.py: OWQ.run, GPTQ_OWQ, Quantizer.find_params with mse, asymmetric, per channel): n_out input columns of a linear stay
+ * fp16 and absorb the error feedback of the quantized ones; every 128-column group of the rest takes its range from a candidate search.  Groups
+ * of 128 only.  All fp32, every operation its own IEEE rounding, IEEE division, rint = round-half-even, except the score's power below.
+ *
+ * Range search of a segment v[0..L) with maxq = 2^bits - 1: xmin = min(min v, 0), xmax = max(max v, 0), xrange = xmax - xmin; for i = 1..num:
+ * tmp_max = (xrange / num) * i, delta = max(tmp_max / maxq, 1e-8f), d16 = max(fp16(delta), 2^-24), r_c = rint(v_c / d16); for zp = 0..maxq:
+ * q_c = clamp(r_c + zp, 0, maxq), w^_c = fp16((q_c - zp) * d16) -- the weight amq_dequantize_hqq_f16 produces from scale d16 and zero zp --,
+ * score = (sum_c |v_c - w^_c|^2.4) / L.  The winner is the first candidate in (i ascending, zp ascending) order with the strictly smallest score,
+ * starting from 1e10; the result is (scale = d16, zero = zp, i, zp, score) of the winner.  |d|^2.4 is exp2(2.4f * log2(d)) on the hardware's
+ * v_log_f32 / v_exp_f32 (1 ulp each; 0 and denormal d give 0): the one place where bits may differ from a host restatement.  A row that holds a
+ * non-finite value ends without a winner (i = 0, scale = 0, score = 1e10).
+ *
+ * amq_owq_range_f16: the search of W[n, col0 .. col0 + L) for every row n, one workgroup of 256 threads per row, the segment staged in LDS.
+ * The sum's order: thread t adds its elements c = t, t + 256, ... in ascending c from 0; a wave's 64 sums meet in a butterfly (xor 1, 2, 4, 8, 16,
+ * 32); the four waves' sums are (w0 + w1) + (w2 + w3).
+ *   W          fp16 [N, K]
+ *   scale/zero fp16 [N]; choice int32 [N, 2] = (i, zp); score fp32 [N]
+ *   wq_err     fp32 [K] or NULL; only with col0 = 0, L = K: frob_c = the sum over the rows n ascending (one chain) of (w - w^)^2, one multiply and
+ *              one add per row, w^ the row's deployed weight under its winner
+ *   info       AMQ_OWQ_INFO_BYTES: {int32 nonfinite (!= 0: some row ended without a winner)}
+ * Refused, in this order: a null or misaligned pointer (AMQ_EINVAL); bits not 2 / 3 / 4 (AMQ_EINVAL); N % 16, K % 128, num outside 1..100, a
+ * segment outside the row or longer than 30720 (LDS), wq_err without the whole row (AMQ_ESHAPE).  Up to three launches (search, column sums, flag).
+ *
+ * amq_owq_quantize_f16: the solve over the PERMUTED W_p [N, K] (the n_out outlier columns last) and U_p = the upper Cholesky factor of the damped
+ * inverse of the equally permuted Hessian; the caller has zeroed dead columns.  n_nonout = K - n_out.  Per row, columns ascending, blocks of 128,
+ * as amq_gptq_quantize_f16 above with three differences: (a) at a block's start its group takes (d16, zp) from the range search over the row's
+ * CURRENT values of the group's columns < n_nonout (the last group may be ragged, L = n_nonout mod 128; the sum's order: a lane adds its up to 8
+ * consecutive columns ascending from 0, the row's 16 lanes meet in a butterfly, xor 1, 2, 4, 8); (b) columns >= n_nonout are never quantized and
+ * contribute no error: they receive w_j -= e * U[i,j] of every earlier quantized column i, each element in ascending i, and leave as
+ * W_out = fp16(w_j); (c) the packed result has Kp = 128 * ceil(n_nonout / 128) columns and the padding columns of a ragged last group take the
+ * code zp, so they dequantize to exactly 0.  n_out = 0 is GPTQ with searched ranges.
+ *   W_p        fp16 [N, K], U_p fp32 [K, K], both 16-byte aligned
+ *   W_q        Format A of a layer [N, Kp] in groups of 128; scale = d16, zero = zp, fp16 [N * Kp / 128]
+ *   W_out      fp16 [N, n_out] (may be NULL when n_out = 0): the outlier columns in W_p's order
+ *   choice     int32 [N, Kp / 128, 2]: the winner's (i, zp) per row and group
+ *   row_loss   fp32 [N]: the quantized columns' ((w - w^)^2 / U[i,i]^2) / 2, summed in ascending i
+ *   info       AMQ_OWQ_INFO_BYTES: {int32 nonfinite (!= 0: some w, e or U[i,i] was not finite, U[i,i] <= 0 or a group had no winner)}
+ *   workspace  amq_owq_quantize_workspace_bytes(N, K, n_out, group) = 5 * N * Kp + N bytes (fp32 errors [N, Kp], int32 flags [N / 4], byte codes
+ *              [N, Kp]), 16-byte aligned; 0 for a shape the call refuses
+ * Refused, in this order: a null or misaligned pointer (AMQ_EINVAL); bits not 2 / 3 / 4 (AMQ_EINVAL); group not 128, N % 16, K % 128, num outside
+ * 1..100, n_out odd, negative or >= K (AMQ_ESHAPE); workspace_bytes too small (AMQ_EINVAL).  Three launches (solve, nonfinite flag, pack).
+ *
+ * The deployment side of a layer y = xg . Wq^T + x[:, out_ids] . W_out^T (two entry points around the packed matmul):
+ * amq_owq_gather_f16: xg[m, c] = x[m, perm[c]], and 0 where perm[c] is not in 0 .. K - 1 (the padding columns: a 0 weight must not meet an inf).
+ *   x fp16 [M, K], perm int32 [Kp], xg fp16 [M, Kp], Kp % 128 == 0
+ * amq_owq_outlier_add_f16: after the packed matmul over xg has written y, y[m, n] = fp16(fp32(y[m, n]) + acc), acc = the fmaf chain over j ascending
+ * of fp32(x[m, out_ids[j]]) * fp32(W_out[n, j]) from 0.
+ *   out_ids int32 [n_out] ascending, W_out fp16 [N, n_out] with its columns in that order, y fp16 [M, N], M <= 65535
+ * None of these calls reads on the host, allocates or uses atomics: the same bits on every run, capturable. */
+#define AMQ_OWQ_INFO_BYTES 4
+int amq_owq_range_f16(const void* W, int N, int K, int col0, int L, int bits, int num, void* scale, void* zero, void* choice, void* score,
+                      void* wq_err, void* info, void* stream);
+size_t amq_owq_quantize_workspace_bytes(int N, int K, int n_out, int group);
+int amq_owq_quantize_f16(const void* W_p, const void* U_p, int N, int K, int n_out, int bits, int group, int num, void* W_q, void* scale,
+                         void* zero, void* W_out, void* choice, void* row_loss, void* info, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int amq_owq_gather_f16(const void* x, int M, int K, const void* perm, int Kp, void* xg, void* stream);
+int amq_owq_outlier_add_f16(const void* x, int M, int K, const void* out_ids, int n_out, const void* W_out, void* y, int N, void* stream);
+
 /* ---- dequantize ---------------------------------------------------------- */
 /* native -> W[N,K] fp16 (row-major, nn.Linear orientation) */
 int amq_dequantize_f16(int bits, int mode, const void* qweight_native, const void* meta_native,
