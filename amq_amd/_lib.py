@@ -82,6 +82,9 @@ SIGNATURES = {
     # dense fp16 + the inverse Hessian's Cholesky factor -> Format A: GPTQ's error-feedback solve (info = {int32 nonfinite})
     "amq_gptq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
     "amq_gptq_quantize_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the same with static groups and an activation order: (W, U_p, perm int32 [K], ...), the packed layer in W's own column order
+    "amq_gptq_quantize_static_workspace_bytes": (_sz, [_i, _i, _i]),
+    "amq_gptq_quantize_static_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # OWQ: the range search of row segments, the solve that leaves n_out columns fp16, the layer's gather and outlier add (info = {int32 nonfinite})
     "amq_owq_range_f16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amq_owq_quantize_workspace_bytes": (_sz, [_i, _i, _i, _i]),

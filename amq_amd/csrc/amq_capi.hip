@@ -171,6 +171,20 @@ int amq_gptq_quantize_f16(const void* W, const void* U, int N, int K, int bits, 
                      "gptq_quantize");
 }
 
+size_t amq_gptq_quantize_static_workspace_bytes(int N, int K, int group) { return amq_gptq_quantize_workspace_bytes(N, K, group); }
+
+int amq_gptq_quantize_static_f16(const void* W, const void* U_p, const void* perm, int N, int K, int bits, int group, void* W_q, void* scale,
+                                 void* zero, void* row_loss, void* info, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!W || !U_p || !perm || !W_q || !scale || !zero || !row_loss || !info || !workspace) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)W & 15) != 0 || ((uintptr_t)U_p & 15) != 0 || ((uintptr_t)perm & 15) != 0 || ((uintptr_t)workspace & 15) != 0 ||
+        ((uintptr_t)W_q & 3) != 0 || ((uintptr_t)row_loss & 3) != 0 || ((uintptr_t)info & 3) != 0)
+        return fail(AMQ_EINVAL, "W, U_p, perm and workspace must be 16-byte aligned, W_q, row_loss and info 4-byte aligned");
+    if (int rc = check_quantize_shape(QUANT_GPTQ, bits, N, K, group)) return rc;
+    if (int rc = check_workspace("GPTQ", amq::gptq_workspace_bytes(N, K), workspace_bytes)) return rc;
+    return check_hip(amq::launch_gptq_quantize_static(W, U_p, perm, N, K, bits, group, W_q, scale, zero, row_loss, info, workspace,
+                                                      (hipStream_t)stream), "gptq_quantize_static");
+}
+
 // OWQ: groups of 128 only (AMQ's); the shape rules of the range search and of the solve, in the order the header documents
 static int check_owq_shape(int bits, int N, int K, int group, int num) {
     if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);

@@ -346,6 +346,10 @@ inline int gptq_flags(int N) { return N / (64 / GPTQ_LANES); }
 inline size_t gptq_workspace_bytes(int N, int K) { return 5 * (size_t)N * K + 4 * (size_t)gptq_flags(N); }
 hipError_t launch_gptq_quantize(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero,
                                 void* row_loss, void* info, void* workspace, hipStream_t st);
+// the same solve with static groups and an activation order (amq_gptq_static.hip): perm int32 [K], U the factor of the permuted Hessian; every
+// group's (scale, zero) comes from W's original columns in a launch of its own, the codes leave in W's own column order.  The same workspace.
+hipError_t launch_gptq_quantize_static(const void* W, const void* U, const void* perm, int N, int K, int bits, int group, void* W_q, void* scale,
+                                       void* zero, void* row_loss, void* info, void* workspace, hipStream_t st);
 // what ends the GPTQ solve and AWQ's passes (amq_quant_pack.hip): the n per-wave nonfinite flags ORed into one word of the info block, and byte
 // codes [R, group] -> Format A (hqq/core/bitpack.py row chunks), one thread per packed word
 hipError_t launch_quant_flags(const int* NF, size_t n, int* info_word, hipStream_t st);

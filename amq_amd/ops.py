@@ -291,25 +291,72 @@ def gptq_quantize_launch(W, U, nbits, group_size, W_q, scale, zero, row_loss, in
                                                  _lib.current_stream()))
 
 
-def gptq_quantize_buffers(N, K, nbits, group_size, device):
+def gptq_quantize_buffers(N, K, nbits, group_size, device, query="amq_gptq_quantize_workspace_bytes"):
     """(W_q, scale, zero, row_loss, info, workspace) of the right sizes for ``gptq_quantize_launch``"""
     serves = "the GPTQ solve serves groups of 32, 64 and 128"
     if int(group_size) == 256:
         serves += ": a group of 256 would span two of its 128-column blocks"
     group_size = _quantize_shape(N, K, nbits, group_size, GPTQ_GROUPS, serves)
-    words = _workspace_words("amq_gptq_quantize_workspace_bytes", "the GPTQ solve", N=N, K=K, group=group_size)
+    words = _workspace_words(query, "the GPTQ solve", N=N, K=K, group=group_size)
     return (*_format_a_buffers(N, K, nbits, group_size, device), torch.empty(N, dtype=torch.float32, device=device),
             _info_block(_lib.GPTQ_INFO_BYTES, device), _gptq_scratch.get(device, words))
 
 
-def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, name=None):
+def gptq_act_order(H):
+    """The reference's activation order of a Hessian H [K, K] (gptq.py:226-227, 239): ``perm`` (int64 [K], on H's device) = the columns by
+    descending ``diag(H)``, a dead column (diagonal 0) ranking as 1.  The sort is stable, so ties go to the lower column: the reference's ``perm``
+    wherever the diagonal has no ties.  Walk column i of ``gptq_quantize(..., perm=perm, static_groups=True)`` is column ``perm[i]``, and its
+    ``U`` is ``gptq_hinv(H[perm][:, perm])``."""
+    d = torch.diag(H.detach()).to(torch.float32)
+    d = torch.where(d == 0, torch.ones_like(d), d)
+    return torch.sort(d, descending=True, stable=True)[1]
+
+
+def _gptq_perm(perm, K, device):
+    """``gptq_quantize``'s ``perm`` as the entry point takes it (int32 [K], contiguous, on ``device``), validated on the host before any launch"""
+    if not isinstance(perm, torch.Tensor) or perm.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"perm: expected an int32 or int64 tensor, got {getattr(perm, 'dtype', type(perm).__name__)}")
+    if perm.device != device:
+        raise ValueError(f"perm: expected a tensor on W's GPU ({device}), got {perm.device}")
+    if tuple(perm.shape) != (K,):
+        raise ValueError(f"perm: expected shape ({K},), got {tuple(perm.shape)}")
+    if not torch.equal(torch.sort(perm.to(torch.int64))[0], torch.arange(K, dtype=torch.int64, device=device)):
+        raise ValueError(f"perm: not a permutation of 0 .. {K - 1}")
+    return perm.to(torch.int32).contiguous()
+
+
+def gptq_quantize_static_launch(W, U, perm, nbits, group_size, W_q, scale, zero, row_loss, info, workspace):
+    """the bare entry point of the static-groups solve over caller-owned buffers (four launches on the current stream; no allocation, no
+    read-back: capturable).  ``perm``: int32 [K], a permutation -- the entry point cannot check it (``gptq_quantize`` does)."""
+    N, K = W.shape
+    _lib.check(_lib.load().amq_gptq_quantize_static_f16(_lib.ptr(W), _lib.ptr(U), _lib.ptr(perm), N, K, int(nbits), int(group_size),
+                                                        _lib.ptr(W_q), _lib.ptr(scale), _lib.ptr(zero), _lib.ptr(row_loss), _lib.ptr(info),
+                                                        _lib.ptr(workspace), _nbytes(workspace), _lib.current_stream()))
+
+
+def gptq_quantize_static_buffers(N, K, nbits, group_size, device):
+    """(W_q, scale, zero, row_loss, info, workspace) of the right sizes for ``gptq_quantize_static_launch`` (the plain solve's sizes)"""
+    return gptq_quantize_buffers(N, K, nbits, group_size, device, query="amq_gptq_quantize_static_workspace_bytes")
+
+
+def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, name=None, perm=None, static_groups=False):
     """Dense W [N, K] and U [K, K] (``gptq_hinv``: fp32, the upper Cholesky factor of the damped inverse Hessian) on the GPU -> HQQWeights (Format
-    A) on the same device by GPTQ's error-feedback solve (gptq.py:206-311: asymmetric, grouped, blocks of 128 columns, no act-order, no static
-    groups) as HIP kernels, in the arithmetic include/amq_hip.h states: the scale is rounded to fp16 before it is used and the error feedback sees
-    the weight the packed layer will dequantize to.  W is fp16 (bf16 / fp32 weights are cast at this boundary); the caller has zeroed its dead
-    columns.  Raises ValueError if a weight, an error or U's diagonal was not finite (or the diagonal not positive).  One synchronising read of the
-    4-byte info block per call.  ``return_info``: also return the :class:`GPTQQuantizeInfo`."""
+    A) on the same device by GPTQ's error-feedback solve (gptq.py:206-311: asymmetric, grouped, blocks of 128 columns) as HIP kernels, in the
+    arithmetic include/amq_hip.h states: the scale is rounded to fp16 before it is used and the error feedback sees the weight the packed layer
+    will dequantize to.  W is fp16 (bf16 / fp32 weights are cast at this boundary); the caller has zeroed its dead columns.  Raises ValueError if a
+    weight, an error or U's diagonal was not finite (or the diagonal not positive).  One synchronising read of the 4-byte info block per call.
+    ``return_info``: also return the :class:`GPTQQuantizeInfo`.
+
+    ``static_groups=True``: every group's (scale, zero) is fixed from W's original columns before the solve (gptq.py:230-236).  With it,
+    ``perm`` (an integer tensor [K] on W's device, a permutation of 0 .. K - 1, e.g. ``gptq_act_order(H)``) makes the solve walk the columns in
+    that order -- the reference's ``actorder=True, static_groups=True`` -- and U must be the factor of the equally permuted Hessian,
+    ``gptq_hinv(H[perm][:, perm])``.  W stays in its own order and so does the packed result: an ordinary Format A layer.  ``perm`` is validated
+    before any launch (ValueError).  ``perm`` without ``static_groups`` raises NotImplementedError: groups formed over the permuted columns are not
+    a Format A layer (it would need a gather at run time)."""
     from .hqq_format import HQQWeights
+    if perm is not None and not static_groups:
+        raise NotImplementedError("gptq_quantize: an activation order without static groups forms its groups over the permuted columns, which is "
+                                  "not a Format A layer (it would need a gather of x at run time); pass static_groups=True")
     W = _dense_f16(W, "W")
     N, K = W.shape
     if not isinstance(U, torch.Tensor) or U.device != W.device:
@@ -317,8 +364,13 @@ def gptq_quantize(W, U, nbits, group_size=GROUP, return_info=False, bias=None, n
     U = U.detach().contiguous()                # (cholesky(upper=True) hands out a transposed view)
     _need(U, torch.float32, "U", K * K)
     nbits = int(nbits)
-    W_q, scale, zero, row_loss, info, workspace = gptq_quantize_buffers(N, K, nbits, group_size, W.device)
-    gptq_quantize_launch(W, U, nbits, group_size, W_q, scale, zero, row_loss, info, workspace)
+    if static_groups:
+        perm = torch.arange(K, dtype=torch.int32, device=W.device) if perm is None else _gptq_perm(perm, K, W.device)
+        W_q, scale, zero, row_loss, info, workspace = gptq_quantize_static_buffers(N, K, nbits, group_size, W.device)
+        gptq_quantize_static_launch(W, U, perm, nbits, group_size, W_q, scale, zero, row_loss, info, workspace)
+    else:
+        W_q, scale, zero, row_loss, info, workspace = gptq_quantize_buffers(N, K, nbits, group_size, W.device)
+        gptq_quantize_launch(W, U, nbits, group_size, W_q, scale, zero, row_loss, info, workspace)
     got = GPTQQuantizeInfo(info.cpu()[0].item(), row_loss)
     _refuse_nonfinite(got.nonfinite, "gptq_quantize", name, ": a weight, an error or U's diagonal was not finite (or the diagonal not positive)")
     h = HQQWeights(W_q, scale, zero, nbits, (N, K), int(group_size), bias, name)
@@ -1903,7 +1955,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_quantize", "gptq_quantize_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
+for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_quantize", "gptq_quantize_launch", "gptq_quantize_static_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup", "decode_tail_lookup_sample"):
     globals()[_name] = _on_tensor_device(globals()[_name])

@@ -419,8 +419,9 @@ def _proxy_loss(W, W_hat, H):
 
 
 @torch.no_grad()
-def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=False, device=None):
-    """The reference's ``GPTQ.run`` (amq/quantization/gptq.py:25-161: asymmetric, grouped, act_order=False, static_groups=False) for a dense HF
+def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=False, device=None, act_order=False,
+                        static_groups=False):
+    """The reference's ``GPTQ.run`` (amq/quantization/gptq.py:25-161: asymmetric, grouped; act_order and static_groups as below) for a dense HF
     llama / mistral / qwen2 / qwen3 model, ending in packed layers: block by block, one Hessian per linear is accumulated over ``samples`` with
     forward hooks (ops.GPTQHessian), every linear is quantized at ``_bits_of(bits, name, block)`` by the error-feedback solve (ops.gptq_hinv,
     ops.gptq_quantize: HIP kernels) and its dense weights are overwritten by what the packed layer dequantizes to, so that the block's second
@@ -429,8 +430,16 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
     down), each calibrated on the outputs of the quantized ones before it.  The whole model works on ``device`` (default: the model's own GPU,
     else cuda:0).  Returns (model, report) with ``report[(block, name)] = {"loss": tr(dW H dW^T), "rtn_loss": the same for
     hqq_format.quantize_rtn at the same bits and group, "solver_loss": the solve's own sum of row losses (the reference's printed error), "dead":
-    the number of dead columns, "bits"}``.  The model is then ready for ``prepare_for_inference(backend='hip')``."""
+    the number of dead columns, "bits", "act_order", "static_groups"}``.  The model is then ready for ``prepare_for_inference(backend='hip')``.
+
+    ``static_groups``: every group's (scale, zero) comes from the layer's original columns, not from the running ones.  ``act_order`` (with
+    ``static_groups``): the solve walks the columns by descending ``diag(H)`` (ops.gptq_act_order) over the factor of the equally permuted Hessian;
+    the packed layer stays in its own column order, an ordinary Format A layer on every fast path.  ``act_order`` without ``static_groups`` is
+    refused (NotImplementedError): its groups run over the permuted columns and would need a gather at run time."""
     from .arch import LINEARS
+    if act_order and not static_groups:
+        raise NotImplementedError("quantize_model_gptq: act_order without static_groups forms its groups over the permuted columns, which is not "
+                                  "a Format A layer (it would need a gather of x at run time); pass static_groups=True as well")
     report = {}
     with _calibrating(model, samples, device) as (device, inps, _, run):
         for b, layer in enumerate(model.model.layers):
@@ -448,14 +457,19 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
                 for name in names:
                     lin, nb = full[name], _bits_of(bits, name, b)
                     H = hess[name].H
-                    U, dead = ops.gptq_hinv(H, percdamp, name=f"{b}.{name}")
+                    perm = ops.gptq_act_order(H) if act_order else None
+                    U, dead = ops.gptq_hinv(H if perm is None else H[perm][:, perm], percdamp, name=f"{b}.{name}")
+                    if perm is not None:
+                        dead = torch.diag(H) == 0              # (gptq_hinv's mask is in walk order)
                     W = lin.weight.detach().to(torch.float16).clone()
                     W[:, dead] = 0
                     bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
-                    h, info = ops.gptq_quantize(W, U, nb, group_size, return_info=True, bias=bias, name=name.split(".")[1])
+                    h, info = ops.gptq_quantize(W, U, nb, group_size, return_info=True, bias=bias, name=name.split(".")[1], perm=perm,
+                                                static_groups=static_groups)
                     W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, *W.shape, group_size)
                     report[(b, name)] = {"loss": _proxy_loss(W, W_hat, H), "rtn_loss": _proxy_loss(W, _rtn_dequantized(W, nb, group_size), H),
-                                         "solver_loss": info.loss, "dead": int(dead.sum().item()), "bits": nb}
+                                         "solver_loss": info.loss, "dead": int(dead.sum().item()), "bits": nb,
+                                         "act_order": bool(act_order), "static_groups": bool(static_groups)}
                     lin.weight.data = W_hat.to(lin.weight.dtype)
                     packed[name] = h
             inps = [run(layer, x).detach() for x in inps]

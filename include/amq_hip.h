@@ -183,6 +183,28 @@ size_t amq_gptq_quantize_workspace_bytes(int N, int K, int group);
 int amq_gptq_quantize_f16(const void* W, const void* U, int N, int K, int bits, int group, void* W_q, void* scale, void* zero, void* row_loss,
                           void* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same solve with static groups and an activation order (gptq.py fasterquant(actorder=True, static_groups=True)), to the same Format A in W's
+ * OWN column order, as four launches on `stream` (parameters, solve, nonfinite flag, pack).  First, for every row and every group of `group`
+ * consecutive columns of W as handed in: xmin = min(min(x), 0), xmax = max(max(x), 0) (-1 / +1 if both are 0), s = (xmax - xmin) / maxq,
+ * s16 = max(fp16(s), 2^-24), z = rint(-xmin / s16) -- the arithmetic above, applied once to the ORIGINAL values instead of per block to the
+ * running ones.  Then per row the columns are walked in perm's order, i = 0 .. K - 1 ascending, in blocks of 128: walk column i is original column
+ * perm[i], w its running value, (s16, z) those of group perm[i] / group; q = clamp(rint(w / s16) + z, 0, maxq), w^ = fp16((q - z) * s16),
+ * e = (w - w^) / U_p[i,i], loss += ((w - w^)^2 / U_p[i,i]^2) / 2; then w_j -= e * U_p[i,j] (one multiply, one subtract) for every walk column
+ * j > i, each element in ascending i.  The code of walk column i is column perm[i] of the packed layer: nothing at inference time knows the order.
+ * All fp32, every operation its own rounding, IEEE division, round-half-even.  No host read, no allocation, no atomics; rows are independent.
+ *   W          fp16 [N, K], 16-byte aligned, in its own column order; the caller has zeroed the columns whose Hessian diagonal is 0
+ *   U_p        fp32 [K, K], 16-byte aligned: the upper Cholesky factor of the damped inverse of the PERMUTED Hessian H[perm][:, perm]
+ *   perm       int32 [K], 16-byte aligned: a permutation of 0 .. K - 1.  The entry point cannot read it: the caller guarantees it (an entry
+ *              outside 0 .. K - 1 is read as 0 and sets info; a repeated entry leaves codes unwritten).  The identity: static groups alone.
+ *   W_q, scale, zero, row_loss, info   as for amq_gptq_quantize_f16
+ *   workspace  amq_gptq_quantize_static_workspace_bytes(N, K, group) = 5 * N * K + N bytes (fp32 errors [N, K] in walk order, int32 flags [N / 4],
+ *              byte codes [N, K] in W's order), 16-byte aligned; 0 for a shape the call refuses
+ * Refused, in this order, as amq_gptq_quantize_f16: a null or misaligned pointer (AMQ_EINVAL); bits not 2 / 3 / 4 (AMQ_EINVAL); group not
+ * 32 / 64 / 128, N % 16, K % 128 (AMQ_ESHAPE); workspace_bytes too small (AMQ_EINVAL). */
+size_t amq_gptq_quantize_static_workspace_bytes(int N, int K, int group);
+int amq_gptq_quantize_static_f16(const void* W, const void* U_p, const void* perm, int N, int K, int bits, int group, void* W_q, void* scale,
+                                 void* zero, void* row_loss, void* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* AWQ's weight-side passes (awq_utils/quantizer.py pseudo_quantize_tensor with zero_point, auto_clip.py auto_clip_layer_asym) to the same Format A.
  * All fp32, every operation its own IEEE rounding, IEEE division, rint = round-half-even, no contraction except the fmaf written out below.
  * RTN of one group v[0..G) of fp16 values: maxq = 2^bits - 1, xmax = max v, xmin = min v, s = max(xmax - xmin, 1e-5f) / maxq, s16 = fp16(s) (never

@@ -12,6 +12,14 @@ calls; where it ran is recorded).  The result is merged into ``--out`` under "ti
 under "parity" there).
 
     python tools/gptq_bench.py [--repeats 5] [--tokens 2048] [--out profiles/gptq_quantize.json]
+
+``--act-order``: the variant instead (activation order + static groups, ops.gptq_quantize(..., perm=, static_groups=True): parameters + solve +
+flag + pack kernels) against the plain solve in the same session, at 2, 3 and 4 bit over the same three shapes.  The calibration gets hot channels
+(every 64th column x 12), as real activations have and as an order by diag(H) needs to matter; both legs see the same W and the same H (the
+variant's U is the factor of H[perm][:, perm]), alternate, and report the median of ``--repeats`` after a warm-up round, the proxy loss
+tr(dW H dW^T) of each result and their ratio.  A synthetic calibration: nothing here says what the variant does to a real model's perplexity.
+
+    python tools/gptq_bench.py --act-order [--repeats 5] [--tokens 2048] [--out profiles/gptq_actorder.json]
 """
 import argparse
 import json
@@ -87,13 +95,66 @@ def _runs(row, leg, ts):
     row[leg + "_spread_pct"] = round(100.0 * (max(ts) - min(ts)) / statistics.median(ts), 2)
 
 
+def act_order_main(a):
+    """the variant against the plain solve: one row per (shape, bits)"""
+    from amq_amd import ops
+    rows, calib = [], {}
+    with torch.inference_mode():
+        for K in sorted({k for _, _, k in SHAPES}):
+            g = torch.Generator(device=DEV).manual_seed(K)
+            r = K // 8
+            X = (torch.randn(a.tokens, r, device=DEV, generator=g) @ (torch.randn(r, K, device=DEV, generator=g) / r ** 0.5)
+                 + 0.3 * torch.randn(a.tokens, K, device=DEV, generator=g))
+            X[:, ::64] *= 12.0
+            acc = ops.GPTQHessian(K, DEV)
+            acc.add_batch(X.to(torch.float16).unsqueeze(0))
+            perm = ops.gptq_act_order(acc.H)
+            calib[K] = (acc.H, perm, ops.gptq_hinv(acc.H, 0.01)[0], ops.gptq_hinv(acc.H[perm][:, perm], 0.01)[0])
+            del X, acc
+        for name, N, K in SHAPES:
+            W = (torch.randn(N, K, device=DEV, generator=torch.Generator(device=DEV).manual_seed(N + K)) * 0.02).to(torch.float16)
+            H, perm, U, U_p = calib[K]
+            for bits in (2, 3, 4):
+                legs = {"plain": lambda: ops.gptq_quantize(W, U, bits, GROUP),
+                        "act_order_static": lambda: ops.gptq_quantize(W, U_p, bits, GROUP, perm=perm, static_groups=True)}
+                runs = {k: [] for k in legs}
+                for rep in range(a.repeats + 1):            # (the first round warms up: not kept)
+                    for leg, fn in legs.items():
+                        ms = _timed(fn)
+                        if rep:
+                            runs[leg].append(ms)
+                row = {"layer": name, "N": N, "K": K, "bits": bits, "group": GROUP, "repeats": a.repeats, "tokens": a.tokens}
+                for leg, fn in legs.items():
+                    _runs(row, leg, runs[leg])
+                    h = fn()
+                    d = W.float() - ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), bits, N, K, GROUP).float()
+                    row[leg + "_proxy_loss"] = float(((d @ H) * d).double().sum().item())
+                    del h, d
+                row["time_over_plain"] = round(row["act_order_static_ms"] / row["plain_ms"], 3)
+                row["proxy_loss_over_plain"] = round(row["act_order_static_proxy_loss"] / row["plain_proxy_loss"], 4)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                torch.cuda.empty_cache()
+    res = {"device": torch.cuda.get_device_name(0), "layers": rows,
+           "note": "synthetic calibration with hot channels; no real model or dataset was measured"}
+    if a.out:
+        doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        doc["timing"] = res
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--tokens", type=int, default=2048)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--act-order", action="store_true", help="time the act-order + static-groups variant against the plain solve")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
+    if a.act_order:
+        return act_order_main(a)
     from amq_amd import ops
     from amq_amd.hqq_format import pack_rows
 
