@@ -20,6 +20,8 @@ MODE_HQQ, MODE_FMA, MODE_FMA1 = 0, 1, 2
 PRO_NONE, PRO_RMSNORM, PRO_SILU_MUL = 0, 1, 2
 PRO_MUL = 4                  # x * x2 over a gate activated where it was written (GemvOpts.act_mask); 3 is internal to the library
 MAX_SEGMENTS = 4
+GEMV_ROUTE_GENERIC, GEMV_ROUTE_KEYED = 0, 1     # amq_gemv_route
+GEMV_DEPTH_GENERIC = -1      # GemvOpts.depth: auto depth, and the generic kernel where the launch would take a keyed one (A/B)
 MATH_DEFAULT, MATH_LINEAR, MATH_GROUPSCALE, MATH_EXACT = 0, 1, 2, 3
 FEWROW_AUTO, FEWROW_TILE, FEWROW_STREAM = 0, 1, 2      # kernel form of the grouped few-row launch (amq_gemm_xfrag_grouped_form_f16)
 ABI_VERSION = 521            # include/amq_hip.h AMQ_VERSION these bindings mirror (checked at load)
@@ -157,6 +159,8 @@ SIGNATURES = {
     "amq_rope_rows_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "amq_silu_mul_f16": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "amq_gemv_grouped_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, ctypes.POINTER(GemvOpts), _vp]),
+    "amq_gemv_route": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(GemvOpts)]),
+    "amq_gemv_segment_order": (_i, [_i, ctypes.POINTER(_i), _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "amq_gemv_grouped_sums_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),
     "amq_gemm_f16w_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "amq_gemm_route_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -326,7 +326,9 @@ int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const
         return fail(AMQ_EINVAL, "opts.math must be AMQ_MATH_DEFAULT, AMQ_MATH_EXACT, AMQ_MATH_GROUPSCALE or AMQ_MATH_LINEAR");
     if (o.math == AMQ_MATH_DEFAULT) o.math = amq_default_gemv_math();
     if (o.waves != 0 && o.waves != 4 && o.waves != 8 && o.waves != 16) return fail(AMQ_EINVAL, "opts.waves must be 0, 4, 8 or 16");
-    if (o.depth != 0 && o.depth != 2 && o.depth != 4) return fail(AMQ_EINVAL, "opts.depth must be 0, 2 or 4");
+    if (o.depth != 0 && o.depth != 2 && o.depth != 4 && o.depth != AMQ_GEMV_DEPTH_GENERIC) return fail(AMQ_EINVAL, "opts.depth must be 0, 2, 4 or AMQ_GEMV_DEPTH_GENERIC");
+    const bool generic = o.depth == AMQ_GEMV_DEPTH_GENERIC;       // (auto depth under the generic kernel: everything below sees 0)
+    if (generic) o.depth = 0;
     if (o.rpt < 0 || o.rpt > 64) return fail(AMQ_EINVAL, "opts.rpt (row-tiles per workgroup) must be 0..64");
     if (o.act_mask < 0 || o.act_mask >= (1 << nseg)) return fail(AMQ_EINVAL, "opts.act_mask names segments 0..%d (got 0x%x)", nseg - 1, o.act_mask);
     // (the activated output and the prologue that multiplies it live in the group-128 kernels; finer groups keep AMQ_PRO_SILU_MUL)
@@ -358,9 +360,34 @@ int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const
     a.force_depth = o.depth;
     a.force_rpt = o.rpt;
     a.gp = amq::meta_pairs(group);
+    a.generic = generic;
     if (a.gp > 1 && (o.dot || o.math == AMQ_MATH_LINEAR || o.depth == 4))
         return fail(AMQ_EINVAL, "groups of %d: the GEMV kernel's default form only (opts.math = AMQ_MATH_EXACT, opts.dot = 0, opts.depth = 0 / 2)", group);
     return check_hip(amq::launch_gemv(a, (hipStream_t)stream), "gemv");
+}
+
+// the flags launch_gemv sees for a set of options (amq_gemv_grouped_f16 builds the same)
+static int gemv_flags_of(const amq_gemv_opts& o) {
+    const int math = o.math == AMQ_MATH_DEFAULT ? amq_default_gemv_math() : o.math;
+    return (o.dot ? amq::GEMV_FLAG_DOT : 0) | (math == AMQ_MATH_LINEAR ? amq::GEMV_FLAG_LINEAR : 0) | (math == AMQ_MATH_GROUPSCALE ? amq::GEMV_FLAG_GS : 0);
+}
+
+int amq_gemv_route(int prologue, int M, int K, int group, int nseg, const int* bits, const int* modes, const amq_gemv_opts* opts) {
+    if (!bits || !modes || nseg < 1 || nseg > AMQ_MAX_SEGMENTS) return fail(AMQ_EINVAL, "nseg must be 1..%d (got %d), bits and modes non-null", AMQ_MAX_SEGMENTS, nseg);
+    if (group != 32 && group != 64 && (group < 128 || group % 128 != 0)) return fail(AMQ_ESHAPE, "group must be 32, 64 or a multiple of 128 (got %d)", group);
+    amq_gemv_opts o{};
+    if (opts) o = *opts;
+    const bool generic = o.depth == AMQ_GEMV_DEPTH_GENERIC;
+    int km[AMQ_MAX_SEGMENTS];
+    for (int i = 0; i < nseg; ++i) km[i] = modes[i] == AMQ_MODE_HQQ ? (int)amq::MODE_HQQ : (int)amq::MODE_FMA;      // (one-rounding buffers are generic either way)
+    return amq::gemv_route(prologue, M, K, amq::meta_pairs(group), nseg, bits, km, gemv_flags_of(o), o.waves, generic ? 0 : o.depth, o.rpt, generic);
+}
+
+int amq_gemv_segment_order(int nseg, const int* bits, int act_mask, int* order, int* act_mask_out) {
+    if (!bits || !order || nseg < 1 || nseg > AMQ_MAX_SEGMENTS) return fail(AMQ_EINVAL, "nseg must be 1..%d (got %d), bits and order non-null", AMQ_MAX_SEGMENTS, nseg);
+    const int m = amq::gemv_segment_order(nseg, bits, act_mask, order);
+    if (act_mask_out) *act_mask_out = m;
+    return AMQ_OK;
 }
 
 int amq_gemv_grouped_sums_f16(const amq_segment* segs, int nseg, const void* x, const void* gamma, float eps, const float* sums_in,

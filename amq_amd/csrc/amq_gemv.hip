@@ -1,6 +1,6 @@
 // amq_gemv.hip -- host side of the weight-streaming GEMV: launch plan (waves, row-tiles per workgroup, segment ranges) and dispatch to the
-// kernel instantiations, which live in one translation unit per fused prologue (amq_gemv_pro{0,1,2}.hip, amq_gemv_fine.hip; kernels and
-// launch templates: amq_gemv_body.cuh).
+// kernel instantiations, which live in one translation unit per fused prologue (amq_gemv_pro{0,1,2}.hip, amq_gemv_fine.hip; the keyed one-row
+// kernels: amq_gemv_keyed{0,1}.hip; kernels and launch templates: amq_gemv_body.cuh).
 #include "amq_gemv_body.cuh"
 
 namespace amq {
@@ -66,12 +66,53 @@ AMQ_GEMV_EXTERN(PRO_SILU_MUL)
 extern template hipError_t launch_pro<PRO_MUL>(const GemvKArgs&, int, int, int, int, size_t, hipStream_t);      // (groups of 128 only: amq_gemv_pro2.hip)
 hipError_t launch_pro_sums_entry(const GemvKArgs&, int nw, int rs, int, size_t, hipStream_t);     // amq_gemv_pro3.hip
 
+bool gemv_keyed_geometry(int prologue, int M, int K, int gp, int nseg, const int* bits, const int* modes, int flags, int force_waves, int force_depth,
+                         int force_rpt) {
+    if (M != 1 || gp > 1 || flags != 0 || force_depth != 0 || force_rpt > 0 || nseg < 1 || K < 128) return false;
+    for (int i = 0; i < nseg; ++i)
+        if (modes[i] != MODE_HQQ || bits[i] < 2 || bits[i] > 4) return false;
+    int nw = force_waves ? force_waves : gemv_pick_waves(0, K);
+    if (!force_waves && nw == 16 && (K >> 3) > 512 && (K >> 3) <= 1024) nw = 8;      // (launch_gemv's mid_k: 4096 < K <= 8192 runs the two-chunk 8-wave kernels)
+    switch (prologue) {
+        case PRO_RMSNORM: return nw == 8 && (K >> 3) <= XCfg<8>::XC * 8 * 64 && nseg <= 3;
+        case PRO_NONE: return nw == 8 && (K >> 3) <= XCfg<8>::XC * 8 * 64 && nseg == 1;
+        case PRO_MUL:
+        case PRO_SILU_MUL: return nw == 16 && (K >> 3) <= XCfg<16>::XC * 16 * 64 && nseg == 1;
+    }
+    return false;
+}
+
+int gemv_segment_order(int nseg, const int* bits, int act_mask, int* order) {
+    int n = 0, mask = 0;
+    for (int b = 0; b <= 32 && n < nseg; ++b)              // (widths are 2 .. 4; anything else a caller passes still gets a stable order)
+        for (int i = 0; i < nseg; ++i)
+            if ((bits[i] < 0 ? 0 : bits[i] > 32 ? 32 : bits[i]) == b) {
+                mask |= ((act_mask >> i) & 1) << n;
+                order[n++] = i;
+            }
+    return mask;
+}
+
 // Fills the per-segment workgroup ranges and launches.  rpt = row-tiles per workgroup.
 #ifndef AMQ_RS128_THREE
 #define AMQ_RS128_THREE 1
 #endif
 hipError_t launch_gemv(GemvArgs& a, hipStream_t st) {
     StreamDevice sd_(st);                                  // kernel attributes are per device: the stream's, not the current one
+    // the launches the keyed kernels cover (gemv_route) run their segments in ascending bit-width -- every per-segment field moves with its segment;
+    // a row-tile's result does not depend on the workgroup that computes it.  (a.generic keeps the order: the same geometry under gemv_kernel)
+    bool keyed_geo = false;
+    if (a.nseg >= 1 && a.nseg <= GEMV_MAX_SEG) {
+        int bits[GEMV_MAX_SEG], modes[GEMV_MAX_SEG], order[GEMV_MAX_SEG];
+        for (int i = 0; i < a.nseg; ++i) { bits[i] = a.seg[i].bits; modes[i] = a.seg[i].mode; }
+        keyed_geo = !a.sums_out && gemv_keyed_geometry(a.prologue, a.M, a.K, a.gp, a.nseg, bits, modes, a.flags, a.force_waves, a.force_depth, a.force_rpt);
+        if (keyed_geo) {
+            gemv_segment_order(a.nseg, bits, 0, order);
+            GemvSeg sorted[GEMV_MAX_SEG];
+            for (int i = 0; i < a.nseg; ++i) sorted[i] = a.seg[order[i]];
+            for (int i = 0; i < a.nseg; ++i) a.seg[i] = sorted[i];
+        }
+    }
     int total_rt = 0;
     for (int i = 0; i < a.nseg; ++i) { a.seg[i].n_rt = a.seg[i].N / 16; total_rt += a.seg[i].n_rt; }
     int nw = a.force_waves ? a.force_waves : gemv_pick_waves(total_rt, a.K);
@@ -179,6 +220,7 @@ hipError_t launch_gemv(GemvArgs& a, hipStream_t st) {
         }
     }
     if (a.prologue == PRO_RMSNORM_SUMS) return launch_pro_sums_entry(k, nw, rs64 ? 64 : 128, wg, lds, st);
+    if (keyed_geo && !a.generic) return launch_keyed(k, a.prologue, wg, lds, st);
     switch (a.prologue) {
         case PRO_NONE: return launch_pro<PRO_NONE>(k, a.flags | (rs128 ? GEMV_FLAG_RS128 : 0) | (rs64 ? GEMV_FLAG_RS64 : 0) | (ph2 ? GEMV_FLAG_PH2 : 0), a.force_depth, nw, wg, lds, st);
         case PRO_RMSNORM: return launch_pro<PRO_RMSNORM>(k, a.flags | (rs128 ? GEMV_FLAG_RS128 : 0) | (rs64 ? GEMV_FLAG_RS64 : 0) | (ph2 ? GEMV_FLAG_PH2 : 0), a.force_depth, nw, wg, lds, st);

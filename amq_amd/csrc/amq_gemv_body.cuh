@@ -1,6 +1,7 @@
 // amq_gemv_body.cuh -- weight-streaming y = x . W^T for few rows (decode), gfx950: the kernel family and its launch templates.
 // Included by amq_gemv_pro{0,1,2}.hip / amq_gemv_fine.hip (one translation unit per fused prologue, so that the ~90 kernel bodies compile in
-// parallel) and by the A/B route amq_gemv_qkvattn.hip; the host-side launch plan is amq_gemv.hip.
+// parallel), by amq_gemv_keyed{0,1}.hip (the one-row kernels with their segments' bit-widths fixed at compile time: gemv_kernel_keyed) and by the
+// A/B route amq_gemv_qkvattn.hip; the host-side launch plan is amq_gemv.hip.
 //
 // Replaces, for rows < 8/128, the reference's
 //   VecQuant{2,3,4}MatMulKernelFaster_old (amq/kernel/AutoGPTQ/auto_gptq_kernel.cu:160-440)
@@ -1055,6 +1056,131 @@ __global__ __launch_bounds__(NW * 64, AMQ_LB_WAVES_R(NW, GP, MATH, XCH, RS)) voi
 #endif
 }
 
+
+// The one-row launches of a 7B-class decode step with the bit-widths of their segments fixed at compile time (launch_gemv sorts a launch's segments by
+// bit-width and picks the instantiation: gemv_route).  KEY0 <= KEY1 <= KEY2 are the segments' bit-widths, 0 = no such segment; every segment is
+// MODE_HQQ, exact math, groups of 128, one row whose chunks the threads hold in registers (xmode 1).  The entry is gemv_kernel's -- the same preloaded
+// arguments (p_key0 travels but is not read), x_issue first, one clause of scalar loads for the other segments' hot fields, the same selects -- but
+// no key is loaded or compared: the body follows from sidx among at most three gemv_body instantiations, equal widths share one, and a launch of one
+// width holds one body and no branch.  Same bodies on the same tiles in the same order as gemv_kernel<PRO, NW, 2, MATH_EXACT, XCH>: the same bits.
+template <int PRO, int NW, int XCH, int KEY0, int KEY1, int KEY2>
+__global__ __launch_bounds__(NW * 64, AMQ_LB_WAVES_R(NW, 1, MATH_EXACT, XCH, 256)) void gemv_kernel_keyed(const void* p_x, const void* p_xw, const void* p_qw0,
+                                                                     const void* p_mt0, int p_K, int p_m_nseg, int p_rpt,
+                                                                     int p_n_rt0, int p_key0, float p_eps, GemvKArgs blk) {
+    static_assert(KEY0 >= 2 && KEY0 <= 4 && (KEY1 == 0 || (KEY1 >= KEY0 && KEY1 <= 4)) && (KEY2 == 0 || (KEY1 != 0 && KEY2 >= KEY1 && KEY2 <= 4)),
+                  "bit-widths in ascending order, absent segments last");
+    constexpr int NSEG = 1 + (KEY1 != 0) + (KEY2 != 0);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#ifndef AMQ_NO_PRIO_PROGRESS
+    __builtin_amdgcn_s_setprio(3);
+#endif
+    GemvHot a;
+    a.x = p_x; a.x2 = p_xw; a.gamma = p_xw;
+    a.K = p_K; a.M = 1; a.rpt = p_rpt; a.eps = p_eps; a.x_stride = p_K;
+    const int xs = a.K + XPAD;
+    _Float16* xl = (_Float16*)smem;
+    const size_t xbytes = ((size_t)xs * 2 + 15) & ~(size_t)15;
+    float* red = (float*)(smem + xbytes);                                       // [2][NW][16][16]
+
+    // x's loads sit in a basic block of their own, behind a condition the compiler cannot see through (always true).  In straight-line code it
+    // sinks them into x_finish's `chunk < chunks` branches, behind the primed ring and a full vmcnt(0) drain, or schedules ring loads ahead of them
+    // (seen in the PRO_NONE and the 16-wave instantiations); gemv_kernel gets the same effect from its run-time xmode.
+    XRegs xr;
+    int issue = 1;
+    asm volatile("" : "+s"(issue));
+    if (issue) x_issue<PRO, NW, XCH>(a, xr);
+
+    const int bid = (int)blockIdx.x;
+    int sidx = 0;
+    int wgb = 0, nrt = p_n_rt0;
+    const void* qwp = p_qw0;
+    const void* mtp = p_mt0;
+    if constexpr (NSEG > 1) {
+        // (one clause of scalar loads and a single wait, as in gemv_kernel)
+        if constexpr (NSEG == 2)
+            asm volatile("" ::"s"(blk.wg_begin[1]), "s"(blk.n_rt[1]), "s"(blk.qweight[1]), "s"(blk.meta[1]));
+        else
+            asm volatile("" ::"s"(blk.wg_begin[1]), "s"(blk.wg_begin[2]), "s"(blk.n_rt[1]), "s"(blk.n_rt[2]), "s"(blk.qweight[1]),
+                         "s"(blk.qweight[2]), "s"(blk.meta[1]), "s"(blk.meta[2]));
+#pragma unroll
+        for (int i = 1; i < NSEG; ++i) {
+            const bool take = bid >= blk.wg_begin[i];
+            sidx = take ? i : sidx;
+            wgb = take ? blk.wg_begin[i] : wgb;
+            nrt = take ? blk.n_rt[i] : nrt;
+            qwp = take ? blk.qweight[i] : qwp;
+            mtp = take ? blk.meta[i] : mtp;
+        }
+    }
+    const int local = bid - wgb;
+#define AMQ_KEYED_BODY(B_) gemv_body<B_, MODE_HQQ, PRO, NW, 2, MATH_EXACT, XCH>(a, blk, sidx, qwp, mtp, nrt, local, xl, xl, nullptr, red, xs, 1, xr)
+    if constexpr (NSEG == 1 || (KEY1 == KEY0 && (NSEG == 2 || KEY2 == KEY0))) {
+        AMQ_KEYED_BODY(KEY0);
+    } else if constexpr (NSEG == 2) {
+        if (sidx == 0) AMQ_KEYED_BODY(KEY0); else AMQ_KEYED_BODY(KEY1);
+    } else if constexpr (KEY1 == KEY0) {
+        if (sidx < 2) AMQ_KEYED_BODY(KEY0); else AMQ_KEYED_BODY(KEY2);
+    } else if constexpr (KEY2 == KEY1) {
+        if (sidx == 0) AMQ_KEYED_BODY(KEY0); else AMQ_KEYED_BODY(KEY1);
+    } else {
+        if (sidx == 0) AMQ_KEYED_BODY(KEY0); else if (sidx == 1) AMQ_KEYED_BODY(KEY1); else AMQ_KEYED_BODY(KEY2);
+    }
+#undef AMQ_KEYED_BODY
+}
+
+template <int PRO, int NW, int XCH, int KEY0, int KEY1 = 0, int KEY2 = 0>
+inline hipError_t launch_keyed_one(const GemvKArgs& a, int total_wg, size_t lds, hipStream_t st) {
+    auto kern = gemv_kernel_keyed<PRO, NW, XCH, KEY0, KEY1, KEY2>;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const void* xw = PRO_X2<PRO> ? a.x2 : a.gamma;
+    hipLaunchKernelGGL(kern, dim3(total_wg), dim3(NW * 64), lds, st, a.x, xw, a.qweight[0], a.meta[0], a.K,
+                       a.M | ((a.x_stride == a.K ? 1 : 0) << 8) | (a.nseg << 16), a.rpt, a.n_rt[0], a.key[0], a.eps, a);
+    return hipGetLastError();
+}
+// a launch's bit-widths (ascending: launch_gemv sorted the segments) -> its instantiation
+template <int PRO, int NW, int XCH>
+inline hipError_t launch_keyed_1(const GemvKArgs& a, int total_wg, size_t lds, hipStream_t st) {
+    switch (a.key[0] >> 2) {
+        case 2: return launch_keyed_one<PRO, NW, XCH, 2>(a, total_wg, lds, st);
+        case 3: return launch_keyed_one<PRO, NW, XCH, 3>(a, total_wg, lds, st);
+        case 4: return launch_keyed_one<PRO, NW, XCH, 4>(a, total_wg, lds, st);
+    }
+    return hipErrorInvalidValue;
+}
+template <int PRO, int NW, int XCH>
+inline hipError_t launch_keyed_2(const GemvKArgs& a, int total_wg, size_t lds, hipStream_t st) {
+    switch ((a.key[0] >> 2) * 10 + (a.key[1] >> 2)) {
+        case 22: return launch_keyed_one<PRO, NW, XCH, 2, 2>(a, total_wg, lds, st);
+        case 23: return launch_keyed_one<PRO, NW, XCH, 2, 3>(a, total_wg, lds, st);
+        case 24: return launch_keyed_one<PRO, NW, XCH, 2, 4>(a, total_wg, lds, st);
+        case 33: return launch_keyed_one<PRO, NW, XCH, 3, 3>(a, total_wg, lds, st);
+        case 34: return launch_keyed_one<PRO, NW, XCH, 3, 4>(a, total_wg, lds, st);
+        case 44: return launch_keyed_one<PRO, NW, XCH, 4, 4>(a, total_wg, lds, st);
+    }
+    return hipErrorInvalidValue;
+}
+template <int PRO, int NW, int XCH>
+inline hipError_t launch_keyed_3(const GemvKArgs& a, int total_wg, size_t lds, hipStream_t st) {
+    switch ((a.key[0] >> 2) * 100 + (a.key[1] >> 2) * 10 + (a.key[2] >> 2)) {
+        case 222: return launch_keyed_one<PRO, NW, XCH, 2, 2, 2>(a, total_wg, lds, st);
+        case 223: return launch_keyed_one<PRO, NW, XCH, 2, 2, 3>(a, total_wg, lds, st);
+        case 224: return launch_keyed_one<PRO, NW, XCH, 2, 2, 4>(a, total_wg, lds, st);
+        case 233: return launch_keyed_one<PRO, NW, XCH, 2, 3, 3>(a, total_wg, lds, st);
+        case 234: return launch_keyed_one<PRO, NW, XCH, 2, 3, 4>(a, total_wg, lds, st);
+        case 244: return launch_keyed_one<PRO, NW, XCH, 2, 4, 4>(a, total_wg, lds, st);
+        case 333: return launch_keyed_one<PRO, NW, XCH, 3, 3, 3>(a, total_wg, lds, st);
+        case 334: return launch_keyed_one<PRO, NW, XCH, 3, 3, 4>(a, total_wg, lds, st);
+        case 344: return launch_keyed_one<PRO, NW, XCH, 3, 4, 4>(a, total_wg, lds, st);
+        case 444: return launch_keyed_one<PRO, NW, XCH, 4, 4, 4>(a, total_wg, lds, st);
+    }
+    return hipErrorInvalidValue;
+}
+// defined in amq_gemv_keyed0.hip (q/k/v: PRO_RMSNORM, three segments) and amq_gemv_keyed1.hip (the others); what gemv_route sends there
+hipError_t launch_keyed_qkv(const GemvKArgs& a, int total_wg, size_t lds, hipStream_t st);
+hipError_t launch_keyed(const GemvKArgs& a, int prologue, int total_wg, size_t lds, hipStream_t st);
 
 template <int PRO, int NW, int U, int MATH, int XCH = XCfg<NW>::XC, int RS = 256, int GP = 1, int PH = 1>
 inline hipError_t launch_one(const GemvKArgs& a, int total_wg, size_t lds, hipStream_t st) {

@@ -77,6 +77,7 @@ struct GemvArgs {
     int gp;                // (scale, zero) pairs per (row, tile) of every segment's meta: 0 / 1 (groups of 128), 2 (64), 4 (32)
     const void* sums_in;   // PRO_RMSNORM_SUMS: fp32 [M][K / 16] partial sums of squares of the x rows (one per 16 columns: what the producing launch's row-tiles left)
     void* sums_out;        // 5 .. 8-row launches of ONE segment: fp32 [M][N / 16], partial sums of squares of the y rows this launch writes (or null)
+    int generic;           // A/B: 1 = a launch gemv_route would send to the keyed kernels runs gemv_kernel instead (segments sorted all the same: identical geometry)
 };
 // how a segment's row-tiles are dealt to its workgroups: the first n_rt % wg_count workgroups walk one row-tile more than the others
 // (packed base | rem << 12: base <= 4095 row-tiles per workgroup, rem < 2^19 workgroups -- launch_gemv refuses what does not fit)
@@ -93,6 +94,21 @@ size_t gemv_lds_bytes_rows(int M, int K, int nw);                   // the 2 .. 
 size_t gemv_min_lds_bytes(int M, int K, bool plain, bool norm = true);   // what the C ABI checks against the LDS limit (norm: an RMSNorm prologue or strided x rows, which cannot be staged in K phases)
 bool gemv_rows_phased(int M, int K, bool plain, bool norm);      // the launch stages x in two K phases (norm: as above -- callers pass `RMSNorm prologue || x_stride != K`)
 hipError_t launch_gemv(GemvArgs& a, hipStream_t st);
+// Which kernel serves a launch: the generic gemv_kernel (every (bits, mode) body, chosen per workgroup from a key) or gemv_kernel_keyed (the segments'
+// bit-widths fixed at compile time, amq_gemv_body.cuh).  A pure function of what launch_gemv knows before it launches.  Keyed: one row, groups of
+// 128 (gp <= 1), exact math (no GEMV_FLAG_*), no forced depth / row-tiles per workgroup, every segment MODE_HQQ at 2 / 3 / 4 bit, and one of the
+// one-row geometries of a 7B-class step: PRO_RMSNORM with 1 .. 3 segments or PRO_NONE with one on 8 waves at K <= 4096; PRO_MUL / PRO_SILU_MUL with
+// one segment on 16 waves at K <= 16384 (waves: force_waves, else gemv_pick_waves).
+enum { GEMV_ROUTE_GENERIC = 0, GEMV_ROUTE_KEYED = 1 };
+bool gemv_keyed_geometry(int prologue, int M, int K, int gp, int nseg, const int* bits, const int* modes, int flags, int force_waves, int force_depth,
+                         int force_rpt);
+inline int gemv_route(int prologue, int M, int K, int gp, int nseg, const int* bits, const int* modes, int flags, int force_waves, int force_depth,
+                      int force_rpt, bool generic) {
+    return !generic && gemv_keyed_geometry(prologue, M, K, gp, nseg, bits, modes, flags, force_waves, force_depth, force_rpt) ? GEMV_ROUTE_KEYED : GEMV_ROUTE_GENERIC;
+}
+// launch order of the segments of such a launch: ascending bit-width, equal widths in the caller's order (stable); order[i] = the caller's index of
+// the segment launched i-th.  Returns act_mask with every bit moved to its segment's launch position.
+int gemv_segment_order(int nseg, const int* bits, int act_mask, int* order);
 
 // y[M,N] = x[M,K] . W^T for any M (MFMA, LDS-staged x tiles)
 struct GemmArgs {

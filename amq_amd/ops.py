@@ -1143,6 +1143,27 @@ def gemv_grouped(x, segments, K, prologue=PRO_NONE, x2=None, gamma=None, eps=0.0
                                                 ctypes.byref(opts) if opts is not None else None, _lib.current_stream()))
 
 
+def gemv_route(prologue, M, K, bits, modes=None, group=GROUP, opts=None):
+    """which kernel :func:`gemv_grouped` launches for these arguments (host logic, no device): ``_lib.GEMV_ROUTE_KEYED`` -- the segments' bit-widths
+    fixed at compile time, the one-row launches of a 7B-class decode step -- or ``_lib.GEMV_ROUTE_GENERIC`` (include/amq_hip.h amq_gemv_route).
+    ``bits`` / ``modes``: per segment (modes default to MODE_HQQ); ``prologue`` as the library sees it (``_lib.PRO_MUL`` for an activated x)."""
+    n = len(bits)
+    modes = [MODE_HQQ] * n if modes is None else list(modes)
+    rc = _lib.load().amq_gemv_route(prologue, M, K, group, n, (ctypes.c_int * n)(*bits), (ctypes.c_int * n)(*modes),
+                                    ctypes.byref(opts) if opts is not None else None)
+    _lib.check(min(rc, 0))
+    return rc
+
+
+def gemv_segment_order(bits, act_mask=0):
+    """launch order of the segments of a keyed-geometry launch (ascending bit-width, stable) and ``act_mask`` with its bits moved along:
+    ``(order, act_mask)``, ``order[i]`` = index of the segment launched i-th (amq_gemv_segment_order)"""
+    n = len(bits)
+    order, mask = (ctypes.c_int * n)(), ctypes.c_int(0)
+    _lib.check(_lib.load().amq_gemv_segment_order(n, (ctypes.c_int * n)(*bits), act_mask, order, ctypes.byref(mask)))
+    return list(order), mask.value
+
+
 # ---------------------------------------------------------------- decode-step surroundings
 def gemv_grouped_sums(x, segments, K, gamma=None, eps=0.0, sums_in=None, sums_out=None):
     """5 .. 8 rows: :func:`gemv_grouped` whose RMSNorm takes the rows' sums of squares as per-16-column partials (``sums_in`` fp32 [M, K / 16], with

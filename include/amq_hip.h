@@ -46,6 +46,7 @@ extern "C" {
 #endif
 
 #define AMQ_VERSION 521            /* 0.5.2: the per-sequence step-state entry points (amq_*_seq_f16) added, nothing else changed (additions keep the number).
+                                    * amq_gemv_route / amq_gemv_segment_order and the value AMQ_GEMV_DEPTH_GENERIC of amq_gemv_opts.depth added, nothing else changed.
                                     * LAYOUT CHANGE under the same number: amq_gemv_opts gained a trailing field, act_mask (and AMQ_PRO_MUL was added).  A caller that
                                     * passes a non-NULL amq_gemv_opts must be rebuilt against this header -- the library reads six ints; NULL opts are unaffected.
                                     * amq_rope_table_freqs_f16 (rope_scaling) and amq_decode_tail_suppress_f16 added, nothing else changed.  0.5.1: the bfloat16 entry points
@@ -101,12 +102,30 @@ int amq_default_gemv_math(void);   /* AMQ_MATH_EXACT or AMQ_MATH_GROUPSCALE */
 typedef struct amq_gemv_opts {            /* (six ints since act_mask was added: see AMQ_VERSION) */
     int math;    /* AMQ_MATH_DEFAULT (0), _EXACT, _GROUPSCALE or _LINEAR */
     int waves;   /* A/B: waves per workgroup, 0 = auto, 4, 8 or 16 */
-    int depth;   /* A/B: tile loads in flight per wave, 0 = auto, 2 or 4 */
+    int depth;   /* A/B: tile loads in flight per wave, 0 = auto, 2 or 4; AMQ_GEMV_DEPTH_GENERIC = auto, and a launch amq_gemv_route() sends to the
+                  * keyed kernels runs the generic kernel instead, geometry and segment order unchanged (the same bits) */
     int rpt;     /* A/B: row-tiles walked by one workgroup, 0 = auto, 1..64 */
     int dot;     /* A/B: 1 = M == 1 runs the v_dot2c + wavefront-shuffle body instead of the MFMA body */
     int act_mask; /* bit i: segment i stores y = fp16(silu(x W^T + bias)) -- gate_proj, for a consumer with AMQ_PRO_MUL.  Not with a residual on that
                    * segment; groups of 128 */
 } amq_gemv_opts;
+#define AMQ_GEMV_DEPTH_GENERIC (-1)
+
+/* Which GEMV kernel amq_gemv_grouped_f16 launches for these arguments -- a host-side function of them alone, no device needed.
+ *   AMQ_GEMV_ROUTE_KEYED    kernels with the segments' bit-widths fixed at compile time (no per-workgroup dispatch on a key): the one-row launches of a
+ *                           7B-class decode step.  All of: M == 1, groups of 128 (or multiples), exact math, every segment AMQ_MODE_HQQ, opts.depth,
+ *                           opts.rpt and opts.dot zero, and AMQ_PRO_RMSNORM with 1 .. 3 segments or AMQ_PRO_NONE with one on 8 waves at K <= 4096, or
+ *                           AMQ_PRO_MUL / AMQ_PRO_SILU_MUL with one segment on 16 waves at K <= 16384.  The waves are opts.waves, or what the launch
+ *                           picks itself: 8 for 2048 <= K <= 4096, 16 beyond.
+ *   AMQ_GEMV_ROUTE_GENERIC  the kernel that holds every (bits, mode) body: everything else, and opts.depth == AMQ_GEMV_DEPTH_GENERIC.
+ * Both compute the same bits.  A launch of the keyed geometry (forced generic or not) runs its segments in ascending bit-width:
+ * amq_gemv_segment_order() gives that order (order[i] = index of the segment launched i-th; equal widths keep the caller's order) and the act_mask
+ * bits moved with their segments (act_mask_out, may be NULL).  Callers see none of it: every output lands in its own segment's y. */
+#define AMQ_GEMV_ROUTE_GENERIC 0
+#define AMQ_GEMV_ROUTE_KEYED   1
+int amq_gemv_route(int prologue, int M, int K, int group, int nseg, const int* bits /* host [nseg] */, const int* modes /* host [nseg] */,
+                   const amq_gemv_opts* opts /* host, may be NULL */);
+int amq_gemv_segment_order(int nseg, const int* bits /* host [nseg] */, int act_mask, int* order /* host [nseg], out */, int* act_mask_out);
 
 /* kernel family of amq_gemm_route_f16 (AUTO = what every other GEMM entry point uses: chosen by shape) */
 #define AMQ_GEMM_AUTO   0
