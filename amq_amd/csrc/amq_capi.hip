@@ -59,6 +59,42 @@ int kernel_mode(int mode) { return mode == AMQ_MODE_FMA1 ? AMQ_MODE_FMA : mode; 
 
 constexpr size_t LDS_LIMIT = 160 * 1024;
 
+// Row strides of the fp16 matmul entry points, in elements as the caller passed them (0 = dense; an entry point without one of the two passes 0).
+// What the kernels behind them assume, none of which they can check themselves:
+//   - a stride is at least the row it steps over (a shorter or negative one makes rows overlap, or walks backwards out of the buffer);
+//   - x rows are read in 16-byte pieces (amq_gemm.hip issue_a / skinny_body, amq_gemv_body.cuh stage_x / x_dma_rows -- x2 of the SiLU*mul / mul
+//     prologues at x's stride --, amq_gemm_ring.hip, amq_gemm_ws.hip, amq_gemm_f16.hip): x_stride % 8;
+//   - y and the residual are accessed in pieces of up to 16 bytes at row * y_stride + 8 j (the split-K reduce kernels of amq_gemm.hip; 8 bytes in the
+//     ring / wave-specialised / fp16-weight epilogues): y_stride % y_align, 8 for every entry point that can reach the reduce, 4 for amq_gemm_f16w_f16;
+//   - the few-row GEMM kernel (up to x_i32_rows rows; 0: not reachable) forms its x offsets row * x_stride + column as 32-bit ints.
+// Dense calls cannot fail the alignment rules: K % 128 == 0 and N % 16 == 0 are required of every call.
+int check_strides(const char* who, int M, int K, int x_stride, int N, int y_stride, int y_align, int x_i32_rows) {
+    if (x_stride < 0 || (x_stride != 0 && x_stride < K))
+        return fail(AMQ_ESHAPE, "%s: x_stride=%d is shorter than a row of x (K=%d); 0 = dense", who, x_stride, K);
+    if (y_stride < 0 || (y_stride != 0 && y_stride < N))
+        return fail(AMQ_ESHAPE, "%s: y_stride=%d is shorter than a row of y (N=%d); 0 = dense", who, y_stride, N);
+    if (x_stride & 7) return fail(AMQ_ESHAPE, "%s: x_stride=%d must be a multiple of 8 elements (rows of x are read in 16-byte pieces)", who, x_stride);
+    if (y_stride % y_align)
+        return fail(AMQ_ESHAPE, "%s: y_stride=%d must be a multiple of %d elements (rows of y and of the residual are accessed in %d-byte pieces)", who,
+                    y_stride, y_align, 2 * y_align);
+    if (x_stride > K && M >= 1 && M <= x_i32_rows && (long long)(M - 1) * x_stride + K > 0x7fffffffll)
+        return fail(AMQ_ESHAPE, "%s: x_stride=%d: %d strided rows of x span 2^31 elements or more (the few-row kernel's offsets are 32-bit)", who, x_stride, M);
+    return AMQ_OK;
+}
+// "<entry point>, segment i" for the messages of the grouped calls
+const char* seg_name(const char* who, int i) {
+    static thread_local char buf[96];
+    snprintf(buf, sizeof(buf), "%s, segment %d", who, i);
+    return buf;
+}
+constexpr int FEWROW_MAX_ROWS = 256;       // rows the few-row GEMM kernel can be given (64; 256 with groups of 64 / 32: gemm_fine_takes_skinny)
+// ... on a route call: a forced tiled / ring / wave-specialised route never ends in the few-row kernel (amq_gemm.hip gemm_is_skinny; a ring call that
+// gemm_ring_ok turns away runs the tiled kernel, whose x offsets are size_t), and AMQ_GEMM_DEQ runs the fp16-weight GEMM or is refused (gemm_f16w_ok
+// holds x below 4 GiB itself); AUTO and SKINNY can
+int fewrow_rows_of(int route) {
+    return (route == AMQ_GEMM_AUTO || route == AMQ_GEMM_SKINNY) ? FEWROW_MAX_ROWS : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -320,6 +356,7 @@ int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const
     if (prologue == AMQ_PRO_SILU_MUL && !x2) return fail(AMQ_EINVAL, "SiLU*mul prologue needs x2");
     if (prologue == AMQ_PRO_MUL && !x2) return fail(AMQ_EINVAL, "mul prologue needs x2");
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
+    if (int rc = check_strides("amq_gemv_grouped_f16", M, K, x_stride, 0, 0, 8, 0)) return rc;
     amq_gemv_opts o{};                                   // all zero = defaults
     if (opts) o = *opts;
     if (o.math < AMQ_MATH_DEFAULT || o.math > AMQ_MATH_EXACT)
@@ -340,6 +377,8 @@ int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const
     if (M > amq::GEMV_MAX_M || amq::gemv_min_lds_bytes(M, K, plain_form && o.waves == 0 && o.rpt == 0, whole_rows) > LDS_LIMIT)
         return fail(AMQ_ESHAPE, "M=%d rows of K=%d%s do not fit LDS for the GEMV path; use amq_gemm_f16", M, K, (x_stride != 0 && x_stride != K) ? " (strided x)" : "");
     amq::GemvArgs a{};
+    for (int i = 0; i < nseg; ++i)          // (every segment's stride before any segment's pointers)
+        if (int rc = check_strides(seg_name("amq_gemv_grouped_f16", i), M, K, 0, segs[i].N, segs[i].y_stride, 8, 0)) return rc;
     for (int i = 0; i < nseg; ++i) {
         const amq_segment& s = segs[i];
         if (int rc = check_shape(s.bits, s.N, K, group)) return rc;
@@ -406,6 +445,8 @@ int amq_gemv_grouped_sums_f16(const amq_segment* segs, int nseg, const void* x, 
     if (amq::gemv_min_lds_bytes(M, K, true, sums_in != nullptr) > LDS_LIMIT)
         return fail(AMQ_ESHAPE, "M=%d rows of K=%d do not fit LDS for the GEMV path", M, K);
     amq::GemvArgs a{};
+    for (int i = 0; i < nseg; ++i)          // (every segment's stride before any segment's pointers)
+        if (int rc = check_strides(seg_name("amq_gemv_grouped_sums_f16", i), M, K, 0, segs[i].N, segs[i].y_stride, 8, 0)) return rc;
     for (int i = 0; i < nseg; ++i) {
         const amq_segment& s = segs[i];
         if (int rc = check_shape(s.bits, s.N, K, group)) return rc;
@@ -437,6 +478,7 @@ int amq_gemm_f16(int bits, int mode, const void* x, const void* qn, const void* 
     if (int rc = check_shape(bits, N, K, group)) return rc;          // (groups of 64 / 32: the few-row or the tiled kernel -- no workspace here, so never dequantize-once)
     if (int rc = check_mode(mode)) return rc;
     mode = kernel_mode(mode);
+    if (int rc = check_strides("amq_gemm_f16", M, K, x_stride, N, y_stride, 8, FEWROW_MAX_ROWS)) return rc;
     if (!x || !qn || !mn || !y) return fail(AMQ_EINVAL, "null pointer");
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
     amq::GemmArgs a{x, qn, mn, bias, y, M, N, K, bits, mode, x_stride ? x_stride : K, y_stride ? y_stride : N, nullptr, 1,
@@ -458,6 +500,7 @@ int amq_gemm_splitk_f16(int bits, int mode, const void* x, const void* qn, const
     if (int rc = check_shape(bits, N, K, group)) return rc;
     if (int rc = check_mode(mode)) return rc;
     mode = kernel_mode(mode);
+    if (int rc = check_strides("amq_gemm_splitk_f16", M, K, x_stride, N, y_stride, 8, FEWROW_MAX_ROWS)) return rc;
     if (!x || !qn || !mn || !y) return fail(AMQ_EINVAL, "null pointer");
     if (!workspace || workspace_bytes < need) return fail(AMQ_EINVAL, "split-K workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     amq::GemmArgs a{x, qn, mn, bias, y, M, N, K, bits, mode, x_stride ? x_stride : K, y_stride ? y_stride : N,
@@ -499,6 +542,7 @@ static int gemm_route_impl(int route, int bits, int mode, const void* x, const v
     if (int rc = check_shape(bits, N, K, group)) return rc;
     if (int rc = check_mode(mode)) return rc;
     mode = kernel_mode(mode);
+    if (int rc = check_strides("amq_gemm_route_f16", M, K, x_stride, N, y_stride, 8, fewrow_rows_of(route))) return rc;
     if (!x || !qn || !mn || !y) return fail(AMQ_EINVAL, "null pointer");
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
     if (route == AMQ_GEMM_SKINNY && M > 64 && !((group == 64 || group == 32) && amq::gemm_fine_takes_skinny(M)))
@@ -556,6 +600,7 @@ int amq_gemm_gated_f16(int route, int bits, int mode, const void* x, const void*
     if (int rc = check_shape(bits, N, K, group)) return rc;
     if (int rc = check_mode(mode)) return rc;
     mode = kernel_mode(mode);
+    if (int rc = check_strides("amq_gemm_gated_f16", M, K, x_stride, N, 0, 8, fewrow_rows_of(route))) return rc;
     if (!x || !qn || !mn || !y || !gate) return fail(AMQ_EINVAL, "null pointer");
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
     if (N % 8) return fail(AMQ_ESHAPE, "the gated product needs N %% 8 == 0 (got %d)", N);
@@ -584,6 +629,7 @@ int amq_gemm_f16w_f16(const void* x, const void* w, const void* bias, const void
                       int M, int N, int K, int x_stride, int y_stride, void* stream) {
     if (!x || !w || !y) return fail(AMQ_EINVAL, "null pointer");
     if (residual && gate) return fail(AMQ_EINVAL, "residual and gate are exclusive");
+    if (int rc = check_strides("amq_gemm_f16w_f16", M, K, x_stride, N, y_stride, 4, 0)) return rc;
     const int xs = x_stride ? x_stride : K, ys = y_stride ? y_stride : N;
     if (!amq::gemm_f16w_ok(M, N, K, xs, ys))
         return fail(AMQ_ESHAPE, "need M >= 1, N %% 16 == 0, K %% 128 == 0, x_stride %% 8 == 0, y_stride %% 4 == 0, x and W < 4 GiB each (got M=%d N=%d K=%d)", M, N, K);
@@ -622,6 +668,7 @@ int amq_gemm_xfrag_f16(int bits, int mode, const void* xf, const void* qn, const
     if (int rc = check_shape128(bits, N, K, group, "amq_gemm_xfrag_f16")) return rc;
     if (int rc = check_mode(mode)) return rc;
     mode = kernel_mode(mode);
+    if (int rc = check_strides("amq_gemm_xfrag_f16", M, K, 0, N, y_stride, 8, 0)) return rc;
     if (!xf || !qn || !mn || !y) return fail(AMQ_EINVAL, "null pointer");
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
     if ((M + 63) / 64 > 65535) return fail(AMQ_ESHAPE, "M=%d exceeds one launch", M);
@@ -643,6 +690,8 @@ int amq_gemm_xfrag_grouped_form_f16(const amq_segment* segs, int nseg, const voi
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
     if ((M + 63) / 64 > 65535) return fail(AMQ_ESHAPE, "M=%d exceeds one launch", M);
     amq::GemvSeg gs[AMQ_MAX_SEGMENTS] = {};
+    for (int i = 0; i < nseg; ++i)          // (every segment's stride before any segment's pointers)
+        if (int rc = check_strides(seg_name("amq_gemm_xfrag_grouped_f16", i), M, K, 0, segs[i].N, segs[i].y_stride, 8, 0)) return rc;
     for (int i = 0; i < nseg; ++i) {
         const amq_segment& s = segs[i];
         if (int rc = check_shape128(s.bits, s.N, K, group, "amq_gemm_xfrag_grouped_f16")) return rc;

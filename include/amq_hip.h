@@ -338,11 +338,19 @@ int amq_dequantize_hqq_f16(int bits, const void* W_q, const void* scale, const v
  * M <= 16 and the rows must fit LDS: M * (K + 8) * 2 bytes + the cross-wave sum buffer (4 - 32 KiB by row count) <= 160 KiB -- except that with
  * default options, no RMSNorm prologue and 5 .. 8 rows a K whose rows do not fit whole is staged in two K phases (8 rows of K = 11008).
  * amq_query(K) returns the row limits; AMQ_ESHAPE beyond -- use amq_gemm_f16.  x_stride / y_stride in elements (0 = dense; 2 .. 8 dense rows
- * take the LDS-DMA staging path, strided rows the generic one: same results). */
+ * take the LDS-DMA staging path, strided rows the generic one: same results).
+ *
+ * ROW STRIDES of every fp16 matmul entry point of this header (x_stride, y_stride, amq_segment.y_stride), checked on the host before anything is
+ * launched, AMQ_ESHAPE otherwise: a stride is 0 (dense) or at least the row it steps over (x_stride >= K, y_stride >= N; never negative);
+ * x_stride % 8 == 0 (rows of x are read in 16-byte pieces) and y_stride % 8 == 0 (the split-K reduce accesses y and the residual in 16-byte pieces;
+ * one rule for every entry point; amq_gemm_f16w_f16 alone asks y_stride % 4 == 0 only).  The residual is read with y's stride.  Where the few-row
+ * GEMM kernel can serve the call (M <= 256; routes AMQ_GEMM_AUTO and _SKINNY), strided rows of x must span fewer than 2^31
+ * elements.  Dense calls meet all of it by N % 16 == 0,
+ * K % 128 == 0.  Nothing outside the N columns of a row of y is written, and nothing outside the K columns of a row of x is read. */
 int amq_gemv_f16(int bits, int mode, const void* x, const void* qweight_native, const void* meta_native,
                  const void* bias, void* y, int M, int N, int K, int group,
                  int x_stride, int y_stride, void* stream);
-/* any M (prefill / batched): LDS-staged x tiles, MFMA 16x16x32 f16 */
+/* any M (prefill / batched): LDS-staged x tiles, MFMA 16x16x32 f16.  x_stride / y_stride: the row-stride rule above (0, or >= K / N and % 8 == 0) */
 int amq_gemm_f16(int bits, int mode, const void* x, const void* qweight_native, const void* meta_native,
                  const void* bias, void* y, int M, int N, int K, int group,
                  int x_stride, int y_stride, void* stream);
@@ -355,7 +363,7 @@ int amq_linear_f16(int bits, int mode, const void* x, const void* qweight_native
  * workgroups splits the K loop over up to 8 workgroup layers; each layer writes fp32 partials into its own slice of a
  * caller-owned workspace, a second kernel sums the slices in a fixed order (deterministic, no atomics).
  * amq_gemm_splitk_workspace_bytes() returns the bytes required (0: the shape does not split and no workspace is
- * needed; the call then forwards to amq_gemm_f16).  Replaces the reference's cross-CTA split-K of gemm_w4a16_T1
+ * needed; the call then forwards to amq_gemm_f16).  x_stride / y_stride: the row-stride rule above (0, or >= K / N and % 8 == 0).  Replaces the reference's cross-CTA split-K of gemm_w4a16_T1
  * (amq/kernel/ft/quantization_new/gemm/gemm_cuda.cu:514-584: semaphore + __hadd2 read-modify-write of C). */
 size_t amq_gemm_splitk_workspace_bytes(int M, int N, int K);
 int amq_gemm_splitk_f16(int bits, int mode, const void* x, const void* qweight_native, const void* meta_native,
@@ -363,7 +371,8 @@ int amq_gemm_splitk_f16(int bits, int mode, const void* x, const void* qweight_n
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* several linears that consume the same x (q/k/v, gate/up), each with its own bit-width,
- * in ONE launch; optional fused prologue on x and residual add on y. */
+ * in ONE launch; optional fused prologue on x and residual add on y.  x_stride (0 = K; else >= K and % 8 == 0) is the row stride of x AND of x2:
+ * the second operand of AMQ_PRO_SILU_MUL / AMQ_PRO_MUL is read at x2 + row * x_stride. */
 typedef struct amq_segment {
     const void* qweight_native;
     const void* meta_native;
@@ -373,7 +382,8 @@ typedef struct amq_segment {
     int N;
     int bits;
     int mode;
-    int y_stride;           /* 0 = N */
+    int y_stride;           /* 0 = N; else >= N and % 8 == 0 (the row-stride rule above); several segments may share one [M, y_stride] buffer, each at
+                             * its own column offset (fused q/k/v): a segment writes its N columns of a row and nothing else */
 } amq_segment;
 
 int amq_gemv_grouped_f16(const amq_segment* segments /* host */, int nseg,
@@ -662,7 +672,7 @@ int amq_decode_tail_lookup_sample_f16(const void* logits, int vocab, const void*
  * they are ~20 tiny launches per block, so they are offered fused. */
 
 /* amq_gemm_splitk_f16 plus a fused residual: y = residual + fp16(x . W^T (+ bias)); residual fp16 [M, y_stride] or
- * NULL, may alias y.  workspace NULL = single pass (no split-K). */
+ * NULL, may alias y.  workspace NULL = single pass (no split-K).  x_stride / y_stride: the row-stride rule at amq_gemv_f16 (0, or >= K / N and % 8 == 0). */
 int amq_gemm_res_f16(int bits, int mode, const void* x, const void* qweight_native, const void* meta_native,
                      const void* bias, const void* residual, void* y, int M, int N, int K, int group, int x_stride,
                      int y_stride, void* workspace, size_t workspace_bytes, void* stream);
@@ -676,7 +686,8 @@ int amq_gemm_res_norm_xfrag_f16(int bits, int mode, const void* x, const void* q
                                 size_t workspace_bytes, const void* gamma, float eps, void* xf, void* stream);
 /* The same with the kernel family chosen by the caller (tests, A/B tools); amq_gemm_route_workspace_bytes is the
  * matching workspace query (0: no workspace needed).  The workspace holds split-K partials (few rows) or the dequantized
- * fp16 weights (AMQ_GEMM_DEQ, and AUTO on MFMA-bound launches) -- never both; without it AUTO runs a fused kernel. */
+ * fp16 weights (AMQ_GEMM_DEQ, and AUTO on MFMA-bound launches) -- never both; without it AUTO runs a fused kernel.
+ * x_stride / y_stride: the same row-stride rule for every route (0, or >= K / N and % 8 == 0). */
 size_t amq_gemm_route_workspace_bytes(int route, int M, int N, int K);
 /* ... for a given group size: groups of 64 / 32 take the few-row kernel up to 256 rows (0 bytes), the tiled kernel beyond (split-K partials as for
  * group 128) and the dequantize-once route (N * K * 2 bytes) for launches that fill 256 x 256 tiles -- the ring / wave-specialised kernels read one
@@ -688,7 +699,8 @@ int amq_gemm_route_f16(int route, int bits, int mode, const void* x, const void*
 /* y = x . W^T (+ bias) (+ residual | silu-gated) with W as DENSE fp16 [N, K] (row-major): the matmul of GPTQLinear.forward's
  * many-row branch (hqq/backends/autogptq.py:283: torch.matmul(x, weights)) as a hand-written kernel -- what AMQ_GEMM_DEQ runs
  * behind amq_dequantize_f16, exported for callers that keep fp16 weights (lm_head, an fp16 base model).  N % 16 == 0,
- * K % 128 == 0, x_stride % 8 == 0, y_stride % 4 == 0 (0 = dense); epilogue operands as amq_gemm_res_f16 / amq_gemm_gated_f16. */
+ * K % 128 == 0, x_stride % 8 == 0, y_stride % 4 == 0 (0 = dense; else x_stride >= K, y_stride >= N); epilogue operands as amq_gemm_res_f16 /
+ * amq_gemm_gated_f16. */
 int amq_gemm_f16w_f16(const void* x, const void* w_f16, const void* bias, const void* residual, const void* gate, void* y,
                       int M, int N, int K, int x_stride, int y_stride, void* stream);
 /* The LlamaMLP product act_fn(gate_proj(x)) * up_proj(x) with up_proj as this GEMM:
@@ -696,7 +708,7 @@ int amq_gemm_f16w_f16(const void* x, const void* w_f16, const void* bias, const 
  * formed in the epilogue of the kernel that serves the shape (256-row ring and few-row kernels) or by the element-wise
  * launch behind it (tiled kernel) -- the same expression as amq_silu_mul_f16 on the separate outputs, bit for bit.
  * gate may alias y only in the first case: amq_gemm_gated_fused(route, M, N, K, use_workspace) says which it is
- * (use_workspace: whether a split-K workspace will be passed).  route / workspace as amq_gemm_route_f16. */
+ * (use_workspace: whether a split-K workspace will be passed).  route / workspace as amq_gemm_route_f16; x_stride: 0, or >= K and % 8 == 0. */
 int amq_gemm_gated_fused(int route, int M, int N, int K, int use_workspace);
 int amq_gemm_gated_fused_g(int route, int M, int N, int K, int use_workspace, int group);   /* ... for a given group size (64 / 32: few-row kernel and dequantize-once yes, tiled no) */
 int amq_gemm_gated_f16(int route, int bits, int mode, const void* x, const void* qweight_native, const void* meta_native,
@@ -713,13 +725,15 @@ int amq_xfrag_f16(const void* src, void* xf, int M, int K, long long stride_m, l
 /* amq_rmsnorm_f16 (rows of K, contiguous) writing its result in fragment order */
 int amq_rmsnorm_xfrag_f16(const void* x, const void* gamma, void* xf, int M, int K, float eps, void* stream);
 /* gate (fp16 [M, y_stride] or NULL, may alias y): y = fp16(silu(gate)) * fp16(x . W^T (+ bias)) -- the LlamaMLP product
- * act_fn(gate_proj(x)) * up_proj(x) formed in up_proj's epilogue (same expression as amq_silu_mul_f16) */
+ * act_fn(gate_proj(x)) * up_proj(x) formed in up_proj's epilogue (same expression as amq_silu_mul_f16).  y_stride (also the gate's and the
+ * residual's): 0, or >= N and % 8 == 0 */
 int amq_gemm_xfrag_f16(int bits, int mode, const void* xf, const void* qweight_native, const void* meta_native,
                        const void* bias, const void* gate, const void* residual, void* y, int M, int N, int K, int group,
                        int y_stride, void* stream);
 /* Several linears over the SAME fragment-ordered x (q/k/v, gate/up of a prompt pass), each with its own bit-width, as
  * segments of one few-row launch (amq_segment as for amq_gemv_grouped_f16; residual optional per segment):
- * y_i = x . W_i^T (+ bias_i) (+ residual_i).  Results are those of amq_gemm_xfrag_f16 per segment, bit for bit. */
+ * y_i = x . W_i^T (+ bias_i) (+ residual_i).  Results are those of amq_gemm_xfrag_f16 per segment, bit for bit.  Every segment's y_stride: 0, or
+ * >= its N and % 8 == 0. */
 int amq_gemm_xfrag_grouped_f16(const amq_segment* segments /* host */, int nseg, const void* xf, int M, int K, int group,
                                void* stream);
 /* The same launch with its kernel form chosen by the caller (tests, A/B tools; the results do not depend on it, bit for bit):

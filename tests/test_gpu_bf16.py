@@ -6,6 +6,7 @@ reference's HQQLinear(compute_dtype=torch.bfloat16) on CPU (tests/golden/gen_gol
 Bar: dequantized weights bit-exact (also the weights the GEMV kernel forms in registers: recovered with x = unit rows); matmul outputs within
 ONE bf16 ulp of the output, |y - ref| <= 2^-7 * |ref| + 2^-8 * rms(ref) -- bfloat16 keeps 8 significant bits, so the fp16 path's 1e-3 bar is
 below its rounding step; the reference side is torch's CPU F.linear on the oracle's bf16 weights."""
+import ctypes
 import glob
 import os
 
@@ -235,6 +236,21 @@ def test_bf16_strided_rows_through_the_c_abi():
         torch.cuda.synchronize()
         _assert_bf16_close(_bits(ybuf[:, :n]), _cpu_linear_bits(xbuf[:, :k].cpu().contiguous(), wb))
         assert torch.count_nonzero(ybuf[:, n:]) == 0           # nothing written past a row's N outputs
+        # the same launch on guarded buffers: NaN behind every row of x (a read past the K columns multiplies it in), y inside an allocation
+        # pre-filled with a sentinel -- a bf16 NaN with a payload, which no arithmetic produces -- with a band of 256 elements before row 0 and
+        # after the last row: the same bits in the live columns, every other element untouched
+        sent, band, ys = 0x7FB7, 256, n + 32
+        xg = xbuf.clone()
+        xg[:, k:] = float("nan")
+        guard = torch.full((band + 4 * ys + band,), sent, dtype=torch.int16, device=_dev())
+        yg = guard[band:band + 4 * ys].view(4, ys)
+        rc = lib.amq_gemv_bf16(bits, _lib.ptr(xg), _lib.ptr(qn), _lib.ptr(mn), None, None, ctypes.c_void_p(yg.data_ptr()), 4, n, k, 128, xs, ys,
+                               _lib.current_stream())
+        assert rc == 0, lib.amq_last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(yg[:, :n], ybuf[:, :n].view(torch.int16)), "NaN behind the rows of x changes the result: read past K columns"
+        assert not (yg[:, :n] == sent).any()
+        assert (yg[:, n:] == sent).all() and (guard[:band] == sent).all() and (guard[band + 4 * ys:] == sent).all(), "written outside the N live columns"
     rc = lib.amq_gemv_bf16(bits, _lib.ptr(xbuf), _lib.ptr(qn), _lib.ptr(mn), None, None, _lib.ptr(ybuf), 4, n, k, 128, k + 4, n + 32, None)
     assert rc == -2                                              # rows are read in 16-byte pieces
 
