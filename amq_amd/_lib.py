@@ -195,6 +195,22 @@ class AmqError(RuntimeError):
     pass
 
 
+def _open(path, signatures, abi=True):
+    """dlopen a build of the library and give every symbol of ``signatures`` its types (AttributeError if the .so lacks a declared symbol)"""
+    # torch bundles its own libamdhip64.so.7; load it FIRST so that this
+    # library binds to the same HIP runtime instance (two runtimes in one
+    # process do not share a device context -> "no ROCm-capable device").
+    import torch  # noqa: F401
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
+    if abi and lib.amq_version() != ABI_VERSION:
+        raise AmqError(f"{path} reports ABI version {lib.amq_version()}, these bindings were written against {ABI_VERSION} "
+                       "(include/amq_hip.h AMQ_VERSION): rebuild with `make -C amq_amd/csrc`")
+    return lib
+
+
 def load():
     """Load libamq_hip.so once; raise if it has not been built."""
     global _lib
@@ -205,19 +221,8 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is not built. "
             "Run `python -c 'import __graft_entry__ as g; g.build()'` (or `make -C amq_amd/csrc`). "
             "There is no CPU fallback.")
-    # torch bundles its own libamdhip64.so.7; load it FIRST so that this
-    # library binds to the same HIP runtime instance (two runtimes in one
-    # process do not share a device context -> "no ROCm-capable device").
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
-        fn.restype, fn.argtypes = res, args
-    if lib.amq_version() != ABI_VERSION:
-        raise AmqError(f"{LIB_PATH} reports ABI version {lib.amq_version()}, these bindings were written against {ABI_VERSION} "
-                       "(include/amq_hip.h AMQ_VERSION): rebuild with `make -C amq_amd/csrc`")
-    _lib = lib
-    return lib
+    _lib = _open(LIB_PATH, SIGNATURES)
+    return _lib
 
 
 def load_ab():
@@ -228,11 +233,7 @@ def load_ab():
     if not os.path.exists(AB_LIB_PATH):
         raise AmqError(f"{AB_LIB_PATH} not found: the A/B routes (decode engine, fused q/k/v + attention) live in their own library -- "
                        "`make -C amq_amd/csrc ab` (or __graft_entry__.build()).  They are slower than the product step and not needed for it.")
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(AB_LIB_PATH)
-    for name, (res, args) in AB_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
+    lib = _open(AB_LIB_PATH, AB_SIGNATURES, abi=False)
     lib.amq_last_error.restype = ctypes.c_char_p
     _ab_lib = lib
     return lib
@@ -262,14 +263,7 @@ def open_twin(path=None):
     path = SAFE_LIB_PATH if path is None else os.path.abspath(path)
     if not os.path.exists(path):
         raise AmqError(f"{path} not found: `make -C amq_amd/csrc safe` (or __graft_entry__.build())")
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    if lib.amq_version() != ABI_VERSION:
-        raise AmqError(f"{path} reports ABI version {lib.amq_version()}, expected {ABI_VERSION}")
-    return lib
+    return _open(path, SIGNATURES)
 
 
 class routed_to:

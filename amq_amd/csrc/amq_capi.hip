@@ -28,14 +28,18 @@ int check_hip(hipError_t e, const char* what) {
     return fail(AMQ_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
 }
 
-int check_shape(int bits, int N, int K, int group) {
-    if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
-    // 128, or a multiple of it that divides K: the repack entry points read such a source format and replicate each group's
-    // (scale, zero) into the native layout's per-128 pairs; the compute entry points work on the native layout either way
-    // 64 / 32: the native meta holds 128 / group pairs per (row, tile) (amq_common.cuh); served by the repack / dequantize entry points, the GEMV
-    // kernel (<= 16 rows, exact math) and the dequantize-once GEMM route -- the other entry points refuse them (check_shape128)
+// 128, or a multiple of it that divides K: the repack entry points read such a source format and replicate each group's
+// (scale, zero) into the native layout's per-128 pairs; the compute entry points work on the native layout either way
+// 64 / 32: the native meta holds 128 / group pairs per (row, tile) (amq_common.cuh); served by the repack / dequantize entry points, the GEMV
+// kernel (<= 16 rows, exact math) and the dequantize-once GEMM route -- the other entry points refuse them (check_shape128)
+int check_group(int group) {
     if (group != 64 && group != 32 && (group < 128 || (group % 128) != 0))
         return fail(AMQ_ESHAPE, "group size must be 32, 64 or a multiple of 128 (got %d)", group);
+    return AMQ_OK;
+}
+int check_shape(int bits, int N, int K, int group) {
+    if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);
+    if (int rc = check_group(group)) return rc;
     if (N <= 0 || K <= 0 || (N % 16) != 0 || (K % 128) != 0)
         return fail(AMQ_ESHAPE, "need N %% 16 == 0 and K %% 128 == 0 (got N=%d K=%d)", N, K);
     if ((K % group) != 0) return fail(AMQ_ESHAPE, "group size %d does not divide K=%d", group, K);
@@ -346,6 +350,55 @@ int amq_dequantize_hqq_f16(int bits, const void* W_q, const void* scale, const v
 #endif
 int amq_default_gemv_math(void) { return AMQ_GEMV_DEFAULT_MATH; }
 
+/* ---- fp16 matmul entry points: one segment reader, one option reader, one packed-GEMM validator and one route plan.  What differs between the
+   entry points of a family is its form constant ("Matmul entry points: what is checked"). */
+
+// The segments of a grouped call.  all_groups: the kernels read the finer groups' pairs (else one pair per 128 columns: check_shape128);
+// raw_mode: the GEMV kernel tells AMQ_MODE_FMA1 apart, the others take it as AMQ_MODE_FMA
+struct SegForm { const char* who; bool all_groups, raw_mode; };
+constexpr SegForm SEG_GEMV{"amq_gemv_grouped_f16", true, true};
+constexpr SegForm SEG_SUMS{"amq_gemv_grouped_sums_f16", true, true};
+constexpr SegForm SEG_XFRAG{"amq_gemm_xfrag_grouped_f16", false, false};
+
+// every segment's stride before any segment's shape, mode and pointers; act_mask: the segments that store fp16(silu(y)) (amq_gemv_grouped_f16 only)
+static int read_segments(const SegForm& f, const amq_segment* segs, int nseg, int M, int K, int group, int act_mask, amq::GemvSeg* out) {
+    for (int i = 0; i < nseg; ++i)
+        if (int rc = check_strides(seg_name(f.who, i), M, K, 0, segs[i].N, segs[i].y_stride, 8, 0)) return rc;
+    for (int i = 0; i < nseg; ++i) {
+        const amq_segment& s = segs[i];
+        if (int rc = f.all_groups ? check_shape(s.bits, s.N, K, group) : check_shape128(s.bits, s.N, K, group, f.who)) return rc;
+        if (int rc = check_mode(s.mode)) return rc;
+        if (!s.qweight_native || !s.meta_native || !s.y) return fail(AMQ_EINVAL, "segment %d: null pointer", i);
+        amq::GemvSeg& d = out[i];
+        d.qweight = s.qweight_native; d.meta = s.meta_native; d.bias = s.bias; d.residual = s.residual; d.y = s.y;
+        d.N = s.N; d.bits = s.bits; d.mode = f.raw_mode ? s.mode : kernel_mode(s.mode);
+        d.y_stride = s.y_stride ? s.y_stride : s.N;
+        d.act = (act_mask >> i) & 1;
+        if (d.act && s.residual) return fail(AMQ_EINVAL, "segment %d: an activated output (opts.act_mask) takes no residual", i);
+    }
+    return AMQ_OK;
+}
+
+// The options of a GEMV launch as launch_gemv / gemv_route see them: NULL = all zero = defaults, the default math resolved, the generic marker
+// taken out of depth (auto depth under the generic kernel: everything below sees 0), the GEMV_FLAG_* of math and dot
+struct GemvOptions { amq_gemv_opts o; bool generic; int flags; };
+static int read_gemv_opts(const amq_gemv_opts* opts, int nseg, GemvOptions* out) {
+    amq_gemv_opts o{};
+    if (opts) o = *opts;
+    if (o.math < AMQ_MATH_DEFAULT || o.math > AMQ_MATH_EXACT)
+        return fail(AMQ_EINVAL, "opts.math must be AMQ_MATH_DEFAULT, AMQ_MATH_EXACT, AMQ_MATH_GROUPSCALE or AMQ_MATH_LINEAR");
+    if (o.math == AMQ_MATH_DEFAULT) o.math = amq_default_gemv_math();
+    if (o.waves != 0 && o.waves != 4 && o.waves != 8 && o.waves != 16) return fail(AMQ_EINVAL, "opts.waves must be 0, 4, 8 or 16");
+    if (o.depth != 0 && o.depth != 2 && o.depth != 4 && o.depth != AMQ_GEMV_DEPTH_GENERIC) return fail(AMQ_EINVAL, "opts.depth must be 0, 2, 4 or AMQ_GEMV_DEPTH_GENERIC");
+    out->generic = o.depth == AMQ_GEMV_DEPTH_GENERIC;
+    if (out->generic) o.depth = 0;
+    if (o.rpt < 0 || o.rpt > 64) return fail(AMQ_EINVAL, "opts.rpt (row-tiles per workgroup) must be 0..64");
+    if (o.act_mask < 0 || o.act_mask >= (1 << nseg)) return fail(AMQ_EINVAL, "opts.act_mask names segments 0..%d (got 0x%x)", nseg - 1, o.act_mask);
+    out->o = o;
+    out->flags = (o.dot ? amq::GEMV_FLAG_DOT : 0) | (o.math == AMQ_MATH_LINEAR ? amq::GEMV_FLAG_LINEAR : 0) | (o.math == AMQ_MATH_GROUPSCALE ? amq::GEMV_FLAG_GS : 0);
+    return AMQ_OK;
+}
+
 int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const void* x2, const void* gamma,
                          float eps, int prologue, int M, int K, int group, int x_stride, const amq_gemv_opts* opts,
                          void* stream) {
@@ -357,69 +410,41 @@ int amq_gemv_grouped_f16(const amq_segment* segs, int nseg, const void* x, const
     if (prologue == AMQ_PRO_MUL && !x2) return fail(AMQ_EINVAL, "mul prologue needs x2");
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
     if (int rc = check_strides("amq_gemv_grouped_f16", M, K, x_stride, 0, 0, 8, 0)) return rc;
-    amq_gemv_opts o{};                                   // all zero = defaults
-    if (opts) o = *opts;
-    if (o.math < AMQ_MATH_DEFAULT || o.math > AMQ_MATH_EXACT)
-        return fail(AMQ_EINVAL, "opts.math must be AMQ_MATH_DEFAULT, AMQ_MATH_EXACT, AMQ_MATH_GROUPSCALE or AMQ_MATH_LINEAR");
-    if (o.math == AMQ_MATH_DEFAULT) o.math = amq_default_gemv_math();
-    if (o.waves != 0 && o.waves != 4 && o.waves != 8 && o.waves != 16) return fail(AMQ_EINVAL, "opts.waves must be 0, 4, 8 or 16");
-    if (o.depth != 0 && o.depth != 2 && o.depth != 4 && o.depth != AMQ_GEMV_DEPTH_GENERIC) return fail(AMQ_EINVAL, "opts.depth must be 0, 2, 4 or AMQ_GEMV_DEPTH_GENERIC");
-    const bool generic = o.depth == AMQ_GEMV_DEPTH_GENERIC;       // (auto depth under the generic kernel: everything below sees 0)
-    if (generic) o.depth = 0;
-    if (o.rpt < 0 || o.rpt > 64) return fail(AMQ_EINVAL, "opts.rpt (row-tiles per workgroup) must be 0..64");
-    if (o.act_mask < 0 || o.act_mask >= (1 << nseg)) return fail(AMQ_EINVAL, "opts.act_mask names segments 0..%d (got 0x%x)", nseg - 1, o.act_mask);
+    GemvOptions g;
+    if (int rc = read_gemv_opts(opts, nseg, &g)) return rc;
+    const amq_gemv_opts& o = g.o;
+    const int gp = amq::meta_pairs(group);
     // (the activated output and the prologue that multiplies it live in the group-128 kernels; finer groups keep AMQ_PRO_SILU_MUL)
-    if ((o.act_mask || prologue == AMQ_PRO_MUL) && amq::meta_pairs(group) != 1)
+    if ((o.act_mask || prologue == AMQ_PRO_MUL) && gp != 1)
         return fail(AMQ_ESHAPE, "opts.act_mask / AMQ_PRO_MUL: groups of 128 (and multiples) only (got %d); use AMQ_PRO_SILU_MUL", group);
-    const bool plain_form = !o.dot && o.math != AMQ_MATH_LINEAR && o.depth != 4 && amq::meta_pairs(group) == 1 && o.waves != 4;
+    const bool plain_form = !o.dot && o.math != AMQ_MATH_LINEAR && o.depth != 4 && gp == 1 && o.waves != 4;
     // (rows staged in two K phases -- 7 - 8 rows of K = 11008 -- need dense x rows and no full-row statistic: launch_gemv makes the same decision)
     const bool whole_rows = prologue == AMQ_PRO_RMSNORM || (x_stride != 0 && x_stride != K);
     if (M > amq::GEMV_MAX_M || amq::gemv_min_lds_bytes(M, K, plain_form && o.waves == 0 && o.rpt == 0, whole_rows) > LDS_LIMIT)
         return fail(AMQ_ESHAPE, "M=%d rows of K=%d%s do not fit LDS for the GEMV path; use amq_gemm_f16", M, K, (x_stride != 0 && x_stride != K) ? " (strided x)" : "");
     amq::GemvArgs a{};
-    for (int i = 0; i < nseg; ++i)          // (every segment's stride before any segment's pointers)
-        if (int rc = check_strides(seg_name("amq_gemv_grouped_f16", i), M, K, 0, segs[i].N, segs[i].y_stride, 8, 0)) return rc;
-    for (int i = 0; i < nseg; ++i) {
-        const amq_segment& s = segs[i];
-        if (int rc = check_shape(s.bits, s.N, K, group)) return rc;
-        if (int rc = check_mode(s.mode)) return rc;
-        if (!s.qweight_native || !s.meta_native || !s.y) return fail(AMQ_EINVAL, "segment %d: null pointer", i);
-        amq::GemvSeg& d = a.seg[i];
-        d.qweight = s.qweight_native; d.meta = s.meta_native; d.bias = s.bias; d.residual = s.residual; d.y = s.y;
-        d.N = s.N; d.bits = s.bits; d.mode = s.mode;
-        d.y_stride = s.y_stride ? s.y_stride : s.N;
-        d.act = (o.act_mask >> i) & 1;
-        if (d.act && s.residual) return fail(AMQ_EINVAL, "segment %d: an activated output (opts.act_mask) takes no residual", i);
-    }
+    if (int rc = read_segments(SEG_GEMV, segs, nseg, M, K, group, o.act_mask, a.seg)) return rc;
     a.nseg = nseg; a.M = M; a.K = K; a.x_stride = x_stride ? x_stride : K;
     a.x = x; a.x2 = x2; a.gamma = gamma; a.eps = eps; a.prologue = prologue;
-    a.flags = (o.dot ? amq::GEMV_FLAG_DOT : 0) | (o.math == AMQ_MATH_LINEAR ? amq::GEMV_FLAG_LINEAR : 0) |
-              (o.math == AMQ_MATH_GROUPSCALE ? amq::GEMV_FLAG_GS : 0);
+    a.flags = g.flags;
     a.force_waves = o.waves;
     a.force_depth = o.depth;
     a.force_rpt = o.rpt;
-    a.gp = amq::meta_pairs(group);
-    a.generic = generic;
-    if (a.gp > 1 && (o.dot || o.math == AMQ_MATH_LINEAR || o.depth == 4))
+    a.gp = gp;
+    a.generic = g.generic;
+    if (gp > 1 && (o.dot || o.math == AMQ_MATH_LINEAR || o.depth == 4))
         return fail(AMQ_EINVAL, "groups of %d: the GEMV kernel's default form only (opts.math = AMQ_MATH_EXACT, opts.dot = 0, opts.depth = 0 / 2)", group);
     return check_hip(amq::launch_gemv(a, (hipStream_t)stream), "gemv");
 }
 
-// the flags launch_gemv sees for a set of options (amq_gemv_grouped_f16 builds the same)
-static int gemv_flags_of(const amq_gemv_opts& o) {
-    const int math = o.math == AMQ_MATH_DEFAULT ? amq_default_gemv_math() : o.math;
-    return (o.dot ? amq::GEMV_FLAG_DOT : 0) | (math == AMQ_MATH_LINEAR ? amq::GEMV_FLAG_LINEAR : 0) | (math == AMQ_MATH_GROUPSCALE ? amq::GEMV_FLAG_GS : 0);
-}
-
 int amq_gemv_route(int prologue, int M, int K, int group, int nseg, const int* bits, const int* modes, const amq_gemv_opts* opts) {
     if (!bits || !modes || nseg < 1 || nseg > AMQ_MAX_SEGMENTS) return fail(AMQ_EINVAL, "nseg must be 1..%d (got %d), bits and modes non-null", AMQ_MAX_SEGMENTS, nseg);
-    if (group != 32 && group != 64 && (group < 128 || group % 128 != 0)) return fail(AMQ_ESHAPE, "group must be 32, 64 or a multiple of 128 (got %d)", group);
-    amq_gemv_opts o{};
-    if (opts) o = *opts;
-    const bool generic = o.depth == AMQ_GEMV_DEPTH_GENERIC;
+    if (int rc = check_group(group)) return rc;
+    GemvOptions g;
+    if (int rc = read_gemv_opts(opts, nseg, &g)) return rc;
     int km[AMQ_MAX_SEGMENTS];
     for (int i = 0; i < nseg; ++i) km[i] = modes[i] == AMQ_MODE_HQQ ? (int)amq::MODE_HQQ : (int)amq::MODE_FMA;      // (one-rounding buffers are generic either way)
-    return amq::gemv_route(prologue, M, K, amq::meta_pairs(group), nseg, bits, km, gemv_flags_of(o), o.waves, generic ? 0 : o.depth, o.rpt, generic);
+    return amq::gemv_route(prologue, M, K, amq::meta_pairs(group), nseg, bits, km, g.flags, g.o.waves, g.o.depth, g.o.rpt, g.generic);
 }
 
 int amq_gemv_segment_order(int nseg, const int* bits, int act_mask, int* order, int* act_mask_out) {
@@ -445,18 +470,7 @@ int amq_gemv_grouped_sums_f16(const amq_segment* segs, int nseg, const void* x, 
     if (amq::gemv_min_lds_bytes(M, K, true, sums_in != nullptr) > LDS_LIMIT)
         return fail(AMQ_ESHAPE, "M=%d rows of K=%d do not fit LDS for the GEMV path", M, K);
     amq::GemvArgs a{};
-    for (int i = 0; i < nseg; ++i)          // (every segment's stride before any segment's pointers)
-        if (int rc = check_strides(seg_name("amq_gemv_grouped_sums_f16", i), M, K, 0, segs[i].N, segs[i].y_stride, 8, 0)) return rc;
-    for (int i = 0; i < nseg; ++i) {
-        const amq_segment& s = segs[i];
-        if (int rc = check_shape(s.bits, s.N, K, group)) return rc;
-        if (int rc = check_mode(s.mode)) return rc;
-        if (!s.qweight_native || !s.meta_native || !s.y) return fail(AMQ_EINVAL, "segment %d: null pointer", i);
-        amq::GemvSeg& d = a.seg[i];
-        d.qweight = s.qweight_native; d.meta = s.meta_native; d.bias = s.bias; d.residual = s.residual; d.y = s.y;
-        d.N = s.N; d.bits = s.bits; d.mode = s.mode;
-        d.y_stride = s.y_stride ? s.y_stride : s.N;
-    }
+    if (int rc = read_segments(SEG_SUMS, segs, nseg, M, K, group, 0, a.seg)) return rc;
     a.nseg = nseg; a.M = M; a.K = K; a.x_stride = K;
     a.x = x; a.x2 = nullptr; a.gamma = gamma; a.eps = eps;
     a.prologue = sums_in ? amq::PRO_RMSNORM_SUMS : amq::PRO_NONE;
@@ -473,17 +487,27 @@ int amq_gemv_f16(int bits, int mode, const void* x, const void* qn, const void* 
     return amq_gemv_grouped_f16(&s, 1, x, nullptr, nullptr, 0.f, AMQ_PRO_NONE, M, K, group, x_stride, nullptr, stream);
 }
 
-int amq_gemm_f16(int bits, int mode, const void* x, const void* qn, const void* mn, const void* bias, void* y,
-                 int M, int N, int K, int group, int x_stride, int y_stride, void* stream) {
-    if (int rc = check_shape(bits, N, K, group)) return rc;          // (groups of 64 / 32: the few-row or the tiled kernel -- no workspace here, so never dequantize-once)
-    if (int rc = check_mode(mode)) return rc;
-    mode = kernel_mode(mode);
-    if (int rc = check_strides("amq_gemm_f16", M, K, x_stride, N, y_stride, 8, FEWROW_MAX_ROWS)) return rc;
-    if (!x || !qn || !mn || !y) return fail(AMQ_EINVAL, "null pointer");
-    if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
-    amq::GemmArgs a{x, qn, mn, bias, y, M, N, K, bits, mode, x_stride ? x_stride : K, y_stride ? y_stride : N, nullptr, 1,
-                    nullptr, nullptr, nullptr, amq::meta_pairs(group)};
-    return check_hip(amq::launch_gemm(a, (hipStream_t)stream), "gemm");
+// What a packed-GEMM call runs, derived here and nowhere else: dequantize-once or a fused kernel, the route the split-K policy is asked with (groups of
+// 64 / 32 beyond their few-row kernel: the tiled kernel), the splits, and the bytes a workspace must hold -- the dequantized fp16 weights or the
+// split-K partials, never both.  Without a workspace the call is a single pass through a fused kernel (splits = 1).  Outside the queries' domain: no workspace.
+struct GemmPlan { bool deq; int sroute, splits; size_t need_bytes; };
+static GemmPlan plan_gemm(int route, int M, int N, int K, int group, bool have_workspace) {
+    if (M < 1 || N < 1 || K < 128 || route < AMQ_GEMM_AUTO || route > AMQ_GEMM_DEQ) return {false, route, 1, 0};
+    const bool fine = group == 64 || group == 32;
+    // few rows of fine groups: the pair-aware few-row kernel; then the tiled kernel; launches that fill 256 x 256 tiles: dequantize-once
+    const bool deq = route == AMQ_GEMM_DEQ || (route == AMQ_GEMM_AUTO && (fine ? amq::gemm_fine_takes_deq(M, N, K) : amq::gemm_takes_deq(M, N, K)));
+    const int sroute = fine && route == AMQ_GEMM_AUTO ? (int)AMQ_GEMM_TILED : route;
+    if (deq) return {true, sroute, 1, (size_t)N * (size_t)K * 2};
+    if (fine && amq::gemm_fine_takes_skinny(M)) return {false, sroute, 1, 0};          // (their few-row kernel takes no workspace)
+    const int s = amq::gemm_pick_splits(M, N, K, sroute);
+    if (s <= 1) return {false, sroute, 1, 0};
+    return {false, sroute, have_workspace ? s : 1, (size_t)s * (size_t)M * (size_t)N * sizeof(float)};
+}
+// the launcher's arguments of a planned call; `workspace` is only looked at where the plan has a use for it
+static amq::GemmArgs planned_args(const GemmPlan& p, const void* x, const void* qn, const void* mn, const void* bias, void* y, int M, int N, int K, int bits,
+                                  int mode, int x_stride, int y_stride, const void* residual, const void* gate, void* workspace, int group) {
+    return {x, qn, mn, bias, y, M, N, K, bits, mode, x_stride ? x_stride : K, y_stride ? y_stride : N, p.splits > 1 ? (float*)workspace : nullptr, p.splits,
+            residual, gate, p.deq ? workspace : nullptr, amq::meta_pairs(group)};
 }
 
 size_t amq_gemm_splitk_workspace_bytes(int M, int N, int K) {
@@ -491,84 +515,79 @@ size_t amq_gemm_splitk_workspace_bytes(int M, int N, int K) {
     const int s = amq::gemm_pick_splits(M, N, K);
     return s > 1 ? (size_t)s * (size_t)M * (size_t)N * sizeof(float) : 0;
 }
+size_t amq_gemm_route_workspace_bytes_g(int route, int M, int N, int K, int group) { return plan_gemm(route, M, N, K, group, false).need_bytes; }
+size_t amq_gemm_route_workspace_bytes(int route, int M, int N, int K) { return amq_gemm_route_workspace_bytes_g(route, M, N, K, 128); }
+
+int amq_gemm_gated_fused_g(int route, int M, int N, int K, int use_workspace, int group) {
+    if (M < 1 || N < 16 || K < 128 || route < AMQ_GEMM_AUTO || route > AMQ_GEMM_DEQ) return 0;
+    static char present;       // (gemm_gate_fused only tests the workspace for presence; asking it without one needs a launcher change)
+    const GemmPlan p = plan_gemm(route, M, N, K, group, use_workspace != 0);
+    return amq::gemm_gate_fused(planned_args(p, nullptr, nullptr, nullptr, nullptr, nullptr, M, N, K, 4, AMQ_MODE_HQQ, 0, 0, nullptr, nullptr,
+                                             use_workspace ? &present : nullptr, group > 0 ? group : 128), route) ? 1 : 0;
+}
+int amq_gemm_gated_fused(int route, int M, int N, int K, int use_workspace) { return amq_gemm_gated_fused_g(route, M, N, K, use_workspace, 128); }
+
+// The packed-GEMM entry points.  ws: no workspace argument / the split-K entry point's (required, sized by amq_gemm_splitk_workspace_bytes) / the
+// route family's (optional, sized by the plan).  gated: `other` is the gate (required, applied to the result) instead of the residual, and may
+// alias y only where a kernel applies it.  deq_refusal: how the entry point words what the fp16-weight GEMM of the dequantize-once route cannot
+// address (none: the entry point never runs it); deq_forced: a forced AMQ_GEMM_DEQ over groups of 128 is held to it too.
+enum { WS_ABSENT, WS_SPLITK, WS_ROUTE };
+struct GemmForm { const char* who; const char* what; int ws; bool gated; const char* deq_refusal; bool deq_forced; };
+constexpr GemmForm GEMM_PLAIN{"amq_gemm_f16", "gemm", WS_ABSENT, false, nullptr, false};
+constexpr GemmForm GEMM_SPLITK{"amq_gemm_splitk_f16", "gemm_splitk", WS_SPLITK, false, nullptr, false};
+constexpr GemmForm GEMM_ROUTE{"amq_gemm_route_f16", "gemm", WS_ROUTE, false,
+                              "AMQ_GEMM_DEQ: strides must be multiples of 8 (x) / 4 (y) halves and x, W must each span < 4 GiB", true};
+constexpr GemmForm GEMM_GATED{"amq_gemm_gated_f16", "gemm_gated", WS_ROUTE, true,
+                              "groups of %d (dequantize-once route): x_stride must be a multiple of 8 halves, N of 4, x and W must each span < 4 GiB", false};
+
+static int gemm_call(const GemmForm& f, int route, int bits, int mode, const void* x, const void* qn, const void* mn, const void* bias, const void* other,
+                     void* y, int M, int N, int K, int group, int x_stride, int y_stride, void* workspace, size_t workspace_bytes, void* stream,
+                     amq::GemmNorm* norm = nullptr) {
+    if (route < AMQ_GEMM_AUTO || route > AMQ_GEMM_DEQ) return fail(AMQ_EINVAL, "unknown GEMM route %d", route);
+    if (int rc = check_shape(bits, N, K, group)) return rc;
+    if (int rc = check_mode(mode)) return rc;
+    if (int rc = check_strides(f.who, M, K, x_stride, N, y_stride, 8, fewrow_rows_of(route))) return rc;
+    if (!x || !qn || !mn || !y || (f.gated && !other)) return fail(AMQ_EINVAL, "null pointer");
+    if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
+    const bool fine = group == 64 || group == 32;
+    // groups of 64 / 32 on a route call: the few-row kernel (AUTO / SKINNY) up to gemm_fine_takes_skinny rows, the tiled kernel (AUTO / TILED) or
+    // dequantize-once (AUTO where it fills the chip, given the workspace; DEQ) beyond; the ring / wave-specialised kernels read one pair per tile
+    if (route == AMQ_GEMM_SKINNY && M > 64 && !(fine && amq::gemm_fine_takes_skinny(M)))
+        return fail(AMQ_ESHAPE, "the few-row kernel takes at most 64 rows (got %d)", M);
+    if (fine && (route == AMQ_GEMM_RING || route == AMQ_GEMM_RING128 || route == AMQ_GEMM_WS))
+        return fail(AMQ_EINVAL, "groups of %d: the ring / wave-specialised kernels read one (scale, zero) per 128 columns (use AMQ_GEMM_AUTO, _SKINNY, _TILED or the dequantize-once route _DEQ)", group);
+    if (route == AMQ_GEMM_DEQ && !workspace) return fail(AMQ_EINVAL, "AMQ_GEMM_DEQ needs a workspace of N * K * 2 bytes for the fp16 weights");
+    GemmPlan p{false, route, 1, 0};                        // (no workspace argument: a single pass through a fused kernel)
+    if (f.ws == WS_SPLITK) p = {false, route, amq::gemm_pick_splits(M, N, K), amq_gemm_splitk_workspace_bytes(M, N, K)};
+    if (f.ws == WS_ROUTE) p = plan_gemm(route, M, N, K, group, workspace != nullptr);
+    if (workspace ? workspace_bytes < p.need_bytes : f.ws == WS_SPLITK)          // (the split-K entry point answers a missing workspace the same way)
+        return fail(AMQ_EINVAL, "%sworkspace too small: need %zu bytes, got %zu", f.ws == WS_SPLITK ? "split-K " : "", p.need_bytes, workspace_bytes);
+    const amq::GemmArgs a = planned_args(p, x, qn, mn, bias, y, M, N, K, bits, kernel_mode(mode), x_stride, y_stride, f.gated ? nullptr : other,
+                                         f.gated ? other : nullptr, workspace, group);
+    if (f.deq_refusal && ((f.deq_forced && route == AMQ_GEMM_DEQ) || (fine && p.deq)) && !amq::gemm_f16w_ok(M, N, K, a.x_stride, a.y_stride))
+        return fail(AMQ_ESHAPE, f.deq_refusal, group);
+    if (f.gated && other == y && !amq::gemm_gate_fused(a, route))
+        return fail(AMQ_EINVAL, "gate may alias y only where the kernel applies it in its epilogue (amq_gemm_gated_fused)");
+    return check_hip(amq::launch_gemm(a, (hipStream_t)stream, route, norm), f.what);
+}
+
+int amq_gemm_f16(int bits, int mode, const void* x, const void* qn, const void* mn, const void* bias, void* y,
+                 int M, int N, int K, int group, int x_stride, int y_stride, void* stream) {
+    // (groups of 64 / 32: the few-row or the tiled kernel -- no workspace here, so never dequantize-once)
+    return gemm_call(GEMM_PLAIN, AMQ_GEMM_AUTO, bits, mode, x, qn, mn, bias, nullptr, y, M, N, K, group, x_stride, y_stride, nullptr, 0, stream);
+}
 
 int amq_gemm_splitk_f16(int bits, int mode, const void* x, const void* qn, const void* mn, const void* bias, void* y,
                         int M, int N, int K, int group, int x_stride, int y_stride, void* workspace, size_t workspace_bytes,
                         void* stream) {
-    const size_t need = amq_gemm_splitk_workspace_bytes(M, N, K);
-    if (need == 0) return amq_gemm_f16(bits, mode, x, qn, mn, bias, y, M, N, K, group, x_stride, y_stride, stream);
-    if (int rc = check_shape(bits, N, K, group)) return rc;
-    if (int rc = check_mode(mode)) return rc;
-    mode = kernel_mode(mode);
-    if (int rc = check_strides("amq_gemm_splitk_f16", M, K, x_stride, N, y_stride, 8, FEWROW_MAX_ROWS)) return rc;
-    if (!x || !qn || !mn || !y) return fail(AMQ_EINVAL, "null pointer");
-    if (!workspace || workspace_bytes < need) return fail(AMQ_EINVAL, "split-K workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    amq::GemmArgs a{x, qn, mn, bias, y, M, N, K, bits, mode, x_stride ? x_stride : K, y_stride ? y_stride : N,
-                    (float*)workspace, amq::gemm_pick_splits(M, N, K), nullptr, nullptr, nullptr, amq::meta_pairs(group)};
-    return check_hip(amq::launch_gemm(a, (hipStream_t)stream), "gemm_splitk");
-}
-
-// the workspace of a route call holds the dequantized fp16 weights (dequantize-once route) or the split-K partials, never both
-static bool route_is_deq(int route, int M, int N, int K, int group = 128) {
-    if (group == 64 || group == 32)       // few rows: the pair-aware few-row kernel; then the tiled kernel; launches that fill 256 x 256 tiles: dequantize-once
-        return route == AMQ_GEMM_DEQ || (route == AMQ_GEMM_AUTO && amq::gemm_fine_takes_deq(M, N, K));
-    return route == AMQ_GEMM_DEQ || (route == AMQ_GEMM_AUTO && amq::gemm_takes_deq(M, N, K));
-}
-
-size_t amq_gemm_route_workspace_bytes_g(int route, int M, int N, int K, int group) {
-    if (M < 1 || N < 1 || K < 128 || route < AMQ_GEMM_AUTO || route > AMQ_GEMM_DEQ) return 0;
-    if (route_is_deq(route, M, N, K, group)) return (size_t)N * (size_t)K * 2;       // the dequantized fp16 weights
-    if ((group == 64 || group == 32) && amq::gemm_fine_takes_skinny(M)) return 0;     // (their few-row kernel takes no workspace)
-    const int s = amq::gemm_pick_splits(M, N, K, (group == 64 || group == 32) && route == AMQ_GEMM_AUTO ? (int)AMQ_GEMM_TILED : route);
-    return s > 1 ? (size_t)s * (size_t)M * (size_t)N * sizeof(float) : 0;
-}
-size_t amq_gemm_route_workspace_bytes(int route, int M, int N, int K) { return amq_gemm_route_workspace_bytes_g(route, M, N, K, 128); }
-
-// groups of 64 / 32 on a route call: the few-row kernel (AUTO / SKINNY) up to gemm_fine_takes_skinny rows, the tiled kernel (AUTO / TILED) or
-// dequantize-once (AUTO where it fills the chip, given the workspace; DEQ) beyond; the ring / wave-specialised kernels read one pair per tile
-static int check_fine_route(int route, int group, int M, int N, int K, const void* workspace) {
-    if (group != 64 && group != 32) return AMQ_OK;
-    if (route == AMQ_GEMM_RING || route == AMQ_GEMM_RING128 || route == AMQ_GEMM_WS)
-        return fail(AMQ_EINVAL, "groups of %d: the ring / wave-specialised kernels read one (scale, zero) per 128 columns (use AMQ_GEMM_AUTO, _SKINNY, _TILED or the dequantize-once route _DEQ)", group);
-    if (route == AMQ_GEMM_DEQ && !workspace) return fail(AMQ_EINVAL, "AMQ_GEMM_DEQ needs a workspace of N * K * 2 bytes for the fp16 weights");
-    (void)M; (void)N; (void)K;
-    return AMQ_OK;
-}
-
-static int gemm_route_impl(int route, int bits, int mode, const void* x, const void* qn, const void* mn, const void* bias,
-                           const void* residual, void* y, int M, int N, int K, int group, int x_stride, int y_stride,
-                           void* workspace, size_t workspace_bytes, void* stream, amq::GemmNorm* norm) {
-    if (route < AMQ_GEMM_AUTO || route > AMQ_GEMM_DEQ) return fail(AMQ_EINVAL, "unknown GEMM route %d", route);
-    if (int rc = check_shape(bits, N, K, group)) return rc;
-    if (int rc = check_mode(mode)) return rc;
-    mode = kernel_mode(mode);
-    if (int rc = check_strides("amq_gemm_route_f16", M, K, x_stride, N, y_stride, 8, fewrow_rows_of(route))) return rc;
-    if (!x || !qn || !mn || !y) return fail(AMQ_EINVAL, "null pointer");
-    if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
-    if (route == AMQ_GEMM_SKINNY && M > 64 && !((group == 64 || group == 32) && amq::gemm_fine_takes_skinny(M)))
-        return fail(AMQ_ESHAPE, "the few-row kernel takes at most 64 rows (got %d)", M);
-    if (int rc = check_fine_route(route, group, M, N, K, workspace)) return rc;
-    const bool fine = group == 64 || group == 32;
-    const size_t need = amq_gemm_route_workspace_bytes_g(route, M, N, K, group);
-    const bool deq = route_is_deq(route, M, N, K, group);
-    if (route == AMQ_GEMM_DEQ && !workspace) return fail(AMQ_EINVAL, "AMQ_GEMM_DEQ needs a workspace of N * K * 2 bytes for the fp16 weights");
-    const bool use_ws = need != 0 && workspace != nullptr;         // no workspace: single pass through a fused kernel
-    if (use_ws && workspace_bytes < need)
-        return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    const bool split = use_ws && !deq;
-    const int sroute = fine && route == AMQ_GEMM_AUTO ? (int)AMQ_GEMM_TILED : route;       // (groups of 64 / 32 beyond the few-row kernel: the tiled kernel)
-    amq::GemmArgs a{x, qn, mn, bias, y, M, N, K, bits, mode, x_stride ? x_stride : K, y_stride ? y_stride : N,
-                    split ? (float*)workspace : nullptr, split ? amq::gemm_pick_splits(M, N, K, sroute) : 1, residual, nullptr,
-                    use_ws && deq ? workspace : nullptr, amq::meta_pairs(group)};
-    if ((route == AMQ_GEMM_DEQ || (fine && deq)) && !amq::gemm_f16w_ok(M, N, K, a.x_stride, a.y_stride))
-        return fail(AMQ_ESHAPE, "AMQ_GEMM_DEQ: strides must be multiples of 8 (x) / 4 (y) halves and x, W must each span < 4 GiB");
-    return check_hip(amq::launch_gemm(a, (hipStream_t)stream, route, norm), "gemm");
+    if (amq_gemm_splitk_workspace_bytes(M, N, K) == 0) return amq_gemm_f16(bits, mode, x, qn, mn, bias, y, M, N, K, group, x_stride, y_stride, stream);
+    return gemm_call(GEMM_SPLITK, AMQ_GEMM_AUTO, bits, mode, x, qn, mn, bias, nullptr, y, M, N, K, group, x_stride, y_stride, workspace, workspace_bytes, stream);
 }
 
 int amq_gemm_route_f16(int route, int bits, int mode, const void* x, const void* qn, const void* mn, const void* bias,
                        const void* residual, void* y, int M, int N, int K, int group, int x_stride, int y_stride,
                        void* workspace, size_t workspace_bytes, void* stream) {
-    return gemm_route_impl(route, bits, mode, x, qn, mn, bias, residual, y, M, N, K, group, x_stride, y_stride, workspace, workspace_bytes, stream, nullptr);
+    return gemm_call(GEMM_ROUTE, route, bits, mode, x, qn, mn, bias, residual, y, M, N, K, group, x_stride, y_stride, workspace, workspace_bytes, stream);
 }
 
 int amq_gemm_res_norm_xfrag_f16(int bits, int mode, const void* x, const void* qn, const void* mn, const void* bias, const void* residual,
@@ -577,52 +596,13 @@ int amq_gemm_res_norm_xfrag_f16(int bits, int mode, const void* x, const void* q
     if (!gamma || !xf) return fail(AMQ_EINVAL, "null pointer");
     if (N < 128 || (N % 128) != 0) return fail(AMQ_ESHAPE, "the normed rows are handed on in fragment order: N %% 128 == 0 (got N=%d)", N);
     amq::GemmNorm norm{gamma, eps, xf, false};
-    return gemm_route_impl(AMQ_GEMM_AUTO, bits, mode, x, qn, mn, bias, residual, y, M, N, K, group, x_stride, 0, workspace, workspace_bytes, stream, &norm);
+    return gemm_call(GEMM_ROUTE, AMQ_GEMM_AUTO, bits, mode, x, qn, mn, bias, residual, y, M, N, K, group, x_stride, 0, workspace, workspace_bytes, stream, &norm);
 }
-
-int amq_gemm_gated_fused_g(int route, int M, int N, int K, int use_workspace, int group) {
-    if (M < 1 || N < 16 || K < 128 || route < AMQ_GEMM_AUTO || route > AMQ_GEMM_DEQ) return 0;
-    const bool fine = group == 64 || group == 32;
-    const bool deq = route_is_deq(route, M, N, K, group);
-    const int sroute = fine && route == AMQ_GEMM_AUTO ? (int)AMQ_GEMM_TILED : route;
-    amq::GemmArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, M, N, K, 4, AMQ_MODE_HQQ, K, N, nullptr,
-                    use_workspace && !deq ? amq::gemm_pick_splits(M, N, K, sroute) : 1, nullptr, nullptr,
-                    use_workspace && deq ? (void*)&a : nullptr,       // (any non-null value: only tested for presence)
-                    amq::meta_pairs(group > 0 ? group : 128)};
-    return amq::gemm_gate_fused(a, route) ? 1 : 0;
-}
-int amq_gemm_gated_fused(int route, int M, int N, int K, int use_workspace) { return amq_gemm_gated_fused_g(route, M, N, K, use_workspace, 128); }
 
 int amq_gemm_gated_f16(int route, int bits, int mode, const void* x, const void* qn, const void* mn, const void* bias,
                        const void* gate, void* y, int M, int N, int K, int group, int x_stride, void* workspace,
                        size_t workspace_bytes, void* stream) {
-    if (route < AMQ_GEMM_AUTO || route > AMQ_GEMM_DEQ) return fail(AMQ_EINVAL, "unknown GEMM route %d", route);
-    if (int rc = check_shape(bits, N, K, group)) return rc;
-    if (int rc = check_mode(mode)) return rc;
-    mode = kernel_mode(mode);
-    if (int rc = check_strides("amq_gemm_gated_f16", M, K, x_stride, N, 0, 8, fewrow_rows_of(route))) return rc;
-    if (!x || !qn || !mn || !y || !gate) return fail(AMQ_EINVAL, "null pointer");
-    if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
-    if (N % 8) return fail(AMQ_ESHAPE, "the gated product needs N %% 8 == 0 (got %d)", N);
-    if (route == AMQ_GEMM_SKINNY && M > 64 && !((group == 64 || group == 32) && amq::gemm_fine_takes_skinny(M)))
-        return fail(AMQ_ESHAPE, "the few-row kernel takes at most 64 rows (got %d)", M);
-    if (int rc = check_fine_route(route, group, M, N, K, workspace)) return rc;
-    const size_t need = amq_gemm_route_workspace_bytes_g(route, M, N, K, group);
-    const bool deq = route_is_deq(route, M, N, K, group);
-    if (route == AMQ_GEMM_DEQ && !workspace) return fail(AMQ_EINVAL, "AMQ_GEMM_DEQ needs a workspace of N * K * 2 bytes for the fp16 weights");
-    const bool use_ws = need != 0 && workspace != nullptr;
-    if (use_ws && workspace_bytes < need)
-        return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    const bool split = use_ws && !deq;
-    const int sroute = (group == 64 || group == 32) && route == AMQ_GEMM_AUTO ? (int)AMQ_GEMM_TILED : route;
-    amq::GemmArgs a{x, qn, mn, bias, y, M, N, K, bits, mode, x_stride ? x_stride : K, N,
-                    split ? (float*)workspace : nullptr, split ? amq::gemm_pick_splits(M, N, K, sroute) : 1, nullptr, gate,
-                    use_ws && deq ? workspace : nullptr, amq::meta_pairs(group)};
-    if ((group == 64 || group == 32) && deq && !amq::gemm_f16w_ok(M, N, K, a.x_stride, a.y_stride))
-        return fail(AMQ_ESHAPE, "groups of %d (dequantize-once route): x_stride must be a multiple of 8 halves, N of 4, x and W must each span < 4 GiB", group);
-    if (gate == y && !amq::gemm_gate_fused(a, route))
-        return fail(AMQ_EINVAL, "gate may alias y only where the kernel applies it in its epilogue (amq_gemm_gated_fused)");
-    return check_hip(amq::launch_gemm(a, (hipStream_t)stream, route), "gemm_gated");
+    return gemm_call(GEMM_GATED, route, bits, mode, x, qn, mn, bias, gate, y, M, N, K, group, x_stride, 0, workspace, workspace_bytes, stream);
 }
 
 int amq_gemm_f16w_f16(const void* x, const void* w, const void* bias, const void* residual, const void* gate, void* y,
@@ -690,20 +670,10 @@ int amq_gemm_xfrag_grouped_form_f16(const amq_segment* segs, int nseg, const voi
     if (M < 1) return fail(AMQ_ESHAPE, "M must be >= 1 (got %d)", M);
     if ((M + 63) / 64 > 65535) return fail(AMQ_ESHAPE, "M=%d exceeds one launch", M);
     amq::GemvSeg gs[AMQ_MAX_SEGMENTS] = {};
-    for (int i = 0; i < nseg; ++i)          // (every segment's stride before any segment's pointers)
-        if (int rc = check_strides(seg_name("amq_gemm_xfrag_grouped_f16", i), M, K, 0, segs[i].N, segs[i].y_stride, 8, 0)) return rc;
-    for (int i = 0; i < nseg; ++i) {
-        const amq_segment& s = segs[i];
-        if (int rc = check_shape128(s.bits, s.N, K, group, "amq_gemm_xfrag_grouped_f16")) return rc;
-        if (int rc = check_mode(s.mode)) return rc;
-        if (!s.qweight_native || !s.meta_native || !s.y) return fail(AMQ_EINVAL, "segment %d: null pointer", i);
-        amq::GemvSeg& d = gs[i];
-        d.qweight = s.qweight_native; d.meta = s.meta_native; d.bias = s.bias; d.residual = s.residual; d.y = s.y;
-        d.N = s.N; d.bits = s.bits; d.mode = kernel_mode(s.mode);
-        d.y_stride = s.y_stride ? s.y_stride : s.N;
-    }
+    if (int rc = read_segments(SEG_XFRAG, segs, nseg, M, K, group, 0, gs)) return rc;
     return check_hip(amq::launch_gemm_xfrag_grouped(xf, M, K, gs, nseg, (hipStream_t)stream, form, blocks_per_wg), "gemm_xfrag_grouped");
 }
+
 
 #ifdef AMQ_AB_ROUTES     /* A/B routes: exported by libamq_hip_ab.so (make ab), declared in include/amq_hip_ab.h */
 int amq_gemv_qkv_attn_f16(const amq_segment* segs, const void* x, const void* gamma, float eps, int K, int group, void* kcache,

@@ -738,6 +738,47 @@ def _prep_x(x, K):
     return x2
 
 
+def _linear_operands(x, qn, mn, bits, N, K, bias, residual, out, fine, M=None):
+    """what the single-layer matmuls check before they call the library -> (x as [M, K] rows, M, the layer's group size, y [M, N]: ``out`` or new).
+    ``fine``: the call serves groups of 64 / 32 too; ``M`` given: x is already in fragment order (:func:`xfrag`)"""
+    _check_shape(bits, N, K)
+    group = _check_native(qn, mn, bits, N, K, fine=fine)
+    if M is None:
+        x = _prep_x(x, K)
+        M = x.shape[0]
+    else:
+        _need(x, torch.float16, "xf", _lib.load().amq_xfrag_bytes(M, K) // 2)
+    if bias is not None:
+        _need(bias, torch.float16, "bias", N)
+    if residual is not None:
+        _need(residual, torch.float16, "residual", M * N)
+    y = out if out is not None else torch.empty(M, N, dtype=torch.float16, device=x.device)
+    _need(y, torch.float16, "y", M * N)
+    return x, M, group, y
+
+
+def _segment_array(segments, M, K, fine):
+    """the amq_segment array of a grouped call over M rows and the group size its segments share (``fine``: the call serves groups of 64 / 32 too)"""
+    if not 1 <= len(segments) <= _lib.MAX_SEGMENTS:
+        raise ValueError(f"1..{_lib.MAX_SEGMENTS} segments")
+    arr = (Segment * len(segments))()
+    group = None
+    for i, s in enumerate(segments):
+        _check_shape(s["bits"], s["N"], K)
+        g = _check_native(s["qn"], s["mn"], s["bits"], s["N"], K, fine=fine)
+        if group is not None and g != group:
+            raise ValueError(f"segments of one launch must share their group size (got {group} and {g})")
+        group = g
+        _need(s["y"], torch.float16, "y", M * s["N"])
+        if s.get("bias") is not None:
+            _need(s["bias"], torch.float16, "bias", s["N"])
+        if s.get("residual") is not None:
+            _need(s["residual"], torch.float16, "residual", M * s["N"])
+        arr[i] = Segment(_lib.ptr(s["qn"]), _lib.ptr(s["mn"]), _lib.ptr(s.get("bias")), _lib.ptr(s.get("residual")),
+                         _lib.ptr(s["y"]), s["N"], s["bits"], s["mode"], 0)
+    return arr, group
+
+
 def gemv(x, qn, mn, bits, mode, N, K, bias=None, out=None, opts=None):
     """y = x . W^T for few rows (weight-streaming kernels).  ``opts``: a :class:`GemvOpts` (per-call A/B / math options)."""
     if opts is None:
@@ -747,14 +788,7 @@ def gemv(x, qn, mn, bits, mode, N, K, bias=None, out=None, opts=None):
         y = out if out is not None else torch.empty(x2.shape[0], N, dtype=torch.float16, device=x.device)
         gemv_grouped(x2, [dict(qn=qn, mn=mn, bits=bits, mode=mode, N=N, y=y, bias=bias)], K, opts=opts)
         return y.reshape(*x.shape[:-1], N)
-    _check_shape(bits, N, K)
-    group = _check_native(qn, mn, bits, N, K, fine=True)
-    x2 = _prep_x(x, K)
-    M = x2.shape[0]
-    if bias is not None:
-        _need(bias, torch.float16, "bias", N)
-    y = out if out is not None else torch.empty(M, N, dtype=torch.float16, device=x.device)
-    _need(y, torch.float16, "y", M * N)
+    x2, M, group, y = _linear_operands(x, qn, mn, bits, N, K, bias, None, out, True)
     _lib.check(_lib.load().amq_gemv_f16(bits, mode, _lib.ptr(x2), _lib.ptr(qn), _lib.ptr(mn), _lib.ptr(bias),
                                         _lib.ptr(y), M, N, K, group, 0, 0, _lib.current_stream()))
     return y.reshape(*x.shape[:-1], N)
@@ -840,22 +874,12 @@ def gemm(x, qn, mn, bits, mode, N, K, bias=None, out=None, residual=None, route=
     (the library path rounds the sum once).  ``gate`` (fp16 [M, N] contiguous, may be ``out``; not with ``residual``):
     y = fp16(silu(gate)) * fp16(x . W^T (+ bias)), i.e. :func:`silu_mul` of the two projections with this one as ``up``.
     ``route`` != GEMM_AUTO forces one hand-written kernel family (tests, tools)."""
-    _check_shape(bits, N, K)
-    group = _check_native(qn, mn, bits, N, K, fine=True)
-    x2 = _prep_x(x, K)
-    M = x2.shape[0]
-    if bias is not None:
-        _need(bias, torch.float16, "bias", N)
-    if residual is not None:
-        _need(residual, torch.float16, "residual", M * N)
+    x2, M, group, y = _linear_operands(x, qn, mn, bits, N, K, bias, residual, out, True)
+    lib = _lib.load()
     if gate is not None:
         if residual is not None:
             raise ValueError("gate and residual are exclusive")
         _need(gate, torch.float16, "gate", M * N)
-    y = out if out is not None else torch.empty(M, N, dtype=torch.float16, device=x.device)
-    _need(y, torch.float16, "y", M * N)
-    lib = _lib.load()
-    if gate is not None:
         ws, ws_bytes = _route_workspace(lib, x.device, route, M, N, K, group)
         if y.data_ptr() == gate.data_ptr() and not lib.amq_gemm_gated_fused_g(route, M, N, K, 1 if ws_bytes else 0, group):
             # the tiled kernel cannot apply the gate itself: in place on the gate needs the projection somewhere else first
@@ -893,17 +917,8 @@ def gemm_res_norm_xfrag(x, qn, mn, bits, mode, N, K, gamma, eps, bias=None, resi
     """:func:`gemm` (``residual`` fused, dense result rows) followed by :func:`rmsnorm_xfrag` of the result, as one call: returns (y, xf).  Where the
     GEMM runs split-K -- a short prompt's down_proj -- the sum over the splits and the norm are one launch (include/amq_hip.h:
     amq_gemm_res_norm_xfrag_f16); same bits as the two calls."""
-    _check_shape(bits, N, K)
-    group = _check_native(qn, mn, bits, N, K, fine=True)
-    x2 = _prep_x(x, K)
-    M = x2.shape[0]
-    if bias is not None:
-        _need(bias, torch.float16, "bias", N)
-    if residual is not None:
-        _need(residual, torch.float16, "residual", M * N)
+    x2, M, group, y = _linear_operands(x, qn, mn, bits, N, K, bias, residual, out, True)
     _need(gamma, torch.float16, "gamma", N)
-    y = out if out is not None else torch.empty(M, N, dtype=torch.float16, device=x.device)
-    _need(y, torch.float16, "y", M * N)
     lib = _lib.load()
     nbytes = lib.amq_xfrag_bytes(M, N)
     if nbytes == 0:
@@ -964,17 +979,9 @@ def rmsnorm_xfrag(x, gamma, eps, out=None):
 def gemm_xfrag(xf, M, qn, mn, bits, mode, N, K, bias=None, out=None, residual=None, gate=None):
     """y[M, N] = x . W^T with x given in fragment order (:func:`xfrag`); ``residual`` as in :func:`gemm`;
     ``gate`` (fp16 [M, N], may be ``out``): y = fp16(silu(gate)) * fp16(x . W^T (+ bias)), i.e. :func:`silu_mul` fused."""
-    _check_shape(bits, N, K)
-    _check_native(qn, mn, bits, N, K)
-    _need(xf, torch.float16, "xf", _lib.load().amq_xfrag_bytes(M, K) // 2)
-    if bias is not None:
-        _need(bias, torch.float16, "bias", N)
-    if residual is not None:
-        _need(residual, torch.float16, "residual", M * N)
+    xf, M, _, y = _linear_operands(xf, qn, mn, bits, N, K, bias, residual, out, False, M=M)
     if gate is not None:
         _need(gate, torch.float16, "gate", M * N)
-    y = out if out is not None else torch.empty(M, N, dtype=torch.float16, device=xf.device)
-    _need(y, torch.float16, "y", M * N)
     _lib.check(_lib.load().amq_gemm_xfrag_f16(bits, mode, _lib.ptr(xf), _lib.ptr(qn), _lib.ptr(mn), _lib.ptr(bias),
                                               _lib.ptr(gate), _lib.ptr(residual), _lib.ptr(y), M, N, K, GROUP, 0,
                                               _lib.current_stream()))
@@ -986,39 +993,21 @@ def gemm_xfrag_grouped(xf, M, segments, K, form=0, blocks_per_wg=0):
     segments: list of dicts {qn, mn, bits, mode, N, y, bias=None, residual=None} (y / residual: fp16 [M, N] contiguous).
     Per segment the result is :func:`gemm_xfrag`'s, bit for bit -- whatever the kernel form (``form``: _lib.FEWROW_AUTO / _TILE / _STREAM,
     ``blocks_per_wg`` with _STREAM: tests and A/B tools)."""
-    if not 1 <= len(segments) <= _lib.MAX_SEGMENTS:
-        raise ValueError(f"1..{_lib.MAX_SEGMENTS} segments")
+    arr, group = _segment_array(segments, M, K, False)
     lib = _lib.load()
     _need(xf, torch.float16, "xf", lib.amq_xfrag_bytes(M, K) // 2)
-    arr = (Segment * len(segments))()
-    for i, s in enumerate(segments):
-        _check_shape(s["bits"], s["N"], K)
-        _check_native(s["qn"], s["mn"], s["bits"], s["N"], K)
-        _need(s["y"], torch.float16, "y", M * s["N"])
-        if s.get("bias") is not None:
-            _need(s["bias"], torch.float16, "bias", s["N"])
-        if s.get("residual") is not None:
-            _need(s["residual"], torch.float16, "residual", M * s["N"])
-        arr[i] = Segment(_lib.ptr(s["qn"]), _lib.ptr(s["mn"]), _lib.ptr(s.get("bias")), _lib.ptr(s.get("residual")),
-                         _lib.ptr(s["y"]), s["N"], s["bits"], s["mode"], 0)
-    _lib.check(lib.amq_gemm_xfrag_grouped_form_f16(arr, len(segments), _lib.ptr(xf), M, K, GROUP, int(form), int(blocks_per_wg), _lib.current_stream()))
+    _lib.check(lib.amq_gemm_xfrag_grouped_form_f16(arr, len(segments), _lib.ptr(xf), M, K, group, int(form), int(blocks_per_wg), _lib.current_stream()))
 
 
 def linear(x, qn, mn, bits, mode, N, K, bias=None):
     """Reference-style dispatch: few rows -> gemv family, otherwise gemm."""
-    _check_shape(bits, N, K)
-    group = _check_native(qn, mn, bits, N, K, fine=True)
-    x2 = _prep_x(x, K)
-    M = x2.shape[0]
-    if bias is not None:
-        _need(bias, torch.float16, "bias", N)
+    x2, M, group, y = _linear_operands(x, qn, mn, bits, N, K, bias, None, None, True)
     if group != GROUP and M > 0:    # groups of 64 / 32: the GEMV kernel as far as it reaches (16 rows), then gemm (few-row kernel up to 256 rows, dequantize once + the fp16 GEMM beyond)
         if M <= gemv_max_rows(K):
-            return gemv(x, qn, mn, bits, mode, N, K, bias=bias)
-        return gemm(x, qn, mn, bits, mode, N, K, bias=bias)
+            return gemv(x, qn, mn, bits, mode, N, K, bias=bias, out=y)
+        return gemm(x, qn, mn, bits, mode, N, K, bias=bias, out=y)
     if M > 8:                       # tiled MFMA GEMM (split-K for few rows); amq_linear_f16 makes the same cut at 8 rows
-        return gemm(x, qn, mn, bits, mode, N, K, bias=bias)
-    y = torch.empty(M, N, dtype=torch.float16, device=x.device)
+        return gemm(x, qn, mn, bits, mode, N, K, bias=bias, out=y)
     if M == 0:
         return y.reshape(*x.shape[:-1], N)
     _lib.check(_lib.load().amq_linear_f16(bits, mode, _lib.ptr(x2), _lib.ptr(qn), _lib.ptr(mn), _lib.ptr(bias),
@@ -1105,23 +1094,7 @@ def gemv_grouped(x, segments, K, prologue=PRO_NONE, x2=None, gamma=None, eps=0.0
     as SiLU*mul over the plain gate).  Groups of 128; ``act`` takes no residual."""
     xx = _prep_x(x, K)
     M = xx.shape[0]
-    if not 1 <= len(segments) <= _lib.MAX_SEGMENTS:
-        raise ValueError(f"1..{_lib.MAX_SEGMENTS} segments")
-    arr = (Segment * len(segments))()
-    group = None
-    for i, s in enumerate(segments):
-        _check_shape(s["bits"], s["N"], K)
-        g = _check_native(s["qn"], s["mn"], s["bits"], s["N"], K, fine=True)
-        if group is not None and g != group:
-            raise ValueError(f"segments of one launch must share their group size (got {group} and {g})")
-        group = g
-        _need(s["y"], torch.float16, "y", M * s["N"])
-        if s.get("bias") is not None:
-            _need(s["bias"], torch.float16, "bias", s["N"])
-        if s.get("residual") is not None:
-            _need(s["residual"], torch.float16, "residual", M * s["N"])
-        arr[i] = Segment(_lib.ptr(s["qn"]), _lib.ptr(s["mn"]), _lib.ptr(s.get("bias")), _lib.ptr(s.get("residual")),
-                         _lib.ptr(s["y"]), s["N"], s["bits"], s["mode"], 0)
+    arr, group = _segment_array(segments, M, K, True)
     if prologue == PRO_RMSNORM:
         _need(gamma, torch.float16, "gamma", K)
     if x_activated and prologue != PRO_SILU_MUL:
@@ -1171,28 +1144,16 @@ def gemv_grouped_sums(x, segments, K, gamma=None, eps=0.0, sums_in=None, sums_ou
     include/amq_hip.h amq_gemv_grouped_sums_f16.  No pass over x for the statistic, no separate rmsnorm launch."""
     xx = _prep_x(x, K)
     M = xx.shape[0]
-    if not 1 <= len(segments) <= _lib.MAX_SEGMENTS:
-        raise ValueError(f"1..{_lib.MAX_SEGMENTS} segments")
     if any(s.get("act") for s in segments):
         raise ValueError("an activated segment (act) is a gate, not a hidden state: the partial-sum launches take none (gemv_grouped)")
-    arr = (Segment * len(segments))()
-    for i, s in enumerate(segments):
-        _check_shape(s["bits"], s["N"], K)
-        _check_native(s["qn"], s["mn"], s["bits"], s["N"], K)
-        _need(s["y"], torch.float16, "y", M * s["N"])
-        if s.get("bias") is not None:
-            _need(s["bias"], torch.float16, "bias", s["N"])
-        if s.get("residual") is not None:
-            _need(s["residual"], torch.float16, "residual", M * s["N"])
-        arr[i] = Segment(_lib.ptr(s["qn"]), _lib.ptr(s["mn"]), _lib.ptr(s.get("bias")), _lib.ptr(s.get("residual")),
-                         _lib.ptr(s["y"]), s["N"], s["bits"], s["mode"], 0)
+    arr, group = _segment_array(segments, M, K, False)
     if sums_in is not None:
         _need(gamma, torch.float16, "gamma", K)
         _need(sums_in, torch.float32, "sums_in", M * (K // 16))
     if sums_out is not None:
         _need(sums_out, torch.float32, "sums_out", M * (segments[0]["N"] // 16))
     _lib.check(_lib.load().amq_gemv_grouped_sums_f16(arr, len(segments), _lib.ptr(xx), _lib.ptr(gamma) if sums_in is not None else None,
-                                                     ctypes.c_float(eps), _lib.ptr(sums_in), _lib.ptr(sums_out), M, K, GROUP, _lib.current_stream()))
+                                                     ctypes.c_float(eps), _lib.ptr(sums_in), _lib.ptr(sums_out), M, K, group, _lib.current_stream()))
 
 
 def rmsnorm(x, gamma, eps, out=None):
