@@ -66,6 +66,15 @@ class QkNorm(ctypes.Structure):
 
 _qkn = ctypes.POINTER(QkNorm)
 
+
+class OwqPart(ctypes.Structure):
+    """mirror of `amq_owq_part` (include/amq_hip.h): one sibling linear of an amq_owq_stage_f16 launch"""
+    _fields_ = [("perm", _vp), ("out_ids", _vp), ("W_out", _vp), ("xg", _vp), ("y", _vp), ("residual", _vp), ("N", _i), ("n_out", _i), ("Kp", _i)]
+
+
+OWQ_ACT_NONE, OWQ_ACT_RMSNORM, OWQ_ACT_SILU_MUL = 0, 1, 2      # include/amq_hip.h AMQ_OWQ_ACT_*
+OWQ_MAX_PARTS = 3
+
 # name -> (restype, argtypes); must list every symbol include/amq_hip.h declares
 SIGNATURES = {
     "amq_version": (_i, []),
@@ -93,6 +102,8 @@ SIGNATURES = {
     "amq_owq_quantize_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amq_owq_gather_f16": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     "amq_owq_outlier_add_f16": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
+    # the token step's stage of OWQ layers: (x, R, K, act, gamma, eps, x2, parts, n_parts, stream)
+    "amq_owq_stage_f16": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, ctypes.POINTER(OwqPart), _i, _vp]),
     # AWQ: round to nearest under a column scale / clip bounds -> Format A and / or the dense fake-quantized matrix; the clip search (info = {int32 nonfinite})
     "amq_awq_quantize_workspace_bytes": (_sz, [_i, _i, _i]),
     "amq_awq_quantize_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -291,6 +291,34 @@ int amq_owq_outlier_add_f16(const void* x, int M, int K, const void* out_ids, in
     return check_hip(amq::launch_owq_outlier_add(x, M, K, out_ids, n_out, W_out, y, N, (hipStream_t)stream), "owq_outlier_add");
 }
 
+int amq_owq_stage_f16(const void* x, int R, int K, int act, const void* gamma, float eps, const void* x2, const amq_owq_part* parts, int n_parts,
+                      void* stream) {
+    static_assert(AMQ_OWQ_MAX_PARTS == amq::OWQ_STAGE_PARTS, "parts");
+    if (!x || !parts || (act == AMQ_OWQ_ACT_RMSNORM && !gamma) || (act == AMQ_OWQ_ACT_SILU_MUL && !x2)) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)x & 15) != 0 || (act == AMQ_OWQ_ACT_RMSNORM && ((uintptr_t)gamma & 15) != 0) ||
+        (act == AMQ_OWQ_ACT_SILU_MUL && ((uintptr_t)x2 & 15) != 0))
+        return fail(AMQ_EINVAL, "x, x2 and gamma must be 16-byte aligned");
+    if (act != AMQ_OWQ_ACT_NONE && act != AMQ_OWQ_ACT_RMSNORM && act != AMQ_OWQ_ACT_SILU_MUL) return fail(AMQ_EINVAL, "unknown activation %d", act);
+    if (n_parts < 1 || n_parts > AMQ_OWQ_MAX_PARTS) return fail(AMQ_ESHAPE, "n_parts must be 1..%d (got %d)", AMQ_OWQ_MAX_PARTS, n_parts);
+    if (R < 1 || R > amq::OWQ_STAGE_ROWS) return fail(AMQ_ESHAPE, "R must be 1..%d (got %d)", (int)amq::OWQ_STAGE_ROWS, R);
+    if (K <= 0 || (K % 128) != 0) return fail(AMQ_ESHAPE, "need K %% 128 == 0 (got K=%d)", K);
+    amq::OwqStageLaunchPart lp[AMQ_OWQ_MAX_PARTS];
+    for (int i = 0; i < n_parts; ++i) {
+        const amq_owq_part& p = parts[i];
+        if (!p.xg || (p.n_out != 0 && (!p.perm || !p.out_ids || !p.W_out || !p.y))) return fail(AMQ_EINVAL, "part %d: null pointer", i);
+        if (((uintptr_t)p.xg & 3) != 0 ||
+            (p.n_out != 0 && (((uintptr_t)p.perm & 3) != 0 || ((uintptr_t)p.out_ids & 3) != 0 || ((uintptr_t)p.W_out & 1) != 0 ||
+                              ((uintptr_t)p.y & 1) != 0 || ((uintptr_t)p.residual & 1) != 0)))
+            return fail(AMQ_EINVAL, "part %d: xg, perm and out_ids must be 4-byte aligned, W_out, y and residual 2-byte aligned", i);
+        if (p.n_out < 0 || (p.n_out % 2) != 0 || p.n_out >= K)
+            return fail(AMQ_ESHAPE, "part %d: n_out must be even and in 0 .. K - 2 (got n_out=%d, K=%d)", i, p.n_out, K);
+        if (p.n_out != 0 && (p.Kp <= 0 || (p.Kp % 128) != 0)) return fail(AMQ_ESHAPE, "part %d: need Kp %% 128 == 0 (got Kp=%d)", i, p.Kp);
+        if (p.n_out != 0 && p.N <= 0) return fail(AMQ_ESHAPE, "part %d: need N > 0 (got N=%d)", i, p.N);
+        lp[i] = {p.perm, p.out_ids, p.W_out, p.xg, p.y, p.residual, p.N, p.n_out, p.Kp};
+    }
+    return check_hip(amq::launch_owq_stage(x, R, K, act, gamma, eps, x2, lp, n_parts, (hipStream_t)stream), "owq_stage");
+}
+
 size_t amq_awq_quantize_workspace_bytes(int N, int K, int group) {
     if (check_quantize_shape(QUANT_AWQ, 4, N, K, group) != AMQ_OK) return 0;
     return amq::awq_quantize_workspace_bytes(N, K);

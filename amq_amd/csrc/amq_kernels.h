@@ -383,6 +383,16 @@ hipError_t launch_owq_quantize(const void* W, const void* U, int N, int K, int n
                                void* W_out, void* choice, void* row_loss, void* info, void* workspace, hipStream_t st);
 hipError_t launch_owq_gather(const void* x, int M, int K, const void* perm, int Kp, void* xg, hipStream_t st);
 hipError_t launch_owq_outlier_add(const void* x, int M, int K, const void* out_ids, int n_out, const void* W_out, void* y, int N, hipStream_t st);
+// the token step's stage in front of the packed GEMVs of OWQ layers (amq_owq_step.hip): one launch per sibling set, the parts as amq_owq_part
+enum { OWQ_STAGE_PARTS = 3, OWQ_STAGE_ROWS = 8 };
+struct OwqStageLaunchPart {
+    const void *perm, *out_ids, *W_out;
+    void *xg, *y;
+    const void* residual;
+    int N, n_out, Kp;
+};
+hipError_t launch_owq_stage(const void* x, int R, int K, int act, const void* gamma, float eps, const void* x2, const OwqStageLaunchPart* parts,
+                            int n_parts, hipStream_t st);
 
 // AWQ (amq_awq.hip).  quantize: 8 columns per thread, 256 threads per workgroup, round-to-nearest per group to byte codes, then the shared pack
 // launch; workspace: int32 nonfinite[N * K / 512] (one per wave), uint8 codes[N][K].  clip: one wave per (8 rows, one group): the rows' 10 clip

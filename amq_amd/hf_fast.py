@@ -162,6 +162,7 @@ def _same_weights(r, model):
     models, amq_speed_benchmark.py:231-251 -- means a new runner)"""
     layer = model.model.layers[0]
     q = layer.self_attn.q_proj
+    q = getattr(q, "inner", q)                  # (an OWQ layer: its packed inner layer owns the buffer the runner shares)
     same = r.blocks[0]["self_attn.q_proj"].qn.data_ptr() == q.qweight.data_ptr() and r.nb == len(model.model.layers)
     if same and r.qk_norm:                      # Qwen3: the per-head norm weights are the modules' own tensors too (fp16 ones: no copy was made)
         for key, m in (("qn", getattr(layer.self_attn, "q_norm", None)), ("kn", getattr(layer.self_attn, "k_norm", None))):

@@ -32,17 +32,25 @@ ROPE_THETA = 10000.0
 
 
 class _Lin:
-    """native weights of one linear (+ its fp16 bias: Qwen2's q / k / v projections carry one)"""
-    __slots__ = ("qn", "mn", "bits", "mode", "N", "K", "bias")
+    """native weights of one linear (+ its fp16 bias: Qwen2's q / k / v projections carry one).  An OWQ layer (HIPOWQLinear) also carries
+    ``perm`` int32 [Kp], ``out_ids`` int32 [n_out] and ``W_out`` fp16 [N, n_out]: K is then the width of its input, ``Kp`` that of the packed
+    layer (qn / mn are [N, Kp]); every other layer has Kp == K and the three fields None."""
+    __slots__ = ("qn", "mn", "bits", "mode", "N", "K", "bias", "perm", "out_ids", "W_out", "Kp")
 
-    def __init__(self, qn, mn, bits, mode, N, K, bias=None):
+    def __init__(self, qn, mn, bits, mode, N, K, bias=None, perm=None, out_ids=None, W_out=None, Kp=None):
         self.qn, self.mn, self.bits, self.mode, self.N, self.K, self.bias = qn, mn, bits, mode, N, K, bias
+        self.perm, self.out_ids, self.W_out, self.Kp = perm, out_ids, W_out, K if Kp is None else Kp
+
+    @property
+    def owq(self):
+        return self.W_out is not None
 
     def seg(self, y, residual=None, act=False):
         return dict(qn=self.qn, mn=self.mn, bits=self.bits, mode=self.mode, N=self.N, y=y, residual=residual, bias=self.bias, act=act)
 
     def nbytes(self):
-        return self.qn.numel() * 4 + self.mn.numel() * 2 + (0 if self.bias is None else self.bias.numel() * 2)
+        own = 0 if self.W_out is None else self.W_out.numel() * 2 + self.perm.numel() * 4 + self.out_ids.numel() * 4
+        return self.qn.numel() * 4 + self.mn.numel() * 2 + (0 if self.bias is None else self.bias.numel() * 2) + own
 
 
 def _synthetic_linear(n, k, bits, gen, device, group=128):
@@ -137,6 +145,8 @@ class StepPlan(NamedTuple):
     #                     of them) | NORM_FROM_SUMS (from the partial sums of squares the o_proj / down_proj launch left: ops.gemv_grouped_sums)
     down: str           # down_proj: DOWN_FUSED (the GEMV with the SiLU*mul prologue) | silu_mul and DOWN_GEMV (the plain GEMV) | DOWN_GEMV_SUMS (the
     #                     GEMV leaving sums) | DOWN_GEMM (the few-row MFMA kernel: the rows do not fit the GEMV's LDS stage even in two K phases)
+    staged: bool = False    # a model with OWQ layers: every sibling set runs ops.owq_stage (its norm / SiLU*mul, the gathers, the outlier partials) and
+    #                         then one plain GEMV per sibling (QuantLlama._step_staged); first_norm / norm / down are then not looked at
 
     @property
     def block_norm(self):
@@ -220,6 +230,7 @@ class QuantLlama:
     # generate loop needs the last row only): final norm + one fp16 GEMM over the prompt rows, inside the captured prompt graph (hf_fast.py sets it)
     all_logits = False
     fine = False                # any layer with groups of 64 / 32 (set by __init__)
+    owq = False                 # any OWQ layer (set by __init__): the staged token step, the plain prompt passes
 
     @classmethod
     def rows_attention_grouped(cls, n_heads, n_kv_heads, max_seq):
@@ -349,14 +360,22 @@ class QuantLlama:
         # layers with groups of 64 / 32 (HQQ's default group_size is 64): the decode step is the same five launches (amq_gemv_grouped_f16 takes the
         # group size); the prompt pass leaves the fragment-ordered few-row kernels alone (they read one (scale, zero) pair per tile) and runs
         # dequantize-once + the fp16 GEMM per linear; the A/B step forms are not offered
-        self.fine = any(blk[n].mn.numel() != ops.native_sizes(blk[n].bits, blk[n].N, blk[n].K)[1] // 2 for blk in self.blocks for n in config["linear"])
+        self.fine = any(blk[n].mn.numel() != ops.native_sizes(blk[n].bits, blk[n].N, blk[n].Kp)[1] // 2 for blk in self.blocks for n in config["linear"])
         if self.fine and engine:
             raise ValueError("the decode engine serves groups of 128")
+        # OWQ layers (from_hf over HIPOWQLinear modules): the token step runs the staged plan (_step_staged), the prompt passes their plain forms
+        self.owq = any(blk[n].owq for blk in self.blocks for n in config["linear"])
+        if self.owq:
+            if engine or self.FUSE_QKV_ATTN:
+                raise ValueError(("the decode engine" if engine else "the fused q/k/v + attention launch") + " does not serve a model with OWQ layers: "
+                                 "their gather and outlier columns run as a stage launch in front of each packed GEMV (the five-launch step's staged plan)")
+            if self.fine:
+                raise ValueError("a model with OWQ layers runs the staged token step, which serves groups of 128 only")
         # q/k/v and gate/up run as segments of ONE launch, which takes one group size: refuse a model that mixes them inside a sibling set here, at
         # build time (amq_gemv_grouped_f16 would refuse it at the first decode step; patching._same_group keeps such siblings apart on the HF side)
         for bi, blk in enumerate(self.blocks):
             for sibs in (("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), ("mlp.gate_proj", "mlp.up_proj")):
-                pairs = {blk[n].mn.numel() * 128 // (2 * blk[n].N * blk[n].K) for n in sibs}      # (scale, zero) pairs per 128 columns: 1 / 2 / 4
+                pairs = {blk[n].mn.numel() * 128 // (2 * blk[n].N * blk[n].Kp) for n in sibs}      # (scale, zero) pairs per 128 columns: 1 / 2 / 4
                 if len(pairs) != 1:
                     raise ValueError(f"block {bi}: {', '.join(sibs)} mix group sizes ({sorted(128 // p for p in pairs)}); the runner issues them as "
                                      "one grouped launch, which needs one group size per sibling set")
@@ -378,6 +397,11 @@ class QuantLlama:
         self.plan = step_plan(R, self.H, self.I, self.fine, ops.gemv_max_rows(self.H, plain=True), ops.gemv_max_rows(self.I, plain=not self.fine),
                               ops.gemv_max_rows(self.I, plain=not self.fine, norm=False), self.NORM_SUMS, self.NORM_FUSED_ROWS, self.DOWN_FUSED_ROWS,
                               rows_q=None if self.qd == self.H else ops.gemv_max_rows(self.qd, plain=True))
+        self._staged = None
+        if self.owq:
+            # no prologue, no partial sums, no activated gate: the stage launch forms the activation; a model without OWQ layers keeps the plan above
+            self.plan = StepPlan(NORM_LAUNCH, NORM_LAUNCH, DOWN_GEMV, staged=True)
+            self._staged = self._build_staged()
         # the sums of squares of self.x's rows, per 16 columns: written by the launch that produced the rows, read by the one that normalises them
         self.ss = torch.zeros(R, self.H // 16, dtype=torch.float32, device=dev) if self.plan.norm == NORM_FROM_SUMS else None
         # the two A/B step forms rotate inside launches of their own, which carry no per-head norm and take q / o of hidden_size: not for Qwen3
@@ -461,8 +485,8 @@ class QuantLlama:
         for li, layer in enumerate(model.model.layers):
             cls._check_qk_norm(layer.self_attn, mt, float(hf.get("rms_norm_eps", 1e-5)), li)
         attn0 = model.model.layers[0].self_attn
-        from .quant_linear import HIPQuantLinear
-        if not isinstance(getattr(attn0, "q_proj", None), HIPQuantLinear):
+        from .quant_linear import HIPOWQLinear, HIPQuantLinear
+        if not isinstance(getattr(attn0, "q_proj", None), (HIPQuantLinear, HIPOWQLinear)):
             raise ValueError("from_hf: the decoder linears are not HIPQuantLinear modules: run prepare_for_inference(model, backend='hip') first")
         rp = hf.get("rope_parameters") or {}
         if hf.get("rope_theta") is None:
@@ -516,7 +540,7 @@ class QuantLlama:
         norm weights (no copies) and the rotary embedding's own frequencies (rope_scaling: Llama-3.1); it is to the swapped model what the
         reference's ``use_ft`` monkeypatch is to its HF model (kernel/monkeypatch/ftllama_modeling.py): the same weights behind a static-cache,
         fused token step.  Needs fp16 weights on one GPU, head_dim 128, SiLU."""
-        from .quant_linear import HIPQuantLinear
+        from .quant_linear import HIPOWQLinear, HIPQuantLinear
         cfg, rope = cls.check_hf(model, max_seq)
         layers = model.model.layers
         pre, arch_linear = {}, {name: [] for name in cfg["linear"]}
@@ -526,6 +550,19 @@ class QuantLlama:
             for name in cfg["linear"]:
                 parent, attr = name.split(".")
                 m = getattr(getattr(layer, parent), attr)
+                if isinstance(m, HIPOWQLinear) and m.inner.qweight.is_cuda:
+                    # an OWQ layer: the packed inner layer [N, Kp] (it holds the bias) and the module's own perm / out_ids / W_out, all shared
+                    i = m.inner
+                    if i.is_bf16:
+                        raise ValueError(f"model.layers.{b}.{name}: a bfloat16 module -- the decode runner is fp16")
+                    if m.perm.dtype is not torch.int32 or m.out_ids.dtype is not torch.int32 or m.W_out.dtype is not torch.float16 or \
+                            tuple(m.W_out.shape) != (m.outfeatures, m.n_out) or m.perm.numel() != i.infeatures or m.out_ids.numel() != m.n_out:
+                        raise ValueError(f"model.layers.{b}.{name}: the OWQ layer's perm / out_ids / W_out do not have the shapes of its packed layer")
+                    dev = dev or i.qweight.device
+                    pre[(b, name)] = _Lin(i.qweight, i.meta, i.bits, i.mode, m.outfeatures, m.infeatures, None if i.bias is None else f16(i.bias),
+                                          perm=m.perm.contiguous(), out_ids=m.out_ids.contiguous(), W_out=m.W_out.contiguous(), Kp=i.infeatures)
+                    arch_linear[name].append(i.bits)
+                    continue
                 if not isinstance(m, HIPQuantLinear) or not m.qweight.is_cuda:
                     raise ValueError(f"model.layers.{b}.{name}: expected a HIPQuantLinear on the GPU (run prepare_for_inference first)")
                 if m.is_bf16:
@@ -556,6 +593,8 @@ class QuantLlama:
         """one token: reads self.x (= embed[self.token], kept in step by set_token / the step's own tail) and self.pos
         (device), writes self.logits, self.token, self.pos and the next step's self.x.  The launches are self.plan's."""
         H, plan = self.H, self.plan
+        if plan.staged:
+            return self._step_staged(sampled)
         if self.engine is not None:
             self.engine.step()
             ops.gemv_f16w(self.x.reshape(-1), self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
@@ -598,6 +637,68 @@ class QuantLlama:
                 d = blk["mlp.down_proj"]
                 ops.gemm(ops.silu_mul(self.gate, self.up, out=self.gate), d.qn, d.mn, d.bits, d.mode, d.N, d.K, bias=d.bias, residual=self.x, out=self.x)
             first = plan.block_norm
+        ops.gemv_f16w(self.x.reshape(-1) if self.R == 1 else self.x, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
+        self._tail(sampled)
+
+    # ------------------------------------------------- the staged plan (OWQ layers)
+    def _build_staged(self):
+        """The staged plan of a model with OWQ layers, built once: per block the four sibling sets (q/k/v behind ln1, o_proj, gate/up behind ln2,
+        down_proj behind SiLU*mul) as (x, activation, gamma, x2, the ops.owq_stage_parts array or None, [(linear, its GEMV's x, K, y, residual)]).
+        The stage launch of a set leaves every OWQ sibling's gathered rows in a buffer of its own and its outlier partial (+ the set's residual)
+        in the sibling's output; the packed GEMV then reads the partial as its residual.  Plain siblings of a set read the staged activation
+        itself (one shared part), with the set's residual.  A plain o_proj needs no stage: its activation is the attention output as it lies.
+        The buffers are the runner's, allocated here."""
+        R, dev = self.R, self.dev
+        f16 = dict(dtype=torch.float16, device=dev)
+        widths = {"self_attn.q_proj": self.H, "self_attn.k_proj": self.H, "self_attn.v_proj": self.H, "self_attn.o_proj": self.qd,
+                  "mlp.gate_proj": self.H, "mlp.up_proj": self.H, "mlp.down_proj": self.I}
+        self.xg = {n: torch.zeros(R * k, **f16) for n, k in widths.items()}       # per linear: [R, Kp] of the block at hand
+        self.act = torch.zeros(R, self.I, **f16)                                    # SiLU*mul rows for a plain down_proj
+        sets = []
+        for blk in self.blocks:
+            per = []
+            for x, act, gamma, x2, plain_buf, names, outs, residual in (
+                    (self.x, ops.OWQ_ACT_RMSNORM, blk["ln1"], None, self.xn, ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"),
+                     (self.q, self.k, self.v), None),
+                    (self.att, ops.OWQ_ACT_NONE, None, None, self.att, ("self_attn.o_proj",), (self.x,), self.x),
+                    (self.x, ops.OWQ_ACT_RMSNORM, blk["ln2"], None, self.xn, ("mlp.gate_proj", "mlp.up_proj"), (self.gate, self.up), None),
+                    (self.gate, ops.OWQ_ACT_SILU_MUL, None, self.up, self.act, ("mlp.down_proj",), (self.x,), self.x)):
+                K = x.shape[1]
+                parts, gemvs, shared = [], [], False
+                for n, y in zip(names, outs):
+                    l = blk[n]
+                    if l.owq:
+                        xg = self.xg[n][:R * l.Kp].view(R, l.Kp)
+                        parts.append(dict(perm=l.perm, out_ids=l.out_ids, W_out=l.W_out, xg=xg, y=y, residual=residual))
+                        gemvs.append((l, xg, l.Kp, y, y))
+                    else:
+                        if not shared and plain_buf is not x:
+                            parts.append(dict(xg=plain_buf))
+                        shared = True
+                        gemvs.append((l, plain_buf, K, y, residual))
+                per.append((x, act, gamma, x2, ops.owq_stage_parts(parts, R, K) if parts else None, gemvs))
+            sets.append(per)
+        return sets
+
+    def _step_staged(self, sampled):
+        """the token step of a model with OWQ layers: per sibling set one stage launch and one plain GEMV per sibling (12 launches a block where
+        every linear has outliers); attention, lm_head and tail as in every step"""
+        for blk, per in zip(self.blocks, self._staged):
+            for i, (x, act, gamma, x2, arr, gemvs) in enumerate(per):
+                if arr is not None:
+                    ops.owq_stage_launch(x, self.R, x.shape[1], act, gamma, self.eps, x2, arr)
+                for l, xin, K, y, residual in gemvs:
+                    if self.R <= ops.gemv_max_rows(K, plain=True, norm=False):
+                        ops.gemv_grouped(xin, [l.seg(y, residual=residual)], K)
+                    else:
+                        ops.gemm(xin, l.qn, l.mn, l.bits, l.mode, l.N, K, bias=l.bias, residual=residual, out=y)
+                if i == 0:
+                    if self.lookup:
+                        ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv,
+                                             grouped=self.rows_attention_grouped(self.nh, self.nkv, self.max_seq), **self._qkn(blk))
+                    else:
+                        ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
+                                        cur=self.rope_cur, **self._qkn(blk))
         ops.gemv_f16w(self.x.reshape(-1) if self.R == 1 else self.x, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
         self._tail(sampled)
 
@@ -1146,6 +1247,8 @@ class QuantLlama:
         x = self.embed.index_select(0, ids)                        # [S, H]; the residual stream, updated in place
 
         def lin(l, inp, residual=None):
+            if l.owq:
+                return self._rows_owq(l, inp, residual)
             if S > 8:
                 return ops.gemm(inp, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias, residual=residual, out=residual)
             y = ops.linear(inp, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias)
@@ -1163,8 +1266,8 @@ class QuantLlama:
         # up to 256 rows the projections that read a normed / attention activation take it in fragment order (written
         # that way by the producing launch): 1.2-1.6x faster few-row GEMMs; down_proj (K = 11008: the
         # per-workgroup x stream is what bounds that kernel) and longer prompts stay on the tiled kernel
-        frag = self.FRAG_ROWS[0] < S <= self.FRAG_ROWS[1] and not self.fine
-        h_next = None                                # the next block's normed input, left behind by this block's down_proj (its split-K reduce carries the norm)
+        frag = self.FRAG_ROWS[0] < S <= self.FRAG_ROWS[1] and not self.fine and not self.owq     # (an OWQ model: the plain, unfused form)
+        h_next = None                               # the next block's normed input, left behind by this block's down_proj (its split-K reduce carries the norm)
         for bi, blk in enumerate(self.blocks):
             if frag:
                 h = h_next if h_next is not None else ops.rmsnorm_xfrag(x, blk["ln1"], self.eps)
@@ -1184,7 +1287,9 @@ class QuantLlama:
                 x = lin(blk["self_attn.o_proj"], self._prefill_attention(q, blk, S, start_pos), residual=x)
                 h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
                 g = lin(blk["mlp.gate_proj"], h2)
-                if S > 8:
+                if blk["mlp.up_proj"].owq:
+                    act = self._rows_up_gated(blk["mlp.up_proj"], h2, g)
+                elif S > 8:
                     u = blk["mlp.up_proj"]                                         # silu(gate) * up in up_proj's epilogue
                     act = ops.gemm(h2, u.qn, u.mn, u.bits, u.mode, u.N, u.K, bias=u.bias, gate=g, out=g)
                 else:
@@ -1199,11 +1304,22 @@ class QuantLlama:
 
     def _rows_linear(self, l, inp, residual=None):
         # y = inp . W^T (+ residual, in place) for many rows
+        if l.owq:
+            return self._rows_owq(l, inp, residual)
         return ops.gemm(inp, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias, residual=residual, out=residual)
 
     def _rows_up_gated(self, l, inp, gate):
         # silu(gate) * (inp . W^T), in place on gate: the LlamaMLP product formed in up_proj's epilogue
+        if l.owq:                               # (the outlier columns come after the packed product: no gate epilogue; plain, then silu_mul)
+            return ops.silu_mul(gate, self._rows_owq(l, inp), out=gate)
         return ops.gemm(inp, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias, gate=gate, out=gate)
+
+    @staticmethod
+    def _rows_owq(l, inp, residual=None):
+        """an OWQ linear over any number of rows, HIPOWQLinear.forward's three steps: gather, the packed matmul over the gathered rows (the
+        residual in its epilogue, in place, where the caller passes one), outlier add"""
+        y = ops.gemm(ops.owq_gather(inp, l.perm), l.qn, l.mn, l.bits, l.mode, l.N, l.Kp, bias=l.bias, residual=residual, out=residual)
+        return ops.owq_outlier_add(inp, l.out_ids, l.W_out, y)
 
     def prefill_batch(self, ids):
         """ids: int64 [B, S].  The many-row pass over B prompts at once (B*S rows through every linear): what the reference
@@ -1255,6 +1371,8 @@ class QuantLlama:
         positions = torch.arange(S, device=self.dev)
 
         def lin(l, inp):
+            if l.owq:
+                return self._rows_owq(l, inp)
             return ops.linear(inp, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias)
 
         for blk in self.blocks:

@@ -91,6 +91,9 @@ class ModuleWalkLlama(nn.Module):
         if getattr(runner, "qk_norm", False):
             raise ValueError("the module walk reaches attention through the extension's amq_attn_decode_cur_f16 binding and the fused layer "
                              "modules, which carry no per-head q / k norm: a qk_norm (Qwen3) runner is served by QuantLlama's own step")
+        if getattr(runner, "owq", False):
+            raise ValueError("the module walk rebuilds plain HIPQuantLinear modules over the runner's weights: a runner with OWQ layers is served by "
+                             "QuantLlama's own staged step (the swapped HF model itself is the module form of such a model)")
         self.r = runner
         self.layers = nn.ModuleList(_Block(blk, runner) for blk in runner.blocks)
         self.graph = None

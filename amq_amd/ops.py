@@ -533,6 +533,63 @@ def owq_outlier_add(x, out_ids, W_out, y):
     return y
 
 
+OWQ_ACT_NONE, OWQ_ACT_RMSNORM, OWQ_ACT_SILU_MUL = _lib.OWQ_ACT_NONE, _lib.OWQ_ACT_RMSNORM, _lib.OWQ_ACT_SILU_MUL
+OWQ_STAGE_ROWS = 8
+
+
+def owq_stage_parts(parts, R, K):
+    """the host array of ``owq_stage_launch`` from a list of dicts, one per sibling linear reading the staged activation: an OWQ linear
+    {perm int32 [Kp], out_ids int32 [n_out], W_out fp16 [N, n_out], xg fp16 [R, Kp], y fp16 [R, N], residual=None | fp16 [R, N] (may be y)}, a
+    plain sibling {xg fp16 [R, K]} alone.  Every shape is checked here: the kernel trusts them."""
+    if not 1 <= len(parts) <= _lib.OWQ_MAX_PARTS:
+        raise ValueError(f"owq_stage: 1..{_lib.OWQ_MAX_PARTS} parts a launch (got {len(parts)})")
+    arr = (_lib.OwqPart * len(parts))()
+    for i, p in enumerate(parts):
+        W_out = p.get("W_out")
+        if W_out is None:
+            _need(p["xg"], torch.float16, f"part {i}: xg", R * K)
+            arr[i] = _lib.OwqPart(None, None, None, _lib.ptr(p["xg"]), None, None, 0, 0, K)
+            continue
+        N, n_out = W_out.shape
+        Kp = p["perm"].numel()
+        _need(W_out, torch.float16, f"part {i}: W_out")
+        _need(p["perm"], torch.int32, f"part {i}: perm")
+        _need(p["out_ids"], torch.int32, f"part {i}: out_ids", n_out)
+        _need(p["xg"], torch.float16, f"part {i}: xg", R * Kp)
+        _need(p["y"], torch.float16, f"part {i}: y", R * N)
+        res = p.get("residual")
+        if res is not None:
+            _need(res, torch.float16, f"part {i}: residual", R * N)
+        arr[i] = _lib.OwqPart(_lib.ptr(p["perm"]), _lib.ptr(p["out_ids"]), _lib.ptr(W_out), _lib.ptr(p["xg"]), _lib.ptr(p["y"]), _lib.ptr(res),
+                              N, n_out, Kp)
+    return arr
+
+
+def owq_stage_launch(x, R, K, act, gamma, eps, x2, arr):
+    """the bare entry point over caller-owned buffers and an ``owq_stage_parts`` array (one launch on the current stream; capturable)"""
+    _lib.check(_lib.load().amq_owq_stage_f16(_lib.ptr(x), R, K, act, _lib.ptr(gamma), ctypes.c_float(eps), _lib.ptr(x2), arr, len(arr),
+                                             _lib.current_stream()))
+
+
+def owq_stage(x, parts, act=OWQ_ACT_NONE, gamma=None, eps=0.0, x2=None):
+    """The token step's stage of OWQ layers (include/amq_hip.h amq_owq_stage_f16): for R = 1 .. 8 rows x [R, K] and a = x (OWQ_ACT_NONE),
+    rmsnorm(x, gamma, eps) (OWQ_ACT_RMSNORM) or silu_mul(x, x2) (OWQ_ACT_SILU_MUL), ONE launch leaves per part xg = owq_gather(a, perm) and
+    y = the outlier product of a (+ residual), bit for bit what those ops give in composition; ``gemv_grouped(xg, [seg(y, residual=y)], Kp)``
+    completes the layer.  ``parts``: see :func:`owq_stage_parts`."""
+    x = _prep_x(x, x.shape[-1])
+    R, K = x.shape
+    if not 1 <= R <= OWQ_STAGE_ROWS:
+        raise ValueError(f"owq_stage: 1..{OWQ_STAGE_ROWS} rows (got {R})")
+    if act == OWQ_ACT_RMSNORM:
+        _need(gamma, torch.float16, "gamma", K)
+    elif act == OWQ_ACT_SILU_MUL:
+        _need(x2, torch.float16, "x2", R * K)
+    elif act != OWQ_ACT_NONE:
+        raise ValueError(f"owq_stage: unknown activation {act}")
+    owq_stage_launch(x, R, K, act, gamma if act == OWQ_ACT_RMSNORM else None, eps, x2 if act == OWQ_ACT_SILU_MUL else None,
+                     owq_stage_parts(parts, R, K))
+
+
 def _awq_check(N, K, nbits, group_size):
     return _quantize_shape(N, K, nbits, group_size, AWQ_GROUPS, "the AWQ kernels serve groups of 32, 64 and 128")
 

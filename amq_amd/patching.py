@@ -514,8 +514,8 @@ def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true
     n_out is 0).  ``n_out``: None = the reference's rule (``owq_n_out`` at the assignment's average bits), an int for every linear, or a dict
     name -> int (names as in arch.LINEARS; a missing name takes the rule).  Groups of 128 only.  Returns (model, report) with
     ``report[(block, name)] = {"loss", "rtn_loss", "solver_loss", "dead", "bits", "n_out", "out_ids"}`` -- loss = tr(dW H dW^T) over all K
-    columns, the outliers' change included.  An OWQ model runs under HF's own forward; ``prepare_for_inference(backend='hip')`` leaves its
-    layers as they are, and the hipGraph runner does not take them."""
+    columns, the outliers' change included.  ``prepare_for_inference(backend='hip')`` leaves an OWQ model's layers as they are; the hipGraph
+    runner takes them (``QuantLlama.from_hf``, ``hf_fast.convert_model_to_hip``, ``evaluate``: the staged token step)."""
     from .arch import LINEARS
     if int(group_size) != 128:
         raise ValueError(f"the OWQ kernels serve groups of 128 only (got {group_size})")
@@ -809,7 +809,8 @@ def _warn_unfused(model, group_siblings, fuse_mlp, fuse_norms, fuse_layers):
     owq = [n for n, m in model.named_modules() if isinstance(m, HIPOWQLinear)]
     if owq:
         warnings.warn(f"prepare_for_inference: {len(owq)} OWQ layers ({', '.join(owq[:3])}{', ...' if len(owq) > 3 else ''}) stay as they are: "
-                      "a HIPOWQLinear is not grouped with its siblings and not fused (its gather has no place in those launches)",
+                      "a HIPOWQLinear is not grouped with its siblings and not fused (its gather has no place in those launches); the hipGraph "
+                      "runner takes them as they are (QuantLlama.from_hf: one stage launch in front of each packed GEMV)",
                       RuntimeWarning, stacklevel=3)
     owq_inner = {id(m.inner) for m in model.modules() if isinstance(m, HIPOWQLinear)}
     lins = [(n.rsplit(".", 1)[-1], m) for n, m in model.named_modules() if isinstance(m, HIPQuantLinear) and id(m) not in owq_inner]

@@ -325,6 +325,40 @@ int amq_owq_quantize_f16(const void* W_p, const void* U_p, int N, int K, int n_o
 int amq_owq_gather_f16(const void* x, int M, int K, const void* perm, int Kp, void* xg, void* stream);
 int amq_owq_outlier_add_f16(const void* x, int M, int K, const void* out_ids, int n_out, const void* W_out, void* y, int N, void* stream);
 
+/* amq_owq_stage_f16: the token step's stage of OWQ layers -- ONE launch in front of the unchanged packed GEMVs of up to three sibling linears that
+ * read the same activation a of R = 1 .. 8 rows of x [R, K]:
+ *   AMQ_OWQ_ACT_NONE      a = x
+ *   AMQ_OWQ_ACT_RMSNORM   a = what amq_rmsnorm_f16(x, gamma, eps) writes (the statistic in its kernel's order:
+ *                         thread t of 256 adds the squares of the 8-element chunks t, t + 256, ..., a wave's sums meet in the xor
+ *                         32, 16, .. 1 butterfly, the four waves' sums are added in order); every workgroup takes it for itself
+ *   AMQ_OWQ_ACT_SILU_MUL  a = what amq_silu_mul_f16(x, x2) writes, x2 [R, K]
+ * and per part (host structs, as amq_segment):
+ *   xg[r, c] = a[r, perm[c]], 0 where perm[c] is not in 0 .. K - 1                                         (amq_owq_gather_f16 over a)
+ *   y[r, n]  = fp16(acc), or fp16(fp32(residual[r, n]) + acc) with a residual (which may be y itself); acc = the fmaf chain over j ascending of
+ *              fp32(a[r, out_ids[j]]) * fp32(W_out[n, j]) from 0                                           (amq_owq_outlier_add_f16 over a)
+ * so that amq_gemv_grouped_f16(xg, segment {y, residual = y}) completes the layer.  A part with n_out == 0 is a plain sibling: perm, out_ids, W_out,
+ * y, residual, N and Kp are not looked at, and xg [R, K] receives a itself.  The results are bit for bit those of the entry points named above in
+ * composition.  One launch; no host read, no allocation, no atomics: the same bits on every run, capturable.
+ * Refused, in this order: x, parts, gamma (RMSNORM) or x2 (SILU_MUL) null, or x / x2 / gamma not 16-byte aligned (AMQ_EINVAL); an unknown act
+ * (AMQ_EINVAL); n_parts outside 1 .. 3, R outside 1 .. 8, K % 128 (AMQ_ESHAPE); then part by part: a null xg, or with outliers a null perm, out_ids,
+ * W_out or y, or a misaligned pointer -- xg and perm / out_ids 4-byte, the rest 2-byte -- (AMQ_EINVAL); n_out negative, odd or >= K, Kp % 128 or
+ * Kp <= 0, N <= 0 (AMQ_ESHAPE). */
+#define AMQ_OWQ_ACT_NONE     0
+#define AMQ_OWQ_ACT_RMSNORM  1
+#define AMQ_OWQ_ACT_SILU_MUL 2
+#define AMQ_OWQ_MAX_PARTS    3
+typedef struct amq_owq_part {
+    const void* perm;      /* int32 [Kp]: the packed layer's columns in x's numbering, -1 = padding */
+    const void* out_ids;   /* int32 [n_out] */
+    const void* W_out;     /* fp16 [N, n_out] */
+    void* xg;              /* fp16 [R, Kp] (n_out == 0: [R, K]) */
+    void* y;               /* fp16 [R, N] */
+    const void* residual;  /* fp16 [R, N] or NULL; may be y */
+    int N, n_out, Kp;
+} amq_owq_part;
+int amq_owq_stage_f16(const void* x, int R, int K, int act, const void* gamma, float eps, const void* x2, const amq_owq_part* parts, int n_parts,
+                      void* stream);
+
 /* ---- dequantize ---------------------------------------------------------- */
 /* native -> W[N,K] fp16 (row-major, nn.Linear orientation) */
 int amq_dequantize_f16(int bits, int mode, const void* qweight_native, const void* meta_native,
