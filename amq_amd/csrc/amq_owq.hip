@@ -6,35 +6,16 @@
 //                            one pass over LDS forms r = rint(v / d16) once and adds the element's term to all 2^bits zero-point sums in registers.
 //   owq_colerr_kernel<BITS>  one thread per column: frob_c = the sum over the rows, ascending, of (w - w^)^2 for the rows' chosen (scale, zero).
 //   owq_range_flag_kernel    one workgroup: a row without a winner (a non-finite value in it) sets the info word.
-//   owq_solve_kernel<BITS>   gptq_solve_kernel's shape (16 lanes per row, 8 columns per lane, U's rows through double-buffered LDS tiles) with the
-//                            group's (d16, zp) from the candidate search over the lane's 8 registers + a 16-lane butterfly per candidate, and with
-//                            the columns >= n_nonout never quantized: they only receive the updates and leave as fp16 W_out.
+//   solve_kernel<SOLVE_OWQ, 128, BITS> (amq_solve_body.cuh, which also holds the candidate arithmetic the range search here shares): the group's
+//                            (d16, zp) from the candidate search over the lane's 8 registers + a 16-lane butterfly per candidate; the columns
+//                            >= n_nonout are never quantized: they only receive the updates and leave as fp16 W_out.
 //   quant_flag_kernel, quant_pack_kernel<BITS> (amq_quant_pack.hip) end the solve.
 //   owq_gather_kernel, owq_outlier_add_kernel   the deployment side of HIPOWQLinear: xg = x[:, perm], and y += x[:, out_ids] . W_out^T.
 // Every operation is its own fp32 rounding (-ffp-contract=off, IEEE division, rintf) except the score's |d|^2.4 = v_exp_f32(2.4f * v_log_f32(|d|)),
 // the one place whose bits a host restatement may miss; the sums' orders are stated at their loops.  No host read, no allocation, no atomics.
-#include "amq_quant.cuh"
+#include "amq_solve_body.cuh"
 
 namespace amq {
-
-// |d|^2.4 for the score: the hardware's log2 and exp2 (1 ulp each; d = 0 -> log2 = -inf -> 0; a denormal d counts as 0, its power underflows anyway)
-__device__ __forceinline__ float owq_pow24(float d) { return __builtin_amdgcn_exp2f(2.4f * __builtin_amdgcn_logf(d)); }
-
-// candidate i's step: tmp_max = (xrange / num) * i, delta = max(tmp_max / maxq, 1e-8), d16 = max(fp16(delta), 2^-24)
-__device__ __forceinline__ float owq_step(float xrange, float numf, int i, float maxq) {
-    const float tmp_max = (xrange / numf) * (float)i;
-    const float delta = fmaxf(tmp_max / maxq, 1e-8f);
-    return fmaxf((float)(_Float16)delta, 0x1p-24f);
-}
-
-// the deployed weight of v's code under (d16, zp), given r = rint(v / d16)
-template <int BITS>
-__device__ __forceinline__ float owq_what(float r, float zp, float d16) {
-    constexpr float maxq = (float)((1 << BITS) - 1);
-    const float q = fminf(fmaxf(r + zp, 0.0f), maxq);
-    const float t = (q - zp) * d16;
-    return (float)(_Float16)t;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- the range search of row segments
 template <int BITS>
@@ -169,206 +150,17 @@ hipError_t launch_owq_range(const void* W, int N, int K, int col0, int L, int bi
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the solve
-// (gptq_fetch of amq_gptq.hip, which stays as it is) a thread's share of one U tile and its row's errors of the tile's rows, into registers
-template <int UP, int EN, int THREADS>
-__device__ __forceinline__ void owq_fetch(f4 (&up)[UP], f4 (&en)[EN], const float* __restrict__ Ut, const float* __restrict__ Et, int K, int tid) {
-#pragma unroll
-    for (int k = 0; k < UP; ++k) {
-        const int f = tid + THREADS * k;
-        up[k] = *(const f4*)(Ut + (size_t)(f / (GPTQ_BLOCK / 4)) * K + 4 * (f % (GPTQ_BLOCK / 4)));
-    }
-#pragma unroll
-    for (int k = 0; k < EN; ++k) en[k] = *(const f4*)(Et + 4 * k);
-}
-
-template <int BITS>
-__global__ __launch_bounds__(64 * GPTQ_WAVES) void owq_solve_kernel(const _Float16* __restrict__ W, const float* __restrict__ U, int K, int nq, int Kp,
-                                                                    int num, float* __restrict__ E, uint8_t* __restrict__ Q,
-                                                                    _Float16* __restrict__ scale, _Float16* __restrict__ zero,
-                                                                    _Float16* __restrict__ Wout, int* __restrict__ choice,
-                                                                    float* __restrict__ row_loss, int* __restrict__ NF) {
-    constexpr int L = GPTQ_LANES, C = GPTQ_BLOCK / GPTQ_LANES;      // 16 lanes x 8 columns
-    constexpr int T = GPTQ_TILE, THREADS = 64 * GPTQ_WAVES;
-    constexpr int UP = T * GPTQ_BLOCK / 4 / THREADS;
-    constexpr int NZ = 1 << BITS;
-    constexpr float maxq = (float)(NZ - 1);
-    static_assert(C == 8 && T % 4 == 0 && GPTQ_BLOCK % T == 0 && UP * THREADS * 4 == T * GPTQ_BLOCK, "layout");
-    __shared__ float utile[2][T * GPTQ_BLOCK];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lg = lane & (L - 1);
-    const size_t row = ((size_t)blockIdx.x * GPTQ_WAVES + wave) * (64 / L) + (lane / L);      // N % 16 == 0: every workgroup is full
-    const size_t rowK = row * (size_t)K, rowP = row * (size_t)Kp;
-    const int n_out = K - nq;
-    const float numf = (float)num;
-    float loss = 0.0f;
-    bool bad = false;
-    for (int i1 = 0; i1 < K; i1 += GPTQ_BLOCK) {
-        const int col0 = i1 + lg * C;
-        float w[C];
-        {
-            const h8 v = *(const h8*)(W + rowK + col0);
-#pragma unroll
-            for (int c = 0; c < C; ++c) w[c] = (float)v[c];
-        }
-        // left-looking: the errors of the QUANTIZED columns before the block (columns >= nq have none), in ascending column order
-        const int prev = i1 < nq ? i1 : nq;                          // (workgroup-uniform)
-        const int ntiles = (prev + T - 1) / T;                       // ntiles * T <= i1 <= K and <= Kp: the last tile may reach past nq, its rows
-        f4 up[UP], en[T / 4];                                        // past nq are fetched and skipped
-        if (ntiles > 0) owq_fetch<UP, T / 4, THREADS>(up, en, U + i1, E + rowP, K, tid);
-        for (int t = 0; t < ntiles; ++t) {
-            float* buf = utile[t & 1];
-#pragma unroll
-            for (int k = 0; k < UP; ++k) *(f4*)(buf + 4 * (tid + THREADS * k)) = up[k];
-            float ev[T];
-#pragma unroll
-            for (int k = 0; k < T / 4; ++k) {
-                ev[4 * k] = en[k].x;
-                ev[4 * k + 1] = en[k].y;
-                ev[4 * k + 2] = en[k].z;
-                ev[4 * k + 3] = en[k].w;
-            }
-            __syncthreads();        // (one barrier per tile, as in gptq_solve_kernel)
-            if (t + 1 < ntiles) owq_fetch<UP, T / 4, THREADS>(up, en, U + (size_t)(t + 1) * T * K + i1, E + rowP + (t + 1) * T, K, tid);
-            const int rows = prev - t * T;                           // rows of this tile that are quantized columns
-#pragma unroll
-            for (int r = 0; r < T; ++r) {
-                if (r < rows) {
-                    const float4 a = *(const float4*)(buf + r * GPTQ_BLOCK + lg * C), b = *(const float4*)(buf + r * GPTQ_BLOCK + lg * C + 4);
-                    const float uv[C] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float p = ev[r] * uv[c];
-                        w[c] = w[c] - p;
-                    }
-                }
-            }
-        }
-        if (i1 < nq) {
-            // the group's range from the row's current values of its columns < nq
-            const int cnt = nq - i1 < GPTQ_BLOCK ? nq - i1 : GPTQ_BLOCK;
-            const float cntf = (float)cnt;
-            float mn = 0.0f, mx = 0.0f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const bool in = col0 + c < nq;
-                mn = in ? fminf(mn, w[c]) : mn;
-                mx = in ? fmaxf(mx, w[c]) : mx;
-            }
-#pragma unroll
-            for (int m = 1; m < L; m <<= 1) {
-                mn = fminf(mn, __shfl_xor(mn, m));
-                mx = fmaxf(mx, __shfl_xor(mx, m));
-            }
-            const float xrange = mx - mn;
-            float best = 1e10f, s16 = 0.0f, z = 0.0f;
-            int bi = 0;
-#pragma unroll 1
-            for (int i = 1; i <= num; ++i) {
-                const float d16 = owq_step(xrange, numf, i, maxq);
-                float r[C];
-#pragma unroll
-                for (int c = 0; c < C; ++c) r[c] = rintf(w[c] / d16);
-                // the sum's order: a lane adds its (up to) 8 columns in ascending order from 0, the row's 16 lanes meet in a butterfly (xor 1, 2, 4,
-                // 8); the score is that sum / the group's column count
-#pragma unroll
-                for (int zi = 0; zi < NZ; ++zi) {
-                    const float zp = (float)zi;
-                    float s = 0.0f;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float term = owq_pow24(fabsf(w[c] - owq_what<BITS>(r[c], zp, d16)));
-                        s = s + (col0 + c < nq ? term : 0.0f);
-                    }
-#pragma unroll
-                    for (int m = 1; m < L; m <<= 1) s = s + __shfl_xor(s, m);
-                    const float sc = s / cntf;
-                    if (sc < best) {
-                        best = sc;
-                        s16 = d16;
-                        z = zp;
-                        bi = i;
-                    }
-                }
-            }
-            bad = bad || bi == 0;                                    // no winner: a non-finite value in the group
-            if (lg == 0) {
-                const size_t g = row * (size_t)(Kp / GPTQ_BLOCK) + (size_t)(i1 / GPTQ_BLOCK);
-                scale[g] = (_Float16)s16;
-                zero[g] = (_Float16)z;
-                choice[2 * g] = bi;
-                choice[2 * g + 1] = (int)z;
-            }
-            // the block's columns: o = the lane of the row that holds column i, c = its register
-            for (int o = 0; o < L; ++o) {
-                float ev[C];
-                Codes8 codes;
-                const bool after = lg > o, from = lg >= o;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const int gi = i1 + o * C + c;
-                    if (gi < nq) {                                   // (workgroup-uniform)
-                        const float* u = U + (size_t)gi * K + col0;
-                        const float4 a = *(const float4*)u, b = *(const float4*)(u + 4);
-                        const float uv[C] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-                        const float d = U[(size_t)gi * K + gi];
-                        const float wi = __shfl(w[c], o, L);
-                        const float q = fminf(fmaxf(rintf(wi / s16) + z, 0.0f), maxq);
-                        const float t = (q - z) * s16;
-                        const float wh = (float)(_Float16)t;
-                        const float r = wi - wh;
-                        const float e = r / d;
-                        const float r2 = r * r, d2 = d * d;
-                        loss = loss + (r2 / d2) / 2.0f;
-                        bad = bad || !(fabsf(wi) < __builtin_inff()) || !(fabsf(e) < __builtin_inff()) || !(d > 0.0f && d < __builtin_inff());
-                        ev[c] = e;
-                        codes.put(c, q);
-#pragma unroll
-                        for (int c2 = 0; c2 < C; ++c2) {
-                            const float p = e * uv[c2];
-                            const float nw = w[c2] - p;
-                            w[c2] = (c2 > c ? from : after) ? nw : w[c2];
-                        }
-                    } else {                                         // padding of a ragged last group: the code that dequantizes to 0
-                        ev[c] = 0.0f;
-                        codes.put(c, z);
-                    }
-                }
-                if (lg == o) {
-                    *(float4*)(E + rowP + col0) = make_float4(ev[0], ev[1], ev[2], ev[3]);
-                    *(float4*)(E + rowP + col0 + 4) = make_float4(ev[4], ev[5], ev[6], ev[7]);
-                    codes.store(Q + rowP + col0);
-                }
-            }
-        }
-        // the columns >= nq this lane holds have all their updates now: they leave as fp16
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int j = col0 + c - nq;
-            if (j >= 0) {
-                bad = bad || !(fabsf(w[c]) < __builtin_inff());
-                Wout[row * (size_t)n_out + j] = (_Float16)w[c];
-            }
-        }
-        __syncthreads();        // the block's E is read by the row's other lanes in the next block
-    }
-    if (lg == 0) row_loss[row] = loss;
-    const bool anybad = __builtin_amdgcn_ballot_w64(bad) != 0;
-    if (lane == 0) NF[blockIdx.x * GPTQ_WAVES + wave] = anybad ? 1 : 0;
-}
-
 hipError_t launch_owq_quantize(const void* W, const void* U, int N, int K, int n_out, int bits, int num, void* W_q, void* scale, void* zero,
                                void* W_out, void* choice, void* row_loss, void* info, void* workspace, hipStream_t st) {
-    const int wgs = gptq_workgroups(N), flags = gptq_flags(N), nq = K - n_out, Kp = owq_packed_columns(K, n_out);
-    float* E = (float*)workspace;
-    int* NF = (int*)(E + (size_t)N * Kp);
-    uint8_t* Q = (uint8_t*)(NF + flags);
-    if (hipError_t e = dispatch_bits(bits, [&](auto B) {
-            hipLaunchKernelGGL((owq_solve_kernel<B()>), dim3(wgs), dim3(64 * GPTQ_WAVES), 0, st, (const _Float16*)W, (const float*)U, K, nq, Kp, num,
-                               E, Q, (_Float16*)scale, (_Float16*)zero, (_Float16*)W_out, (int*)choice, (float*)row_loss, NF);
+    const int nq = K - n_out, Kp = owq_packed_columns(K, n_out);
+    return launch_solve(workspace, N, Kp, GPTQ_BLOCK, bits, W_q, info, st, [&](float* E, int* NF, uint8_t* Q) {
+        return dispatch_bits(bits, [&](auto B) {
+            hipLaunchKernelGGL((solve_kernel<SOLVE_OWQ, GPTQ_BLOCK, B()>), dim3(gptq_workgroups(N)), dim3(64 * GPTQ_WAVES), 0, st, (const _Float16*)W,
+                               (const float*)U, K, E, Q, (_Float16*)scale, (_Float16*)zero, (float*)row_loss, NF, (const int*)nullptr, nq, Kp, num,
+                               (_Float16*)W_out, (int*)choice);
             return hipGetLastError();
-        }))
-        return e;
-    if (hipError_t e = launch_quant_flags(NF, flags, (int*)info, st)) return e;
-    return launch_pack_codes(Q, (size_t)N * Kp / GPTQ_BLOCK, GPTQ_BLOCK, bits, W_q, st);
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the layer's two own launches

@@ -1,5 +1,5 @@
-// amq_quant.cuh -- what the device quantizers share (amq_quantize.hip, amq_gptq.hip, amq_gptq_static.hip, amq_awq.hip, amq_quant_pack.hip; no hot-path unit includes
-// this): the Format A word, byte codes in pairs of words, the finite test and the bits x group dispatch of their launchers.  None of it rounds:
+// amq_quant.cuh -- what the device quantizers share (amq_quantize.hip, amq_awq.hip, amq_quant_pack.hip, and through amq_solve_body.cuh the three
+// solves amq_gptq.hip, amq_gptq_static.hip, amq_owq.hip; no hot-path unit includes this): the Format A word, byte codes in pairs of words, the finite test and the bits x group dispatch of their launchers.  None of it rounds:
 // the kernels' arithmetic stays where DESIGN.md 3.9 - 3.11 state it.  (The 8-column group extremes of the GPTQ solve and AWQ's round-to-nearest
 // stay written out in both: as a shared function they rescheduled the solve)
 #pragma once
