@@ -1124,6 +1124,42 @@ int amq_attn_decode_split_qkn_f16(const amq_qk_norm* norm, const void* q, const 
                        n_splits, workspace, workspace_bytes, tickets, stream);
 }
 
+/* ---- 8-bit KV cache (amq_attn_kv8.hip) ---- */
+int amq_kv8_store_f16(const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, int pos0, int S, int batch, int n_kv_heads,
+                      int head_dim, int max_seq, void* stream) {
+    if (!k || !v || !kc8 || !ks || !vc8 || !vs) return fail(AMQ_EINVAL, "null pointer");
+    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
+    if (batch < 1 || S < 1 || n_kv_heads < 1 || n_kv_heads > 255) return fail(AMQ_ESHAPE, "need batch, S >= 1 and 1..255 kv heads (got %d, %d, %d)", batch, S, n_kv_heads);
+    if (max_seq < 1 || pos0 < 0 || (long long)pos0 + S > max_seq)
+        return fail(AMQ_ESHAPE, "rows %d .. %lld outside the cache (max_seq=%d)", pos0, (long long)pos0 + S - 1, max_seq);
+    return check_hip(amq::launch_kv8_store(k, v, kc8, ks, vc8, vs, pos0, S, batch, n_kv_heads, max_seq, (hipStream_t)stream), "kv8_store");
+}
+
+size_t amq_attn_decode_kv8_workspace_bytes(int batch, int n_heads, int n_splits) {
+    if (batch < 1 || n_heads < 1 || n_splits < 1) return 0;
+    return (size_t)batch * n_heads * n_splits * 132 * sizeof(float);
+}
+
+int amq_attn_decode_kv8_f16(const void* q, const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, void* out,
+                            const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
+                            int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
+                            void* tickets, void* stream) {
+    if (!q || !k || !v || !kc8 || !ks || !vc8 || !vs || !out || !workspace || !tickets) return fail(AMQ_EINVAL, "null pointer");
+    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
+    if (batch < 1 || batch > 65535) return fail(AMQ_ESHAPE, "batch must be 1..65535 (got %d)", batch);
+    if (n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0 || n_heads / n_kv_heads > 16)
+        return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads; 1..16 query heads per kv head)", n_heads, n_kv_heads);
+    if (max_seq < 1 || (!step_state && !pos_dev && (pos < 0 || pos >= max_seq)))
+        return fail(AMQ_ESHAPE, "position %d outside the cache (max_seq=%d)", pos, max_seq);
+    if (n_splits < 1 || n_splits > 1024) return fail(AMQ_EINVAL, "n_splits must be 1..1024 (got %d)", n_splits);
+    const size_t need = amq_attn_decode_kv8_workspace_bytes(batch, n_heads, n_splits);
+    if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    // a step state carries the position and its cos/sin row: pos_dev, rope_theta and rope_table are then not looked at
+    amq::Kv8Args a{q, k, v, kc8, ks, vc8, vs, out, step_state ? nullptr : pos_dev, pos, n_heads, n_kv_heads, max_seq,
+                   step_state ? 10000.0f : rope_theta, step_state ? nullptr : rope_table, step_state};
+    return check_hip(amq::launch_attn_decode_kv8(a, batch, n_splits, workspace, tickets, (hipStream_t)stream), "attn_decode_kv8");
+}
+
 static int amq_attn_prefill_check(const void* q, const void* k, const void* v, const void* out, int batch, int S, int pos0, int n_heads,
                                   int n_kv_heads, int head_dim, long long q_rstride, long long q_bstride, long long k_rstride,
                                   long long k_bstride, long long k_hstride, long long v_rstride, long long v_bstride, long long v_hstride,

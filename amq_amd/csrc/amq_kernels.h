@@ -199,6 +199,27 @@ hipError_t launch_attn_decode_gqa(const AttnArgs& a, int batch, int n_splits, vo
 // rows' step-state blocks, one cache slice; n_splits >= 1 chunks of 128 * attn_decode_gqa_iters keys; ws = fp32 [rows][n_heads][n_splits][132]
 int attn_decode_gqa_rows_blocks(int rows, int n_heads, int n_kv_heads);       // MFMA row blocks of 16 query rows (step row, head of the group)
 hipError_t launch_attn_decode_gqa_rows(const AttnArgs& a, int rows, int n_splits, void* ws, hipStream_t st);
+// 8-bit KV cache (amq_attn_kv8.hip): int8 [B][n_kv_heads][max_seq][128] codes + fp32 [B][n_kv_heads][max_seq] scales, K and V
+struct Kv8Args {
+    const void* q;        // fp16 [B, n_heads, 128]      (un-rotated)
+    const void* k;        // fp16 [B, n_kv_heads, 128]   (un-rotated new key)
+    const void* v;        // fp16 [B, n_kv_heads, 128]
+    void* kc8; void* ks; void* vc8; void* vs;
+    void* out;            // fp16 [B, n_heads, 128]
+    const int* pos_dev;   // device int32 position, or null -> pos
+    int pos;
+    int n_heads, n_kv_heads, max_seq;
+    float rope_theta;
+    const void* rope_table;   // as AttnArgs
+    const void* step_state;   // one step-state block for the whole batch (the `cur` mode), or null
+};
+int kv8_head_blocks(int n_heads, int n_kv_heads);     // workgroups a kv head's query heads are dealt over (<= 8 heads each)
+int kv8_chunk(int max_seq, int n_splits);             // keys per workgroup (multiple of 32)
+// rotated k / v rows [batch * S][n_kv_heads * 128] -> cache rows pos0 .. pos0 + S - 1 of every sequence
+hipError_t launch_kv8_store(const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, int pos0, int S, int batch, int n_kv_heads,
+                            int max_seq, hipStream_t st);
+// ws = fp32 [batch][n_heads][n_splits][132]; tickets = int32 [batch][n_kv_heads][kv8_head_blocks], zero before (and after) every launch
+hipError_t launch_attn_decode_kv8(const Kv8Args& a, int batch, int n_splits, void* ws, void* tickets, hipStream_t st);
 hipError_t launch_rmsnorm(const void* x, const void* gamma, void* y, int M, int K, float eps, hipStream_t st);
 hipError_t launch_rmsnorm_xfrag(const void* x, const void* gamma, void* xf, int M, int K, float eps, hipStream_t st);
 // causal attention over a whole prompt (amq_attn_prefill.hip).  Element (b, s, head, d) of q / out sits at

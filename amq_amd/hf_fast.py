@@ -144,14 +144,15 @@ def _runner(model, batch, need, ragged=False):
     one carries nothing over."""
     if need > _limit(model):
         raise ValueError(f"{need} positions exceed the model's max_position_embeddings ({_limit(model)})")
-    r, old = _bound(model, ("ragged", batch) if ragged else batch, need, batch=batch, ragged=ragged)
+    kv_bits = model.__dict__.get("_amq_kv_bits", 16)            # convert_model_to_hip(model, kv_bits=8): never together with padded / lookup
+    r, old = _bound(model, ("ragged", batch) if ragged else batch, need, batch=batch, ragged=ragged, kv_bits=kv_bits)
     if ragged:
         return r
     r.all_logits = True
     if old is not None and _same_weights(old, model) and old.host_pos > 0:
         for nb, ob in zip(r.blocks, old.blocks):
-            nb["kc"][:, :, :old.host_pos].copy_(ob["kc"][:, :, :old.host_pos])
-            nb["vc"][:, :, :old.host_pos].copy_(ob["vc"][:, :, :old.host_pos])
+            for key in (("kc8", "ks", "vc8", "vs") if kv_bits == 8 else ("kc", "vc")):       # an 8-bit cache: codes and scales
+                nb[key][:, :, :old.host_pos].copy_(ob[key][:, :, :old.host_pos])
         r.set_pos(old.host_pos)
         r.set_token(old.token)
     return r
@@ -370,7 +371,7 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     return torch.cat([ids, new.view(B, -1).to(ids.dtype)], dim=1)
 
 
-def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scoring=False):
+def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scoring=False, kv_bits=16):
     """convert_model_to_ft(model) + replace_generate_functions() (ftllama_modeling.py:569-580, ftllama_generate.py:613-622) for the HIP backend:
     call it on the model ``prepare_for_inference(model, backend='hip')`` returned (a Llama-family ``*ForCausalLM`` whose decoder linears are
     HIPQuantLinear modules on one GPU).  Patches THIS instance's ``forward`` and ``generate`` (see the module docstring); idempotent; returns the
@@ -378,9 +379,19 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
     ``padded=True`` also routes ``generate`` calls whose ``attention_mask`` is LEFT padding (``padding_side="left"``) to a runner that decodes every
     row at a position of its own; ``lookup=True`` also routes ``generate(prompt_lookup_num_tokens=k, ...)`` calls for one sequence to a
     prompt-lookup speculative runner (``lookup_request``), greedy ones -- and with ``sampling=True`` as well ``do_sample=True`` ones; ``scoring=True`` keeps ``model(ids, start_pos=0, labels=..., use_cache=False)`` on the runner and
-    returns HF's shifted cross-entropy as ``loss``.  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
+    returns HF's shifted cross-entropy as ``loss``; ``kv_bits=8``: the runners keep an 8-bit KV cache (int8 rows with a scale per row, DESIGN.md 3.13:
+    ``generate`` greedy and sampled, one-row ``model(ids, start_pos=p)`` steps; a many-row call at ``start_pos`` > 0 raises; refused together with
+    ``lookup=True`` / ``padded=True``).  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
+    if kv_bits not in (8, 16):
+        raise ValueError(f"kv_bits must be 16 (fp16 cache) or 8 (int8 rows with a scale per row), got {kv_bits!r}")
+    if kv_bits == 8 and (lookup or padded):
+        raise ValueError("kv_bits=8 is not offered together with " + ("lookup=True" if lookup else "padded=True") + ": the 8-bit attention kernel "
+                         "runs one row per sequence at one position for the batch (QuantLlama(kv_bits=8))")
+    if model.__dict__.get("_amq_kv_bits", kv_bits) != kv_bits:
+        _RUNNERS.pop(model, None)                               # runners hold a cache of the other format
+    model.__dict__["_amq_kv_bits"] = int(kv_bits)
     if "_amq_orig_forward" in model.__dict__:
         model.__dict__["_amq_sampling"] = bool(sampling)
         model.__dict__["_amq_padded"] = bool(padded)
@@ -409,6 +420,7 @@ def revert_model_to_hf(model):
     model.__dict__.pop("_amq_padded", None)
     model.__dict__.pop("_amq_lookup", None)
     model.__dict__.pop("_amq_scoring", None)
+    model.__dict__.pop("_amq_kv_bits", None)
     _RUNNERS.pop(model, None)
     return model
 

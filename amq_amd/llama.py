@@ -225,6 +225,7 @@ class QuantLlama:
     # (32/8 heads, R = 2, 2048) up to 787 -> 63 us (64/8, R = 8, 32768) -- so the threshold is its floor; shorter caches were not measured and keep the
     # per-head kernels (every grouped-query lookup runner of the older tests keeps its arithmetic).
     ROWS_GQA_FROM = 2048
+    kv_bits = 16                # (the instance's own after QuantLlama.__init__; the fp16 baseline runner, which has its own __init__, keeps fp16 rows)
     ENGINE_DEFAULT = False      # what engine=None means (the engine is opt-in until it beats the five-launch step: HISTORY.md 3.2b)
     # prompt passes also leave the logits of EVERY prompt row in self.logits_rows [B, S, vocab] (HF's forward returns them all; the runner's own
     # generate loop needs the last row only): final norm + one fp16 GEMM over the prompt rows, inside the captured prompt graph (hf_fast.py sets it)
@@ -241,7 +242,7 @@ class QuantLlama:
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
                  hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2,
-                 lookup_sampling=False):
+                 lookup_sampling=False, kv_bits=16):
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
@@ -263,9 +264,28 @@ class QuantLlama:
         counter i), so the output is what one-row sampled decoding draws from the same logits, whatever is proposed.  False: ``set_sampling`` is
         refused, as lookup runners always have.
         rope: (inv_freq fp32 [64], attention_scaling) of the rotary embedding when it is not the plain ``rope_theta`` form (from_hf hands over
-        the HF module's own; otherwise derived from config["rope_scaling"]: Llama-3.1's "llama3")."""
+        the HF module's own; otherwise derived from config["rope_scaling"]: Llama-3.1's "llama3").
+        kv_bits: 16 -- the fp16 KV cache, the object, graphs and bits the runner has always had; 8 -- int8 rows with one fp32 scale per (sequence,
+        kv head, position) (blocks hold kc8 / ks / vc8 / vs, 132 bytes per row instead of 256; the token step issues
+        ops.attn_decode_kv8, the prompt pass stays exact fp16 and stores its rows with one ops.kv8_store).  Not offered with ragged=True, lookup=,
+        a qk_norm config, the decode engine, the fused q/k/v + attention launch or a prompt pass at start_pos > 0."""
         if isinstance(config, str):
             config = MODEL_CONFIGS[config]
+        if kv_bits not in (8, 16):
+            raise ValueError(f"kv_bits must be 16 (fp16 cache) or 8 (int8 rows with a scale per row), got {kv_bits!r}")
+        self.kv_bits = int(kv_bits)
+        if self.kv_bits == 8:
+            # the 8-bit attention kernel keeps one position for the batch, runs one row per sequence and carries no per-head norm
+            if ragged:
+                raise ValueError("kv_bits=8: the 8-bit attention kernel keeps one position for the batch: not offered with ragged=True")
+            if lookup:
+                raise ValueError("kv_bits=8: a verify step runs 2 .. 8 rows of one sequence, the 8-bit attention kernel one: not offered with lookup=")
+            if config.get("qk_norm"):
+                raise ValueError("kv_bits=8: the 8-bit attention kernel has no per-head q / k norm: not offered for a qk_norm model")
+            if engine:
+                raise ValueError("kv_bits=8: the decode engine reads an fp16 cache")
+            if self.FUSE_QKV_ATTN:
+                raise ValueError("kv_bits=8: the fused q/k/v + attention launch reads an fp16 cache")
         if not 1 <= int(batch) <= 8:
             raise ValueError("batch must be 1..8")
         self.B = int(batch)
@@ -347,8 +367,11 @@ class QuantLlama:
                 if self.qk_norm:
                     blk["qn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
                     blk["kn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
-            blk["kc"] = torch.zeros(self.B, self.nkv, max_seq, 128, dtype=torch.float16, device=dev)
-            blk["vc"] = torch.zeros(self.B, self.nkv, max_seq, 128, dtype=torch.float16, device=dev)
+            if self.kv_bits == 8:
+                blk["kc8"], blk["ks"], blk["vc8"], blk["vs"] = ops.kv8_alloc(self.B, self.nkv, max_seq, dev)
+            else:
+                blk["kc"] = torch.zeros(self.B, self.nkv, max_seq, 128, dtype=torch.float16, device=dev)
+                blk["vc"] = torch.zeros(self.B, self.nkv, max_seq, 128, dtype=torch.float16, device=dev)
             self.blocks.append(blk)
         if dense is not None:
             self.embed, self.lm_head, self.norm = dense["embed"].to(dev), dense["lm_head"].to(dev), dense["norm"].to(dev)
@@ -410,11 +433,11 @@ class QuantLlama:
             raise ValueError(("the decode engine" if engine else "the fused q/k/v + attention launch") + " does not serve this model: "
                              + ("it has no per-head q / k norm" if self.qk_norm else f"q / o widths of heads * 128 = {self.qd} != hidden_size {self.H}"))
         self.can_fuse_qkv_attn = (R == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
-                                  and not self.ragged and not qwen3_shape)
+                                  and not self.ragged and not qwen3_shape and self.kv_bits == 16)
         self.fuse_qkv_attn = self.FUSE_QKV_ATTN and self.can_fuse_qkv_attn
         self._tickets = torch.zeros(max(self.nh, 64), dtype=torch.int32, device=dev)
         eligible = (self.R == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias and not self.ragged
-                    and not self.qk_norm)
+                    and not self.qk_norm and self.kv_bits == 16)
         if engine and not eligible:
             raise ValueError("the decode engine needs batch 1 and max_seq <= %d" % self.ENGINE_MAX_SEQ)
         self.engine = None
@@ -533,7 +556,7 @@ class QuantLlama:
                 raise ValueError(f"{where}.{name}: eps {m_eps} is not the model's rms_norm_eps {eps} (the runner keeps one eps)")
 
     @classmethod
-    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False):
+    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False, kv_bits=16):
         """The hipGraph runner over a SWAPPED HF causal LM of the Llama family (``HF_MODEL_TYPES``: Llama 2 / 3.x, Mistral, Qwen2.5) -- what
         ``prepare_for_inference(model, backend="hip")`` (or the reference's deepcopy + setattr assembly of a mixed-precision model,
         amq_speed_benchmark.py:231-256) leaves behind.  The runner shares the modules' native weight buffers and biases, the embedding, lm_head and
@@ -577,7 +600,7 @@ class QuantLlama:
             dense["qn"] = [f16(l.self_attn.q_norm.weight).contiguous() for l in layers]
             dense["kn"] = [f16(l.self_attn.k_norm.weight).contiguous() for l in layers]
         return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
-                   ragged=ragged, lookup=lookup, ngram_max=ngram_max, lookup_sampling=lookup_sampling)
+                   ragged=ragged, lookup=lookup, ngram_max=ngram_max, lookup_sampling=lookup_sampling, kv_bits=kv_bits)
 
     # ----------------------------------------------------------------- sizes
     def linear_bytes_per_token(self):
@@ -585,7 +608,7 @@ class QuantLlama:
         return sum(blk[name].nbytes() for blk in self.blocks for name in self.cfg["linear"])
 
     def total_bytes_per_token(self, context):
-        kv = 2 * self.nb * self.nkv * 128 * 2 * context
+        kv = 2 * self.nb * self.nkv * (ops.KV8_ROW_BYTES if self.kv_bits == 8 else 256) * context       # K and V rows: 256 bytes of fp16, or 128 codes + a scale
         return self.linear_bytes_per_token() + self.lm_head.numel() * 2 + kv
 
     # ----------------------------------------------------------------- decode
@@ -615,6 +638,9 @@ class QuantLlama:
                 if self.lookup:                 # the R rows are consecutive positions of the one sequence: causal among them, one cache slice
                     ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv,
                                          grouped=self.rows_attention_grouped(self.nh, self.nkv, self.max_seq), **self._qkn(blk))
+                elif self.kv_bits == 8:
+                    ops.attn_decode_kv8(self.q, self.k, self.v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], self.att, self.pos, self.nh, self.nkv,
+                                        cur=self.rope_cur)
                 else:
                     ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
                                     cur=self.rope_cur, **self._qkn(blk))
@@ -696,6 +722,9 @@ class QuantLlama:
                     if self.lookup:
                         ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv,
                                              grouped=self.rows_attention_grouped(self.nh, self.nkv, self.max_seq), **self._qkn(blk))
+                    elif self.kv_bits == 8:
+                        ops.attn_decode_kv8(self.q, self.k, self.v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], self.att, self.pos, self.nh, self.nkv,
+                                            cur=self.rope_cur)
                     else:
                         ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
                                         cur=self.rope_cur, **self._qkn(blk))
@@ -928,6 +957,7 @@ class QuantLlama:
             raise ValueError("prompt longer than the KV cache")
         if self.lookup and start_pos != 0:
             raise ValueError("lookup: the history holds the whole sequence -- a prompt pass starts at position 0")
+        self._kv8_prompt_check(start_pos)
         if self.lookup:
             self._prompt_len = S
         if lengths is not None and not self.ragged:
@@ -1086,6 +1116,19 @@ class QuantLlama:
             raise ValueError(f"expected {self.B} prompt(s) of equal length, got ids of shape {tuple(ids.shape)}")
         return ids
 
+    def _kv8_prompt_check(self, start_pos):
+        """an 8-bit cache is written by the prompt pass and read by the token step only: a prompt pass behind cached rows would have to attend them"""
+        if self.kv_bits == 8 and start_pos != 0:
+            raise ValueError("kv_bits=8: a prompt pass starts at position 0 (the prompt kernels read no 8-bit cache: chunked prompts are not served)")
+
+    def _prompt_kv(self, blk, q, k, v, S):
+        """the rotation and the cache write of a prompt pass at position 0 -> (k, v, kv_cache) for ops.attn_prefill.  fp16 cache: one launch rotates
+        q / k and writes the cache, which the attention reads.  8-bit cache: q / k are rotated in place, the attention reads the projection outputs
+        (exact fp16: the prompt's own attention is the no-cache pass bit for bit) and ONE ops.kv8_store quantizes the rows into the cache."""
+        ops.rope_rows(q, k, self.rope_tab, S, self.nh, self.nkv)
+        ops.kv8_store(k, v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], 0, self.nkv)
+        return k, v, False
+
     def _prefill_rows(self, ids, start_pos):
         """the prompt pass of every sequence (each into its own slice of the caches), then position(s) and first token(s); all device work: what
         the prompt graph captures"""
@@ -1134,7 +1177,11 @@ class QuantLlama:
         for blk in self.blocks:
             h = ops.rmsnorm(x, blk["ln1"], self.eps)
             q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
-            if cache:
+            if cache and self.kv_bits == 8:
+                self._kv8_prompt_check(start_pos)
+                kk, vv, _ = self._prompt_kv(blk, q, k, v, S)
+                a = ops.attn_prefill(q, kk, vv, torch.empty_like(q), S, nh, nkv, batch=B)
+            elif cache:
                 ops.rope_cache(q, k, v, blk["kc"], blk["vc"], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
                 a = ops.attn_prefill(q, blk["kc"], blk["vc"], torch.empty_like(q), S, nh, nkv, batch=B, pos0=start_pos, kv_cache=True)
             else:
@@ -1242,6 +1289,7 @@ class QuantLlama:
         S = ids.numel()
         if start_pos + S > self.max_seq:
             raise ValueError("prompt longer than the KV cache")
+        self._kv8_prompt_check(start_pos)
         H, nh, nkv = self.H, self.nh, self.nkv
         ids = ids.to(self.dev)
         x = self.embed.index_select(0, ids)                        # [S, H]; the residual stream, updated in place
@@ -1275,16 +1323,20 @@ class QuantLlama:
             else:
                 h = ops.rmsnorm(x, blk["ln1"], self.eps)
                 q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
-            kc, vc = blk["kc"], blk["vc"]
-            ops.rope_cache(q, k, v, kc[0], vc[0], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
+            if self.kv_bits == 8:
+                kc, vc, cached = self._prompt_kv(blk, q, k, v, S)
+            else:
+                kc, vc, cached = blk["kc"], blk["vc"], True
+                ops.rope_cache(q, k, v, kc[0], vc[0], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
             if frag:
-                a_xf = ops.attn_prefill(q, kc, vc, None, S, nh, nkv, batch=1, pos0=start_pos, kv_cache=True, out_xfrag=True)
+                a_xf = ops.attn_prefill(q, kc, vc, None, S, nh, nkv, batch=1, pos0=start_pos, kv_cache=cached, out_xfrag=True)
                 x = lin_xf(blk["self_attn.o_proj"], a_xf, residual=x)              # attention output handed over in fragment order
                 h2 = ops.rmsnorm_xfrag(x, blk["ln2"], self.eps)
                 g, u = lin_xf_group([blk["mlp.gate_proj"], blk["mlp.up_proj"]], h2)                            # one launch
                 act = ops.silu_mul(g, u, out=g)
             else:
-                x = lin(blk["self_attn.o_proj"], self._prefill_attention(q, blk, S, start_pos), residual=x)
+                a = self._prefill_attention(q, blk, S, start_pos) if cached else ops.attn_prefill(q, kc, vc, torch.empty_like(q), S, nh, nkv)
+                x = lin(blk["self_attn.o_proj"], a, residual=x)
                 h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
                 g = lin(blk["mlp.gate_proj"], h2)
                 if blk["mlp.up_proj"].owq:
@@ -1365,6 +1417,8 @@ class QuantLlama:
             raise ValueError("prompt longer than the KV cache")
         if self.qk_norm:
             raise ValueError("the framework-op comparison pass has no per-head q / k norm: not offered for a qk_norm model")
+        if self.kv_bits == 8:
+            raise ValueError("kv_bits=8: the framework-op comparison pass (SDPA over the fp16 cache) is not offered")
         H, nh, nkv = self.H, self.nh, self.nkv
         ids = ids.to(self.dev)
         x = self.embed.index_select(0, ids)

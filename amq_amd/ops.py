@@ -1857,6 +1857,109 @@ def attn_decode(q, k, v, kcache, vcache, out, pos, n_heads, n_kv_heads, rope_the
     return _attn_call(lib, "amq_attn_decode_f16", norm, tensors, (pos_dev, pos_i), heads, (ctypes.c_float(rope_theta), _lib.ptr(table)))
 
 
+# ---- 8-bit KV cache (include/amq_hip.h: "8-bit KV cache"; amq_attn_kv8.hip)
+KV8_ROW_BYTES = 132        # 128 int8 codes + one fp32 scale (the fp16 cache: 256)
+KV8_CHUNK_MIN = 256        # fewest keys the policy gives a workgroup: one tile of the kernel's online softmax
+KV8_HEADS_PER_WG = 8       # query heads of a kv head one workgroup serves (amq_attn_kv8.hip: kv8_head_blocks)
+KV8_WGS = 2 * ATTN_CUS     # workgroups a launch aims at: two of its 256-thread workgroups fit a CU's registers and LDS
+
+
+def kv8_alloc(B, n_kv_heads, max_seq, device):
+    """-> (kc8, ks, vc8, vs): int8 [B, n_kv_heads, max_seq, 128] codes and fp32 [B, n_kv_heads, max_seq] scales of K and of V, zeroed (a zero
+    scale with zero codes stands for a zero row)"""
+    mk = lambda: (torch.zeros(B, n_kv_heads, max_seq, 128, dtype=torch.int8, device=device),
+                  torch.zeros(B, n_kv_heads, max_seq, dtype=torch.float32, device=device))
+    (kc8, ks), (vc8, vs) = mk(), mk()
+    return kc8, ks, vc8, vs
+
+
+def _need_kv8(kc8, ks, vc8, vs):
+    if kc8.dim() != 4 or kc8.shape[3] != 128:
+        raise ValueError("kc8 must be int8 [B, n_kv_heads, max_seq, 128]")
+    B, nkv, max_seq = kc8.shape[:3]
+    for t, name in ((kc8, "kc8"), (vc8, "vc8")):
+        _need(t, torch.int8, name, B * nkv * max_seq * 128)
+    for t, name in ((ks, "ks"), (vs, "vs")):
+        _need(t, torch.float32, name, B * nkv * max_seq)
+    return B, nkv, max_seq
+
+
+def kv8_store(k, v, kc8, ks, vc8, vs, pos0, n_kv_heads):
+    """the prompt pass' glue: ROTATED k and v, fp16 [B * S, n_kv_heads * 128], quantized into rows pos0 .. pos0 + S - 1 of every sequence's slice
+    of the 8-bit caches (one launch)"""
+    B, nkv, max_seq = _need_kv8(kc8, ks, vc8, vs)
+    if nkv != n_kv_heads:
+        raise ValueError(f"caches of {nkv} kv heads, n_kv_heads={n_kv_heads}")
+    rows = k.numel() // (n_kv_heads * 128)
+    if rows < B or rows % B:
+        raise ValueError(f"{rows} rows of k for caches of {B} sequences")
+    S = rows // B
+    _need(k, torch.float16, "k", rows * n_kv_heads * 128)
+    _need(v, torch.float16, "v", rows * n_kv_heads * 128)
+    pos0 = int(pos0)
+    if pos0 < 0 or pos0 + S > max_seq:
+        raise ValueError(f"rows {pos0} .. {pos0 + S - 1} outside the cache (max_seq={max_seq})")
+    _lib.check(_lib.load().amq_kv8_store_f16(*map(_lib.ptr, (k, v, kc8, ks, vc8, vs)), pos0, S, B, n_kv_heads, 128, max_seq, _lib.current_stream()))
+
+
+def kv8_dequantize(kc8, ks, dtype=torch.float32):
+    """the rows an 8-bit cache stands for: fp32(code) * scale (fp32), or that value rounded to fp16 -- plain torch, for tests and tools"""
+    x = kc8.to(torch.float32) * ks.unsqueeze(-1)
+    return x if dtype is torch.float32 else x.to(dtype)
+
+
+def attn_decode_kv8_splits(max_seq, n_heads=32, batch=1, n_kv_heads=None):
+    """workgroups per (sequence, kv head, head block) the auto policy gives an 8-bit cache of ``max_seq`` rows: enough chunks of at least
+    KV8_CHUNK_MIN keys for KV8_WGS workgroups in the launch (chunks beyond the position leave at once)"""
+    if max_seq <= KV8_CHUNK_MIN:
+        return 1
+    nkv = n_kv_heads or n_heads
+    hblk = -(-(n_heads // nkv) // KV8_HEADS_PER_WG)
+    want = -(-KV8_WGS // max(1, nkv * hblk * batch))
+    return max(1, min(want, max_seq // KV8_CHUNK_MIN))
+
+
+def attn_decode_kv8_chunk(max_seq, n_splits):
+    """keys per workgroup of a launch over ``n_splits`` chunks (amq_attn_kv8.hip: kv8_chunk)"""
+    return max(32, (-(-max_seq // n_splits) + 31) // 32 * 32)
+
+
+def attn_decode_kv8(q, k, v, kc8, ks, vc8, vs, out, pos, n_heads, n_kv_heads, table=None, cur=None, n_splits=0, rope_theta=10000.0):
+    """One new token per sequence over the 8-bit caches (ops.kv8_alloc): q [B, n_heads*128], k / v [B, n_kv_heads*128] un-rotated; the new row is
+    quantized and appended at ``pos`` (shared by the batch) and out [B, n_heads*128] is the attention over the dequantized rows 0 .. pos.  ``pos``:
+    an int with ``table`` (or neither: cos/sin computed in the kernel), or with ``cur`` the two views of one step-state block (ops.new_step_state).
+    ``n_splits``: workgroups per (sequence, kv head); 0 = :func:`attn_decode_kv8_splits`."""
+    B, nkv, max_seq = _need_kv8(kc8, ks, vc8, vs)
+    if nkv != n_kv_heads:
+        raise ValueError(f"caches of {nkv} kv heads, n_kv_heads={n_kv_heads}")
+    if n_splits == 0:
+        n_splits = attn_decode_kv8_splits(max_seq, n_heads, B, n_kv_heads)
+    _need(q, torch.float16, "q", B * n_heads * 128)
+    _need(k, torch.float16, "k", B * n_kv_heads * 128)
+    _need(v, torch.float16, "v", B * n_kv_heads * 128)
+    _need(out, torch.float16, "out", B * n_heads * 128)
+    if isinstance(pos, torch.Tensor):
+        _need(pos, torch.int32, "pos", 1)
+        pos_dev, pos_i = ctypes.cast(pos.data_ptr(), ctypes.c_void_p), 0
+    else:
+        pos_dev, pos_i = None, int(pos)
+        if not 0 <= pos_i < max_seq:
+            raise ValueError(f"pos {pos_i} outside the cache (max_seq={max_seq})")
+    if cur is not None:
+        _need(cur, torch.float16, "rope_cur", 128)
+        if pos_dev is None or pos.data_ptr() != cur.data_ptr() + 256:
+            raise ValueError("cur / pos must be the two views of one step-state block (ops.new_step_state)")
+    if table is not None:
+        _need(table, torch.float16, "rope table", max_seq * 128)
+    lib = _lib.load()
+    wsb = lib.amq_attn_decode_kv8_workspace_bytes(B, n_heads, n_splits)
+    ws, tickets = _ATTN_WS.get(q.device, wsb // 4), _ATTN_TICKETS.get(q.device, B * n_kv_heads * 2)
+    _lib.check(lib.amq_attn_decode_kv8_f16(*map(_lib.ptr, (q, k, v, kc8, ks, vc8, vs, out, cur)), pos_dev, pos_i, B, n_heads, n_kv_heads, 128, max_seq,
+                                           ctypes.c_float(rope_theta), _lib.ptr(table), n_splits, _lib.ptr(ws), wsb, _lib.ptr(tickets),
+                                           _lib.current_stream()))
+    return out
+
+
 # ---- prompt-lookup speculative decoding (include/amq_hip.h: "prompt-lookup speculative decoding"; amq_decode.hip ROWS instantiations, amq_lookup.hip)
 LOOKUP_STATE_WORDS = _lib.LOOKUP_STATE_WORDS
 LOOKUP_DRAFTS, LOOKUP_NGRAM, LOOKUP_MODE, LOOKUP_COUNT, LOOKUP_STEPS, LOOKUP_ACCEPTED, LOOKUP_TICKET, LOOKUP_DRAFT, LOOKUP_ARGMAX = 0, 1, 2, 3, 4, 5, 6, 8, 16

@@ -175,21 +175,24 @@ class HFForwardRunner:
 
 
 @torch.inference_mode()
-def benchmark_speed(model, tokenizer=None, use_ft=True, iteration=1, sizes=(1, 128, 128), mode="TPS", get_peak_memory=True):
+def benchmark_speed(model, tokenizer=None, use_ft=True, iteration=1, sizes=(1, 128, 128), mode="TPS", get_peak_memory=True, kv_bits=16):
     """speed.py:131-255.  ``model``: a runner with reset()/prefill()/decode_step()/generate() (QuantLlama or DenseLlama), or --
     the reference's calling convention (amq_speed_benchmark.py:152, 253) -- a swapped HF ``LlamaForCausalLM`` itself: with
     ``use_ft`` (default, the reference's fast path) the runner is built over its modules (QuantLlama.from_hf: shared weights,
     static cache, fused token step), as the reference's FT monkeypatch does to its HF model; with ``use_ft=False`` HF's own forward /
     ``generate`` is timed (HFForwardRunner: the reference's non-FT loops).  ``tokenizer``: used by TTFT mode as in
-    the reference (None: ids are used directly)."""
+    the reference (None: ids are used directly).  ``kv_bits`` (extension): the KV cache of the runner built over an HF model here (8: int8 rows
+    with a scale per row; a runner handed in keeps the cache it was built with)."""
     assert mode.lower() in ["tps", "gemv", "gemm", "ttft"], \
         "speed benchmark mode should be one of ['TPS', 'GeMV', 'GeMM', 'TTFT']"
     batch_size, input_seq_len, gen_seq_len = sizes
     if not hasattr(model, "decode_step") and hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers"):
         if use_ft:
             from .llama import QuantLlama
-            model = QuantLlama.from_hf(model, max_seq=max(input_seq_len + gen_seq_len, 64), batch=batch_size if batch_size <= 8 else 1)
+            model = QuantLlama.from_hf(model, max_seq=max(input_seq_len + gen_seq_len, 64), batch=batch_size if batch_size <= 8 else 1, kv_bits=kv_bits)
         else:
+            if kv_bits != 16:
+                raise ValueError("kv_bits=8 is the runner's cache: not offered with use_ft=False (HF's own forward keeps its own)")
             model = HFForwardRunner(model, batch=batch_size)
     if batch_size != getattr(model, "B", 1):
         # a runner built for another batch (the reference's FT path has a batch-1 cache, ftllama_modeling.py:61-68): the

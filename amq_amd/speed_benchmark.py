@@ -52,6 +52,8 @@ def main(argv=None):
     p.add_argument("--tokenizer", type=str, default="auto",
                    help="(extension) TTFT tokenizer: a tokenizer.json path, 'synthetic' (one word per vocabulary id), 'none' (ids "
                         "used directly), or 'auto' = tokenizer.json of the checkpoint directory if present, else synthetic")
+    p.add_argument("--kv_bits", type=int, default=16, choices=(16, 8),
+                   help="(extension) KV cache of the quantized runner: 16 = fp16 rows, 8 = int8 rows with a scale per row")
     args = p.parse_args(argv)
 
     def ckpt_dir(bits):
@@ -129,14 +131,17 @@ def main(argv=None):
         missing = [ckpt_dir(b) for b in used if not os.path.isdir(ckpt_dir(b))]
         if missing:
             raise FileNotFoundError(f"the arch needs HQQ checkpoints that are not there: {missing}")
-        model = checkpoint.load_mixed({b: ckpt_dir(b) for b in used}, linear, max_seq=max_seq, batch=run_batch)
+        model = checkpoint.load_mixed({b: ckpt_dir(b) for b in used}, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits)
     else:
-        model = QuantLlama(cfg, linear, max_seq=max_seq, batch=run_batch)
+        model = QuantLlama(cfg, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits)
     run(model, f"{args.target_bits}bit")
     del model
     cleanup()
 
-    result.update({"args": vars(args)})
+    shown = dict(vars(args))
+    if shown.get("kv_bits") == 16:
+        del shown["kv_bits"]                     # the default: the reference-compatible output as it was
+    result.update({"args": shown})
     if args.file_name:
         out_path = os.path.join("benchmark/outputs", args.file_name)      # amq_speed_benchmark.py:290-293
         os.makedirs(os.path.dirname(out_path), exist_ok=True)

@@ -520,6 +520,32 @@ int amq_attn_decode_split_f16(const void* q, const void* k, const void* v, void*
                               int head_dim, int max_seq, float rope_theta, const void* rope_table, int n_splits,
                               void* workspace, size_t workspace_bytes, void* tickets, void* stream);
 
+/* 8-bit KV cache.  Per block four caller-owned tensors: kc8 / vc8 int8 [batch][n_kv_heads][max_seq][128] and ks / vs fp32
+ * [batch][n_kv_heads][max_seq] -- one scale per (sequence, kv head, position), K and V separately; 132 bytes per row instead of 256.  A row r
+ * (the fp16 values the fp16 cache would hold) is stored as a = max |r_i| (fp32), s = a / 127, c_i = clamp(rint(r_i / s), -127, 127) with ties to
+ * even -- every step ONE rounded fp32 operation; a == 0 gives s = 0 and codes 0; a row that holds inf or NaN gives a NaN scale and codes 0.
+ * The value a row stands for is fp32(c_i) * s.
+ * amq_kv8_store_f16: the prompt pass.  k / v fp16 [batch * S][n_kv_heads * 128] contiguous (k ROTATED, e.g. by amq_rope_rows_f16) go into rows
+ * pos0 .. pos0 + S - 1 of every sequence's slice in one launch. */
+int amq_kv8_store_f16(const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, int pos0, int S, int batch, int n_kv_heads,
+                      int head_dim, int max_seq, void* stream);
+/* amq_attn_decode_kv8_f16: one new token per sequence at a position shared by the batch.  q and the new k are rotated with the fp16 expression
+ * of amq_attn_decode_f16, the new k / v rows are quantized (the bytes amq_kv8_store_f16 writes for the same row) and appended by exactly one
+ * workgroup per (sequence, kv head), and out = softmax(q K^T / sqrt 128) V over the DEQUANTIZED rows 0 .. pos -- the new row included in its
+ * dequantized form.  Scores (sum_i q_i c_ti) * s_t * (1 / sqrt 128) in fp32 (never rounded to fp16), softmax in fp32, probabilities NOT rounded
+ * to fp16, sum_t (p_t s_t) c_ti in fp32, fp16 output.  1 .. 16 query heads per kv head: one workgroup serves up to 8 heads of a kv head from one
+ * read of its rows.  n_splits >= 1 workgroups share a (sequence, kv head): chunks of ceil(max_seq / n_splits) keys rounded up to 32; chunks beyond
+ * the position leave at once, the last arriver combines in chunk order (deterministic).  step_state != NULL: position / rotation / error word
+ * from the step-state block (as amq_attn_decode_cur_f16; pos_dev, pos, rope_theta, rope_table ignored); else as amq_attn_decode_f16.  A device
+ * position outside 0 .. max_seq - 1 is a no-op (nothing appended, no output; error word raised in step-state mode).  workspace:
+ * amq_attn_decode_kv8_workspace_bytes bytes, no initialisation; tickets: int32 [batch * n_kv_heads * 2], ZERO before the first launch, left zero
+ * by every launch; neither may be shared by launches that can run concurrently. */
+size_t amq_attn_decode_kv8_workspace_bytes(int batch, int n_heads, int n_splits);
+int amq_attn_decode_kv8_f16(const void* q, const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, void* out,
+                            const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
+                            int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
+                            void* tickets, void* stream);
+
 /* End of a greedy token step in one launch: token[0] = argmax(logits[0..vocab)) (first maximum), pos[0] += 1,
  * x[0..hidden) = embed[token][0..hidden); when rope_table / rope_cur are given (both or neither) also
  * rope_cur[0..128) = rope_table[min(pos, rope_rows - 1)][0..128), the cos/sin row amq_attn_decode_cur_f16 reads in the next step.  Replaces the `torch.argmax` / position increment / embedding gather that follow
