@@ -149,6 +149,9 @@ SIGNATURES = {
     "amq_gemm_xfrag_grouped_form_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "amq_attn_prefill_xfrag_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 5 + [_vp]),
     "amq_gemv_f16w_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
+    # the 8-bit lm_head: (x, codes, meta, y, gamma, eps, M, N, K, group, stream) / (codes, meta, out, row0, rows, N, K, group, stream)
+    "amq_lm8_gemv_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    "amq_lm8_dequantize_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "amq_decode_tail_batch_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "amq_decode_tail_suppress_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "amq_sample_f16": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

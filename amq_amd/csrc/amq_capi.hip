@@ -1007,6 +1007,45 @@ int amq_gemv_f16w_rows(const void* x, const void* W, const void* bias, void* y, 
     return check_hip(amq::launch_gemv_f16w(x, W, bias, y, gamma, eps, N, K, (hipStream_t)stream, M), "gemv_f16w_rows");
 }
 
+/* ---- the 8-bit lm_head (amq_lm8.hip): what both entry points require of the layer, one rule per refusal ---- */
+static int check_lm8(const char* who, int N, int K, int group) {
+    if (group != 128) return fail(AMQ_ESHAPE, "%s: group must be 128 (got %d)", who, group);
+    if (K < 128 || (K % 128) != 0) return fail(AMQ_ESHAPE, "%s: K must be a positive multiple of 128 (got %d)", who, K);
+    if (N < 1) return fail(AMQ_ESHAPE, "%s: N must be >= 1 (got %d)", who, N);
+    return AMQ_OK;
+}
+// the kernels move x, gamma, codes and the dequantized rows in 16-byte pieces and a (scale, zero) pair as one dword
+static int check_lm8_aligned(const char* who, const char* name, const void* p, size_t align) {
+    if (p && ((size_t)p % align) != 0) return fail(AMQ_EINVAL, "%s: %s must be %d-byte aligned", who, name, (int)align);
+    return AMQ_OK;
+}
+
+int amq_lm8_gemv_f16(const void* x, const void* codes, const void* meta, void* y, const void* gamma, float eps, int M, int N, int K, int group,
+                     void* stream) {
+    const char* who = "amq_lm8_gemv_f16";
+    if (!x || !codes || !meta || !y) return fail(AMQ_EINVAL, "%s: null pointer", who);
+    if (int rc = check_lm8_aligned(who, "x", x, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "codes", codes, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "meta", meta, 4)) return rc;
+    if (int rc = check_lm8_aligned(who, "gamma", gamma, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "y", y, 2)) return rc;
+    if (M < 1 || M > 8) return fail(AMQ_ESHAPE, "%s: M must be 1..8 (got %d)", who, M);
+    if (int rc = check_lm8(who, N, K, group)) return rc;
+    if (amq::lm8_gemv_lds_bytes(M, K) > LDS_LIMIT) return fail(AMQ_ESHAPE, "%s: %d rows of K=%d do not fit LDS", who, M, K);
+    return check_hip(amq::launch_lm8_gemv(x, codes, meta, y, gamma, eps, M, N, K, (hipStream_t)stream), "lm8_gemv");
+}
+
+int amq_lm8_dequantize_f16(const void* codes, const void* meta, void* out, int row0, int rows, int N, int K, int group, void* stream) {
+    const char* who = "amq_lm8_dequantize_f16";
+    if (!codes || !meta || !out) return fail(AMQ_EINVAL, "%s: null pointer", who);
+    if (int rc = check_lm8_aligned(who, "codes", codes, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "meta", meta, 4)) return rc;
+    if (int rc = check_lm8_aligned(who, "out", out, 16)) return rc;
+    if (int rc = check_lm8(who, N, K, group)) return rc;
+    if (row0 < 0 || rows < 1 || rows > N - row0) return fail(AMQ_ESHAPE, "%s: rows %d .. %d + %d outside the layer's %d rows", who, row0, row0, rows, N);
+    return check_hip(amq::launch_lm8_dequantize(codes, meta, out, row0, rows, K, (hipStream_t)stream), "lm8_dequantize");
+}
+
 /* ---- decode attention: ten entry points, one validator and dispatcher.  What differs between them is the AttnForm ("Decode-step
    entry points: what is checked"); the checks run in the order of this function for every one of them ---- */
 enum : unsigned {           // where the position(s) of the new token(s) may come from

@@ -247,6 +247,11 @@ hipError_t launch_set_token(const void* token_in, int n_in, const void* embed, i
                             const void* rope_table, void* rope_cur, int rope_rows, int batch, hipStream_t st, bool seq = false);
 hipError_t launch_gemv_f16w(const void* x, const void* W, const void* bias, void* y, const void* gamma, float eps,
                             int N, int K, hipStream_t st, int M = 1);      // x [M, K], y [M, N], M <= 8
+// the 8-bit lm_head (amq_lm8.hip): codes uint8 [N, K], meta fp16 [N, K / 128, 2]; K % 128 == 0, 1 <= M <= 8
+size_t lm8_gemv_lds_bytes(int M, int K);
+hipError_t launch_lm8_gemv(const void* x, const void* codes, const void* meta, void* y, const void* gamma, float eps, int M, int N, int K,
+                           hipStream_t st);
+hipError_t launch_lm8_dequantize(const void* codes, const void* meta, void* out, int row0, int rows, int K, hipStream_t st);
 
 // sampling tail / row sampler (amq_sample.hip).  state: the 128-byte device block of include/amq_hip.h (int32 word indices below)
 enum { SMP_TEMPERATURE = 0, SMP_TOP_K = 1, SMP_TOP_P = 2, SMP_PAD_ID = 3, SMP_SEED = 4, SMP_DRAW = 6, SMP_EOS = 8, SMP_FINISHED = 16,

@@ -123,8 +123,23 @@ def _bound(model, key, need, **build):
     old = per.get(key)
     if old is not None and old.max_seq >= need and _same_weights(old, model):
         return old, None
-    per[key] = QuantLlama.from_hf(model, max_seq=_bucket(need, _limit(model)), **build)
+    per[key] = QuantLlama.from_hf(model, max_seq=_bucket(need, _limit(model)), **build, **_lm_head_build(model))
     return per[key], old
+
+
+def _lm_head_build(model):
+    """from_hf's lm_head arguments: nothing for the fp16 lm_head; convert_model_to_hip(model, lm_head_bits=8 / 4): the bits and the ONE packed
+    lm_head kept per converted model -- quantized on first use, shared by every runner built or rebuilt for it (growth, batch sizes, ragged,
+    lookup), quantized again only when the module's weight is no longer the tensor it was made from"""
+    from .llama import QuantLlama
+    bits = model.__dict__.get("_amq_lm_head_bits", 16)
+    if bits == 16:
+        return {}
+    w = model.lm_head.weight
+    kept = model.__dict__.get("_amq_lm_head_packed")
+    if kept is None or kept[0] != (bits, w.data_ptr(), w._version):
+        kept = model.__dict__["_amq_lm_head_packed"] = ((bits, w.data_ptr(), w._version), QuantLlama.pack_lm_head(w.detach().to(torch.float16), bits))
+    return dict(lm_head_bits=bits, lm_head_packed=kept[1])
 
 
 def _lookup_runner(model, need, k, g):
@@ -371,7 +386,7 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     return torch.cat([ids, new.view(B, -1).to(ids.dtype)], dim=1)
 
 
-def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scoring=False, kv_bits=16):
+def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scoring=False, kv_bits=16, lm_head_bits=16):
     """convert_model_to_ft(model) + replace_generate_functions() (ftllama_modeling.py:569-580, ftllama_generate.py:613-622) for the HIP backend:
     call it on the model ``prepare_for_inference(model, backend='hip')`` returned (a Llama-family ``*ForCausalLM`` whose decoder linears are
     HIPQuantLinear modules on one GPU).  Patches THIS instance's ``forward`` and ``generate`` (see the module docstring); idempotent; returns the
@@ -381,7 +396,9 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
     prompt-lookup speculative runner (``lookup_request``), greedy ones -- and with ``sampling=True`` as well ``do_sample=True`` ones; ``scoring=True`` keeps ``model(ids, start_pos=0, labels=..., use_cache=False)`` on the runner and
     returns HF's shifted cross-entropy as ``loss``; ``kv_bits=8``: the runners keep an 8-bit KV cache (int8 rows with a scale per row, DESIGN.md 3.13:
     ``generate`` greedy and sampled, one-row ``model(ids, start_pos=p)`` steps; a many-row call at ``start_pos`` > 0 raises; refused together with
-    ``lookup=True`` / ``padded=True``).  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
+    ``lookup=True`` / ``padded=True``); ``lm_head_bits=8`` / ``4``: the runners read a packed lm_head (QuantLlama(lm_head_bits=)),
+    quantized once from ``model.lm_head.weight`` and shared by every runner of the model; the module itself keeps its fp16 weight, so HF's own
+    forward and a reverted model are untouched.  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
     if kv_bits not in (8, 16):
@@ -389,9 +406,16 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
     if kv_bits == 8 and (lookup or padded):
         raise ValueError("kv_bits=8 is not offered together with " + ("lookup=True" if lookup else "padded=True") + ": the 8-bit attention kernel "
                          "runs one row per sequence at one position for the batch (QuantLlama(kv_bits=8))")
-    if model.__dict__.get("_amq_kv_bits", kv_bits) != kv_bits:
-        _RUNNERS.pop(model, None)                               # runners hold a cache of the other format
+    if lm_head_bits not in (16, 8, 4):
+        raise ValueError(f"lm_head_bits must be 16 (fp16 lm_head), 8 (the LM8 layer) or 4 (a packed 4-bit layer), got {lm_head_bits!r}")
+    if model.__dict__.get("_amq_kv_bits", kv_bits) != kv_bits or model.__dict__.get("_amq_lm_head_bits", 16) != lm_head_bits:
+        _RUNNERS.pop(model, None)                               # runners hold a cache of the other format / another lm_head
+        model.__dict__.pop("_amq_lm_head_packed", None)
     model.__dict__["_amq_kv_bits"] = int(kv_bits)
+    if lm_head_bits == 16:
+        model.__dict__.pop("_amq_lm_head_bits", None)
+    else:
+        model.__dict__["_amq_lm_head_bits"] = int(lm_head_bits)
     if "_amq_orig_forward" in model.__dict__:
         model.__dict__["_amq_sampling"] = bool(sampling)
         model.__dict__["_amq_padded"] = bool(padded)
@@ -421,6 +445,8 @@ def revert_model_to_hf(model):
     model.__dict__.pop("_amq_lookup", None)
     model.__dict__.pop("_amq_scoring", None)
     model.__dict__.pop("_amq_kv_bits", None)
+    model.__dict__.pop("_amq_lm_head_bits", None)
+    model.__dict__.pop("_amq_lm_head_packed", None)
     _RUNNERS.pop(model, None)
     return model
 

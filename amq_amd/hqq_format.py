@@ -91,6 +91,49 @@ def quantize_rtn(W: torch.Tensor, nbits: int, group_size: int = GROUP, bias=None
                       nbits, (n, k), group_size, bias, name)
 
 
+@dataclass
+class LM8Weights:
+    """the 8-bit lm_head ("LM8"): what ops.lm8_gemv / ops.lm8_dequantize take.  The order on the device is the logical one."""
+    codes: torch.Tensor          # uint8 [N, K]
+    meta: torch.Tensor           # fp16 [N, K / 128, 2] = (scale, zero) per group of 128 along K: the scale multiplies, the zero is fractional
+    shape: tuple                 # (N, K)
+    group_size: int = GROUP
+    nbits: int = 8
+
+    def to(self, device):
+        return LM8Weights(self.codes.to(device), self.meta.to(device), tuple(self.shape), self.group_size)
+
+    def nbytes(self):
+        return self.codes.numel() + self.meta.numel() * 2
+
+
+def quantize_lm8(W: torch.Tensor) -> LM8Weights:
+    """Min/max round-to-nearest at 8 bits over groups of 128 along K, with the arithmetic of :func:`quantize_rtn` at maxv = 255 (fp32 min / max per
+    group, the same degenerate-range rule and scale clamp, codes round(w * scale + zero).clamp(0, 255), meta rounded to fp16), as torch ops on W's
+    device: it runs once per model.  HQQ's proximal solver is not run at 8 bits.  A value of W that is not finite raises ValueError."""
+    if W.dim() != 2 or W.shape[0] < 1 or W.shape[1] < GROUP or W.shape[1] % GROUP:
+        raise ValueError(f"quantize_lm8: expected W [N, K] with K a multiple of {GROUP}, got {tuple(W.shape)}")
+    if not bool(torch.isfinite(W).all()):
+        raise ValueError("quantize_lm8: W holds inf or NaN")
+    n, k = W.shape
+    codes = torch.empty(n, k, dtype=torch.uint8, device=W.device)
+    meta = torch.empty(n, k // GROUP, 2, dtype=torch.float16, device=W.device)
+    step = max(1, (64 << 20) // k)              # rows a pass: the fp32 temporaries stay at a few times 256 MB whatever the vocabulary (groups are independent)
+    for r0 in range(0, n, step):
+        wg = W[r0:r0 + step].float().reshape(-1, GROUP)
+        mn = wg.min(dim=1, keepdim=True)[0]
+        mx = wg.max(dim=1, keepdim=True)[0]
+        denom = mx - mn
+        scale = 255.0 / denom
+        scale = torch.where(denom.abs() <= 1e-4, torch.ones_like(scale), scale).clamp(max=2e4)
+        zero = -mn * scale
+        q = (wg * scale + zero).round().clamp(0, 255.0)
+        rows = wg.shape[0] * GROUP // k
+        codes[r0:r0 + rows] = q.to(torch.uint8).reshape(rows, k)
+        meta[r0:r0 + rows] = torch.cat([(1.0 / scale).to(torch.float16), zero.to(torch.float16)], dim=1).reshape(rows, k // GROUP, 2)
+    return LM8Weights(codes, meta, (n, k))
+
+
 def quantize_hqq(W: torch.Tensor, nbits: int, group_size: int = GROUP, bias=None, name=None) -> HQQWeights:
     """HQQ's quantizer with its proximal solver (quantize.py:76-180, optimize.py:201-255) on W's GPU: the device sibling of
     :func:`quantize_rtn`, same conventions and return type.  Groups of 32, 64, 128 and 256."""

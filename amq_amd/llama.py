@@ -67,6 +67,19 @@ def _synthetic_linear(n, k, bits, gen, device, group=128):
     return _Lin(qn, meta.reshape(-1).contiguous(), bits, ops.MODE_HQQ, n, k)
 
 
+def lm8_logits_sliced(xn, w8, out, scratch):
+    """out [n, vocab] = xn [n, H] . W^T over the 8-bit lm_head ``w8`` (xn already normed), a slice of ``scratch.shape[0]`` vocabulary rows at a
+    time (a multiple of 16, as the vocabulary): ops.lm8_dequantize into the scratch, the fp16 GEMM into the slice's columns of ``out``"""
+    vocab, step = w8.shape[0], scratch.shape[0]
+    if vocab % 16 or step % 16:
+        raise ValueError(f"the fp16 GEMM writes 16-column blocks: a vocabulary of {vocab} in slices of {step} rows is not served")
+    for n0 in range(0, vocab, step):
+        rows = min(step, vocab - n0)
+        w = ops.lm8_dequantize(w8, n0, rows, out=scratch[:rows])
+        ops.gemm_f16w(xn, w, out=out if rows == vocab else out[:, n0:n0 + rows])
+    return out
+
+
 _GRAPH_STATE_PRIMED = set()
 
 
@@ -226,6 +239,14 @@ class QuantLlama:
     # per-head kernels (every grouped-query lookup runner of the older tests keeps its arithmetic).
     ROWS_GQA_FROM = 2048
     kv_bits = 16                # (the instance's own after QuantLlama.__init__; the fp16 baseline runner, which has its own __init__, keeps fp16 rows)
+    lm_head_bits, lm_head_q = 16, None      # (the instance's own after QuantLlama.__init__; the fp16 baseline runner keeps its fp16 lm_head)
+    # many-row logits over the 8-bit lm_head: vocabulary rows dequantized at a time (the fp16 scratch: 128 MB at H = 4096), and the row count from
+    # which that route is taken.  One pass of the dequantize kernel over the whole layer moves what about three 8-row launches of the
+    # weight-streaming kernel move (codes read, fp16 written), and the GEMM comes on top: 64 rows = 8 launches is past that by a safe factor.
+    # Reasoned, not tuned; profiles/lm_head_bits.json has both routes at 2048 rows.
+    LM8_SLICE_ROWS = 16384
+    LM8_SLICED_FROM = 64
+    _lm8_scratch = None
     ENGINE_DEFAULT = False      # what engine=None means (the engine is opt-in until it beats the five-launch step: HISTORY.md 3.2b)
     # prompt passes also leave the logits of EVERY prompt row in self.logits_rows [B, S, vocab] (HF's forward returns them all; the runner's own
     # generate loop needs the last row only): final norm + one fp16 GEMM over the prompt rows, inside the captured prompt graph (hf_fast.py sets it)
@@ -242,7 +263,7 @@ class QuantLlama:
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
                  hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2,
-                 lookup_sampling=False, kv_bits=16):
+                 lookup_sampling=False, kv_bits=16, lm_head_bits=16, lm_head_packed=None):
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
@@ -268,12 +289,25 @@ class QuantLlama:
         kv_bits: 16 -- the fp16 KV cache, the object, graphs and bits the runner has always had; 8 -- int8 rows with one fp32 scale per (sequence,
         kv head, position) (blocks hold kc8 / ks / vc8 / vs, 132 bytes per row instead of 256; the token step issues
         ops.attn_decode_kv8, the prompt pass stays exact fp16 and stores its rows with one ops.kv8_store).  Not offered with ragged=True, lookup=,
-        a qk_norm config, the decode engine, the fused q/k/v + attention launch or a prompt pass at start_pos > 0."""
+        a qk_norm config, the decode engine, the fused q/k/v + attention launch or a prompt pass at start_pos > 0.
+        lm_head_bits: 16 -- the fp16 lm_head, the object, graphs and bits the runner has always had; 8 -- the lm_head is quantized once, here, to
+        the LM8 layer (hqq_format.quantize_lm8) and every logit comes from ops.lm8_gemv; 4 -- ops.hqq_quantize(W, 4) and the packed
+        GEMV / GEMM kernels of the block linears.  The runner then keeps no fp16 lm_head (self.lm_head is None; self.lm_head_q is the packed layer).
+        Not offered with the decode engine or the fused q/k/v + attention launch.  lm_head_packed: the packed layer of an earlier runner over the
+        same weights (hf_fast shares one among the runners it builds), instead of quantizing again."""
         if isinstance(config, str):
             config = MODEL_CONFIGS[config]
         if kv_bits not in (8, 16):
             raise ValueError(f"kv_bits must be 16 (fp16 cache) or 8 (int8 rows with a scale per row), got {kv_bits!r}")
         self.kv_bits = int(kv_bits)
+        if lm_head_bits not in (16, 8, 4):
+            raise ValueError(f"lm_head_bits must be 16 (fp16 lm_head), 8 (the LM8 layer) or 4 (a packed 4-bit layer), got {lm_head_bits!r}")
+        self.lm_head_bits = int(lm_head_bits)
+        if self.lm_head_bits != 16:
+            if engine:
+                raise ValueError(f"lm_head_bits={self.lm_head_bits}: not offered with the decode engine (an A/B route: it is followed by the fp16 lm_head only)")
+            if self.FUSE_QKV_ATTN:
+                raise ValueError(f"lm_head_bits={self.lm_head_bits}: not offered with the fused q/k/v + attention launch (an A/B route: fp16 lm_head only)")
         if self.kv_bits == 8:
             # the 8-bit attention kernel keeps one position for the batch, runs one row per sequence and carries no per-head norm
             if ragged:
@@ -379,6 +413,12 @@ class QuantLlama:
             self.embed = (torch.randn(self.vocab, self.H, device=dev, generator=gen)).to(torch.float16)
             self.lm_head = (torch.randn(self.vocab, self.H, device=dev, generator=gen) / math.sqrt(self.H)).to(torch.float16)
             self.norm = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
+        self.lm_head_q = None
+        if self.lm_head_bits != 16:
+            # quantized once, here; the fp16 tensor is dropped (from_hf: the HF module keeps its own) so that no path can read a dense lm_head
+            self.lm_head_q = lm_head_packed if lm_head_packed is not None else self.pack_lm_head(self.lm_head, self.lm_head_bits)
+            self._check_lm_head_q()
+            self.lm_head = None
 
         # layers with groups of 64 / 32 (HQQ's default group_size is 64): the decode step is the same five launches (amq_gemv_grouped_f16 takes the
         # group size); the prompt pass leaves the fragment-ordered few-row kernels alone (they read one (scale, zero) pair per tile) and runs
@@ -556,7 +596,8 @@ class QuantLlama:
                 raise ValueError(f"{where}.{name}: eps {m_eps} is not the model's rms_norm_eps {eps} (the runner keeps one eps)")
 
     @classmethod
-    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False, kv_bits=16):
+    def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False, kv_bits=16,
+                lm_head_bits=16, lm_head_packed=None):
         """The hipGraph runner over a SWAPPED HF causal LM of the Llama family (``HF_MODEL_TYPES``: Llama 2 / 3.x, Mistral, Qwen2.5) -- what
         ``prepare_for_inference(model, backend="hip")`` (or the reference's deepcopy + setattr assembly of a mixed-precision model,
         amq_speed_benchmark.py:231-256) leaves behind.  The runner shares the modules' native weight buffers and biases, the embedding, lm_head and
@@ -600,7 +641,90 @@ class QuantLlama:
             dense["qn"] = [f16(l.self_attn.q_norm.weight).contiguous() for l in layers]
             dense["kn"] = [f16(l.self_attn.k_norm.weight).contiguous() for l in layers]
         return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
-                   ragged=ragged, lookup=lookup, ngram_max=ngram_max, lookup_sampling=lookup_sampling, kv_bits=kv_bits)
+                   ragged=ragged, lookup=lookup, ngram_max=ngram_max, lookup_sampling=lookup_sampling, kv_bits=kv_bits,
+                   lm_head_bits=lm_head_bits, lm_head_packed=lm_head_packed)
+
+    # ----------------------------------------------------------------- the lm_head
+    @staticmethod
+    def pack_lm_head(W, bits):
+        """the packed lm_head of ``bits`` (8: hqq_format.LM8Weights; 4: a _Lin in the native layout) from the fp16 weights W [vocab, H] on the GPU"""
+        vocab, H = W.shape
+        if bits == 8:
+            from .hqq_format import quantize_lm8
+            if H % 128:
+                raise ValueError(f"lm_head_bits=8: the LM8 layer has groups of 128 along the hidden size (got {H})")
+            return quantize_lm8(W.contiguous())
+        if vocab % 16 or H % 128:
+            raise ValueError(f"lm_head_bits=4: the packed kernels need N % 16 == 0 and K % 128 == 0 (got a vocabulary of {vocab}, hidden size {H})")
+        h = ops.hqq_quantize(W.contiguous(), 4)
+        qn, mn = ops.repack_from_hqq(h.W_q.contiguous(), h.scale.reshape(-1).contiguous(), h.zero.reshape(-1).contiguous(), 4, vocab, H)
+        return _Lin(qn, mn, 4, ops.MODE_HQQ, vocab, H)
+
+    def _check_lm_head_q(self):
+        q, want = self.lm_head_q, (self.vocab, self.H)
+        if self.lm_head_bits == 8:
+            ok = tuple(getattr(q, "shape", ())) == want and getattr(q, "nbits", 0) == 8 and q.codes.device == self.dev
+        else:
+            ok = isinstance(q, _Lin) and (q.N, q.K, q.bits) == want + (4,) and q.qn.device == self.dev
+        if not ok:
+            raise ValueError(f"lm_head_packed is not a {self.lm_head_bits}-bit lm_head of shape {want} on {self.dev}")
+
+    def lm_head_bytes(self):
+        """bytes of the lm_head a token step streams: fp16, or the packed layer's codes + meta"""
+        return self.lm_head.numel() * 2 if self.lm_head_bits == 16 else self.lm_head_q.nbytes()
+
+    def lm_head_weights(self):
+        """the fp16 weights [vocab, H] the lm_head stands for (a packed one: dequantized, a new tensor)"""
+        if self.lm_head_bits == 16:
+            return self.lm_head
+        if self.lm_head_bits == 8:
+            return ops.lm8_dequantize(self.lm_head_q)
+        q = self.lm_head_q
+        return ops.dequantize(q.qn, q.mn, q.bits, q.mode, q.N, q.K)
+
+    def _lm_logits(self, x, out):
+        """out = lm_head(final RMSNorm(x)) for up to 8 hidden rows -- x [H] -> out [vocab], or x [M, H] -> out [M, vocab] --: the ONE place a token
+        step, a prompt pass' last rows and the streamed many-row loop form logits.  16: the fp16 weight-streaming kernel with the norm as its
+        prologue; 8: ops.lm8_gemv, the same shape; 4: the packed GEMV with the RMSNorm prologue as far as its LDS stage reaches
+        (ops.gemv_max_rows(H)), an rmsnorm launch + the plain GEMV beyond (what _behind_norm does), the GEMM past that"""
+        if self.lm_head_bits == 16:
+            return ops.gemv_f16w(x, self.lm_head, gamma=self.norm, eps=self.eps, out=out)
+        if self.lm_head_bits == 8:
+            return ops.lm8_gemv(x, self.lm_head_q, gamma=self.norm, eps=self.eps, out=out)
+        q = self.lm_head_q
+        x2, y = x.reshape(-1, self.H), out.view(-1, self.vocab)
+        M = x2.shape[0]
+        if M <= ops.gemv_max_rows(self.H):
+            ops.gemv_grouped(x2, [q.seg(y)], self.H, prologue=ops.PRO_RMSNORM, gamma=self.norm, eps=self.eps)
+        elif M <= ops.gemv_max_rows(self.H, plain=True, norm=False):
+            ops.gemv_grouped(ops.rmsnorm(x2, self.norm, self.eps), [q.seg(y)], self.H)
+        else:
+            ops.gemm(ops.rmsnorm(x2, self.norm, self.eps), q.qn, q.mn, q.bits, q.mode, q.N, q.K, out=y)
+        return out
+
+    def _lm_logits_many(self, x, out=None):
+        """out [n, vocab] = lm_head(final RMSNorm(x [n, H])) for any number of rows (an all-logits prompt pass, a piece of score_rows).  16: one
+        fp16 MFMA GEMM (the weight-streaming kernel, 8 rows a launch, for a vocabulary that is no multiple of 16: test models); 4: ops.gemm over
+        the packed layer; 8: from LM8_SLICED_FROM rows on (and a vocabulary the fp16 GEMM takes) slices of LM8_SLICE_ROWS vocabulary rows dequantized
+        into one bounded fp16 scratch and the fp16 GEMM on each slice, writing its columns of ``out`` (lm8_logits_sliced); fewer rows: the
+        weight-streaming kernel, 8 rows a launch.  profiles/lm_head_bits.json has what a 2048-row window costs either way."""
+        n = x.shape[0]
+        if self.lm_head_bits == 8 and n >= self.LM8_SLICED_FROM and self.vocab % 16 == 0:
+            if out is None:
+                out = torch.empty(n, self.vocab, dtype=torch.float16, device=x.device)
+            rows = min(int(self.LM8_SLICE_ROWS), self.vocab)
+            if self._lm8_scratch is None or self._lm8_scratch.shape[0] != rows:
+                self._lm8_scratch = torch.empty(rows, self.H, dtype=torch.float16, device=self.dev)
+            return lm8_logits_sliced(ops.rmsnorm(x, self.norm, self.eps), self.lm_head_q, out, self._lm8_scratch)
+        if self.lm_head_bits == 16 and self.vocab % 16 == 0:
+            return ops.gemm_f16w(ops.rmsnorm(x, self.norm, self.eps), self.lm_head, out=out)
+        if out is None:
+            out = torch.empty(n, self.vocab, dtype=torch.float16, device=x.device)
+        if self.lm_head_bits == 4:
+            q = self.lm_head_q
+            ops.gemm(ops.rmsnorm(x, self.norm, self.eps), q.qn, q.mn, q.bits, q.mode, q.N, q.K, out=out)
+            return out
+        return self._lm_head_streamed(x, out)
 
     # ----------------------------------------------------------------- sizes
     def linear_bytes_per_token(self):
@@ -609,7 +733,7 @@ class QuantLlama:
 
     def total_bytes_per_token(self, context):
         kv = 2 * self.nb * self.nkv * (ops.KV8_ROW_BYTES if self.kv_bits == 8 else 256) * context       # K and V rows: 256 bytes of fp16, or 128 codes + a scale
-        return self.linear_bytes_per_token() + self.lm_head.numel() * 2 + kv
+        return self.linear_bytes_per_token() + self.lm_head_bytes() + kv
 
     # ----------------------------------------------------------------- decode
     def _step(self, sampled=False):
@@ -620,7 +744,7 @@ class QuantLlama:
             return self._step_staged(sampled)
         if self.engine is not None:
             self.engine.step()
-            ops.gemv_f16w(self.x.reshape(-1), self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
+            self._lm_logits(self.x.reshape(-1), self.logits)
             self._tail(sampled)
             return
         if self.ragged and self.fuse_qkv_attn:
@@ -663,7 +787,7 @@ class QuantLlama:
                 d = blk["mlp.down_proj"]
                 ops.gemm(ops.silu_mul(self.gate, self.up, out=self.gate), d.qn, d.mn, d.bits, d.mode, d.N, d.K, bias=d.bias, residual=self.x, out=self.x)
             first = plan.block_norm
-        ops.gemv_f16w(self.x.reshape(-1) if self.R == 1 else self.x, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
+        self._lm_logits(self.x.reshape(-1) if self.R == 1 else self.x, self.logits)
         self._tail(sampled)
 
     # ------------------------------------------------- the staged plan (OWQ layers)
@@ -728,7 +852,7 @@ class QuantLlama:
                     else:
                         ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
                                         cur=self.rope_cur, **self._qkn(blk))
-        ops.gemv_f16w(self.x.reshape(-1) if self.R == 1 else self.x, self.lm_head, gamma=self.norm, eps=self.eps, out=self.logits)
+        self._lm_logits(self.x.reshape(-1) if self.R == 1 else self.x, self.logits)
         self._tail(sampled)
 
     def _behind_norm(self, how, gamma, segments):
@@ -1149,7 +1273,7 @@ class QuantLlama:
                 out.copy_(self.logits_rows[each, lengths - 1])
         else:
             last = (x.view(B, S, self.H)[:, S - 1] if lengths is None else x.view(B, S, self.H)[each, lengths - 1]).contiguous()
-            ops.gemv_f16w(last[0] if B == 1 else last, self.lm_head, gamma=self.norm, eps=self.eps, out=out[0] if B == 1 else out)
+            self._lm_logits(last[0] if B == 1 else last, out[0] if B == 1 else out)
         if self.lookup:
             # the prompt goes into the history with a device copy, and the verify-and-propose tail itself -- run on the last prompt row's logits as
             # row 0 of a step at position S - 1 without drafts -- emits the first token, proposes the first drafts and leaves the step inputs of
@@ -1196,10 +1320,7 @@ class QuantLlama:
     def _logits_of_rows(self, x, B, S, last_logits):
         """logits of every prompt row, [B, S, vocab] fp16: final RMSNorm + ONE pass over the lm_head for all rows (fp16 MFMA GEMM); each sequence's
         last row is copied into ``last_logits`` (the runner's token choice), instead of a second pass over the lm_head for it"""
-        if self.vocab % 16 == 0:
-            rows = ops.gemm_f16w(ops.rmsnorm(x, self.norm, self.eps), self.lm_head).view(B, S, self.vocab)
-        else:                                   # (the fp16 GEMM writes 16-column blocks; odd vocabularies -- test models -- go through the weight-streaming kernel, 8 rows a launch)
-            rows = self._lm_head_streamed(x, torch.empty(B * S, self.vocab, dtype=torch.float16, device=x.device)).view(B, S, self.vocab)
+        rows = self._lm_logits_many(x).view(B, S, self.vocab)
         last_logits.view(B, self.vocab).copy_(rows[:, S - 1])
         return rows
 
@@ -1209,9 +1330,9 @@ class QuantLlama:
         for r0 in range(0, n, 8):
             r1 = min(n, r0 + 8)
             if r1 - r0 == 1:
-                ops.gemv_f16w(x[r0], self.lm_head, gamma=self.norm, eps=self.eps, out=out[r0])
+                self._lm_logits(x[r0], out[r0])
             else:
-                ops.gemv_f16w(x[r0:r1], self.lm_head, gamma=self.norm, eps=self.eps, out=out[r0:r1])
+                self._lm_logits(x[r0:r1], out[r0:r1])
         return out
 
     # rows of logits formed at a time by score_rows: the fp16 scratch is [SCORE_ROWS, vocab] (156 MB at 512 x 152064, against the 1.87 GB of a
@@ -1267,10 +1388,7 @@ class QuantLlama:
             for t0, t1 in chunks:
                 n = t1 - t0
                 rows, lg = x[b, t0:t1], scratch[:n]
-                if self.vocab % 16 == 0:
-                    ops.gemm_f16w(ops.rmsnorm(rows, self.norm, self.eps), self.lm_head, out=lg)
-                else:
-                    self._lm_head_streamed(rows, lg)
+                self._lm_logits_many(rows, lg)
                 ops.logit_nll(lg, labels[b, t0:t1], out=(nll[b, t0:t1], lse[:n], amax[:n]))
                 if jsd is not None:
                     ops.logit_jsd(lg, dense_logits[b, t0:t1].to(self.dev, non_blocking=True), out=jsd[b, t0:t1])
@@ -1388,9 +1506,9 @@ class QuantLlama:
         for b0 in range(0, B, 8):                   # the lm_head is streamed once per 8 sequences
             rows = slice(b0, min(B, b0 + 8))
             if rows.stop - rows.start == 1:
-                ops.gemv_f16w(last[b0], self.lm_head, gamma=self.norm, eps=self.eps, out=logits[b0])
+                self._lm_logits(last[b0], logits[b0])
             else:
-                ops.gemv_f16w(last[rows], self.lm_head, gamma=self.norm, eps=self.eps, out=logits[rows])
+                self._lm_logits(last[rows], logits[rows])
         return logits
 
     def _prefill_attention(self, q, blk, S, start_pos=0):
@@ -1618,7 +1736,7 @@ def get_memory_footprint(model, return_buffers=True):
     if isinstance(model, torch.nn.Module):
         mem = sum(p.nelement() * p.element_size() for p in model.parameters())
         return mem + (sum(b.nelement() * b.element_size() for b in model.buffers()) if return_buffers else 0)
-    tot = model.embed.numel() * 2 + model.lm_head.numel() * 2 + model.norm.numel() * 2
+    tot = model.embed.numel() * 2 + model.lm_head_bytes() + model.norm.numel() * 2
     for blk in model.blocks:
         for k, v in blk.items():
             if isinstance(v, torch.Tensor):

@@ -113,7 +113,7 @@ class ModuleWalkLlama(nn.Module):
         x = r.x
         for layer in self.layers:
             x = layer(x)
-        ops.gemv_f16w(x.reshape(-1), r.lm_head, gamma=r.norm, eps=r.eps, out=r.logits)     # final norm + fp16 lm_head
+        r._lm_logits(x.reshape(-1), r.logits)     # final norm + lm_head (fp16, or the runner's packed one)
         ops.decode_tail(r.logits, r.embed, r.token, r.pos, r.x, table=r.rope_tab, cur=r.rope_cur)
 
     def n_module_calls(self):

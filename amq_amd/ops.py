@@ -991,12 +991,23 @@ def gemm_res_norm_xfrag(x, qn, mn, bits, mode, N, K, gamma, eps, bias=None, resi
 
 def gemm_f16w(x, w, bias=None, out=None, residual=None, gate=None):
     """y = x . w^T for DENSE fp16 weights w [N, K] (hand-written ping-pong MFMA kernel, amq_gemm_f16.hip): what GEMM_DEQ runs behind
-    :func:`dequantize`; ``residual`` / ``gate`` as in :func:`gemm`."""
+    :func:`dequantize`; ``residual`` / ``gate`` as in :func:`gemm`.  ``out`` may be a column slice [M, N] of a wider row-major matrix (rows
+    ``out.stride(0)`` elements apart, a multiple of 4; no residual / gate then): the C entry point's y_stride."""
     _need(w, torch.float16, "w")
     N, K = w.shape
     x2 = _prep_x(x, K)
     M = x2.shape[0]
     y = out if out is not None else torch.empty(M, N, dtype=torch.float16, device=x.device)
+    if y.dim() == 2 and not y.is_contiguous():
+        if not y.is_cuda or y.dtype != torch.float16 or tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.stride(0) < N or y.stride(0) % 4 \
+                or y.data_ptr() % 8 or residual is not None or gate is not None:
+            raise ValueError("y: a strided out must be an fp16 [M, N] column slice of a row-major matrix, rows a multiple of 4 elements apart, "
+                             "8-byte aligned, without residual / gate")
+        if bias is not None:
+            _need(bias, torch.float16, "bias", N)
+        _lib.check(_lib.load().amq_gemm_f16w_f16(_lib.ptr(x2), _lib.ptr(w), _lib.ptr(bias), None, None, _lib.ptr(y), M, N, K, 0, y.stride(0),
+                                                 _lib.current_stream()))
+        return y
     _need(y, torch.float16, "y", M * N)
     for t, nm, n in ((bias, "bias", N), (residual, "residual", M * N), (gate, "gate", M * N)):
         if t is not None:
@@ -1246,6 +1257,51 @@ def gemv_f16w(x, W, bias=None, gamma=None, eps=0.0, out=None):
             raise ValueError("at most 8 rows")
         _lib.check(_lib.load().amq_gemv_f16w_rows(_lib.ptr(x), _lib.ptr(W), _lib.ptr(bias), _lib.ptr(y), _lib.ptr(gamma),
                                                   ctypes.c_float(eps), M, N, K, _lib.current_stream()))
+    return y
+
+
+def _lm8_layer(w8):
+    """checks of an hqq_format.LM8Weights on the GPU -> (N, K)"""
+    N, K = w8.shape
+    if w8.group_size != GROUP or K < GROUP or K % GROUP or N < 1:
+        raise ValueError(f"an LM8 layer has groups of {GROUP} along K (got N={N}, K={K}, group {w8.group_size})")
+    _need(w8.codes, torch.uint8, "codes", N * K)
+    _need(w8.meta, torch.float16, "meta", N * (K // GROUP) * 2)
+    return N, K
+
+
+def lm8_gemv(x, w8, gamma=None, eps=0.0, out=None):
+    """y = (RMSNorm'ed if gamma) x . W^T over the 8-bit lm_head ``w8`` (hqq_format.LM8Weights): x [K] -> y [N], or x [M, K] with 1 <= M <= 8 ->
+    y [M, N], W streamed once for all rows (include/amq_hip.h amq_lm8_gemv_f16)."""
+    N, K = _lm8_layer(w8)
+    M = x.shape[0] if x.dim() == 2 else 1
+    if M > 8:
+        raise ValueError("at most 8 rows")
+    _need(x, torch.float16, "x", M * K)
+    if gamma is not None:
+        _need(gamma, torch.float16, "gamma", K)
+    shape = (M, N) if x.dim() == 2 else (N,)
+    y = out if out is not None else torch.empty(shape, dtype=torch.float16, device=x.device)
+    _need(y, torch.float16, "y", M * N)
+    _lib.check(_lib.load().amq_lm8_gemv_f16(_lib.ptr(x), _lib.ptr(w8.codes), _lib.ptr(w8.meta), _lib.ptr(y), _lib.ptr(gamma), ctypes.c_float(eps),
+                                            M, N, K, GROUP, _lib.current_stream()))
+    return y
+
+
+def lm8_dequantize(w8, row0=0, rows=None, out=None):
+    """rows row0 .. row0 + rows - 1 (default: to the last) of the 8-bit lm_head's weights as fp16 [rows, K]: w = fp16(fp16(fp16(c) - zero) * scale)"""
+    N, K = _lm8_layer(w8)
+    row0 = int(row0)
+    rows = N - row0 if rows is None else int(rows)
+    if row0 < 0 or rows < 1 or row0 + rows > N:
+        raise ValueError(f"rows {row0} .. {row0 + rows - 1} outside the layer's {N} rows")
+    y = out if out is not None else torch.empty(rows, K, dtype=torch.float16, device=w8.codes.device)
+    _need(y, torch.float16, "out", rows * K)
+    if y.data_ptr() % 16:
+        raise ValueError("out: must be 16-byte aligned")
+    with torch.cuda.device(w8.codes.device):    # (the layer is no tensor argument: _on_tensor_device cannot name its device)
+        _lib.check(_lib.load().amq_lm8_dequantize_f16(_lib.ptr(w8.codes), _lib.ptr(w8.meta), _lib.ptr(y), row0, rows, N, K, GROUP,
+                                                      _lib.current_stream()))
     return y
 
 
@@ -2098,7 +2154,7 @@ def _on_tensor_device(fn):
 
 
 for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_quantize", "gptq_quantize_launch", "gptq_quantize_static_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
-              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
+              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "lm8_gemv", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup", "decode_tail_lookup_sample"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name

@@ -175,7 +175,7 @@ class HFForwardRunner:
 
 
 @torch.inference_mode()
-def benchmark_speed(model, tokenizer=None, use_ft=True, iteration=1, sizes=(1, 128, 128), mode="TPS", get_peak_memory=True, kv_bits=16):
+def benchmark_speed(model, tokenizer=None, use_ft=True, iteration=1, sizes=(1, 128, 128), mode="TPS", get_peak_memory=True, kv_bits=16, lm_head_bits=16):
     """speed.py:131-255.  ``model``: a runner with reset()/prefill()/decode_step()/generate() (QuantLlama or DenseLlama), or --
     the reference's calling convention (amq_speed_benchmark.py:152, 253) -- a swapped HF ``LlamaForCausalLM`` itself: with
     ``use_ft`` (default, the reference's fast path) the runner is built over its modules (QuantLlama.from_hf: shared weights,
@@ -189,7 +189,8 @@ def benchmark_speed(model, tokenizer=None, use_ft=True, iteration=1, sizes=(1, 1
     if not hasattr(model, "decode_step") and hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers"):
         if use_ft:
             from .llama import QuantLlama
-            model = QuantLlama.from_hf(model, max_seq=max(input_seq_len + gen_seq_len, 64), batch=batch_size if batch_size <= 8 else 1, kv_bits=kv_bits)
+            model = QuantLlama.from_hf(model, max_seq=max(input_seq_len + gen_seq_len, 64), batch=batch_size if batch_size <= 8 else 1, kv_bits=kv_bits,
+                                       lm_head_bits=lm_head_bits)
         else:
             if kv_bits != 16:
                 raise ValueError("kv_bits=8 is the runner's cache: not offered with use_ft=False (HF's own forward keeps its own)")

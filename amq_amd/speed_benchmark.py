@@ -29,7 +29,8 @@ from .llama import DenseLlama, QuantLlama, get_memory_footprint
 from .speed import benchmark_speed, cleanup
 
 
-def main(argv=None):
+def build_parser():
+    """the command line of this driver (the reference's flags + the extensions marked as such)"""
     p = argparse.ArgumentParser()
     p.add_argument("--model_path", type=str, default="meta-llama")
     p.add_argument("--model_name", type=str, default="Llama-2-7b-hf")
@@ -54,7 +55,13 @@ def main(argv=None):
                         "used directly), or 'auto' = tokenizer.json of the checkpoint directory if present, else synthetic")
     p.add_argument("--kv_bits", type=int, default=16, choices=(16, 8),
                    help="(extension) KV cache of the quantized runner: 16 = fp16 rows, 8 = int8 rows with a scale per row")
-    args = p.parse_args(argv)
+    p.add_argument("--lm_head_bits", type=int, default=16, choices=(16, 8, 4),
+                   help="(extension) lm_head of the quantized runner: 16 = fp16 as the reference keeps it, 8 = the LM8 layer, 4 = a packed 4-bit layer")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     def ckpt_dir(bits):
         return os.path.join(args.save_path, f"{args.model_name}_{bits}bit_128gs_1axis")     # amq_speed_benchmark.py:129-131
@@ -131,9 +138,10 @@ def main(argv=None):
         missing = [ckpt_dir(b) for b in used if not os.path.isdir(ckpt_dir(b))]
         if missing:
             raise FileNotFoundError(f"the arch needs HQQ checkpoints that are not there: {missing}")
-        model = checkpoint.load_mixed({b: ckpt_dir(b) for b in used}, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits)
+        model = checkpoint.load_mixed({b: ckpt_dir(b) for b in used}, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits,
+                                      lm_head_bits=args.lm_head_bits)
     else:
-        model = QuantLlama(cfg, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits)
+        model = QuantLlama(cfg, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits, lm_head_bits=args.lm_head_bits)
     run(model, f"{args.target_bits}bit")
     del model
     cleanup()
@@ -141,6 +149,8 @@ def main(argv=None):
     shown = dict(vars(args))
     if shown.get("kv_bits") == 16:
         del shown["kv_bits"]                     # the default: the reference-compatible output as it was
+    if shown.get("lm_head_bits") == 16:
+        del shown["lm_head_bits"]
     result.update({"args": shown})
     if args.file_name:
         out_path = os.path.join("benchmark/outputs", args.file_name)      # amq_speed_benchmark.py:290-293

@@ -470,6 +470,18 @@ int amq_gemv_f16w(const void* x, const void* W, const void* bias, void* y, const
 /* the same for M = 1 .. 8 rows (batched decode): x fp16 [M, K], y fp16 [M, N], both contiguous; W is streamed once */
 int amq_gemv_f16w_rows(const void* x, const void* W, const void* bias, void* y, const void* gamma, float eps, int M,
                        int N, int K, void* stream);
+/* ---- the 8-bit lm_head, "LM8" (additive, AMQ_VERSION unchanged) ----
+ * codes uint8 [N, K] row-major; meta fp16 [N, K / 128, 2] = (scale, zero) of every group of 128 along K (HQQ conventions: the stored scale
+ * multiplies, the zero is fractional).  The weight of a code c is w = fp16(fp16(fp16(c) - zero) * scale): two fp16 roundings, bit for bit the
+ * reference's dequantize(), overflow to inf included.  group must be 128 and K a multiple of it.
+ * amq_lm8_gemv_f16: y [M, N] = fp16 of the fp32 sum of exact fp16 products of x [M, K] (with gamma: gamma * fp16(x * rsqrt(mean x^2 + eps)), the
+ * prologue of amq_gemv_f16w) with those weights; x and y contiguous, 1 <= M <= 8, W streamed once; the rows of an M-row call equal M one-row
+ * calls bit for bit.  M rows of K rounded up to 1024 must fit LDS (AMQ_ESHAPE otherwise).
+ * amq_lm8_dequantize_f16: rows row0 .. row0 + rows - 1 of the weights as fp16 [rows, K].
+ * x, gamma, codes and out must be 16-byte aligned, meta 4-byte (AMQ_EINVAL otherwise). */
+int amq_lm8_gemv_f16(const void* x, const void* codes, const void* meta, void* y, const void* gamma, float eps, int M, int N, int K, int group,
+                     void* stream);
+int amq_lm8_dequantize_f16(const void* codes, const void* meta, void* out, int row0, int rows, int N, int K, int group, void* stream);
 /* one new token per sequence: RoPE(q, k) at position *pos_dev (or pos if pos_dev is NULL), append k/v to the
  * cache [B, n_kv_heads, max_seq, 128], out = softmax(q K^T / sqrt(128)) V.  head_dim must be 128.
  * Replaces FT single_query_attention (ft/attention/decoder_masked_multihead_attention.cu:30-61) with HF-Llama numerics. */
