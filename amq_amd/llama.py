@@ -759,15 +759,7 @@ class QuantLlama:
             else:
                 self._behind_norm(first, blk["ln1"], [blk["self_attn.q_proj"].seg(self.q), blk["self_attn.k_proj"].seg(self.k),
                                                       blk["self_attn.v_proj"].seg(self.v)])
-                if self.lookup:                 # the R rows are consecutive positions of the one sequence: causal among them, one cache slice
-                    ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv,
-                                         grouped=self.rows_attention_grouped(self.nh, self.nkv, self.max_seq), **self._qkn(blk))
-                elif self.kv_bits == 8:
-                    ops.attn_decode_kv8(self.q, self.k, self.v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], self.att, self.pos, self.nh, self.nkv,
-                                        cur=self.rope_cur)
-                else:
-                    ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
-                                    cur=self.rope_cur, **self._qkn(blk))
+                self._step_attention(blk)
             o_proj, down = [blk["self_attn.o_proj"].seg(self.x, residual=self.x)], [blk["mlp.down_proj"].seg(self.x, residual=self.x)]
             if from_sums:
                 ops.gemv_grouped_sums(self.att, o_proj, self.qd, sums_out=self.ss)
@@ -843,17 +835,21 @@ class QuantLlama:
                     else:
                         ops.gemm(xin, l.qn, l.mn, l.bits, l.mode, l.N, K, bias=l.bias, residual=residual, out=y)
                 if i == 0:
-                    if self.lookup:
-                        ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv,
-                                             grouped=self.rows_attention_grouped(self.nh, self.nkv, self.max_seq), **self._qkn(blk))
-                    elif self.kv_bits == 8:
-                        ops.attn_decode_kv8(self.q, self.k, self.v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], self.att, self.pos, self.nh, self.nkv,
-                                            cur=self.rope_cur)
-                    else:
-                        ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
-                                        cur=self.rope_cur, **self._qkn(blk))
+                    self._step_attention(blk)
         self._lm_logits(self.x.reshape(-1) if self.R == 1 else self.x, self.logits)
         self._tail(sampled)
+
+    def _step_attention(self, blk):
+        """rotation, cache append and attention of a token step's rows: self.q / self.k / self.v -> self.att"""
+        if self.lookup:                         # the R rows are consecutive positions of the one sequence: causal among them, one cache slice
+            ops.attn_decode_rows(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.rope_cur, self.pos, self.nh, self.nkv,
+                                 grouped=self.rows_attention_grouped(self.nh, self.nkv, self.max_seq), **self._qkn(blk))
+        elif self.kv_bits == 8:
+            ops.attn_decode_kv8(self.q, self.k, self.v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], self.att, self.pos, self.nh, self.nkv,
+                                cur=self.rope_cur)
+        else:
+            ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
+                            cur=self.rope_cur, **self._qkn(blk))
 
     def _behind_norm(self, how, gamma, segments):
         """one grouped launch (q/k/v, gate/up) over self.x behind the RMSNorm ``gamma``, which runs as the plan says"""
@@ -1245,21 +1241,24 @@ class QuantLlama:
         if self.kv_bits == 8 and start_pos != 0:
             raise ValueError("kv_bits=8: a prompt pass starts at position 0 (the prompt kernels read no 8-bit cache: chunked prompts are not served)")
 
-    def _prompt_kv(self, blk, q, k, v, S):
-        """the rotation and the cache write of a prompt pass at position 0 -> (k, v, kv_cache) for ops.attn_prefill.  fp16 cache: one launch rotates
-        q / k and writes the cache, which the attention reads.  8-bit cache: q / k are rotated in place, the attention reads the projection outputs
-        (exact fp16: the prompt's own attention is the no-cache pass bit for bit) and ONE ops.kv8_store quantizes the rows into the cache."""
-        ops.rope_rows(q, k, self.rope_tab, S, self.nh, self.nkv)
-        ops.kv8_store(k, v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], 0, self.nkv)
+    def _rows_kv(self, blk, q, k, v, S, start_pos, cache):
+        """the rotation and the cache write of a prompt pass -> (k, v, kv_cache) as ops.attn_prefill is to read them.  fp16 cache: one launch
+        rotates q / k and writes rows start_pos .. of the cache, which the attention reads.  No cache: q / k are rotated in place and the attention
+        reads the projection outputs.  8-bit cache (position 0): the same -- exact fp16, the prompt's own attention is the no-cache pass bit for
+        bit -- and ONE ops.kv8_store quantizes the rows into the cache."""
+        if cache and self.kv_bits == 16:
+            ops.rope_cache(q, k, v, blk["kc"], blk["vc"], self.rope_tab, start_pos, self.nh, self.nkv, **self._qkn(blk))
+            return blk["kc"], blk["vc"], True
+        ops.rope_rows(q, k, self.rope_tab, S, self.nh, self.nkv, **self._qkn(blk))
+        if cache:
+            ops.kv8_store(k, v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], 0, self.nkv)
         return k, v, False
 
     def _prefill_rows(self, ids, start_pos):
         """the prompt pass of every sequence (each into its own slice of the caches), then position(s) and first token(s); all device work: what
         the prompt graph captures"""
-        if self.B == 1 and not self.ragged:
-            return self._prefill_eager(ids[0], start_pos)
         B, S = ids.shape
-        return self._prompt_finish(self._rows_pass(ids, start_pos, cache=True), B, S, start_pos, self.lengths)
+        return self._prompt_finish(self._rows_pass(ids, start_pos, cache=True), B, S, start_pos, self.lengths, prompt_ids=ids)
 
     def _prompt_finish(self, x, B, S, start_pos=0, lengths=None, prompt_ids=None):
         """the end of a prompt pass over B prompts of S rows, x [B * S, H] its final hidden rows: the logits of every sequence's last row (all_logits:
@@ -1293,29 +1292,53 @@ class QuantLlama:
         the weights), RoPE and the causal attention run as ONE launch each over all sequences.  ``cache``: the rotated keys /
         values are written into the runner's KV caches (rows start_pos .. start_pos + S - 1 of every sequence) and the
         attention reads them there (a batched decode runner's prompt); otherwise q / k are rotated in place and the
-        attention reads the projection outputs (the harness' GeMM mode, no cache).  Returns the final hidden rows [B * S, H]."""
+        attention reads the projection outputs (the harness' GeMM mode, no cache).  Returns the final hidden rows [B * S, H].
+        The ONE walk over the blocks of a prompt pass, for every runner; which kernels it takes: _rows_route."""
         B, S = ids.shape
         nh, nkv = self.nh, self.nkv
-        x = self.embed.index_select(0, ids.reshape(-1).to(self.dev))
-        lin = self._rows_linear
-        for blk in self.blocks:
-            h = ops.rmsnorm(x, blk["ln1"], self.eps)
-            q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
-            if cache and self.kv_bits == 8:
-                self._kv8_prompt_check(start_pos)
-                kk, vv, _ = self._prompt_kv(blk, q, k, v, S)
-                a = ops.attn_prefill(q, kk, vv, torch.empty_like(q), S, nh, nkv, batch=B)
-            elif cache:
-                ops.rope_cache(q, k, v, blk["kc"], blk["vc"], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
-                a = ops.attn_prefill(q, blk["kc"], blk["vc"], torch.empty_like(q), S, nh, nkv, batch=B, pos0=start_pos, kv_cache=True)
+        if cache:
+            self._kv8_prompt_check(start_pos)
+        route = self._rows_route(B, S, cache)
+        frag = route == "frag"
+        lin, up_gated = (self._few_linear, self._few_up_gated) if route == "few" else (self._rows_linear, self._rows_up_gated)
+        x = self.embed.index_select(0, ids.reshape(-1).to(self.dev))        # the residual stream, updated in place
+        h = None                                # frag: the normed input of this block, where the block in front left it behind
+        for bi, blk in enumerate(self.blocks):
+            if frag:
+                if h is None:
+                    h = ops.rmsnorm_xfrag(x, blk["ln1"], self.eps)
+                q, k, v = self._frag_group([blk["self_attn.q_proj"], blk["self_attn.k_proj"], blk["self_attn.v_proj"]], h, S)     # one launch
             else:
-                ops.rope_rows(q, k, self.rope_tab, S, nh, nkv, **self._qkn(blk))
-                a = ops.attn_prefill(q, k, v, torch.empty_like(q), S, nh, nkv, batch=B)      # reads the projections in place
-            x = lin(blk["self_attn.o_proj"], a, residual=x)
-            h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
-            act = self._rows_up_gated(blk["mlp.up_proj"], h2, lin(blk["mlp.gate_proj"], h2))
-            x = lin(blk["mlp.down_proj"], act, residual=x)
+                h = ops.rmsnorm(x, blk["ln1"], self.eps)
+                q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
+            kk, vv, cached = self._rows_kv(blk, q, k, v, S, start_pos, cache)
+            a = ops.attn_prefill(q, kk, vv, None if frag else torch.empty_like(q), S, nh, nkv, batch=B, pos0=start_pos if cached else 0,
+                                 kv_cache=cached, out_xfrag=frag)
+            if not frag:
+                x = lin(blk["self_attn.o_proj"], a, residual=x)
+                h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
+                act = up_gated(blk["mlp.up_proj"], h2, lin(blk["mlp.gate_proj"], h2))
+                x = lin(blk["mlp.down_proj"], act, residual=x)
+                continue
+            # the projections that read a normed / attention activation take it in fragment order (written that way by the producing launch):
+            # 1.2-1.6x faster few-row GEMMs (DESIGN.md 3.3); down_proj (K = 11008: the per-workgroup x stream is what bounds that kernel) stays on
+            # the tiled kernel, whose split-K reduce also writes the next block's normed input (FUSE_DOWN_NORM)
+            l = blk["self_attn.o_proj"]
+            x = ops.gemm_xfrag(a, S, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias, residual=x, out=x)
+            g, u = self._frag_group([blk["mlp.gate_proj"], blk["mlp.up_proj"]], ops.rmsnorm_xfrag(x, blk["ln2"], self.eps), S)    # one launch
+            act, l, h = ops.silu_mul(g, u, out=g), blk["mlp.down_proj"], None
+            if self.FUSE_DOWN_NORM and bi + 1 < len(self.blocks):
+                x, h = ops.gemm_res_norm_xfrag(act, l.qn, l.mn, l.bits, l.mode, l.N, l.K, self.blocks[bi + 1]["ln1"], self.eps,
+                                               bias=l.bias, residual=x, out=x)
+            else:
+                x = lin(l, act, residual=x)
         return x
+
+    def _frag_group(self, ls, xf, S):
+        """the linears ``ls`` over the same S rows in fragment order ``xf``, as one launch -> their outputs [S, N] each"""
+        ys = [torch.empty(S, l.N, dtype=torch.float16, device=self.dev) for l in ls]
+        ops.gemm_xfrag_grouped(xf, S, [l.seg(y) for l, y in zip(ls, ys)], ls[0].K)
+        return ys
 
     def _logits_of_rows(self, x, B, S, last_logits):
         """logits of every prompt row, [B, S, vocab] fp16: final RMSNorm + ONE pass over the lm_head for all rows (fp16 MFMA GEMM); each sequence's
@@ -1400,77 +1423,29 @@ class QuantLlama:
     FRAG_ROWS = (16, 384)
     FUSE_DOWN_NORM = True       # down_proj's split-K reduce also writes the next block's normed input (A/B: tools/prompt64_time.py)
 
-    def _prefill_eager(self, ids, start_pos=0):
-        """Many-row pass over the prompt: per block 2 RMSNorm + 7 GEMMs (residuals fused into the o_proj / down_proj
-        epilogues) + one RoPE-and-cache-write launch + causal attention (library SDPA reading K/V straight from the
-        cache) + one SiLU*up launch."""
-        S = ids.numel()
-        if start_pos + S > self.max_seq:
-            raise ValueError("prompt longer than the KV cache")
-        self._kv8_prompt_check(start_pos)
-        H, nh, nkv = self.H, self.nh, self.nkv
-        ids = ids.to(self.dev)
-        x = self.embed.index_select(0, ids)                        # [S, H]; the residual stream, updated in place
+    def _rows_route(self, B, S, cache):
+        """which kernels the walk of a prompt pass takes (_rows_pass).  Only the one prompt of a batch-1 runner into its cache
+        leaves the tiled kernels:
+          "frag"   FRAG_ROWS[0] < S <= FRAG_ROWS[1], groups of 128, no OWQ layer: the fragment-ordered few-row kernels -- rmsnorm_xfrag, q/k/v and
+                   gate/up as grouped launches, attention and o_proj handing over in fragment order, down_proj's reduce carrying the next norm;
+          "few"    S <= 8: ops.linear (the GEMV) per linear, residual and SiLU*mul as launches of their own (_few_linear / _few_up_gated);
+          "tiled"  everything else -- any batch, ragged runners, passes without a cache (score_rows, prefill_batch) at ANY row count: the tiled
+                   MFMA GEMM with residual / SiLU*mul epilogues (_rows_linear / _rows_up_gated)."""
+        if B != 1 or not cache or self.ragged:
+            return "tiled"
+        if self.FRAG_ROWS[0] < S <= self.FRAG_ROWS[1] and not self.fine and not self.owq:     # (an OWQ model: the plain, unfused form)
+            return "frag"
+        return "few" if S <= 8 else "tiled"
 
-        def lin(l, inp, residual=None):
-            if l.owq:
-                return self._rows_owq(l, inp, residual)
-            if S > 8:
-                return ops.gemm(inp, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias, residual=residual, out=residual)
-            y = ops.linear(inp, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias)
-            return y if residual is None else residual.add_(y)
+    def _few_linear(self, l, inp, residual=None):
+        # _rows_linear for up to 8 rows of one prompt
+        if l.owq:
+            return self._rows_owq(l, inp, residual)
+        y = ops.linear(inp, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias)
+        return y if residual is None else residual.add_(y)
 
-        def lin_xf(l, xf, residual=None, gate=None):
-            return ops.gemm_xfrag(xf, S, l.qn, l.mn, l.bits, l.mode, l.N, l.K, bias=l.bias, residual=residual, gate=gate,
-                                  out=residual if residual is not None else gate)
-
-        def lin_xf_group(ls, xf):
-            ys = [torch.empty(S, l.N, dtype=torch.float16, device=self.dev) for l in ls]
-            ops.gemm_xfrag_grouped(xf, S, [l.seg(y) for l, y in zip(ls, ys)], ls[0].K)
-            return ys
-
-        # up to 256 rows the projections that read a normed / attention activation take it in fragment order (written
-        # that way by the producing launch): 1.2-1.6x faster few-row GEMMs (DESIGN.md 3.3); down_proj (K = 11008: the
-        # per-workgroup x stream is what bounds that kernel) and longer prompts stay on the tiled kernel
-        frag = self.FRAG_ROWS[0] < S <= self.FRAG_ROWS[1] and not self.fine and not self.owq     # (an OWQ model: the plain, unfused form)
-        h_next = None                               # the next block's normed input, left behind by this block's down_proj (its split-K reduce carries the norm)
-        for bi, blk in enumerate(self.blocks):
-            if frag:
-                h = h_next if h_next is not None else ops.rmsnorm_xfrag(x, blk["ln1"], self.eps)
-                q, k, v = lin_xf_group([blk["self_attn." + n] for n in ("q_proj", "k_proj", "v_proj")], h)   # one launch
-            else:
-                h = ops.rmsnorm(x, blk["ln1"], self.eps)
-                q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
-            if self.kv_bits == 8:
-                kc, vc, cached = self._prompt_kv(blk, q, k, v, S)
-            else:
-                kc, vc, cached = blk["kc"], blk["vc"], True
-                ops.rope_cache(q, k, v, kc[0], vc[0], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
-            if frag:
-                a_xf = ops.attn_prefill(q, kc, vc, None, S, nh, nkv, batch=1, pos0=start_pos, kv_cache=cached, out_xfrag=True)
-                x = lin_xf(blk["self_attn.o_proj"], a_xf, residual=x)              # attention output handed over in fragment order
-                h2 = ops.rmsnorm_xfrag(x, blk["ln2"], self.eps)
-                g, u = lin_xf_group([blk["mlp.gate_proj"], blk["mlp.up_proj"]], h2)                            # one launch
-                act = ops.silu_mul(g, u, out=g)
-            else:
-                a = self._prefill_attention(q, blk, S, start_pos) if cached else ops.attn_prefill(q, kc, vc, torch.empty_like(q), S, nh, nkv)
-                x = lin(blk["self_attn.o_proj"], a, residual=x)
-                h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
-                g = lin(blk["mlp.gate_proj"], h2)
-                if blk["mlp.up_proj"].owq:
-                    act = self._rows_up_gated(blk["mlp.up_proj"], h2, g)
-                elif S > 8:
-                    u = blk["mlp.up_proj"]                                         # silu(gate) * up in up_proj's epilogue
-                    act = ops.gemm(h2, u.qn, u.mn, u.bits, u.mode, u.N, u.K, bias=u.bias, gate=g, out=g)
-                else:
-                    act = ops.silu_mul(g, lin(blk["mlp.up_proj"], h2), out=g)
-            if frag and self.FUSE_DOWN_NORM and bi + 1 < len(self.blocks):
-                l = blk["mlp.down_proj"]
-                x, h_next = ops.gemm_res_norm_xfrag(act, l.qn, l.mn, l.bits, l.mode, l.N, l.K, self.blocks[bi + 1]["ln1"], self.eps,
-                                                    bias=l.bias, residual=x, out=x)
-            else:
-                x = lin(blk["mlp.down_proj"], act, residual=x)
-        return self._prompt_finish(x, 1, S, start_pos, prompt_ids=ids)
+    def _few_up_gated(self, l, inp, gate):
+        return ops.silu_mul(gate, self._few_linear(l, inp), out=gate)
 
     def _rows_linear(self, l, inp, residual=None):
         # y = inp . W^T (+ residual, in place) for many rows
@@ -1502,21 +1477,11 @@ class QuantLlama:
         if S > self.max_seq:
             raise ValueError("prompt longer than the RoPE table")
         last = self._rows_pass(ids, 0, cache=False).view(B, S, self.H)[:, S - 1].contiguous()
-        logits = torch.empty(B, self.vocab, dtype=torch.float16, device=self.dev)
-        for b0 in range(0, B, 8):                   # the lm_head is streamed once per 8 sequences
-            rows = slice(b0, min(B, b0 + 8))
-            if rows.stop - rows.start == 1:
-                self._lm_logits(last[b0], logits[b0])
-            else:
-                self._lm_logits(last[rows], logits[rows])
-        return logits
-
-    def _prefill_attention(self, q, blk, S, start_pos=0):
-        """causal attention of the prompt rows: q [S, nh*128] rotated, K / V = cache rows 0 .. start_pos + S - 1 -> [S, nh*128]"""
-        return ops.attn_prefill(q, blk["kc"], blk["vc"], torch.empty_like(q), S, self.nh, self.nkv, batch=1, pos0=start_pos, kv_cache=True)
+        return self._lm_head_streamed(last, torch.empty(B, self.vocab, dtype=torch.float16, device=self.dev))   # the lm_head once per 8 sequences
 
     def _prefill_attention_sdpa(self, q, blk, S):
-        """the same through the framework's SDPA (comparison point for tests / tools; not on the product path)"""
+        """causal attention of a batch-1 prompt at position 0 through the framework's SDPA: q [S, nh*128] rotated, K / V = cache rows 0 .. S - 1 ->
+        [S, nh*128] (comparison point for tests / tools; not on the product path)"""
         nh, nkv = self.nh, self.nkv
         qh = q.view(S, nh, 128).transpose(0, 1)
         kh, vh = blk["kc"][0, :, :S], blk["vc"][0, :, :S]
@@ -1712,22 +1677,8 @@ class DenseLlama(QuantLlama):
     def _rows_up_gated(self, w, inp, gate):
         return ops.silu_mul(gate, torch.nn.functional.linear(inp, w), out=gate)
 
-    def _prefill_eager(self, ids, start_pos=0):
-        F = torch.nn.functional
-        S = ids.numel()
-        if start_pos + S > self.max_seq:
-            raise ValueError("prompt longer than the KV cache")
-        nh, nkv = self.nh, self.nkv
-        x = self.embed.index_select(0, ids.to(self.dev))
-        for blk in self.blocks:
-            h = ops.rmsnorm(x, blk["ln1"], self.eps)
-            q, k, v = F.linear(h, blk["self_attn.q_proj"]), F.linear(h, blk["self_attn.k_proj"]), F.linear(h, blk["self_attn.v_proj"])
-            ops.rope_cache(q, k, v, blk["kc"][0], blk["vc"][0], self.rope_tab, start_pos, nh, nkv, **self._qkn(blk))
-            x = torch.addmm(x, self._prefill_attention(q, blk, S, start_pos), blk["self_attn.o_proj"].t())
-            h2 = ops.rmsnorm(x, blk["ln2"], self.eps)
-            g, u = F.linear(h2, blk["mlp.gate_proj"]), F.linear(h2, blk["mlp.up_proj"])
-            x = torch.addmm(x, ops.silu_mul(g, u, out=g), blk["mlp.down_proj"].t())
-        return self._prompt_finish(x, 1, S, start_pos)
+    def _rows_route(self, B, S, cache):
+        return "tiled"                          # (library GEMMs at every row count: the two methods above)
 
 
 def get_memory_footprint(model, return_buffers=True):
