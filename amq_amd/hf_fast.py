@@ -159,14 +159,14 @@ def _runner(model, batch, need, ragged=False):
     one carries nothing over."""
     if need > _limit(model):
         raise ValueError(f"{need} positions exceed the model's max_position_embeddings ({_limit(model)})")
-    kv_bits = model.__dict__.get("_amq_kv_bits", 16)            # convert_model_to_hip(model, kv_bits=8): never together with padded / lookup
-    r, old = _bound(model, ("ragged", batch) if ragged else batch, need, batch=batch, ragged=ragged, kv_bits=kv_bits)
+    # (convert_model_to_hip(model, kv_bits=8): never together with padded / lookup)
+    r, old = _bound(model, ("ragged", batch) if ragged else batch, need, batch=batch, ragged=ragged, kv_bits=model.__dict__.get("_amq_kv_bits", 16))
     if ragged:
         return r
     r.all_logits = True
     if old is not None and _same_weights(old, model) and old.host_pos > 0:
         for nb, ob in zip(r.blocks, old.blocks):
-            for key in (("kc8", "ks", "vc8", "vs") if kv_bits == 8 else ("kc", "vc")):       # an 8-bit cache: codes and scales
+            for key in r.cache_keys:                # (an 8-bit cache: codes and scales)
                 nb[key][:, :, :old.host_pos].copy_(ob[key][:, :, :old.host_pos])
         r.set_pos(old.host_pos)
         r.set_token(old.token)
@@ -401,13 +401,12 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
     forward and a reverted model are untouched.  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
-    if kv_bits not in (8, 16):
-        raise ValueError(f"kv_bits must be 16 (fp16 cache) or 8 (int8 rows with a scale per row), got {kv_bits!r}")
+    from .llama import check_kv_bits, check_lm_head_bits
+    check_kv_bits(kv_bits)
     if kv_bits == 8 and (lookup or padded):
         raise ValueError("kv_bits=8 is not offered together with " + ("lookup=True" if lookup else "padded=True") + ": the 8-bit attention kernel "
                          "runs one row per sequence at one position for the batch (QuantLlama(kv_bits=8))")
-    if lm_head_bits not in (16, 8, 4):
-        raise ValueError(f"lm_head_bits must be 16 (fp16 lm_head), 8 (the LM8 layer) or 4 (a packed 4-bit layer), got {lm_head_bits!r}")
+    check_lm_head_bits(lm_head_bits)
     if model.__dict__.get("_amq_kv_bits", kv_bits) != kv_bits or model.__dict__.get("_amq_lm_head_bits", 16) != lm_head_bits:
         _RUNNERS.pop(model, None)                               # runners hold a cache of the other format / another lm_head
         model.__dict__.pop("_amq_lm_head_packed", None)

@@ -146,6 +146,92 @@ def _ints(values, n, lo, hi, message):
     return each
 
 
+def check_kv_bits(kv_bits):
+    if kv_bits not in (8, 16):
+        raise ValueError(f"kv_bits must be 16 (fp16 cache) or 8 (int8 rows with a scale per row), got {kv_bits!r}")
+    return int(kv_bits)
+
+
+def check_lm_head_bits(lm_head_bits):
+    if lm_head_bits not in (16, 8, 4):
+        raise ValueError(f"lm_head_bits must be 16 (fp16 lm_head), 8 (the LM8 layer) or 4 (a packed 4-bit layer), got {lm_head_bits!r}")
+    return int(lm_head_bits)
+
+
+# The two A/B routes of the token step, as the messages call them: the one-launch-per-token engine (ops.DecodeEngine; engine=True) and q/k/v +
+# attention as one launch (ops.gemv_qkv_attn; the class switch FUSE_QKV_ATTN).  Both run ONE row at ONE position over a short fp16 cache in front of
+# the fp16 lm_head.  What they require is written twice only: runner_options' no_route calls (an option that excludes them) and route_reasons.
+ROUTES = {"engine": "the decode engine", "fuse_qkv_attn": "the fused q/k/v + attention launch"}
+ENGINE_MAX_SEQ = 512            # the single-workgroup-per-head attention regime (the same bound as ops.ATTN_SPLIT_FROM)
+FUSE_UNFIT = "the fused q/k/v + attention launch needs batch 1, a short cache, hidden_size <= 8192, groups of 128 and no biases"     # (never raised)
+RunnerOptions = NamedTuple("RunnerOptions", [("B", int), ("R", int), ("ragged", bool), ("lookup", int), ("ngram_max", int), ("lookup_sampling", bool),
+                                             ("kv_bits", int), ("lm_head_bits", int), ("engine", object)])
+
+
+def runner_options(batch=1, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False, kv_bits=16, lm_head_bits=16, engine=None,
+                   fuse_qkv_attn=False, qk_norm=False):
+    """A runner's options checked against each other, the two A/B routes (``engine`` as requested, ``fuse_qkv_attn``: the class switch) and the
+    config's ``qk_norm`` -- host logic, before anything is built: ValueError for what is not offered (the first broken rule wins), else RunnerOptions
+    (R: rows of a token step -- B, or lookup + 1 rows of the one sequence; engine: as requested -- None = QuantLlama.ENGINE_DEFAULT)"""
+    def no_route(*messages):        # an option neither A/B route serves: (the engine's message, the fused launch's)
+        for asked, message in zip((engine, fuse_qkv_attn), messages):
+            if asked:
+                raise ValueError(message)
+
+    kv_bits, lm_head_bits = check_kv_bits(kv_bits), check_lm_head_bits(lm_head_bits)
+    if lm_head_bits != 16:
+        no_route(f"lm_head_bits={lm_head_bits}: not offered with the decode engine (an A/B route: it is followed by the fp16 lm_head only)",
+                 f"lm_head_bits={lm_head_bits}: not offered with the fused q/k/v + attention launch (an A/B route: fp16 lm_head only)")
+    if kv_bits == 8:
+        if ragged:
+            raise ValueError("kv_bits=8: the 8-bit attention kernel keeps one position for the batch: not offered with ragged=True")
+        if lookup:
+            raise ValueError("kv_bits=8: a verify step runs 2 .. 8 rows of one sequence, the 8-bit attention kernel one: not offered with lookup=")
+        if qk_norm:
+            raise ValueError("kv_bits=8: the 8-bit attention kernel has no per-head q / k norm: not offered for a qk_norm model")
+        no_route("kv_bits=8: the decode engine reads an fp16 cache", "kv_bits=8: the fused q/k/v + attention launch reads an fp16 cache")
+    if not 1 <= int(batch) <= 8:
+        raise ValueError("batch must be 1..8")
+    B, ragged, D = int(batch), bool(ragged), int(lookup or 0)
+    if lookup_sampling and not D:
+        raise ValueError("lookup_sampling: sampled verify steps need a runner built with lookup=D (a plain runner samples after set_sampling)")
+    if D:
+        if not 1 <= D <= ops.LOOKUP_MAX_ROWS - 1:
+            raise ValueError(f"lookup: 1..{ops.LOOKUP_MAX_ROWS - 1} drafts per step (the 2 .. 8-row launches), got {lookup}")
+        if not 1 <= int(ngram_max) <= 4:
+            raise ValueError(f"ngram_max must be 1..4, got {ngram_max}")
+        if B != 1:
+            raise ValueError("lookup: the rows of a step are the drafts of ONE sequence (batch 1); batches are not served")
+        if ragged:
+            raise ValueError("lookup: a ragged runner's step-state blocks are sequences, a lookup runner's are the rows of one sequence: not offered with ragged=True")
+        no_route("lookup: the decode engine runs one row per launch; a verify step runs 2 .. 8",
+                 "lookup: the fused q/k/v + attention launch runs one row; a verify step runs 2 .. 8")
+    if ragged:
+        no_route("the decode engine keeps one position (batch 1): not offered with ragged=True",
+                 "the fused q/k/v + attention launch keeps one position (batch 1): not offered with ragged=True")
+    return RunnerOptions(B, D + 1 if D else B, ragged, D, int(ngram_max), bool(lookup_sampling), kv_bits, lm_head_bits, engine)
+
+
+def route_reasons(route, *, R, ragged, kv_bits, fine, owq, has_bias, qk_norm, qd, H, max_seq):
+    """Why ``route`` (a key of ROUTES) cannot serve a runner of these options and model facts (fine: groups of 64 / 32; qd: heads * 128), in the
+    order a request is refused with them: what has a message of its own first, the generic line for everything else last; [] = it can"""
+    what, reasons = ROUTES[route], []
+    if fine and route == "engine":
+        reasons.append("the decode engine serves groups of 128")
+    if owq:
+        reasons.append(what + " does not serve a model with OWQ layers: their gather and outlier columns run as a stage launch in front of each "
+                       "packed GEMV (the five-launch step's staged plan)")
+    if qk_norm or qd != H:      # both rotate inside launches of their own, which carry no per-head norm and take q / o of hidden_size: not for Qwen3
+        reasons.append(what + " does not serve this model: "
+                       + ("it has no per-head q / k norm" if qk_norm else f"q / o widths of heads * 128 = {qd} != hidden_size {H}"))
+    fits = R == 1 and not fine and not has_bias and not ragged and kv_bits == 16
+    if route == "engine" and not (fits and max_seq <= ENGINE_MAX_SEQ):
+        reasons.append("the decode engine needs batch 1 and max_seq <= %d" % ENGINE_MAX_SEQ)
+    if route == "fuse_qkv_attn" and not (fits and max_seq <= ops.ATTN_SPLIT_FROM and H <= 8192):
+        reasons.append(FUSE_UNFIT)
+    return reasons
+
+
 # how a norm of the token step runs / which form down_proj takes (StepPlan)
 NORM_FUSED, NORM_LAUNCH, NORM_FROM_SUMS = "fused", "launch", "sums"
 DOWN_FUSED, DOWN_GEMV, DOWN_GEMV_SUMS, DOWN_GEMM = "silu_mul prologue", "silu_mul + gemv", "silu_mul + gemv leaving sums", "silu_mul + gemm"
@@ -212,10 +298,7 @@ class _held_back:
 
 
 class QuantLlama:
-    # decode steps run as ONE persistent launch per token (ops.DecodeEngine) when the runner is batch 1 and its KV cache is in the
-    # single-workgroup-per-head attention regime (the same bound as ops.ATTN_SPLIT_FROM); otherwise, and with engine=False, as
-    # five launches per block
-    ENGINE_MAX_SEQ = 512
+    ENGINE_MAX_SEQ = ENGINE_MAX_SEQ     # (decode steps run as ONE launch per token, ops.DecodeEngine, where asked for and route_reasons has nothing against it)
     # rows up to which down_proj's SiLU*mul stays fused into its GEMV's prologue (beyond: one silu_mul launch + the GEMV without a prologue -- every
     # workgroup of a fused launch takes in gate AND up and repeats the transform on all rows, which from 2 rows on costs more than the extra launch:
     # profiles/r05_decode_batch.txt)
@@ -238,8 +321,6 @@ class QuantLlama:
     # (32/8 heads, R = 2, 2048) up to 787 -> 63 us (64/8, R = 8, 32768) -- so the threshold is its floor; shorter caches were not measured and keep the
     # per-head kernels (every grouped-query lookup runner of the older tests keeps its arithmetic).
     ROWS_GQA_FROM = 2048
-    kv_bits = 16                # (the instance's own after QuantLlama.__init__; the fp16 baseline runner, which has its own __init__, keeps fp16 rows)
-    lm_head_bits, lm_head_q = 16, None      # (the instance's own after QuantLlama.__init__; the fp16 baseline runner keeps its fp16 lm_head)
     # many-row logits over the 8-bit lm_head: vocabulary rows dequantized at a time (the fp16 scratch: 128 MB at H = 4096), and the row count from
     # which that route is taken.  One pass of the dequantize kernel over the whole layer moves what about three 8-row launches of the
     # weight-streaming kernel move (codes read, fp16 written), and the GEMM comes on top: 64 rows = 8 launches is past that by a safe factor.
@@ -251,6 +332,7 @@ class QuantLlama:
     # prompt passes also leave the logits of EVERY prompt row in self.logits_rows [B, S, vocab] (HF's forward returns them all; the runner's own
     # generate loop needs the last row only): final norm + one fp16 GEMM over the prompt rows, inside the captured prompt graph (hf_fast.py sets it)
     all_logits = False
+    engine = None               # the ops.DecodeEngine of a runner that takes that route (set by _take_routes)
     fine = False                # any layer with groups of 64 / 32 (set by __init__)
     owq = False                 # any OWQ layer (set by __init__): the staged token step, the plain prompt passes
 
@@ -288,131 +370,88 @@ class QuantLlama:
         the HF module's own; otherwise derived from config["rope_scaling"]: Llama-3.1's "llama3").
         kv_bits: 16 -- the fp16 KV cache, the object, graphs and bits the runner has always had; 8 -- int8 rows with one fp32 scale per (sequence,
         kv head, position) (blocks hold kc8 / ks / vc8 / vs, 132 bytes per row instead of 256; the token step issues
-        ops.attn_decode_kv8, the prompt pass stays exact fp16 and stores its rows with one ops.kv8_store).  Not offered with ragged=True, lookup=,
-        a qk_norm config, the decode engine, the fused q/k/v + attention launch or a prompt pass at start_pos > 0.
+        ops.attn_decode_kv8, the prompt pass stays exact fp16 and stores its rows with one ops.kv8_store; no prompt pass at start_pos > 0).
         lm_head_bits: 16 -- the fp16 lm_head, the object, graphs and bits the runner has always had; 8 -- the lm_head is quantized once, here, to
         the LM8 layer (hqq_format.quantize_lm8) and every logit comes from ops.lm8_gemv; 4 -- ops.hqq_quantize(W, 4) and the packed
         GEMV / GEMM kernels of the block linears.  The runner then keeps no fp16 lm_head (self.lm_head is None; self.lm_head_q is the packed layer).
-        Not offered with the decode engine or the fused q/k/v + attention launch.  lm_head_packed: the packed layer of an earlier runner over the
-        same weights (hf_fast shares one among the runners it builds), instead of quantizing again."""
-        if isinstance(config, str):
-            config = MODEL_CONFIGS[config]
-        if kv_bits not in (8, 16):
-            raise ValueError(f"kv_bits must be 16 (fp16 cache) or 8 (int8 rows with a scale per row), got {kv_bits!r}")
-        self.kv_bits = int(kv_bits)
-        if lm_head_bits not in (16, 8, 4):
-            raise ValueError(f"lm_head_bits must be 16 (fp16 lm_head), 8 (the LM8 layer) or 4 (a packed 4-bit layer), got {lm_head_bits!r}")
-        self.lm_head_bits = int(lm_head_bits)
-        if self.lm_head_bits != 16:
-            if engine:
-                raise ValueError(f"lm_head_bits={self.lm_head_bits}: not offered with the decode engine (an A/B route: it is followed by the fp16 lm_head only)")
-            if self.FUSE_QKV_ATTN:
-                raise ValueError(f"lm_head_bits={self.lm_head_bits}: not offered with the fused q/k/v + attention launch (an A/B route: fp16 lm_head only)")
-        if self.kv_bits == 8:
-            # the 8-bit attention kernel keeps one position for the batch, runs one row per sequence and carries no per-head norm
-            if ragged:
-                raise ValueError("kv_bits=8: the 8-bit attention kernel keeps one position for the batch: not offered with ragged=True")
-            if lookup:
-                raise ValueError("kv_bits=8: a verify step runs 2 .. 8 rows of one sequence, the 8-bit attention kernel one: not offered with lookup=")
-            if config.get("qk_norm"):
-                raise ValueError("kv_bits=8: the 8-bit attention kernel has no per-head q / k norm: not offered for a qk_norm model")
-            if engine:
-                raise ValueError("kv_bits=8: the decode engine reads an fp16 cache")
-            if self.FUSE_QKV_ATTN:
-                raise ValueError("kv_bits=8: the fused q/k/v + attention launch reads an fp16 cache")
-        if not 1 <= int(batch) <= 8:
-            raise ValueError("batch must be 1..8")
-        self.B = int(batch)
-        self.ragged = bool(ragged)
-        self.lookup = int(lookup or 0)
-        self.lookup_sampling = bool(lookup_sampling)
-        if self.lookup_sampling and not self.lookup:
-            raise ValueError("lookup_sampling: sampled verify steps need a runner built with lookup=D (a plain runner samples after set_sampling)")
-        if self.lookup:
-            if not 1 <= self.lookup <= ops.LOOKUP_MAX_ROWS - 1:
-                raise ValueError(f"lookup: 1..{ops.LOOKUP_MAX_ROWS - 1} drafts per step (the 2 .. 8-row launches), got {lookup}")
-            if not 1 <= int(ngram_max) <= 4:
-                raise ValueError(f"ngram_max must be 1..4, got {ngram_max}")
-            if self.B != 1:
-                raise ValueError("lookup: the rows of a step are the drafts of ONE sequence (batch 1); batches are not served")
-            if self.ragged:
-                raise ValueError("lookup: a ragged runner's step-state blocks are sequences, a lookup runner's are the rows of one sequence: not offered with ragged=True")
-            if engine:
-                raise ValueError("lookup: the decode engine runs one row per launch; a verify step runs 2 .. 8")
-            if self.FUSE_QKV_ATTN:
-                raise ValueError("lookup: the fused q/k/v + attention launch runs one row; a verify step runs 2 .. 8")
-        self.ngram_max = int(ngram_max)
-        self.R = self.lookup + 1 if self.lookup else self.B      # rows of a token step
-        if self.ragged and engine:
-            raise ValueError("the decode engine keeps one position (batch 1): not offered with ragged=True")
-        if self.ragged and self.FUSE_QKV_ATTN:
-            raise ValueError("the fused q/k/v + attention launch keeps one position (batch 1): not offered with ragged=True")
-        self.cfg = config
-        self.dev = torch.device(device)
+        lm_head_packed: the packed layer of an earlier runner over the same weights (hf_fast shares one among the runners it builds), instead of
+        quantizing again.  What is not offered with what: runner_options, route_reasons ("Runner options")."""
+        config = MODEL_CONFIGS[config] if isinstance(config, str) else config
+        opts = runner_options(batch, ragged, lookup, ngram_max, lookup_sampling, kv_bits, lm_head_bits, engine, self.FUSE_QKV_ATTN, config.get("qk_norm"))
+        self._frame(config, device, max_seq, opts)
+        self.arch_linear = arch_linear or uniform_arch(config, 4)["linear"]
+        gen = torch.Generator(device=self.dev).manual_seed(seed)
+        self.blocks = [{**{name: self._linear(b, name, gen, prebuilt, hqq_layers, synthetic, group) for name in config["linear"]},
+                        **self._block_norms(b, gen, dense), **self._alloc_cache()} for b in range(self.nb)]
+        self._dense_tensors(gen, dense, lm_head_packed)
+        self._model_facts()
+        self._alloc_step_buffers()
+        # the cos/sin table every rotating kernel reads: plain rope_theta frequencies, or the rotary embedding's own (rope_scaling)
+        self._init_step_state(rope if rope is not None else rope_inv_freq(config))
+        self._plan_step()
+        self._take_routes(opts.engine)
+
+    # ----------------------------------------------------------------- construction, step by step (DenseLlama takes the same steps around its linears)
+    def _frame(self, config, device, max_seq, opts):
+        """what a runner knows before it has weights: its options (a RunnerOptions) and the model's dimensions"""
+        self.B, self.R, self.ragged, self.lookup, self.ngram_max, self.lookup_sampling, self.kv_bits, self.lm_head_bits = opts[:8]
+        self.cache_keys = ("kc8", "ks", "vc8", "vs") if self.kv_bits == 8 else ("kc", "vc")     # a block's cache tensors: codes and scales, or fp16 rows
+        self.cfg, self.dev = config, torch.device(device)
         _prime_graph_state(self.dev)
-        self.H = config["hidden_size"]
-        self.I = config["intermediate_size"]
+        self.H, self.I = config["hidden_size"], config["intermediate_size"]
         self.nh, self.nkv = config["num_heads"], config["num_kv_heads"]
         if config["head_dim"] != 128:
             raise ValueError("head_dim must be 128")
-        self.kvd = self.nkv * 128
-        self.qd = self.nh * 128                 # width of q and of the attention output = o_proj's K (Qwen3: not H at every size)
+        self.kvd, self.qd = self.nkv * 128, self.nh * 128       # qd: width of q and of the attention output = o_proj's K (Qwen3: not H at every size)
         self.qk_norm = bool(config.get("qk_norm"))      # Qwen3: q and k are RMS-normalised per head in front of the rotation, inside the rotating kernels
-        self.nb = config["n_block"]
-        self.vocab = config["vocab_size"]
-        self.max_seq = max_seq
+        self.nb, self.vocab, self.max_seq = config["n_block"], config["vocab_size"], max_seq
         self.eps = float(config.get("rms_norm_eps", EPS))
         self.theta = float(config.get("rope_theta", ROPE_THETA))
-        arch_linear = arch_linear or uniform_arch(config, 4)["linear"]
-        self.arch_linear = arch_linear
-        gen = torch.Generator(device=self.dev).manual_seed(seed)
-        dev = self.dev
 
-        def lin(block, name):
-            n, k = config["linear_shape"][name]
-            bits = arch_bits(arch_linear, name, block)
-            if prebuilt is not None:
-                l = prebuilt[(block, name)]
-                assert l.bits == bits and (l.N, l.K) == (n, k) and l.qn.device == dev
-                return l
-            if hqq_layers is not None:
-                h: HQQWeights = hqq_layers[(block, name)].to(dev)
-                assert h.nbits == bits and tuple(h.shape) == (n, k)
-                qn, mn = ops.repack_from_hqq(h.W_q.contiguous(), h.scale.reshape(-1).contiguous(),
-                                             h.zero.reshape(-1).contiguous(), bits, n, k, group=h.group_size)
-                return _Lin(qn, mn, bits, ops.MODE_HQQ, n, k, None if h.bias is None else h.bias.to(dev, torch.float16).contiguous())
-            if not synthetic:
-                raise ValueError("no weights given")
-            l = _synthetic_linear(n, k, bits, gen, dev, group)
-            if config.get("qkv_bias") and name in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"):
-                l.bias = (0.1 * torch.randn(n, device=dev, generator=gen)).to(torch.float16)
+    def _linear(self, block, name, gen, prebuilt=None, hqq_layers=None, synthetic=True, group=128):
+        """the _Lin of a block's linear: the prebuilt one, the HQQ layer repacked, or a synthetic one (with the q/k/v bias of a qkv_bias config)"""
+        config, dev = self.cfg, self.dev
+        n, k = config["linear_shape"][name]
+        bits = arch_bits(self.arch_linear, name, block)
+        if prebuilt is not None:
+            l = prebuilt[(block, name)]
+            assert l.bits == bits and (l.N, l.K) == (n, k) and l.qn.device == dev
             return l
+        if hqq_layers is not None:
+            h: HQQWeights = hqq_layers[(block, name)].to(dev)
+            assert h.nbits == bits and tuple(h.shape) == (n, k)
+            qn, mn = ops.repack_from_hqq(h.W_q.contiguous(), h.scale.reshape(-1).contiguous(),
+                                         h.zero.reshape(-1).contiguous(), bits, n, k, group=h.group_size)
+            return _Lin(qn, mn, bits, ops.MODE_HQQ, n, k, None if h.bias is None else h.bias.to(dev, torch.float16).contiguous())
+        if not synthetic:
+            raise ValueError("no weights given")
+        l = _synthetic_linear(n, k, bits, gen, dev, group)
+        if config.get("qkv_bias") and name in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"):
+            l.bias = (0.1 * torch.randn(n, device=dev, generator=gen)).to(torch.float16)
+        return l
 
-        self.blocks = []
-        for b in range(self.nb):
-            blk = {name: lin(b, name) for name in config["linear"]}
-            if dense is not None:
-                blk["ln1"], blk["ln2"] = dense["ln1"][b].to(dev), dense["ln2"][b].to(dev)
-                if self.qk_norm:
-                    blk["qn"], blk["kn"] = dense["qn"][b].to(dev), dense["kn"][b].to(dev)
-            else:
-                blk["ln1"] = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
-                blk["ln2"] = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
-                if self.qk_norm:
-                    blk["qn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
-                    blk["kn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
-            if self.kv_bits == 8:
-                blk["kc8"], blk["ks"], blk["vc8"], blk["vs"] = ops.kv8_alloc(self.B, self.nkv, max_seq, dev)
-            else:
-                blk["kc"] = torch.zeros(self.B, self.nkv, max_seq, 128, dtype=torch.float16, device=dev)
-                blk["vc"] = torch.zeros(self.B, self.nkv, max_seq, 128, dtype=torch.float16, device=dev)
-            self.blocks.append(blk)
+    def _block_norms(self, b, gen, dense=None):
+        """block b's norm weights -- ln1, ln2 and (qk_norm) qn, kn: ``dense``'s, or synthetic ones drawn in that order"""
+        names = ("ln1", "ln2") + (("qn", "kn") if self.qk_norm else ())
         if dense is not None:
-            self.embed, self.lm_head, self.norm = dense["embed"].to(dev), dense["lm_head"].to(dev), dense["norm"].to(dev)
+            return {name: dense[name][b].to(self.dev) for name in names}
+        return {name: (1.0 + 0.05 * torch.randn(128 if name in ("qn", "kn") else self.H, device=self.dev, generator=gen)).to(torch.float16)
+                for name in names}
+
+    def _alloc_cache(self):
+        """a block's cache tensors, zeroed, under self.cache_keys"""
+        if self.kv_bits == 8:
+            return dict(zip(self.cache_keys, ops.kv8_alloc(self.B, self.nkv, self.max_seq, self.dev)))
+        return {key: torch.zeros(self.B, self.nkv, self.max_seq, 128, dtype=torch.float16, device=self.dev) for key in self.cache_keys}
+
+    def _dense_tensors(self, gen, dense=None, lm_head_packed=None):
+        """embedding, lm_head and final norm: ``dense``'s, or synthetic ones drawn in that order (after every block's draws); then the packed lm_head"""
+        if dense is not None:
+            self.embed, self.lm_head, self.norm = (dense[name].to(self.dev) for name in ("embed", "lm_head", "norm"))
         else:
-            self.embed = (torch.randn(self.vocab, self.H, device=dev, generator=gen)).to(torch.float16)
-            self.lm_head = (torch.randn(self.vocab, self.H, device=dev, generator=gen) / math.sqrt(self.H)).to(torch.float16)
-            self.norm = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
+            self.embed = (torch.randn(self.vocab, self.H, device=self.dev, generator=gen)).to(torch.float16)
+            self.lm_head = (torch.randn(self.vocab, self.H, device=self.dev, generator=gen) / math.sqrt(self.H)).to(torch.float16)
+            self.norm = (1.0 + 0.05 * torch.randn(self.H, device=self.dev, generator=gen)).to(torch.float16)
         self.lm_head_q = None
         if self.lm_head_bits != 16:
             # quantized once, here; the fp16 tensor is dropped (from_hf: the HF module keeps its own) so that no path can read a dense lm_head
@@ -420,20 +459,18 @@ class QuantLlama:
             self._check_lm_head_q()
             self.lm_head = None
 
+    def _model_facts(self):
+        """what the weights as built say about the model -- fine, owq, has_bias -- and the refusals of a model no token step serves"""
+        linears = [blk[n] for blk in self.blocks for n in self.cfg["linear"]]
         # layers with groups of 64 / 32 (HQQ's default group_size is 64): the decode step is the same five launches (amq_gemv_grouped_f16 takes the
         # group size); the prompt pass leaves the fragment-ordered few-row kernels alone (they read one (scale, zero) pair per tile) and runs
         # dequantize-once + the fp16 GEMM per linear; the A/B step forms are not offered
-        self.fine = any(blk[n].mn.numel() != ops.native_sizes(blk[n].bits, blk[n].N, blk[n].Kp)[1] // 2 for blk in self.blocks for n in config["linear"])
-        if self.fine and engine:
-            raise ValueError("the decode engine serves groups of 128")
+        self.fine = any(l.mn.numel() != ops.native_sizes(l.bits, l.N, l.Kp)[1] // 2 for l in linears)
         # OWQ layers (from_hf over HIPOWQLinear modules): the token step runs the staged plan (_step_staged), the prompt passes their plain forms
-        self.owq = any(blk[n].owq for blk in self.blocks for n in config["linear"])
-        if self.owq:
-            if engine or self.FUSE_QKV_ATTN:
-                raise ValueError(("the decode engine" if engine else "the fused q/k/v + attention launch") + " does not serve a model with OWQ layers: "
-                                 "their gather and outlier columns run as a stage launch in front of each packed GEMV (the five-launch step's staged plan)")
-            if self.fine:
-                raise ValueError("a model with OWQ layers runs the staged token step, which serves groups of 128 only")
+        self.owq = any(l.owq for l in linears)
+        self.has_bias = any(l.bias is not None for l in linears)
+        if self.owq and self.fine:
+            raise ValueError("a model with OWQ layers runs the staged token step, which serves groups of 128 only")
         # q/k/v and gate/up run as segments of ONE launch, which takes one group size: refuse a model that mixes them inside a sibling set here, at
         # build time (amq_gemv_grouped_f16 would refuse it at the first decode step; patching._same_group keeps such siblings apart on the HF side)
         for bi, blk in enumerate(self.blocks):
@@ -443,20 +480,14 @@ class QuantLlama:
                     raise ValueError(f"block {bi}: {', '.join(sibs)} mix group sizes ({sorted(128 // p for p in pairs)}); the runner issues them as "
                                      "one grouped launch, which needs one group size per sibling set")
 
-        f16 = dict(dtype=torch.float16, device=dev)
+    def _alloc_step_buffers(self):
+        """the activations of a token step of R rows (xn: normed rows, NORM_LAUNCH)"""
+        for name, width in (("x", self.H), ("xn", self.H), ("q", self.qd), ("k", self.kvd), ("v", self.kvd), ("att", self.qd), ("gate", self.I), ("up", self.I)):
+            setattr(self, name, torch.zeros(self.R, width, dtype=torch.float16, device=self.dev))
+
+    def _plan_step(self):
+        """which launches make up a step of R rows: decided here, once (the class switches as they stand now), walked by _step"""
         R = self.R
-        self.x = torch.zeros(R, self.H, **f16)
-        self.xn = torch.zeros(R, self.H, **f16)          # normed rows (NORM_LAUNCH)
-        self.q = torch.zeros(R, self.qd, **f16)
-        self.k = torch.zeros(R, self.kvd, **f16)
-        self.v = torch.zeros(R, self.kvd, **f16)
-        self.att = torch.zeros(R, self.qd, **f16)
-        self.gate = torch.zeros(R, self.I, **f16)
-        self.up = torch.zeros(R, self.I, **f16)
-        # the cos/sin table every rotating kernel reads: plain rope_theta frequencies, or the rotary embedding's own (rope_scaling)
-        self._init_step_state(rope if rope is not None else rope_inv_freq(config))
-        self.has_bias = any(blk[n].bias is not None for blk in self.blocks for n in config["linear"])
-        # which launches make up a step of R rows: decided here, once (the class switches as they stand now), walked by _step
         self.plan = step_plan(R, self.H, self.I, self.fine, ops.gemv_max_rows(self.H, plain=True), ops.gemv_max_rows(self.I, plain=not self.fine),
                               ops.gemv_max_rows(self.I, plain=not self.fine, norm=False), self.NORM_SUMS, self.NORM_FUSED_ROWS, self.DOWN_FUSED_ROWS,
                               rows_q=None if self.qd == self.H else ops.gemv_max_rows(self.qd, plain=True))
@@ -466,28 +497,25 @@ class QuantLlama:
             self.plan = StepPlan(NORM_LAUNCH, NORM_LAUNCH, DOWN_GEMV, staged=True)
             self._staged = self._build_staged()
         # the sums of squares of self.x's rows, per 16 columns: written by the launch that produced the rows, read by the one that normalises them
-        self.ss = torch.zeros(R, self.H // 16, dtype=torch.float32, device=dev) if self.plan.norm == NORM_FROM_SUMS else None
-        # the two A/B step forms rotate inside launches of their own, which carry no per-head norm and take q / o of hidden_size: not for Qwen3
-        qwen3_shape = self.qk_norm or self.qd != self.H
-        if qwen3_shape and (engine or self.FUSE_QKV_ATTN):
-            raise ValueError(("the decode engine" if engine else "the fused q/k/v + attention launch") + " does not serve this model: "
-                             + ("it has no per-head q / k norm" if self.qk_norm else f"q / o widths of heads * 128 = {self.qd} != hidden_size {self.H}"))
-        self.can_fuse_qkv_attn = (R == 1 and max_seq <= ops.ATTN_SPLIT_FROM and self.H <= 8192 and not self.fine and not self.has_bias
-                                  and not self.ragged and not qwen3_shape and self.kv_bits == 16)
+        self.ss = torch.zeros(R, self.H // 16, dtype=torch.float32, device=self.dev) if self.plan.norm == NORM_FROM_SUMS else None
+
+    def _take_routes(self, engine):
+        """the two A/B routes by the one rule: can_fuse_qkv_attn / fuse_qkv_attn, and the engine where asked for (``engine``: None = ENGINE_DEFAULT)"""
+        why_not = {route: route_reasons(route, R=self.R, ragged=self.ragged, kv_bits=self.kv_bits, fine=self.fine, owq=self.owq, has_bias=self.has_bias,
+                                        qk_norm=self.qk_norm, qd=self.qd, H=self.H, max_seq=self.max_seq) for route in ROUTES}
+        for route, asked in (("engine", engine), ("fuse_qkv_attn", self.FUSE_QKV_ATTN)):
+            # a requested route with reasons: the first one (FUSE_QKV_ATTN holds for every runner of a class: where the launch merely does not fit
+            # -- FUSE_UNFIT alone -- it stays off, silently)
+            if asked and why_not[route] and why_not[route][0] != FUSE_UNFIT:
+                raise ValueError(why_not[route][0])
+        self.can_fuse_qkv_attn = not why_not["fuse_qkv_attn"]
         self.fuse_qkv_attn = self.FUSE_QKV_ATTN and self.can_fuse_qkv_attn
-        self._tickets = torch.zeros(max(self.nh, 64), dtype=torch.int32, device=dev)
-        eligible = (self.R == 1 and max_seq <= self.ENGINE_MAX_SEQ and self.H == self.nh * 128 and not self.fine and not self.has_bias and not self.ragged
-                    and not self.qk_norm and self.kv_bits == 16)
-        if engine and not eligible:
-            raise ValueError("the decode engine needs batch 1 and max_seq <= %d" % self.ENGINE_MAX_SEQ)
-        self.engine = None
-        if engine is None:
-            engine = self.ENGINE_DEFAULT
-        if eligible and engine:
+        self._tickets = torch.zeros(max(self.nh, 64), dtype=torch.int32, device=self.dev)
+        if (self.ENGINE_DEFAULT if engine is None else engine) and not why_not["engine"]:
             self.engine = ops.DecodeEngine(
                 [dict({n: dict(qn=blk[n].qn, mn=blk[n].mn, bits=blk[n].bits, mode=blk[n].mode, N=blk[n].N) for n in ops.ENGINE_LINEARS},
                       ln1=blk["ln1"], ln2=blk["ln2"], kc=blk["kc"], vc=blk["vc"]) for blk in self.blocks],
-                self.H, self.I, self.nh, self.nkv, max_seq, self.eps, self.x.view(-1), self.rope_cur)
+                self.H, self.I, self.nh, self.nkv, self.max_seq, self.eps, self.x.view(-1), self.rope_cur)
 
     def _init_step_state(self, rope):
         """everything a runner keeps besides weights, caches and activations (needs B, R, ragged, lookup, ngram_max, vocab, max_seq, theta, dev);
@@ -1603,46 +1631,16 @@ class DenseLlama(QuantLlama):
             raise ValueError("the fp16 baseline runs one row per sequence: lookup= is served by QuantLlama")
         if ragged:
             raise ValueError("the fp16 baseline keeps one position for the whole batch: ragged=True is served by QuantLlama")
-        if isinstance(config, str):
-            config = MODEL_CONFIGS[config]
-        if not 1 <= int(batch) <= 8:
-            raise ValueError("batch must be 1..8")
-        self.B = self.R = int(batch)
-        self.ragged, self.lookup, self.ngram_max = False, 0, 0     # (one position for the whole batch, one row per sequence and step)
-        self.cfg = config
-        self.dev = torch.device(device)
-        _prime_graph_state(self.dev)
-        self.H, self.I = config["hidden_size"], config["intermediate_size"]
-        self.nh, self.nkv = config["num_heads"], config["num_kv_heads"]
-        self.kvd, self.qd = self.nkv * 128, self.nh * 128
-        self.qk_norm = bool(config.get("qk_norm"))
-        self.nb, self.vocab, self.max_seq = config["n_block"], config["vocab_size"], max_seq
-        self.eps = float(config.get("rms_norm_eps", EPS))
-        self.theta = float(config.get("rope_theta", ROPE_THETA))
+        config = MODEL_CONFIGS[config] if isinstance(config, str) else config
+        # (one position for the whole batch, one row per sequence and step; fp16 cache and lm_head)
+        self._frame(config, device, max_seq, runner_options(batch, ngram_max=0))
         gen = torch.Generator(device=self.dev).manual_seed(seed)
-        dev = self.dev
-        f16 = dict(dtype=torch.float16, device=dev)
-        self.blocks = []
-        for _ in range(self.nb):
-            blk = {}
-            for name in config["linear"]:
-                n, k = config["linear_shape"][name]
-                blk[name] = (torch.randn(n, k, device=dev, generator=gen) * (0.5 / math.sqrt(k))).to(torch.float16)
-            blk["ln1"] = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
-            blk["ln2"] = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
-            if self.qk_norm:
-                blk["qn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
-                blk["kn"] = (1.0 + 0.05 * torch.randn(128, device=dev, generator=gen)).to(torch.float16)
-            blk["kc"] = torch.zeros(self.B, self.nkv, max_seq, 128, **f16)
-            blk["vc"] = torch.zeros(self.B, self.nkv, max_seq, 128, **f16)
-            self.blocks.append(blk)
-        self.embed = torch.randn(self.vocab, self.H, device=dev, generator=gen).to(torch.float16)
-        self.lm_head = (torch.randn(self.vocab, self.H, device=dev, generator=gen) / math.sqrt(self.H)).to(torch.float16)
-        self.norm = (1.0 + 0.05 * torch.randn(self.H, device=dev, generator=gen)).to(torch.float16)
-        self.x = torch.zeros(self.B, self.H, **f16)
-        self.att = torch.zeros(self.B, self.qd, **f16)
+        lin = lambda n, k: (torch.randn(n, k, device=self.dev, generator=gen) * (0.5 / math.sqrt(k))).to(torch.float16)
+        self.blocks = [{**{name: lin(*config["linear_shape"][name]) for name in config["linear"]}, **self._block_norms(b, gen), **self._alloc_cache()}
+                       for b in range(self.nb)]
+        self._dense_tensors(gen)
+        self._alloc_step_buffers()
         self._init_step_state((None, 1.0))      # (plain rope_theta frequencies)
-        self.engine = None           # (the one-launch-per-token engine serves the quantized runner only)
 
     def linear_bytes_per_token(self):
         return sum(blk[name].numel() * 2 for blk in self.blocks for name in self.cfg["linear"])
