@@ -32,6 +32,7 @@ HQQ_ITERS = 20              # iterations of the quantizer's solver; its info blo
 HQQ_INFO_BYTES = 88         # include/amq_hip.h AMQ_HQQ_INFO_BYTES
 GPTQ_INFO_BYTES = 4         # include/amq_hip.h AMQ_GPTQ_INFO_BYTES
 AWQ_INFO_BYTES = 4          # include/amq_hip.h AMQ_AWQ_INFO_BYTES
+HINV_INFO_BYTES = 16        # include/amq_hip.h AMQ_HINV_INFO_BYTES
 OWQ_INFO_BYTES = 4          # include/amq_hip.h AMQ_OWQ_INFO_BYTES
 AWQ_STEPS = 10              # shrink steps of the AWQ clip search (err is [N, K / group, AWQ_STEPS])
 
@@ -96,6 +97,9 @@ SIGNATURES = {
     # the same with static groups and an activation order: (W, U_p, perm int32 [K], ...), the packed layer in W's own column order
     "amq_gptq_quantize_static_workspace_bytes": (_sz, [_i, _i, _i]),
     "amq_gptq_quantize_static_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the factor those solves take: fp32 H (+ perm) -> the upper Cholesky factor of the damped inverse (info = {nonfinite, failed, index, 0})
+    "amq_gptq_hinv_workspace_bytes": (_sz, [_i]),
+    "amq_gptq_hinv_f32": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     # OWQ: the range search of row segments, the solve that leaves n_out columns fp16, the layer's gather and outlier add (info = {int32 nonfinite})
     "amq_owq_range_f16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amq_owq_quantize_workspace_bytes": (_sz, [_i, _i, _i, _i]),

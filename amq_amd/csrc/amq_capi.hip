@@ -225,6 +225,24 @@ int amq_gptq_quantize_static_f16(const void* W, const void* U_p, const void* per
                                                       (hipStream_t)stream), "gptq_quantize_static");
 }
 
+size_t amq_gptq_hinv_workspace_bytes(int K) {
+    if (K <= 0 || (K % 32) != 0 || K > amq::HINV_MAX_K) return 0;
+    return amq::hinv_workspace_bytes(K);
+}
+
+int amq_gptq_hinv_f32(const void* H, const void* perm, int K, float percdamp, void* U, void* dead, void* info, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    static_assert(AMQ_HINV_INFO_BYTES == amq::HINV_INFO_BYTES, "info block");
+    if (!H || !U || !dead || !info || !workspace) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)H & 3) != 0 || ((uintptr_t)perm & 3) != 0 || ((uintptr_t)U & 3) != 0 || ((uintptr_t)info & 3) != 0 ||
+        ((uintptr_t)workspace & 15) != 0)
+        return fail(AMQ_EINVAL, "H, perm, U and info must be 4-byte aligned, workspace 16-byte aligned");
+    if (K <= 0 || (K % 32) != 0 || K > amq::HINV_MAX_K)
+        return fail(AMQ_EINVAL, "need K a positive multiple of 32, at most %d (got K=%d)", (int)amq::HINV_MAX_K, K);
+    if (int rc = check_workspace("hinv", amq::hinv_workspace_bytes(K), workspace_bytes)) return rc;
+    return check_hip(amq::launch_gptq_hinv(H, perm, K, percdamp, U, dead, info, workspace, (hipStream_t)stream), "gptq_hinv");
+}
+
 // OWQ: groups of 128 only (AMQ's); the shape rules of the range search and of the solve, in the order the header documents
 static int check_owq_shape(int bits, int N, int K, int group, int num) {
     if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);

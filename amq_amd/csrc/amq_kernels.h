@@ -392,6 +392,14 @@ hipError_t launch_gptq_quantize(const void* W, const void* U, int N, int K, int 
 // group's (scale, zero) comes from W's original columns in a launch of its own, the codes leave in W's own column order.  The same workspace.
 hipError_t launch_gptq_quantize_static(const void* W, const void* U, const void* perm, int N, int K, int bits, int group, void* W_q, void* scale,
                                        void* zero, void* row_loss, void* info, void* workspace, hipStream_t st);
+// fp32 H[K,K] -> fp32 U[K,K], the upper Cholesky factor of the damped inverse Hessian, as U = R^-1 of the backward factorisation A = R R^T
+// (amq_hinv.hip).  Blocks and tiles of 64; the matrices are padded at the top-left to Kp = ceil(K / 64) * 64.  workspace: fp32 A[Kp][Kp] (becomes
+// R), fp32 Um[Kp][Kp] (the inverse and its partial sums), 64 bytes (damp).  info: {int32 nonfinite, int32 failed pivot, int32 its index, 0}.
+enum { HINV_NB = 64, HINV_INFO_BYTES = 16, HINV_MAX_K = 65504 };
+inline int hinv_blocks(int K) { return (K + HINV_NB - 1) / HINV_NB; }
+inline size_t hinv_workspace_bytes(int K) { const size_t Kp = (size_t)hinv_blocks(K) * HINV_NB; return 8 * Kp * Kp + 64; }
+hipError_t launch_gptq_hinv(const void* H, const void* perm, int K, float percdamp, void* U, void* dead, void* info, void* workspace,
+                            hipStream_t st);
 // what ends the GPTQ solve and AWQ's passes (amq_quant_pack.hip): the n per-wave nonfinite flags ORed into one word of the info block, and byte
 // codes [R, group] -> Format A (hqq/core/bitpack.py row chunks), one thread per packed word
 hipError_t launch_quant_flags(const int* NF, size_t n, int* info_word, hipStream_t st);

@@ -239,11 +239,58 @@ class GPTQHessian:
         self.H += x.matmul(x.t())
 
 
-def gptq_hinv(H, percdamp=0.01, name=None, return_where=False):
+def gptq_hinv_launch(H, perm, percdamp, U, dead, info, workspace):
+    """the bare entry point of the factor kernels over caller-owned buffers (4 * ceil(K / 64) launches on the current stream; no allocation, no
+    read-back: capturable).  ``perm``: int32 [K], a permutation, or None -- the entry point cannot check it (``gptq_hinv`` does)."""
+    K = H.shape[0]
+    _lib.check(_lib.load().amq_gptq_hinv_f32(_lib.ptr(H), _lib.ptr(perm), K, float(percdamp), _lib.ptr(U), _lib.ptr(dead), _lib.ptr(info),
+                                             _lib.ptr(workspace), _nbytes(workspace), _lib.current_stream()))
+
+
+def gptq_hinv_buffers(K, device):
+    """(U fp32 [K, K], dead uint8 [K], info, workspace) of the right sizes for ``gptq_hinv_launch``"""
+    words = _workspace_words("amq_gptq_hinv_workspace_bytes", "the factor kernels (K a positive multiple of 32)", K=int(K))
+    return (torch.empty(K, K, dtype=torch.float32, device=device), torch.empty(K, dtype=torch.uint8, device=device),
+            _info_block(_lib.HINV_INFO_BYTES, device), _quantize_scratch.get(device, words))
+
+
+def _gptq_hinv_hip(H, percdamp, name, perm):
+    if not isinstance(H, torch.Tensor) or not H.is_cuda:
+        raise ValueError("gptq_hinv: method='hip' runs on the GPU; H is not a GPU tensor (method='torch' factors it where it is)")
+    if H.dim() != 2 or H.shape[0] != H.shape[1]:
+        raise ValueError(f"gptq_hinv: expected a square H, got {tuple(H.shape)}")
+    H = H.detach().to(torch.float32).contiguous()
+    K = H.shape[0]
+    if perm is not None:
+        perm = _gptq_perm(perm, K, H.device)
+    U, dead, info, workspace = gptq_hinv_buffers(K, H.device)
+    gptq_hinv_launch(H, perm, percdamp, U, dead, info, workspace)
+    nonfinite, failed, index = info.cpu()[:3].tolist()
+    if nonfinite:
+        raise ValueError(f"gptq_hinv: the Hessian of {'layer ' + name if name else 'the layer'} holds inf or NaN values")
+    if failed:
+        raise ValueError(f"gptq_hinv: the damped Hessian of {'layer ' + name if name else 'the layer'} is not positive definite "
+                         f"(the pivot of walk column {index} is not positive)")
+    return U, dead.bool()
+
+
+def gptq_hinv(H, percdamp=0.01, name=None, return_where=False, perm=None, method="torch"):
     """(U, dead): the upper Cholesky factor of the damped inverse of H (gptq.py:224-253: dead columns get a unit diagonal, the diagonal is damped
     by ``percdamp`` of its mean, then cholesky, cholesky_inverse, cholesky(upper)) and the bool mask of the dead columns.  H is not modified.
-    ``torch.linalg`` runs on H's device; a build that lacks the factorisation there runs it on the host and brings U back
-    (``return_where``: also return ``'device'`` or ``'host'``).  A failed factorisation raises ValueError naming the layer."""
+    ``perm`` (an integer tensor [K], a permutation): the factor and the mask of ``H[perm][:, perm]``, in walk order.
+
+    ``method="torch"``: ``torch.linalg`` runs on H's device; a build that lacks the factorisation there runs it on the host and brings U back
+    (``return_where``: also return ``'device'`` or ``'host'``).  ``method="hip"``: the HIP kernels of include/amq_hip.h amq_gptq_hinv_f32 (one
+    backward factorisation A = R R^T and U = R^-1: half the flops, the same matrix to fp32 round-off, not the same bits; H on the GPU, K a multiple
+    of 32; ``perm`` is read by the kernel, no permuted copy is made; one synchronising read of the 16-byte info block); ``return_where`` gives
+    ``'kernel'``.  A failed factorisation raises ValueError naming the layer, with either method."""
+    if method == "hip":
+        U, dead = _gptq_hinv_hip(H, percdamp, name, perm)
+        return (U, dead, "kernel") if return_where else (U, dead)
+    if method != "torch":
+        raise ValueError(f"gptq_hinv: method must be 'torch' or 'hip' (got {method!r})")
+    if perm is not None:
+        H = H[perm][:, perm]
     H = H.detach().to(torch.float32).clone()
     dead = torch.diag(H) == 0
     idx = torch.arange(H.shape[0], device=H.device)
@@ -2153,7 +2200,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_quantize", "gptq_quantize_launch", "gptq_quantize_static_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
+for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_hinv", "gptq_hinv_launch", "gptq_quantize", "gptq_quantize_launch", "gptq_quantize_static_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "lm8_gemv", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup", "decode_tail_lookup_sample"):
     globals()[_name] = _on_tensor_device(globals()[_name])

@@ -420,7 +420,7 @@ def _proxy_loss(W, W_hat, H):
 
 @torch.no_grad()
 def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=False, device=None, act_order=False,
-                        static_groups=False):
+                        static_groups=False, hinv="torch"):
     """The reference's ``GPTQ.run`` (amq/quantization/gptq.py:25-161: asymmetric, grouped; act_order and static_groups as below) for a dense HF
     llama / mistral / qwen2 / qwen3 model, ending in packed layers: block by block, one Hessian per linear is accumulated over ``samples`` with
     forward hooks (ops.GPTQHessian), every linear is quantized at ``_bits_of(bits, name, block)`` by the error-feedback solve (ops.gptq_hinv,
@@ -430,7 +430,9 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
     down), each calibrated on the outputs of the quantized ones before it.  The whole model works on ``device`` (default: the model's own GPU,
     else cuda:0).  Returns (model, report) with ``report[(block, name)] = {"loss": tr(dW H dW^T), "rtn_loss": the same for
     hqq_format.quantize_rtn at the same bits and group, "solver_loss": the solve's own sum of row losses (the reference's printed error), "dead":
-    the number of dead columns, "bits", "act_order", "static_groups"}``.  The model is then ready for ``prepare_for_inference(backend='hip')``.
+    the number of dead columns, "bits", "act_order", "static_groups", "hinv": where the factor was computed}``.  The model is then ready for
+    ``prepare_for_inference(backend='hip')``.  ``hinv``: ``ops.gptq_hinv``'s ``method`` -- ``"torch"`` (torch.linalg) or ``"hip"`` (the factor
+    kernels, which read ``perm`` themselves: no permuted copy of H is made).
 
     ``static_groups``: every group's (scale, zero) comes from the layer's original columns, not from the running ones.  ``act_order`` (with
     ``static_groups``): the solve walks the columns by descending ``diag(H)`` (ops.gptq_act_order) over the factor of the equally permuted Hessian;
@@ -458,7 +460,7 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
                     lin, nb = full[name], _bits_of(bits, name, b)
                     H = hess[name].H
                     perm = ops.gptq_act_order(H) if act_order else None
-                    U, dead = ops.gptq_hinv(H if perm is None else H[perm][:, perm], percdamp, name=f"{b}.{name}")
+                    U, dead, where = ops.gptq_hinv(H, percdamp, name=f"{b}.{name}", return_where=True, perm=perm, method=hinv)
                     if perm is not None:
                         dead = torch.diag(H) == 0              # (gptq_hinv's mask is in walk order)
                     W = lin.weight.detach().to(torch.float16).clone()
@@ -469,7 +471,7 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
                     W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, *W.shape, group_size)
                     report[(b, name)] = {"loss": _proxy_loss(W, W_hat, H), "rtn_loss": _proxy_loss(W, _rtn_dequantized(W, nb, group_size), H),
                                          "solver_loss": info.loss, "dead": int(dead.sum().item()), "bits": nb,
-                                         "act_order": bool(act_order), "static_groups": bool(static_groups)}
+                                         "act_order": bool(act_order), "static_groups": bool(static_groups), "hinv": where}
                     lin.weight.data = W_hat.to(lin.weight.dtype)
                     packed[name] = h
             inps = [run(layer, x).detach() for x in inps]
@@ -503,7 +505,8 @@ def _owq_avg_bits(model, bits, group_size):
 
 
 @torch.no_grad()
-def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=True, frob_norm=True, n_out=None, device=None):
+def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=True, frob_norm=True, n_out=None, device=None,
+                       hinv="torch"):
     """The reference's ``OWQ.run`` (amq/quantization/owq.py:50-237: asymmetric, grouped, act_order=False) for a dense HF llama / mistral / qwen2 /
     qwen3 model, ending in deployable layers (the reference only writes fake-quantized fp16 weights): block by block and subset by subset (the
     four ``TRUE_SEQUENTIAL`` subsets by default, as the reference's), one Hessian per linear is accumulated over ``samples`` with forward hooks
@@ -513,7 +516,8 @@ def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true
     the new layer dequantizes to for the block's second forward; at the block's end the linears become HIPOWQLinear modules (HIPQuantLinear where
     n_out is 0).  ``n_out``: None = the reference's rule (``owq_n_out`` at the assignment's average bits), an int for every linear, or a dict
     name -> int (names as in arch.LINEARS; a missing name takes the rule).  Groups of 128 only.  Returns (model, report) with
-    ``report[(block, name)] = {"loss", "rtn_loss", "solver_loss", "dead", "bits", "n_out", "out_ids"}`` -- loss = tr(dW H dW^T) over all K
+    ``report[(block, name)] = {"loss", "rtn_loss", "solver_loss", "dead", "bits", "n_out", "out_ids", "hinv"}`` (``hinv``: ``ops.gptq_hinv``'s
+    ``method``, ``"torch"`` or ``"hip"``; the report holds where the factor was computed) -- loss = tr(dW H dW^T) over all K
     columns, the outliers' change included.  ``prepare_for_inference(backend='hip')`` leaves an OWQ model's layers as they are; the hipGraph
     runner takes them (``QuantLlama.from_hf``, ``hf_fast.convert_model_to_hip``, ``evaluate``: the staged token step)."""
     from .arch import LINEARS
@@ -549,8 +553,7 @@ def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true
                         ids, out_ids = ops.owq_select(W, H, no, nb)
                     else:
                         ids, out_ids = ops.owq_select(W, H, 0, nb) if no == 0 else _owq_select_by_hessian(H, no)
-                    Hp = H[ids][:, ids]
-                    U, dead = ops.gptq_hinv(Hp, percdamp, name=f"{b}.{name}")
+                    U, dead, where = ops.gptq_hinv(H, percdamp, name=f"{b}.{name}", return_where=True, perm=ids, method=hinv)
                     Wp = W[:, ids].contiguous()
                     Wp[:, dead] = 0
                     bias = None if lin.bias is None else lin.bias.detach().to(device, torch.float16)
@@ -561,7 +564,7 @@ def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true
                     W0[:, ids[dead]] = 0
                     report[(b, name)] = {"loss": _proxy_loss(W0, W_hat, H), "rtn_loss": _proxy_loss(W0, _rtn_dequantized(W0, nb, group_size), H),
                                          "solver_loss": info.loss, "dead": int(dead.sum().item()), "bits": nb, "n_out": no,
-                                         "out_ids": out_ids.cpu()}
+                                         "out_ids": out_ids.cpu(), "hinv": where}
                     lin.weight.data = W_hat.to(lin.weight.dtype)
                     made[name] = mod
             inps = [run(layer, x).detach() for x in inps]

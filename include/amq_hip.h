@@ -224,6 +224,32 @@ size_t amq_gptq_quantize_static_workspace_bytes(int N, int K, int group);
 int amq_gptq_quantize_static_f16(const void* W, const void* U_p, const void* perm, int N, int K, int bits, int group, void* W_q, void* scale,
                                  void* zero, void* row_loss, void* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The factor the three solves above take as U: the upper-triangular U with U^T U = A^-1, A the damped Hessian (gptq.py:224-253), on `stream`.
+ * A = H (with a permutation: A[i][j] = H[perm[i]][perm[j]], walk order) with the diagonal entries that are 0 (dead columns) set to 1 and
+ * damp = percdamp * mean(diag) added to the diagonal; the diagonal is summed in a fixed order in fp64 and damp rounded once to fp32.  Only H's upper
+ * triangle (in walk order) is read.  A = R R^T is factored with R UPPER triangular -- a Cholesky factorisation walking from the bottom-right corner
+ * up-left, in blocks of 64 -- and U = R^-1, since A^-1 = R^-T R^-1 and the upper factor with a positive diagonal is unique: one factorisation and
+ * one triangular inverse (2 K^3 / 3 flops), no explicit A^-1.  fp32 throughout; sqrt and the divisions by pivots correctly rounded; the block
+ * products on the fp32 matrix instructions, the triangular solves as products with the inverted diagonal blocks.  Not bit for bit what
+ * cholesky, cholesky_inverse, cholesky(upper) give; the same matrix to fp32 round-off.  4 * ceil(K / 64) launches; no host read, no
+ * allocation, no atomics: a call gives the same bits as the next, and perm gives the bits of the call on the permuted matrix.
+ *   H          fp32 [K, K], 4-byte aligned; never written
+ *   perm       int32 [K], 4-byte aligned, a permutation of 0 .. K - 1, or NULL (the identity).  The entry point cannot read it: the caller
+ *              guarantees it (an entry outside 0 .. K - 1 is read as 0 and sets info's first word)
+ *   U          fp32 [K, K], 4-byte aligned: every element is written, the strict lower triangle as exact zeros
+ *   dead       uint8 [K]: 1 where the diagonal of H (walk order) is 0
+ *   info       AMQ_HINV_INFO_BYTES: {int32 nonfinite (!= 0: H's upper triangle held an inf or NaN), int32 failed (!= 0: a pivot was <= 0 or not
+ *              finite -- A is not positive definite in fp32; the walk went on with 1 in its place), int32 index (walk order) of the first pivot
+ *              that failed -- the walk runs from K - 1 down --, int32 0}.  With either flag set U is meaningless.
+ *   workspace  amq_gptq_hinv_workspace_bytes(K) = 8 * Kp^2 + 64 bytes, Kp = ceil(K / 64) * 64 (fp32 A [Kp, Kp], which becomes R; fp32 [Kp, Kp] for
+ *              the inverse and its partial sums; damp), 16-byte aligned; 0 for a K the call refuses
+ * Refused, in this order: a null (perm excepted) or misaligned pointer; K not a positive multiple of 32 (or above 65504); workspace_bytes too
+ * small (all AMQ_EINVAL). */
+#define AMQ_HINV_INFO_BYTES 16
+size_t amq_gptq_hinv_workspace_bytes(int K);
+int amq_gptq_hinv_f32(const void* H, const void* perm, int K, float percdamp, void* U, void* dead, void* info, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* AWQ's weight-side passes (awq_utils/quantizer.py pseudo_quantize_tensor with zero_point, auto_clip.py auto_clip_layer_asym) to the same Format A.
  * All fp32, every operation its own IEEE rounding, IEEE division, rint = round-half-even, no contraction except the fmaf written out below.
  * RTN of one group v[0..G) of fp16 values: maxq = 2^bits - 1, xmax = max v, xmin = min v, s = max(xmax - xmin, 1e-5f) / maxq, s16 = fp16(s) (never

@@ -20,6 +20,13 @@ variant's U is the factor of H[perm][:, perm]), alternate, and report the median
 tr(dW H dW^T) of each result and their ratio.  A synthetic calibration: nothing here says what the variant does to a real model's perplexity.
 
     python tools/gptq_bench.py --act-order [--repeats 5] [--tokens 2048] [--out profiles/gptq_actorder.json]
+
+``--hinv``: the factorise leg's two routes, ops.gptq_hinv(H, method="torch") (three torch.linalg calls) and method="hip" (csrc/amq_hinv.hip),
+alternating in one process at K = 4096, 11008 and 14336 on a Hessian of ``--tokens`` rows (at least 2 K here): median of ``--repeats`` after a
+warm-up round, spreads, where each ran, and per K the error figures of tests/test_gpu_gptq_hinv.py -- E(U) = max |U^T U A - I| in fp64 for the
+kernels' U, the device route's U and the route run on the host in fp32, and E(kernel) / E(host) -- at these sizes and at the tests' own.
+
+    python tools/gptq_bench.py --hinv [--repeats 5] [--out profiles/gptq_hinv.json]
 """
 import argparse
 import json
@@ -145,16 +152,91 @@ def act_order_main(a):
             f.write("\n")
 
 
+HINV_SIZES = (4096, 11008, 14336)
+HINV_TEST_SIZES = (32, 64, 96, 288, 1408)
+
+
+def hinv_main(a):
+    """the two routes of ops.gptq_hinv: one row per K"""
+    from amq_amd import ops
+
+    def hessian(K, on_device):
+        acc = ops.GPTQHessian(K, DEV)
+        if on_device:
+            g = torch.Generator(device=DEV).manual_seed(K)
+            for lo in range(0, 2 * K, 2048):
+                acc.add_batch(torch.randn(2048, K, device=DEV, generator=g).unsqueeze(0))
+        else:                                       # the tests' construction
+            X = torch.randn(2 * K, K, generator=torch.Generator().manual_seed(K))
+            for lo in range(0, 2 * K, 64):
+                acc.add_batch(X[lo:lo + 64].unsqueeze(0).to(DEV))
+        return acc.H
+
+    def residual(U, H):
+        A = H.clone()
+        idx = torch.arange(A.shape[0], device=A.device)
+        A[idx, idx] += 0.01 * torch.mean(torch.diag(A))
+        U = U.to(A.device).double()
+        P = (U.t() @ U) @ A.double()
+        P[idx, idx] -= 1.0
+        return float(P.abs().max().item())
+
+    def errors(H):
+        e = {"kernel": residual(ops.gptq_hinv(H, 0.01, method="hip")[0], H), "device_route": residual(ops.gptq_hinv(H, 0.01)[0], H),
+             "host_fp32_route": residual(ops.gptq_hinv(H.cpu(), 0.01)[0], H)}
+        e["kernel_over_host"] = round(e["kernel"] / e["host_fp32_route"], 4)
+        return e
+
+    rows, small = [], {}
+    with torch.inference_mode():
+        for K in HINV_TEST_SIZES:
+            small[str(K)] = errors(hessian(K, False))
+        print(json.dumps(small), flush=True)
+        for K in HINV_SIZES:
+            H = hessian(K, True)
+            where = {}
+            legs = {"torch": lambda: where.__setitem__("torch", ops.gptq_hinv(H, 0.01, return_where=True)[2]),
+                    "hip": lambda: where.__setitem__("hip", ops.gptq_hinv(H, 0.01, return_where=True, method="hip")[2])}
+            runs = {k: [] for k in legs}
+            for rep in range(a.repeats + 1):            # (the first round warms up: not kept)
+                for leg, fn in legs.items():
+                    ms = _timed(fn)
+                    if rep:
+                        runs[leg].append(ms)
+            row = {"K": K, "repeats": a.repeats, "ran_on": dict(where), "launches": 4 * ((K + 63) // 64)}
+            for leg, ts in runs.items():
+                _runs(row, leg, ts)
+            row["torch_over_hip"] = round(row["torch_ms"] / row["hip_ms"], 2)
+            row["hip_gflops"] = round(2.0 * K ** 3 / 3.0 / row["hip_ms"] / 1e6, 1)      # the algorithm's 2 K^3 / 3 over the call's time
+            row["error"] = errors(H)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del H
+            torch.cuda.empty_cache()
+    res = {"device": torch.cuda.get_device_name(0), "per_K": rows, "test_sizes_error": small,
+           "worst_kernel_over_host": max(e["kernel_over_host"] for e in list(small.values()) + [r["error"] for r in rows]),
+           "note": "call times (host clock around a synchronised call, one 16-byte read-back included), not kernel times; random calibration"}
+    if a.out:
+        doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        doc["timing"] = res
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--tokens", type=int, default=2048)
     ap.add_argument("--out", default=None)
     ap.add_argument("--act-order", action="store_true", help="time the act-order + static-groups variant against the plain solve")
+    ap.add_argument("--hinv", action="store_true", help="time the two routes of ops.gptq_hinv (torch.linalg, the HIP kernels) and record their errors")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     if a.act_order:
         return act_order_main(a)
+    if a.hinv:
+        return hinv_main(a)
     from amq_amd import ops
     from amq_amd.hqq_format import pack_rows
 
