@@ -100,6 +100,9 @@ SIGNATURES = {
     # the factor those solves take: fp32 H (+ perm) -> the upper Cholesky factor of the damped inverse (info = {nonfinite, failed, index, 0})
     "amq_gptq_hinv_workspace_bytes": (_sz, [_i]),
     "amq_gptq_hinv_f32": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the Hessian they start from: fp16 x [T, K] (row stride) into the running fp32 H [K, K]: (x, stride, T, K, H, n_before, b, workspace, bytes, stream)
+    "amq_gptq_hessian_workspace_bytes": (_sz, [_i, _i]),
+    "amq_gptq_hessian_f16": (_i, [_vp, ctypes.c_long, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
     # OWQ: the range search of row segments, the solve that leaves n_out columns fp16, the layer's gather and outlier add (info = {int32 nonfinite})
     "amq_owq_range_f16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amq_owq_quantize_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -243,6 +243,27 @@ int amq_gptq_hinv_f32(const void* H, const void* perm, int K, float percdamp, vo
     return check_hip(amq::launch_gptq_hinv(H, perm, K, percdamp, U, dead, info, workspace, (hipStream_t)stream), "gptq_hinv");
 }
 
+// the Hessian kernel makes one pass over T per tile and needs no workspace: the query answers 0 for every shape, the argument is not looked at
+size_t amq_gptq_hessian_workspace_bytes(int T, int K) {
+    (void)T;
+    (void)K;
+    return 0;
+}
+
+int amq_gptq_hessian_f16(const void* x, long x_row_stride, int T, int K, void* H, int n_before, int b, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    (void)workspace;
+    (void)workspace_bytes;
+    if (!x || !H) return fail(AMQ_EINVAL, "null pointer");
+    if (((uintptr_t)x & 15) != 0 || ((uintptr_t)H & 15) != 0) return fail(AMQ_EINVAL, "x and H must be 16-byte aligned");
+    if (K <= 0 || (K % 32) != 0 || K > amq::HINV_MAX_K)
+        return fail(AMQ_EINVAL, "need K a positive multiple of 32, at most %d (got K=%d)", (int)amq::HINV_MAX_K, K);
+    if (T < 1 || b < 1 || n_before < 0) return fail(AMQ_EINVAL, "need T >= 1, b >= 1, n_before >= 0 (got T=%d b=%d n_before=%d)", T, b, n_before);
+    if (x_row_stride < K || (x_row_stride % 8) != 0)
+        return fail(AMQ_EINVAL, "x_row_stride must be a multiple of 8 and at least K (got %ld, K=%d)", x_row_stride, K);
+    return check_hip(amq::launch_gptq_hessian(x, x_row_stride, T, K, H, n_before, b, (hipStream_t)stream), "gptq_hessian");
+}
+
 // OWQ: groups of 128 only (AMQ's); the shape rules of the range search and of the solve, in the order the header documents
 static int check_owq_shape(int bits, int N, int K, int group, int num) {
     if (bits != 2 && bits != 3 && bits != 4) return fail(AMQ_EINVAL, "bits must be 2, 3 or 4 (got %d)", bits);

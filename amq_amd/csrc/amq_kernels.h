@@ -400,6 +400,10 @@ inline int hinv_blocks(int K) { return (K + HINV_NB - 1) / HINV_NB; }
 inline size_t hinv_workspace_bytes(int K) { const size_t Kp = (size_t)hinv_blocks(K) * HINV_NB; return 8 * Kp * Kp + 64; }
 hipError_t launch_gptq_hinv(const void* H, const void* perm, int K, float percdamp, void* U, void* dead, void* info, void* workspace,
                             hipStream_t st);
+// fp16 x[T, K] (row stride in elements) into the running fp32 H[K, K]: H = H n / (n + b) + (2 / (n + b)) x^T x, one launch over the 128 x 128 tiles
+// on or above the diagonal, each written with its mirror (amq_hessian.hip).  No workspace: T is not split.
+enum { HESS_TILE = 128 };
+hipError_t launch_gptq_hessian(const void* x, long x_row_stride, int T, int K, void* H, int n_before, int b, hipStream_t st);
 // what ends the GPTQ solve and AWQ's passes (amq_quant_pack.hip): the n per-wave nonfinite flags ORed into one word of the info block, and byte
 // codes [R, group] -> Format A (hqq/core/bitpack.py row chunks), one thread per packed word
 hipError_t launch_quant_flags(const int* NF, size_t n, int* info_word, hipStream_t st);

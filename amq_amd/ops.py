@@ -220,11 +220,36 @@ def hqq_quantize(W, nbits, group_size=GROUP, round_zero=None, return_info=False,
     return (h, got) if return_info else h
 
 
+def gptq_hessian_launch(x, H, n_before, b, workspace=None):
+    """the bare entry point of the Hessian kernel over caller-owned buffers: fp16 x [T, K] (rows of ``b`` sequences; unit column stride, row stride
+    a multiple of 8) into fp32 H [K, K], ``H = H n_before / (n_before + b) + (2 / (n_before + b)) x^T x``.  One launch on the current stream; no
+    allocation, no read-back: capturable.  The kernel needs no workspace (``amq_gptq_hessian_workspace_bytes`` is 0): ``workspace`` may be None."""
+    T, K = x.shape
+    if x.dtype != torch.float16 or H.dtype != torch.float32 or tuple(H.shape) != (K, K) or not H.is_contiguous() or x.stride(1) != 1:
+        raise ValueError(f"gptq_hessian_launch: need fp16 x [T, K] with unit column stride and a contiguous fp32 H [K, K] "
+                         f"(got {x.dtype} {tuple(x.shape)} strides {x.stride()}, {H.dtype} {tuple(H.shape)})")
+    _lib.check(_lib.load().amq_gptq_hessian_f16(_lib.ptr(x), x.stride(0) if T > 1 else K, T, K, _lib.ptr(H), int(n_before), int(b), _lib.ptr(workspace),
+                                                0 if workspace is None else _nbytes(workspace), _lib.current_stream()))
+
+
 class GPTQHessian:
     """The running Hessian of one linear's inputs, the reference's form (amq/quantization/gptq.py:199-204) as torch fp32 ops on ``device``:
-    ``H <- H * n / (n + b); n += b; H += (sqrt(2 / n) x)^T (sqrt(2 / n) x)`` per batch of b sequences, x the batch's rows [b * seqlen, K]."""
+    ``H <- H * n / (n + b); n += b; H += (sqrt(2 / n) x)^T (sqrt(2 / n) x)`` per batch of b sequences, x the batch's rows [b * seqlen, K].
 
-    def __init__(self, K, device):
+    ``method="hip"``: the same update, ``H <- H n / (n + b) + (2 / (n + b)) x^T x``, as one launch of the Hessian kernel (include/amq_hip.h
+    amq_gptq_hessian_f16: exact fp16 products summed in fp32 on the matrix cores, upper tiles computed and mirrored, H read and written once; not
+    the torch route's bits).  H on a GPU, x fp16, K a multiple of 32; x is copied only where its row stride or alignment rules it out;
+    ``add_batch`` does not synchronise."""
+
+    def __init__(self, K, device, method="torch"):
+        if method not in ("torch", "hip"):
+            raise ValueError(f"GPTQHessian: method must be 'torch' or 'hip' (got {method!r})")
+        if method == "hip":
+            if torch.device(device).type != "cuda":
+                raise ValueError(f"GPTQHessian: method='hip' runs on the GPU, not on {device} (method='torch' accumulates where H is)")
+            if int(K) <= 0 or int(K) % 32:
+                raise ValueError(f"GPTQHessian: method='hip' needs K a positive multiple of 32, got {K} (method='torch' takes any K)")
+        self.method = method
         self.H = torch.zeros(int(K), int(K), dtype=torch.float32, device=device)
         self.nsamples = 0
 
@@ -232,6 +257,18 @@ class GPTQHessian:
         if x.dim() == 2:
             x = x.unsqueeze(0)
         b = x.shape[0]
+        if self.method == "hip":
+            if x.dtype != torch.float16:
+                raise ValueError(f"GPTQHessian: method='hip' takes fp16 activations, got {x.dtype} (method='torch' takes any dtype)")
+            x = x.reshape(-1, x.shape[-1])
+            bad_rows = x.shape[0] > 1 and (x.stride(0) < x.shape[1] or x.stride(0) % 8)
+            if x.device != self.H.device or x.stride(1) != 1 or bad_rows or x.data_ptr() % 16:
+                x = x.to(self.H.device).contiguous()
+                if x.data_ptr() % 16:
+                    x = x.clone()
+            gptq_hessian_launch(x, self.H, self.nsamples, b)       # (makes x's device current)
+            self.nsamples += b
+            return
         x = x.reshape(-1, x.shape[-1]).t()
         self.H *= self.nsamples / (self.nsamples + b)
         self.nsamples += b
@@ -2200,7 +2237,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_hinv", "gptq_hinv_launch", "gptq_quantize", "gptq_quantize_launch", "gptq_quantize_static_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
+for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_hinv", "gptq_hessian_launch", "gptq_hinv_launch", "gptq_quantize", "gptq_quantize_launch", "gptq_quantize_static_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
               "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "lm8_gemv", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup", "decode_tail_lookup_sample"):
     globals()[_name] = _on_tensor_device(globals()[_name])

@@ -418,9 +418,16 @@ def _proxy_loss(W, W_hat, H):
     return float(((d @ H) * d).sum().item())
 
 
+def _hessian_route(hessian, who):
+    """what the reports call the route of ``ops.GPTQHessian(method=hessian)``"""
+    if hessian not in ("torch", "hip"):
+        raise ValueError(f"{who}: hessian must be 'torch' (the default accumulation) or 'hip' (the Hessian kernel), got {hessian!r}")
+    return "kernel" if hessian == "hip" else "torch"
+
+
 @torch.no_grad()
 def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=False, device=None, act_order=False,
-                        static_groups=False, hinv="torch"):
+                        static_groups=False, hinv="torch", hessian="torch"):
     """The reference's ``GPTQ.run`` (amq/quantization/gptq.py:25-161: asymmetric, grouped; act_order and static_groups as below) for a dense HF
     llama / mistral / qwen2 / qwen3 model, ending in packed layers: block by block, one Hessian per linear is accumulated over ``samples`` with
     forward hooks (ops.GPTQHessian), every linear is quantized at ``_bits_of(bits, name, block)`` by the error-feedback solve (ops.gptq_hinv,
@@ -432,7 +439,9 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
     hqq_format.quantize_rtn at the same bits and group, "solver_loss": the solve's own sum of row losses (the reference's printed error), "dead":
     the number of dead columns, "bits", "act_order", "static_groups", "hinv": where the factor was computed}``.  The model is then ready for
     ``prepare_for_inference(backend='hip')``.  ``hinv``: ``ops.gptq_hinv``'s ``method`` -- ``"torch"`` (torch.linalg) or ``"hip"`` (the factor
-    kernels, which read ``perm`` themselves: no permuted copy of H is made).
+    kernels, which read ``perm`` themselves: no permuted copy of H is made).  ``hessian``: ``ops.GPTQHessian``'s ``method`` for the accumulators the
+    hooks feed -- ``"torch"`` or ``"hip"`` (the Hessian kernel: fp16 models, in_features a multiple of 32); the report's ``"hessian"`` is
+    ``"torch"`` or ``"kernel"``.
 
     ``static_groups``: every group's (scale, zero) comes from the layer's original columns, not from the running ones.  ``act_order`` (with
     ``static_groups``): the solve walks the columns by descending ``diag(H)`` (ops.gptq_act_order) over the factor of the equally permuted Hessian;
@@ -442,13 +451,14 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
     if act_order and not static_groups:
         raise NotImplementedError("quantize_model_gptq: act_order without static_groups forms its groups over the permuted columns, which is not "
                                   "a Format A layer (it would need a gather of x at run time); pass static_groups=True as well")
+    accumulated = _hessian_route(hessian, "quantize_model_gptq")
     report = {}
     with _calibrating(model, samples, device) as (device, inps, _, run):
         for b, layer in enumerate(model.model.layers):
             full = _block_linears(layer)
             packed = {}
             for names in (TRUE_SEQUENTIAL if true_sequential else (tuple(LINEARS),)):
-                hess = {name: ops.GPTQHessian(full[name].in_features, device) for name in names}
+                hess = {name: ops.GPTQHessian(full[name].in_features, device, method=hessian) for name in names}
                 handles = [full[name].register_forward_hook(lambda _, inp, out, acc=hess[name]: acc.add_batch(inp[0].detach())) for name in names]
                 try:
                     for x in inps:
@@ -471,7 +481,8 @@ def quantize_model_gptq(model, bits, samples, group_size=128, percdamp=0.01, tru
                     W_hat = ops.dequantize_hqq(h.W_q, h.scale.reshape(-1), h.zero.reshape(-1), nb, *W.shape, group_size)
                     report[(b, name)] = {"loss": _proxy_loss(W, W_hat, H), "rtn_loss": _proxy_loss(W, _rtn_dequantized(W, nb, group_size), H),
                                          "solver_loss": info.loss, "dead": int(dead.sum().item()), "bits": nb,
-                                         "act_order": bool(act_order), "static_groups": bool(static_groups), "hinv": where}
+                                         "act_order": bool(act_order), "static_groups": bool(static_groups), "hinv": where,
+                                         "hessian": accumulated}
                     lin.weight.data = W_hat.to(lin.weight.dtype)
                     packed[name] = h
             inps = [run(layer, x).detach() for x in inps]
@@ -506,7 +517,7 @@ def _owq_avg_bits(model, bits, group_size):
 
 @torch.no_grad()
 def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true_sequential=True, frob_norm=True, n_out=None, device=None,
-                       hinv="torch"):
+                       hinv="torch", hessian="torch"):
     """The reference's ``OWQ.run`` (amq/quantization/owq.py:50-237: asymmetric, grouped, act_order=False) for a dense HF llama / mistral / qwen2 /
     qwen3 model, ending in deployable layers (the reference only writes fake-quantized fp16 weights): block by block and subset by subset (the
     four ``TRUE_SEQUENTIAL`` subsets by default, as the reference's), one Hessian per linear is accumulated over ``samples`` with forward hooks
@@ -517,12 +528,14 @@ def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true
     n_out is 0).  ``n_out``: None = the reference's rule (``owq_n_out`` at the assignment's average bits), an int for every linear, or a dict
     name -> int (names as in arch.LINEARS; a missing name takes the rule).  Groups of 128 only.  Returns (model, report) with
     ``report[(block, name)] = {"loss", "rtn_loss", "solver_loss", "dead", "bits", "n_out", "out_ids", "hinv"}`` (``hinv``: ``ops.gptq_hinv``'s
-    ``method``, ``"torch"`` or ``"hip"``; the report holds where the factor was computed) -- loss = tr(dW H dW^T) over all K
+    ``method``, ``"torch"`` or ``"hip"``; the report holds where the factor was computed; ``hessian``: ``ops.GPTQHessian``'s ``method`` for the
+    accumulators the hooks feed, reported as ``"hessian": "torch" | "kernel"``) -- loss = tr(dW H dW^T) over all K
     columns, the outliers' change included.  ``prepare_for_inference(backend='hip')`` leaves an OWQ model's layers as they are; the hipGraph
     runner takes them (``QuantLlama.from_hf``, ``hf_fast.convert_model_to_hip``, ``evaluate``: the staged token step)."""
     from .arch import LINEARS
     if int(group_size) != 128:
         raise ValueError(f"the OWQ kernels serve groups of 128 only (got {group_size})")
+    accumulated = _hessian_route(hessian, "quantize_model_owq")
     report = {}
     avg_bits = _owq_avg_bits(model, bits, group_size)
 
@@ -535,7 +548,7 @@ def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true
             full = _block_linears(layer)
             made = {}
             for names in (TRUE_SEQUENTIAL if true_sequential else (tuple(LINEARS),)):
-                hess = {name: ops.GPTQHessian(full[name].in_features, device) for name in names}
+                hess = {name: ops.GPTQHessian(full[name].in_features, device, method=hessian) for name in names}
                 handles = [full[name].register_forward_hook(lambda _, inp, out, acc=hess[name]: acc.add_batch(inp[0].detach())) for name in names]
                 try:
                     for x in inps:
@@ -564,7 +577,7 @@ def quantize_model_owq(model, bits, samples, group_size=128, percdamp=0.01, true
                     W0[:, ids[dead]] = 0
                     report[(b, name)] = {"loss": _proxy_loss(W0, W_hat, H), "rtn_loss": _proxy_loss(W0, _rtn_dequantized(W0, nb, group_size), H),
                                          "solver_loss": info.loss, "dead": int(dead.sum().item()), "bits": nb, "n_out": no,
-                                         "out_ids": out_ids.cpu(), "hinv": where}
+                                         "out_ids": out_ids.cpu(), "hinv": where, "hessian": accumulated}
                     lin.weight.data = W_hat.to(lin.weight.dtype)
                     made[name] = mod
             inps = [run(layer, x).detach() for x in inps]

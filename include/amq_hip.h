@@ -250,6 +250,24 @@ size_t amq_gptq_hinv_workspace_bytes(int K);
 int amq_gptq_hinv_f32(const void* H, const void* perm, int K, float percdamp, void* U, void* dead, void* info, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* The Hessian those factors start from, accumulated the reference's way (gptq.py:199-204) by one kernel on `stream`:
+ *     H = H * (n_before / (n_before + b)) + (2 / (n_before + b)) * x^T x
+ * for one call of b sequences whose rows are x.  Arithmetic, one rounding per step: the products of fp16 values are exact in fp32; they are summed
+ * over the T rows in fp32 on v_mfma_f32_32x32x16_f16, rows ascending in blocks of 16; the sum is multiplied once by fp32(2 / (n_before + b)), the
+ * old element once by fp32(n_before / (n_before + b)), and the two are added once; both factors are computed in double on the host and rounded
+ * once.  Only the 128 x 128 tiles on or above the diagonal are computed; the strict lower triangle receives the mirrored bits (H == H^T exactly),
+ * and every element of H is written.  With n_before == 0, H is not read: an uninitialised H (NaN included) is a valid first-call input.  One
+ * launch; no host read, no allocation, no atomics, no split of T: a call gives the same bits as the next and as a replayed graph.
+ *   x             fp16 [T, K], 16-byte aligned, rows x_row_stride elements apart (>= K, a multiple of 8); never written
+ *   H             fp32 [K, K], contiguous, 16-byte aligned; only its upper triangle is read
+ *   workspace     none is needed: amq_gptq_hessian_workspace_bytes answers 0 for every shape, workspace (NULL allowed) and workspace_bytes are
+ *                 not looked at
+ * Refused, in this order: a null or misaligned x or H; K not a positive multiple of 32 (or above 65504); T < 1, b < 1 or n_before < 0; a row stride
+ * below K or not a multiple of 8 (all AMQ_EINVAL). */
+size_t amq_gptq_hessian_workspace_bytes(int T, int K);
+int amq_gptq_hessian_f16(const void* x, long x_row_stride, int T, int K, void* H, int n_before, int b, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* AWQ's weight-side passes (awq_utils/quantizer.py pseudo_quantize_tensor with zero_point, auto_clip.py auto_clip_layer_asym) to the same Format A.
  * All fp32, every operation its own IEEE rounding, IEEE division, rint = round-half-even, no contraction except the fmaf written out below.
  * RTN of one group v[0..G) of fp16 values: maxq = 2^bits - 1, xmax = max v, xmin = min v, s = max(xmax - xmin, 1e-5f) / maxq, s16 = fp16(s) (never

@@ -27,6 +27,14 @@ warm-up round, spreads, where each ran, and per K the error figures of tests/tes
 kernels' U, the device route's U and the route run on the host in fp32, and E(kernel) / E(host) -- at these sizes and at the tests' own.
 
     python tools/gptq_bench.py --hinv [--repeats 5] [--out profiles/gptq_hinv.json]
+
+``--hessian``: the accumulation leg's two routes, ops.GPTQHessian(method="torch") (four framework passes over H and an fp32 GEMM) and
+method="hip" (csrc/amq_hessian.hip), alternating in one process at K = 4096, 11008 and 14336: one add_batch of a ``--tokens``-row fp16 window
+(hot columns: every 64th x 12) into an accumulator that already holds samples, median of ``--repeats`` after a warm-up round, spreads; per K and
+at the sizes of tests/test_gpu_gptq_hessian.py the test's figure for both routes, max |H - H64| / ((T_total + 3 c) 2^-24 A) after two windows
+(fp64 on the device); and one "block" leg: the seven accumulators of a Llama-2-7B block fed one window each.
+
+    python tools/gptq_bench.py --hessian [--repeats 5] [--tokens 2048] [--out profiles/gptq_hessian.json]
 """
 import argparse
 import json
@@ -224,6 +232,83 @@ def hinv_main(a):
             f.write("\n")
 
 
+HESSIAN_TEST_SIZES = (32, 96, 160, 288)
+BLOCK_K = (4096, 4096, 4096, 4096, 4096, 4096, 11008)       # q, k, v, o, gate, up, down of Llama-2-7B
+
+
+def hessian_main(a):
+    """the two routes of ops.GPTQHessian.add_batch: one row per K, and one block"""
+    from amq_amd import ops
+    routes = ("torch", "hip")
+
+    def window(K, T, seed):
+        x = torch.randn(1, T, K, device=DEV, generator=torch.Generator(device=DEV).manual_seed(seed))
+        x[..., ::64] *= 12
+        return x.to(torch.float16)
+
+    def shares(K, T):
+        """largest error / bound of either route after two windows of T rows"""
+        xs = [window(K, T, K + i) for i in range(2)]
+        flat = torch.cat([x[0] for x in xs]).double()
+        H64, A = flat.t() @ flat, flat.abs().t() @ flat.abs()       # (2 / n) with n = 2 is 1
+        bound = (2 * T + 3 * 2) * 2.0 ** -24 * A
+        out = {}
+        for m in routes:
+            acc = ops.GPTQHessian(K, DEV, method=m)
+            for x in xs:
+                acc.add_batch(x)
+            out[m] = round(float(((acc.H.double() - H64).abs() / bound).max().item()), 5)
+        return out
+
+    def alternate(legs):
+        runs = {k: [] for k in legs}
+        for r in range(a.repeats + 1):                  # (the first round warms up: not kept)
+            for leg, fn in legs.items():
+                ms = _timed(fn)
+                if r:
+                    runs[leg].append(ms)
+        return runs
+
+    rows, small = [], {}
+    with torch.inference_mode():
+        for K in HESSIAN_TEST_SIZES:
+            small[str(K)] = shares(K, 130)
+        print(json.dumps(small), flush=True)
+        for K in HINV_SIZES:
+            x = window(K, a.tokens, K)
+            accs = {m: ops.GPTQHessian(K, DEV, method=m) for m in routes}
+            for acc in accs.values():
+                acc.add_batch(x)                        # the timed calls rescale and read H
+            row = {"K": K, "tokens": a.tokens, "repeats": a.repeats}
+            for leg, ts in alternate({m: (lambda acc=accs[m]: acc.add_batch(x)) for m in routes}).items():
+                _runs(row, leg, ts)
+            row["torch_over_hip"] = round(row["torch_ms"] / row["hip_ms"], 2)
+            row["hip_tflops"] = round(K * (K + 128.0) * a.tokens / row["hip_ms"] / 1e9, 1)      # the upper tiles' products over the call's time
+            del accs, x
+            torch.cuda.empty_cache()
+            row["error_over_bound"] = shares(K, a.tokens)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            torch.cuda.empty_cache()
+        xs = {K: window(K, a.tokens, 7 + K) for K in set(BLOCK_K)}
+        accs = {m: [ops.GPTQHessian(K, DEV, method=m) for K in BLOCK_K] for m in routes}
+        block = {"K": list(BLOCK_K), "tokens": a.tokens, "repeats": a.repeats}
+        for leg, ts in alternate({m: (lambda m=m: [acc.add_batch(xs[acc.H.shape[0]]) for acc in accs[m]]) for m in routes}).items():
+            _runs(block, leg, ts)
+        block["torch_over_hip"] = round(block["torch_ms"] / block["hip_ms"], 2)
+        print(json.dumps(block), flush=True)
+    res = {"device": torch.cuda.get_device_name(0), "per_K": rows, "block": block, "test_sizes_error_over_bound": small,
+           "worst_error_over_bound": {m: max(e[m] for e in list(small.values()) + [r["error_over_bound"] for r in rows]) for m in routes},
+           "note": "call times (host clock around a synchronised add_batch), not kernel times; synthetic activations; a whole-model calibration "
+                   "was not timed"}
+    if a.out:
+        doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        doc["timing"] = res
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -231,8 +316,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--act-order", action="store_true", help="time the act-order + static-groups variant against the plain solve")
     ap.add_argument("--hinv", action="store_true", help="time the two routes of ops.gptq_hinv (torch.linalg, the HIP kernels) and record their errors")
+    ap.add_argument("--hessian", action="store_true", help="time the two routes of ops.GPTQHessian.add_batch (torch ops, the HIP kernel) and record their errors")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
+    if a.hessian:
+        return hessian_main(a)
     if a.act_order:
         return act_order_main(a)
     if a.hinv:
