@@ -715,6 +715,14 @@ hipError_t launch_attn_decode_gqa(const AttnArgs& a, int batch, int n_splits, vo
     return hipGetLastError();
 }
 
+// the shared-position combine as a launch for another translation unit's chunks (amq_attn_kv8_gqa.hip: the same workspace records)
+hipError_t launch_attn_gqa_combine(const void* ws, void* out, const void* state, int pos, int cur_mode, int n_heads, int batch, int max_seq,
+                                   int n_splits, int chunk, hipStream_t st) {
+    hipLaunchKernelGGL(attn_gqa_combine_kernel<false>, dim3(n_heads, batch), dim3(128), 0, st, (const float*)ws, out, state, pos, cur_mode, n_heads, max_seq,
+                       n_splits, chunk);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------
 // The verify step of prompt-lookup decoding on a GROUPED-QUERY model (amq_attn_decode_rows_gqa_f16): R = 2 .. 8 rows at consecutive positions
 // p .. p + R - 1 of ONE sequence.  attn_decode_gqa_kernel's staging, slicing, operand layouts and merge orders with R x G query rows where it has G:

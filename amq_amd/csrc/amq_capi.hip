@@ -1103,6 +1103,7 @@ struct AttnForm {
     const char* what;       // names the launch in a HIP error
     const char* rows;       // what `batch` counts, in messages
     bool grouped = false;   // the matrix-core grouped-query kernels only: 2 <= n_heads / n_kv_heads <= 16, their fixed LDS, tickets unused
+    bool kv8 = false;       // ... over the 8-bit cache: kcache / vcache are the int8 codes (16-byte aligned), the fp32 scales are required pointers
 };
 constexpr int NO_BOUND = 0x7fffffff;
 constexpr AttnForm ATTN_POS{POS_HOST | POS_DEV, 1, NO_BOUND, SPLITS_NONE, 0, "attn_decode", "batch"};
@@ -1112,6 +1113,7 @@ constexpr AttnForm ATTN_SEQ{POS_BLOCKS, 1, 65535, SPLITS_OPTIONAL, 0, "attn_deco
 // (rows: the earlier rows' rotated keys and values sit behind the score array)
 constexpr AttnForm ATTN_ROWS{POS_ROWS, 2, AMQ_LOOKUP_MAX_ROWS, SPLITS_OPTIONAL, 2 * 7 * 128 * 2 + 16, "attn_decode_rows", "rows"};
 constexpr AttnForm ATTN_ROWS_GQA{POS_ROWS, 2, AMQ_LOOKUP_MAX_ROWS, SPLITS_REQUIRED, 0, "attn_decode_rows_gqa", "rows", true};
+constexpr AttnForm ATTN_KV8_GQA{POS_HOST | POS_DEV | POS_BLOCK, 1, 65535, SPLITS_REQUIRED, 0, "attn_decode_kv8_gqa", "batch", true, true};
 
 size_t amq_attn_decode_split_workspace_bytes(int batch, int n_heads, int n_splits) {
     if (batch < 1 || n_heads < 1 || n_splits < 1) return 0;
@@ -1121,16 +1123,22 @@ size_t amq_attn_decode_split_workspace_bytes(int batch, int n_heads, int n_split
 // An entry point passes what its signature lacks as: state / pos_dev / rope_table / workspace / tickets null, pos 0, rope_theta 10000, n_splits 0.
 static int attn_decode(const AttnForm& f, const amq_qk_norm* norm, const void* q, const void* k, const void* v, void* kcache, void* vcache, void* out,
                        const void* state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim, int max_seq,
-                       float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes, void* tickets, void* stream) {
+                       float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes, void* tickets, void* stream,
+                       void* ks = nullptr, void* vs = nullptr) {
     amq::QkNorm nrm;
     if (int rc = qk_norm_arg(norm, &nrm)) return rc;
     const bool state_required = !(f.pos & (POS_HOST | POS_DEV));
     if (!q || !k || !v || !kcache || !vcache || !out || (state_required && !state) || (f.splits == SPLITS_REQUIRED && (!workspace || !tickets)))
         return fail(AMQ_EINVAL, "null pointer");
+    if (f.kv8 && (!ks || !vs)) return fail(AMQ_EINVAL, "null pointer");
+    if (f.kv8 && (((size_t)kcache | (size_t)vcache) % 16) != 0) return fail(AMQ_EINVAL, "%s: kc8 / vc8 must be 16-byte aligned", f.what);
     if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
     if (batch < f.batch_min || batch > f.batch_max) return fail(AMQ_ESHAPE, "%s must be %d..%d (got %d)", f.rows, f.batch_min, f.batch_max, batch);
     if (n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
         return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads)", n_heads, n_kv_heads);
+    if (f.kv8 && n_heads == n_kv_heads)
+        return fail(AMQ_ESHAPE, "%s serves grouped-query models (got %d / %d heads); multi-head models: the per-head 8-bit kernel (amq_attn_decode_kv8_f16)",
+                    f.what, n_heads, n_kv_heads);
     if (f.grouped && (n_heads / n_kv_heads < 2 || n_heads / n_kv_heads > 16))
         return fail(AMQ_ESHAPE, "%s serves 2..16 query heads per kv head (got %d / %d)", f.what, n_heads, n_kv_heads);
     if (max_seq < 1 || (!state && !pos_dev && (pos < 0 || pos >= max_seq)))
@@ -1148,11 +1156,15 @@ static int attn_decode(const AttnForm& f, const amq_qk_norm* norm, const void* q
         return n_splits ? fail(AMQ_ESHAPE, "max_seq=%d over %d splits leaves chunks of %d keys: too long", max_seq, n_splits, keys)
                         : fail(AMQ_ESHAPE, "max_seq=%d too long for the single-pass decode attention", max_seq);
     const size_t need = amq_attn_decode_split_workspace_bytes(batch, n_heads, n_splits);
-    if (workspace_bytes < need) return fail(AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (workspace_bytes < need) return fail(f.kv8 ? AMQ_ESHAPE : AMQ_EINVAL, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     // a step state carries the position and its cos/sin row: pos_dev, rope_theta and rope_table are then not looked at
     amq::AttnArgs a{q, k, v, kcache, vcache, out, state ? nullptr : pos_dev, pos, n_heads, n_kv_heads, max_seq, state ? 10000.0f : rope_theta,
                     state ? nullptr : rope_table, state, (f.pos & (POS_BLOCKS | POS_ROWS)) != 0, (f.pos & POS_ROWS) != 0};
     a.norm = nrm;
+    if (f.kv8) {
+        amq::Kv8Args a8{q, k, v, kcache, ks, vcache, vs, out, a.pos_dev, pos, n_heads, n_kv_heads, max_seq, a.rope_theta, a.rope_table, state};
+        return check_hip(amq::launch_attn_decode_kv8_gqa(a8, batch, n_splits, workspace, (hipStream_t)stream), f.what);
+    }
     const hipError_t e = f.grouped ? amq::launch_attn_decode_gqa_rows(a, batch, n_splits, workspace, (hipStream_t)stream)
                          : n_splits ? amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream)
                                     : amq::launch_attn_decode(a, batch, (hipStream_t)stream);
@@ -1236,6 +1248,18 @@ int amq_attn_decode_kv8_f16(const void* q, const void* k, const void* v, void* k
     amq::Kv8Args a{q, k, v, kc8, ks, vc8, vs, out, step_state ? nullptr : pos_dev, pos, n_heads, n_kv_heads, max_seq,
                    step_state ? 10000.0f : rope_theta, step_state ? nullptr : rope_table, step_state};
     return check_hip(amq::launch_attn_decode_kv8(a, batch, n_splits, workspace, tickets, (hipStream_t)stream), "attn_decode_kv8");
+}
+
+size_t amq_attn_decode_kv8_gqa_workspace_bytes(int batch, int n_heads, int n_splits) {
+    return amq_attn_decode_split_workspace_bytes(batch, n_heads, n_splits);
+}
+
+int amq_attn_decode_kv8_gqa_f16(const void* q, const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, void* out,
+                                const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
+                                int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
+                                void* tickets, void* stream) {
+    return attn_decode(ATTN_KV8_GQA, nullptr, q, k, v, kc8, vc8, out, step_state, pos_dev, pos, batch, n_heads, n_kv_heads, head_dim, max_seq, rope_theta,
+                       rope_table, n_splits, workspace, workspace_bytes, tickets, stream, ks, vs);
 }
 
 static int amq_attn_prefill_check(const void* q, const void* k, const void* v, const void* out, int batch, int S, int pos0, int n_heads,

@@ -220,6 +220,12 @@ hipError_t launch_kv8_store(const void* k, const void* v, void* kc8, void* ks, v
                             int max_seq, hipStream_t st);
 // ws = fp32 [batch][n_heads][n_splits][132]; tickets = int32 [batch][n_kv_heads][kv8_head_blocks], zero before (and after) every launch
 hipError_t launch_attn_decode_kv8(const Kv8Args& a, int batch, int n_splits, void* ws, void* tickets, hipStream_t st);
+// the same step of a grouped-query model (2 .. 16 query heads per kv head) on the matrix cores (amq_attn_kv8_gqa.hip): chunks of
+// 128 * attn_decode_kv8_gqa_iters keys, ws as above, no tickets -- attn_gqa_combine_kernel (launch_attn_gqa_combine) adds the chunks
+int attn_decode_kv8_gqa_iters(int max_seq, int n_splits);
+hipError_t launch_attn_decode_kv8_gqa(const Kv8Args& a, int batch, int n_splits, void* ws, hipStream_t st);
+hipError_t launch_attn_gqa_combine(const void* ws, void* out, const void* state, int pos, int cur_mode, int n_heads, int batch, int max_seq,
+                                   int n_splits, int chunk, hipStream_t st);
 hipError_t launch_rmsnorm(const void* x, const void* gamma, void* y, int M, int K, float eps, hipStream_t st);
 hipError_t launch_rmsnorm_xfrag(const void* x, const void* gamma, void* xf, int M, int K, float eps, hipStream_t st);
 // causal attention over a whole prompt (amq_attn_prefill.hip).  Element (b, s, head, d) of q / out sits at

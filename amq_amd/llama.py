@@ -152,6 +152,18 @@ def check_kv_bits(kv_bits):
     return int(kv_bits)
 
 
+def check_kv8_kernel(kv8_kernel, kv_bits, n_heads, n_kv_heads):
+    """the 8-bit cache's attention kernel of a runner: a step of its own behind runner_options (whose answers it does not change)"""
+    ops.check_kv8_kernel(kv8_kernel)
+    if kv8_kernel == "mfma":
+        if kv_bits != 8:
+            raise ValueError(f"kv8_kernel='mfma' chooses among the 8-bit cache's attention kernels: it needs kv_bits=8 (got kv_bits={kv_bits})")
+        if not 2 <= n_heads // n_kv_heads <= 16:
+            raise ValueError(f"kv8_kernel='mfma' is the grouped-query kernel (2 .. 16 query heads per kv head share a matrix-core row block): "
+                             f"a model of {n_heads} / {n_kv_heads} heads keeps kv8_kernel='dot'")
+    return kv8_kernel
+
+
 def check_lm_head_bits(lm_head_bits):
     if lm_head_bits not in (16, 8, 4):
         raise ValueError(f"lm_head_bits must be 16 (fp16 lm_head), 8 (the LM8 layer) or 4 (a packed 4-bit layer), got {lm_head_bits!r}")
@@ -345,7 +357,7 @@ class QuantLlama:
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
                  hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2,
-                 lookup_sampling=False, kv_bits=16, lm_head_bits=16, lm_head_packed=None):
+                 lookup_sampling=False, kv_bits=16, lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot"):
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
@@ -371,6 +383,9 @@ class QuantLlama:
         kv_bits: 16 -- the fp16 KV cache, the object, graphs and bits the runner has always had; 8 -- int8 rows with one fp32 scale per (sequence,
         kv head, position) (blocks hold kc8 / ks / vc8 / vs, 132 bytes per row instead of 256; the token step issues
         ops.attn_decode_kv8, the prompt pass stays exact fp16 and stores its rows with one ops.kv8_store; no prompt pass at start_pos > 0).
+        kv8_kernel: the attention kernel of a kv_bits=8 token step.  "dot" -- the per-head kernel on the vector units, the launch the option has
+        always issued; "mfma" -- grouped-query models only: the group's heads on the matrix cores from one staging of the raw rows
+        (ops.attn_decode_kv8(kernel="mfma")): the same cache bytes, probabilities rounded to fp16 before P.V.
         lm_head_bits: 16 -- the fp16 lm_head, the object, graphs and bits the runner has always had; 8 -- the lm_head is quantized once, here, to
         the LM8 layer (hqq_format.quantize_lm8) and every logit comes from ops.lm8_gemv; 4 -- ops.hqq_quantize(W, 4) and the packed
         GEMV / GEMM kernels of the block linears.  The runner then keeps no fp16 lm_head (self.lm_head is None; self.lm_head_q is the packed layer).
@@ -379,6 +394,7 @@ class QuantLlama:
         config = MODEL_CONFIGS[config] if isinstance(config, str) else config
         opts = runner_options(batch, ragged, lookup, ngram_max, lookup_sampling, kv_bits, lm_head_bits, engine, self.FUSE_QKV_ATTN, config.get("qk_norm"))
         self._frame(config, device, max_seq, opts)
+        self.kv8_kernel = check_kv8_kernel(kv8_kernel, self.kv_bits, self.nh, self.nkv)
         self.arch_linear = arch_linear or uniform_arch(config, 4)["linear"]
         gen = torch.Generator(device=self.dev).manual_seed(seed)
         self.blocks = [{**{name: self._linear(b, name, gen, prebuilt, hqq_layers, synthetic, group) for name in config["linear"]},
@@ -396,6 +412,7 @@ class QuantLlama:
         """what a runner knows before it has weights: its options (a RunnerOptions) and the model's dimensions"""
         self.B, self.R, self.ragged, self.lookup, self.ngram_max, self.lookup_sampling, self.kv_bits, self.lm_head_bits = opts[:8]
         self.cache_keys = ("kc8", "ks", "vc8", "vs") if self.kv_bits == 8 else ("kc", "vc")     # a block's cache tensors: codes and scales, or fp16 rows
+        self.kv8_kernel = "dot"
         self.cfg, self.dev = config, torch.device(device)
         _prime_graph_state(self.dev)
         self.H, self.I = config["hidden_size"], config["intermediate_size"]
@@ -625,7 +642,7 @@ class QuantLlama:
 
     @classmethod
     def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False, kv_bits=16,
-                lm_head_bits=16, lm_head_packed=None):
+                lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot"):
         """The hipGraph runner over a SWAPPED HF causal LM of the Llama family (``HF_MODEL_TYPES``: Llama 2 / 3.x, Mistral, Qwen2.5) -- what
         ``prepare_for_inference(model, backend="hip")`` (or the reference's deepcopy + setattr assembly of a mixed-precision model,
         amq_speed_benchmark.py:231-256) leaves behind.  The runner shares the modules' native weight buffers and biases, the embedding, lm_head and
@@ -670,7 +687,7 @@ class QuantLlama:
             dense["kn"] = [f16(l.self_attn.k_norm.weight).contiguous() for l in layers]
         return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
                    ragged=ragged, lookup=lookup, ngram_max=ngram_max, lookup_sampling=lookup_sampling, kv_bits=kv_bits,
-                   lm_head_bits=lm_head_bits, lm_head_packed=lm_head_packed)
+                   lm_head_bits=lm_head_bits, lm_head_packed=lm_head_packed, kv8_kernel=kv8_kernel)
 
     # ----------------------------------------------------------------- the lm_head
     @staticmethod
@@ -874,7 +891,7 @@ class QuantLlama:
                                  grouped=self.rows_attention_grouped(self.nh, self.nkv, self.max_seq), **self._qkn(blk))
         elif self.kv_bits == 8:
             ops.attn_decode_kv8(self.q, self.k, self.v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], self.att, self.pos, self.nh, self.nkv,
-                                cur=self.rope_cur)
+                                cur=self.rope_cur, kernel=self.kv8_kernel)
         else:
             ops.attn_decode(self.q, self.k, self.v, blk["kc"], blk["vc"], self.att, self.pos, self.nh, self.nkv, self.theta,
                             cur=self.rope_cur, **self._qkn(blk))

@@ -601,6 +601,19 @@ int amq_attn_decode_kv8_f16(const void* q, const void* k, const void* v, void* k
                             const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
                             int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
                             void* tickets, void* stream);
+/* amq_attn_decode_kv8_gqa_f16: the same step, arguments and cache bytes for GROUPED-QUERY models (2 .. 16 query heads per kv head) on the matrix
+ * cores: one workgroup per (kv head, sequence, chunk) stages the raw int8 rows and scales in LDS and scores them against all the group's heads
+ * (S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_f16, codes as exact fp16 integers).  Scores as above in fp32; un-normalised
+ * probabilities times s_t / S (S: the largest V scale of a 32-key block) are rounded to fp16 before P.V, S is applied in fp32.  Chunks are whole
+ * stages of 128 keys (ceil(ceil(max_seq / n_splits) / 128) of them); with n_splits > 1 a second launch adds the chunks in chunk order
+ * (deterministic).  The cache after the launch is bit for bit what amq_attn_decode_kv8_f16 leaves.  Refused (AMQ_ESHAPE): one query head per kv
+ * head (multi-head models: the per-head 8-bit kernel above), more than 16, head_dim != 128, max_seq > 2^24.  kc8 / vc8 16-byte aligned.
+ * workspace: amq_attn_decode_kv8_gqa_workspace_bytes bytes, no initialisation; tickets: accepted for the shared signature, never touched. */
+size_t amq_attn_decode_kv8_gqa_workspace_bytes(int batch, int n_heads, int n_splits);
+int amq_attn_decode_kv8_gqa_f16(const void* q, const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, void* out,
+                                const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
+                                int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
+                                void* tickets, void* stream);
 
 /* End of a greedy token step in one launch: token[0] = argmax(logits[0..vocab)) (first maximum), pos[0] += 1,
  * x[0..hidden) = embed[token][0..hidden); when rope_table / rope_cur are given (both or neither) also

@@ -11,7 +11,11 @@
   drift    max |logit(kv_bits=8) - logit(kv_bits=16)| / max |logit| over 32 decode steps of the tiny test model and of the synthetic 7B, both runners
            fed the fp16 runner's tokens.  Synthetic weights: a recorded number, not a perplexity.
 
-usage: kv8_attention_time.py [--out profiles/kv8_attention.json] [--part launch,step,drift] [--rounds 3]"""
+  gqa      (--part gqa -> profiles/kv8_gqa_attention.json) the launch grid's grouped-query rows with a THIRD leg, ops.attn_decode_kv8(kernel="mfma")
+           (amq_attn_decode_kv8_gqa_f16), alternating with the other two in the same run, and the whole-step tokens/s of the synthetic
+           Meta-Llama-3-8B shape (32 / 8 heads) at 64 and 4000 cached keys with kv_bits 16, 8 ("dot") and 8 ("mfma").
+
+usage: kv8_attention_time.py [--out profiles/kv8_attention.json] [--part launch,step,drift | gqa] [--rounds 3]"""
 import argparse
 import json
 import os
@@ -59,7 +63,7 @@ def timed(g, reps):
     return e0.elapsed_time(e1) * 1e-3 / reps
 
 
-def launch_shape(nh, nkv, T, B, rounds):
+def launch_shape(nh, nkv, T, B, rounds, mfma=False):
     max_seq = T + 64
     row16, row8 = 2 * B * nkv * (T + 1) * 256, 2 * B * nkv * (T + 1) * 132          # K + V bytes one launch reads
     L = max(2, min(32, -(-LEG_BYTES // (2 * B * nkv * max_seq * 256))))
@@ -90,15 +94,28 @@ def launch_shape(nh, nkv, T, B, rounds):
         for l in range(L):
             ops.attn_decode_kv8(q, k, v, *c8[l], out, pos, nh, nkv, cur=cur)
 
+    def leg8m():
+        for l in range(L):
+            ops.attn_decode_kv8(q, k, v, *c8[l], out, pos, nh, nkv, cur=cur, kernel="mfma")
+
     g16, g8 = graph_of(leg16), graph_of(leg8)
+    g8m = graph_of(leg8m) if mfma else None
     reps = max(3, int(0.04 / max(timed(g16, 2), 1e-6)) + 1)
-    t16, t8 = [], []
+    t16, t8, t8m = [], [], []
     for _ in range(rounds):                                  # the legs alternate
         t16.append(timed(g16, reps) / L)
         t8.append(timed(g8, reps) / L)
+        if mfma:
+            t8m.append(timed(g8m, reps) / L)
     assert int(err.item()) == 0
     m16, m8 = statistics.median(t16), statistics.median(t8)
-    return dict(n_heads=nh, n_kv_heads=nkv, keys=T, batch=B, layers=L, replays=reps, rounds=rounds,
+    extra = {}
+    if mfma:
+        mm = statistics.median(t8m)
+        extra = dict(kv8_mfma_us=round(mm * 1e6, 2), kv8_mfma_over_fp16=round(mm / m16, 3), kv8_mfma_over_kv8=round(mm / m8, 3),
+                     kv8_mfma_us_rounds=[round(t * 1e6, 2) for t in t8m], kv8_mfma_read_gbps=round(row8 / mm / 1e9, 1),
+                     kv8_mfma_splits=ops.attn_decode_kv8_gqa_splits(max_seq, nh, B, nkv))
+    return dict(**extra, n_heads=nh, n_kv_heads=nkv, keys=T, batch=B, layers=L, replays=reps, rounds=rounds,
                 fp16_us=round(m16 * 1e6, 2), kv8_us=round(m8 * 1e6, 2), kv8_over_fp16=round(m8 / m16, 3),
                 fp16_us_rounds=[round(t * 1e6, 2) for t in t16], kv8_us_rounds=[round(t * 1e6, 2) for t in t8],
                 fp16_read_gbps=round(row16 / m16 / 1e9, 1), kv8_read_gbps=round(row8 / m8 / 1e9, 1),
@@ -111,11 +128,19 @@ def synthetic_7b(max_seq, kv_bits):
     return QuantLlama(cfg, linear, device="cuda:0", max_seq=max_seq, seed=0, kv_bits=kv_bits)
 
 
-def step_rate(keys, steps=64, rounds=3):
+def synthetic_gqa(max_seq, kv_bits):
+    """kv_bits: 16, 8 (the per-head kernel) or "8mfma" (the matrix-core kernel)"""
+    cfg = arch_mod.MODEL_CONFIGS["Meta-Llama-3-8B"]
+    linear = arch_mod.synthesize_arch(cfg, 3.0, seed=0)[0]["linear"]
+    return QuantLlama(cfg, linear, device="cuda:0", max_seq=max_seq, seed=0, kv_bits=16 if kv_bits == 16 else 8,
+                      kv8_kernel="mfma" if kv_bits == "8mfma" else "dot")
+
+
+def step_rate(keys, steps=64, rounds=3, legs=(16, 8), build=synthetic_7b, model="Llama-2-7b-hf, synthetic weights, 3.0 bits on average"):
     res = {}
     ids = torch.randint(0, 31999, (keys,), generator=torch.Generator().manual_seed(keys)).to(DEV)
-    models = {kb: synthetic_7b(keys + 4 * steps + 32, kb) for kb in (16, 8)}
-    rates = {16: [], 8: []}
+    models = {kb: build(keys + 4 * steps + 32, kb) for kb in legs}
+    rates = {kb: [] for kb in legs}
     for _ in range(rounds):
         for kb, m in models.items():                         # the two runners alternate
             m.reset()
@@ -129,11 +154,11 @@ def step_rate(keys, steps=64, rounds=3):
             torch.cuda.synchronize()
             rates[kb].append(steps / (time.perf_counter() - t0))
             m.check()
-    for kb in (16, 8):
+    for kb in legs:
         res[f"kv{kb}_tokens_per_s"] = round(statistics.median(rates[kb]), 1)
         res[f"kv{kb}_rounds"] = [round(r, 1) for r in rates[kb]]
         res[f"kv{kb}_kv_gb_per_token"] = round((models[kb].total_bytes_per_token(keys) - models[kb].total_bytes_per_token(0)) / 1e9, 3)
-    res.update(keys=keys, steps=steps, model="Llama-2-7b-hf, synthetic weights, 3.0 bits on average")
+    res.update(keys=keys, steps=steps, model=model)
     return res
 
 
@@ -179,6 +204,25 @@ def main():
         res["step"] = []
         for keys in (64, 4000):
             r = step_rate(keys, rounds=args.rounds)
+            res["step"].append(r)
+            print(json.dumps(r), flush=True)
+            torch.cuda.empty_cache()
+            save()
+    if "gqa" in parts:
+        if args.out.endswith("kv8_attention.json"):
+            args.out = args.out[:-len("kv8_attention.json")] + "kv8_gqa_attention.json"
+        res["launch"], res["step"] = [], []
+        for nh, nkv in HEADS[1:]:
+            for T in KEYS:
+                for B in BATCHES:
+                    r = launch_shape(nh, nkv, T, B, args.rounds, mfma=True)
+                    res["launch"].append(r)
+                    print(json.dumps(r), flush=True)
+                    torch.cuda.empty_cache()
+                    save()
+        for keys in (64, 4000):
+            r = step_rate(keys, rounds=args.rounds, legs=(16, 8, "8mfma"), build=synthetic_gqa,
+                          model="Meta-Llama-3-8B shape (32 / 8 heads), synthetic weights, 3.0 bits on average")
             res["step"].append(r)
             print(json.dumps(r), flush=True)
             torch.cuda.empty_cache()
