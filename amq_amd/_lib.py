@@ -156,7 +156,9 @@ SIGNATURES = {
     "amq_attn_decode_kv8_gqa_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _sz, _vp, _vp]),
     "amq_gemm_xfrag_grouped_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _i, _i, _i, _vp]),
     "amq_gemm_xfrag_grouped_form_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _i, _i, _i, _i, _i, _vp]),
-    "amq_attn_prefill_xfrag_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 5 + [_vp]),
+    "amq_attn_prefill_kv8_f16": (_i, [_vp] * 6 + [_i] * 7 + [ctypes.c_longlong] * 4 + [_vp]),
+    "amq_attn_prefill_kv8_xfrag_f16": (_i, [_vp] * 6 + [_i] * 6 + [ctypes.c_longlong, _vp]),
+    "amq_attn_prefill_xfrag_f16":(_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 5 + [_vp]),
     "amq_gemv_f16w_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
     # the 8-bit lm_head: (x, codes, meta, y, gamma, eps, M, N, K, group, stream) / (codes, meta, out, row0, rows, N, K, group, stream)
     "amq_lm8_gemv_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),

@@ -1304,6 +1304,48 @@ int amq_attn_prefill_xfrag_f16(const void* q, const void* k, const void* v, void
     return check_hip(amq::launch_attn_prefill(a, (hipStream_t)stream), "attn_prefill_xfrag");
 }
 
+/* the prompt chunk over the 8-bit KV cache (amq_attn_prefill_kv8.hip): both entry points, one check */
+static int amq_attn_prefill_kv8_check(const void* q, const void* kc8, const void* ks, const void* vc8, const void* vs, const void* out, int batch,
+                                      int S, int pos0, int n_heads, int n_kv_heads, int head_dim, int max_seq, long long q_rstride,
+                                      long long q_bstride, long long o_rstride, long long o_bstride) {
+    if (!q || !kc8 || !ks || !vc8 || !vs || !out) return fail(AMQ_EINVAL, "null pointer");
+    if (head_dim != 128) return fail(AMQ_ESHAPE, "head_dim must be 128 (got %d)", head_dim);
+    if (batch < 1 || batch > 65535 || S < 1 || pos0 < 0 || n_heads < 1 || n_heads > 65535 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
+        return fail(AMQ_ESHAPE, "bad sizes (batch %d, S %d, pos0 %d, %d q heads, %d kv heads)", batch, S, pos0, n_heads, n_kv_heads);
+    if (n_heads / n_kv_heads > 16)
+        return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads; 1..16 query heads per kv head)", n_heads, n_kv_heads);
+    if (max_seq < 1 || (long long)pos0 + S > max_seq)
+        return fail(AMQ_ESHAPE, "rows %d .. %lld outside the cache (max_seq=%d)", pos0, (long long)pos0 + S - 1, max_seq);
+    const long long strides[] = {q_rstride, q_bstride, o_rstride, o_bstride};
+    for (long long sv : strides)
+        if (sv < 0 || (sv % 8) != 0) return fail(AMQ_ESHAPE, "strides must be non-negative multiples of 8 halves (16-byte vector access)");
+    if (q_rstride < (long long)n_heads * 128 || o_rstride < (long long)n_heads * 128)
+        return fail(AMQ_ESHAPE, "row strides smaller than the rows they separate");
+    // the kernel forms key * 128 as a 32-bit byte offset inside a (sequence, kv head) slice; a sequence's slice is held below 2^32 bytes
+    if ((long long)n_kv_heads * max_seq * 128 >= (1ll << 32) || (long long)((S + 63) / 64) * n_heads * batch >= (1ll << 31))
+        return fail(AMQ_ESHAPE, "the codes of one sequence must span fewer than 2^32 bytes (%d kv heads x max_seq %d x 128) and the launch fewer than "
+                                "2^31 workgroups", n_kv_heads, max_seq);
+    return AMQ_OK;
+}
+
+int amq_attn_prefill_kv8_f16(const void* q, const void* kc8, const void* ks, const void* vc8, const void* vs, void* out, int batch, int S, int pos0,
+                             int n_heads, int n_kv_heads, int head_dim, int max_seq, long long q_rstride, long long q_bstride,
+                             long long o_rstride, long long o_bstride, void* stream) {
+    if (int rc = amq_attn_prefill_kv8_check(q, kc8, ks, vc8, vs, out, batch, S, pos0, n_heads, n_kv_heads, head_dim, max_seq, q_rstride, q_bstride,
+                                            o_rstride, o_bstride)) return rc;
+    amq::AttnPrefillKv8Args a{q, kc8, ks, vc8, vs, out, S, pos0, n_heads, n_kv_heads, batch, max_seq, (long)q_rstride, (long)q_bstride,
+                              (long)o_rstride, (long)o_bstride, 0};
+    return check_hip(amq::launch_attn_prefill_kv8(a, (hipStream_t)stream), "attn_prefill_kv8");
+}
+
+int amq_attn_prefill_kv8_xfrag_f16(const void* q, const void* kc8, const void* ks, const void* vc8, const void* vs, void* out_xf, int S, int pos0,
+                                   int n_heads, int n_kv_heads, int head_dim, int max_seq, long long q_rstride, void* stream) {
+    if (int rc = amq_attn_prefill_kv8_check(q, kc8, ks, vc8, vs, out_xf, 1, S, pos0, n_heads, n_kv_heads, head_dim, max_seq, q_rstride, 0,
+                                            (long long)n_heads * 128, 0)) return rc;
+    amq::AttnPrefillKv8Args a{q, kc8, ks, vc8, vs, out_xf, S, pos0, n_heads, n_kv_heads, 1, max_seq, (long)q_rstride, 0, 0, 0, 1};
+    return check_hip(amq::launch_attn_prefill_kv8(a, (hipStream_t)stream), "attn_prefill_kv8_xfrag");
+}
+
 /* ---- token tails and set_token: ten entry points, one set of shared checks.  What differs between them is the TailForm ("Decode-step
    entry points: what is checked") and what each adds behind tail_check ---- */
 enum Vocab8 { V8_NEVER, V8_TWO_ROWS, V8_ALWAYS };       // when vocab % 8 == 0 is demanded (16-byte aligned rows of logits): never / from two rows / always

@@ -239,6 +239,15 @@ struct AttnPrefillArgs {
     int out_xfrag;          // 1: out is the fragment-ordered image of the [S, n_heads * 128] result (batch 1), o_* strides unused
 };
 hipError_t launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st);
+// the same over the 8-bit KV cache (amq_attn_prefill_kv8.hip): kc8 / vc8 int8 [batch][n_kv_heads][max_seq][128], ks / vs fp32
+// [batch][n_kv_heads][max_seq], rows 0 .. pos0 + S - 1 stored before the launch; query s attends the dequantized rows 0 .. pos0 + s
+struct AttnPrefillKv8Args {
+    const void* q; const void* kc8; const void* ks; const void* vc8; const void* vs; void* out;
+    int S, pos0, n_heads, n_kv_heads, batch, max_seq;
+    long q_rstride, q_bstride, o_rstride, o_bstride;
+    int out_xfrag;          // as AttnPrefillArgs
+};
+hipError_t launch_attn_prefill_kv8(const AttnPrefillKv8Args& a, hipStream_t st);
 // prefill glue (amq_decode.hip)
 hipError_t launch_rope_cache(void* q, const void* k, const void* v, void* kcache, void* vcache, const void* rope_table,
                              int rope_rows, int pos0, int S, int n_heads, int n_kv_heads, int max_seq, hipStream_t st,

@@ -164,6 +164,17 @@ def check_kv8_kernel(kv8_kernel, kv_bits, n_heads, n_kv_heads):
     return kv8_kernel
 
 
+def check_kv8_prompt(kv8_prompt, kv_bits):
+    """-> kv8_prompt, or ValueError: how a kv_bits=8 runner's cached prompt pass attends ("exact": fp16 projections, position 0 only; "cache": the
+    dequantized cache rows through ops.attn_prefill_kv8, any start_pos)"""
+    if kv8_prompt not in ops.KV8_PROMPTS:
+        raise ValueError(f"kv8_prompt must be 'exact' (the prompt attends its fp16 rows; a prompt pass starts at position 0) or 'cache' (the prompt "
+                         f"attends the 8-bit cache rows; chunked prompts are served), got {kv8_prompt!r}")
+    if kv8_prompt == "cache" and kv_bits != 8:
+        raise ValueError(f"kv8_prompt='cache' chooses how the prompt pass reads the 8-bit cache: it needs kv_bits=8 (got kv_bits={kv_bits})")
+    return kv8_prompt
+
+
 def check_lm_head_bits(lm_head_bits):
     if lm_head_bits not in (16, 8, 4):
         raise ValueError(f"lm_head_bits must be 16 (fp16 lm_head), 8 (the LM8 layer) or 4 (a packed 4-bit layer), got {lm_head_bits!r}")
@@ -357,7 +368,7 @@ class QuantLlama:
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
                  hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2,
-                 lookup_sampling=False, kv_bits=16, lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot"):
+                 lookup_sampling=False, kv_bits=16, lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot", kv8_prompt="exact"):
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
@@ -386,6 +397,11 @@ class QuantLlama:
         kv8_kernel: the attention kernel of a kv_bits=8 token step.  "dot" -- the per-head kernel on the vector units, the launch the option has
         always issued; "mfma" -- grouped-query models only: the group's heads on the matrix cores from one staging of the raw rows
         (ops.attn_decode_kv8(kernel="mfma")): the same cache bytes, probabilities rounded to fp16 before P.V.
+        kv8_prompt: how a kv_bits=8 runner's cached prompt pass attends.  "exact" -- the behaviour above: bits of the fp16-cache runner's prompt
+        logits, and ``prefill(..., start_pos > 0)`` refused.  "cache" -- EVERY cached prompt pass (start_pos 0 included) rotates, stores its rows
+        with ops.kv8_store and attends the dequantized cache rows 0 .. its own through ops.attn_prefill_kv8, the kernel that reads the int8 rows
+        directly: chunked prompts and the next turn of a conversation are served; prompt logits are no longer the fp16-cache runner's bit for
+        bit, and in exchange a row sees the same arithmetic however the prompt is cut into chunks.  Passes without a cache are untouched.
         lm_head_bits: 16 -- the fp16 lm_head, the object, graphs and bits the runner has always had; 8 -- the lm_head is quantized once, here, to
         the LM8 layer (hqq_format.quantize_lm8) and every logit comes from ops.lm8_gemv; 4 -- ops.hqq_quantize(W, 4) and the packed
         GEMV / GEMM kernels of the block linears.  The runner then keeps no fp16 lm_head (self.lm_head is None; self.lm_head_q is the packed layer).
@@ -395,6 +411,7 @@ class QuantLlama:
         opts = runner_options(batch, ragged, lookup, ngram_max, lookup_sampling, kv_bits, lm_head_bits, engine, self.FUSE_QKV_ATTN, config.get("qk_norm"))
         self._frame(config, device, max_seq, opts)
         self.kv8_kernel = check_kv8_kernel(kv8_kernel, self.kv_bits, self.nh, self.nkv)
+        self.kv8_prompt = check_kv8_prompt(kv8_prompt, self.kv_bits)
         self.arch_linear = arch_linear or uniform_arch(config, 4)["linear"]
         gen = torch.Generator(device=self.dev).manual_seed(seed)
         self.blocks = [{**{name: self._linear(b, name, gen, prebuilt, hqq_layers, synthetic, group) for name in config["linear"]},
@@ -412,7 +429,7 @@ class QuantLlama:
         """what a runner knows before it has weights: its options (a RunnerOptions) and the model's dimensions"""
         self.B, self.R, self.ragged, self.lookup, self.ngram_max, self.lookup_sampling, self.kv_bits, self.lm_head_bits = opts[:8]
         self.cache_keys = ("kc8", "ks", "vc8", "vs") if self.kv_bits == 8 else ("kc", "vc")     # a block's cache tensors: codes and scales, or fp16 rows
-        self.kv8_kernel = "dot"
+        self.kv8_kernel, self.kv8_prompt = "dot", "exact"
         self.cfg, self.dev = config, torch.device(device)
         _prime_graph_state(self.dev)
         self.H, self.I = config["hidden_size"], config["intermediate_size"]
@@ -642,7 +659,7 @@ class QuantLlama:
 
     @classmethod
     def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False, kv_bits=16,
-                lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot"):
+                lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot", kv8_prompt="exact"):
         """The hipGraph runner over a SWAPPED HF causal LM of the Llama family (``HF_MODEL_TYPES``: Llama 2 / 3.x, Mistral, Qwen2.5) -- what
         ``prepare_for_inference(model, backend="hip")`` (or the reference's deepcopy + setattr assembly of a mixed-precision model,
         amq_speed_benchmark.py:231-256) leaves behind.  The runner shares the modules' native weight buffers and biases, the embedding, lm_head and
@@ -687,7 +704,7 @@ class QuantLlama:
             dense["kn"] = [f16(l.self_attn.k_norm.weight).contiguous() for l in layers]
         return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
                    ragged=ragged, lookup=lookup, ngram_max=ngram_max, lookup_sampling=lookup_sampling, kv_bits=kv_bits,
-                   lm_head_bits=lm_head_bits, lm_head_packed=lm_head_packed, kv8_kernel=kv8_kernel)
+                   lm_head_bits=lm_head_bits, lm_head_packed=lm_head_packed, kv8_kernel=kv8_kernel, kv8_prompt=kv8_prompt)
 
     # ----------------------------------------------------------------- the lm_head
     @staticmethod
@@ -1282,21 +1299,26 @@ class QuantLlama:
         return ids
 
     def _kv8_prompt_check(self, start_pos):
-        """an 8-bit cache is written by the prompt pass and read by the token step only: a prompt pass behind cached rows would have to attend them"""
-        if self.kv_bits == 8 and start_pos != 0:
+        """kv8_prompt="exact": an 8-bit cache is written by the prompt pass and read by the token step only -- a prompt pass behind cached rows
+        would have to attend them ("cache": it does)"""
+        if self.kv_bits == 8 and self.kv8_prompt == "exact" and start_pos != 0:
             raise ValueError("kv_bits=8: a prompt pass starts at position 0 (the prompt kernels read no 8-bit cache: chunked prompts are not served)")
 
     def _rows_kv(self, blk, q, k, v, S, start_pos, cache):
         """the rotation and the cache write of a prompt pass -> (k, v, kv_cache) as ops.attn_prefill is to read them.  fp16 cache: one launch
         rotates q / k and writes rows start_pos .. of the cache, which the attention reads.  No cache: q / k are rotated in place and the attention
         reads the projection outputs.  8-bit cache (position 0): the same -- exact fp16, the prompt's own attention is the no-cache pass bit for
-        bit -- and ONE ops.kv8_store quantizes the rows into the cache."""
+        bit -- and ONE ops.kv8_store quantizes the rows into the cache.  8-bit cache with kv8_prompt="cache": q / k rotated at start_pos, the rows
+        stored at start_pos, and the attention reads the CACHE (-> the block's four cache tensors, "kv8")."""
         if cache and self.kv_bits == 16:
             ops.rope_cache(q, k, v, blk["kc"], blk["vc"], self.rope_tab, start_pos, self.nh, self.nkv, **self._qkn(blk))
             return blk["kc"], blk["vc"], True
-        ops.rope_rows(q, k, self.rope_tab, S, self.nh, self.nkv, **self._qkn(blk))
+        by_cache = cache and self.kv8_prompt == "cache"
+        ops.rope_rows(q, k, self.rope_tab, S, self.nh, self.nkv, pos0=start_pos if by_cache else 0, **self._qkn(blk))
         if cache:
-            ops.kv8_store(k, v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], 0, self.nkv)
+            ops.kv8_store(k, v, blk["kc8"], blk["ks"], blk["vc8"], blk["vs"], start_pos if by_cache else 0, self.nkv)
+        if by_cache:
+            return tuple(blk[key] for key in self.cache_keys), None, "kv8"
         return k, v, False
 
     def _prefill_rows(self, ids, start_pos):
@@ -1357,8 +1379,11 @@ class QuantLlama:
                 h = ops.rmsnorm(x, blk["ln1"], self.eps)
                 q, k, v = lin(blk["self_attn.q_proj"], h), lin(blk["self_attn.k_proj"], h), lin(blk["self_attn.v_proj"], h)
             kk, vv, cached = self._rows_kv(blk, q, k, v, S, start_pos, cache)
-            a = ops.attn_prefill(q, kk, vv, None if frag else torch.empty_like(q), S, nh, nkv, batch=B, pos0=start_pos if cached else 0,
-                                 kv_cache=cached, out_xfrag=frag)
+            if cached == "kv8":
+                a = ops.attn_prefill_kv8(q, *kk, None if frag else torch.empty_like(q), S, nh, nkv, batch=B, pos0=start_pos, out_xfrag=frag)
+            else:
+                a = ops.attn_prefill(q, kk, vv, None if frag else torch.empty_like(q), S, nh, nkv, batch=B, pos0=start_pos if cached else 0,
+                                     kv_cache=cached, out_xfrag=frag)
             if not frag:
                 x = lin(blk["self_attn.o_proj"], a, residual=x)
                 h2 = ops.rmsnorm(x, blk["ln2"], self.eps)

@@ -2122,6 +2122,38 @@ def attn_decode_kv8(q, k, v, kc8, ks, vc8, vs, out, pos, n_heads, n_kv_heads, ta
     return out
 
 
+KV8_PROMPTS = ("exact", "cache")
+
+
+def attn_prefill_kv8(q, kc8, ks, vc8, vs, out, S, n_heads, n_kv_heads, batch=1, pos0=0, out_xfrag=False):
+    """Causal attention of a prompt chunk over the 8-bit caches (amq_attn_prefill_kv8_f16): q / out fp16 [batch*S, n_heads*128] (q rotated), the
+    caches hold rows 0 .. pos0+S-1 (the chunk's own rows stored by :func:`kv8_store` before this call); query row s attends the dequantized rows
+    0 .. pos0+s.  1 .. 16 query heads per kv head.  A row's bits do not depend on ``pos0``, ``S`` or ``batch``: however a prompt is cut into
+    chunks, a row sees the same arithmetic.  out_xfrag (batch 1): as :func:`attn_prefill`."""
+    B, nkv, max_seq = _need_kv8(kc8, ks, vc8, vs)
+    if nkv != n_kv_heads or B != batch:
+        raise ValueError(f"caches of {B} sequences x {nkv} kv heads, batch={batch}, n_kv_heads={n_kv_heads}")
+    pos0, H = int(pos0), n_heads * 128
+    if pos0 < 0 or pos0 + S > max_seq:
+        raise ValueError(f"keys 0..{pos0 + S - 1} do not fit the cache (max_seq={max_seq})")
+    _need(q, torch.float16, "q", batch * S * H)
+    lib = _lib.load()
+    if out_xfrag:
+        if batch != 1:
+            raise ValueError("out_xfrag needs batch == 1")
+        nb = lib.amq_xfrag_bytes(S, H)
+        if out is None:
+            out = torch.empty(nb // 2, dtype=torch.float16, device=q.device)
+        _need(out, torch.float16, "out_xf", nb // 2)
+        _lib.check(lib.amq_attn_prefill_kv8_xfrag_f16(*map(_lib.ptr, (q, kc8, ks, vc8, vs, out)), S, pos0, n_heads, n_kv_heads, 128, max_seq, H,
+                                                      _lib.current_stream()))
+        return out
+    _need(out, torch.float16, "out", batch * S * H)
+    _lib.check(lib.amq_attn_prefill_kv8_f16(*map(_lib.ptr, (q, kc8, ks, vc8, vs, out)), batch, S, pos0, n_heads, n_kv_heads, 128, max_seq,
+                                            H, S * H, H, S * H, _lib.current_stream()))
+    return out
+
+
 # ---- prompt-lookup speculative decoding (include/amq_hip.h: "prompt-lookup speculative decoding"; amq_decode.hip ROWS instantiations, amq_lookup.hip)
 LOOKUP_STATE_WORDS = _lib.LOOKUP_STATE_WORDS
 LOOKUP_DRAFTS, LOOKUP_NGRAM, LOOKUP_MODE, LOOKUP_COUNT, LOOKUP_STEPS, LOOKUP_ACCEPTED, LOOKUP_TICKET, LOOKUP_DRAFT, LOOKUP_ARGMAX = 0, 1, 2, 3, 4, 5, 6, 8, 16

@@ -614,6 +614,21 @@ int amq_attn_decode_kv8_gqa_f16(const void* q, const void* k, const void* v, voi
                                 const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
                                 int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
                                 void* tickets, void* stream);
+/* amq_attn_prefill_kv8_f16: a prompt chunk over the 8-bit caches.  S query rows at positions pos0 .. pos0 + S - 1 of every sequence, q fp16
+ * ALREADY ROTATED with row / batch strides in halves as amq_attn_prefill_f16; the caches already hold rows 0 .. pos0 + S - 1 (the chunk's own rows
+ * stored by amq_kv8_store_f16 before this launch).  out[b, s, h, :] = softmax(q . K^T / sqrt 128) V over the DEQUANTIZED rows 0 .. pos0 + s, the
+ * row's own included.  One matrix-core kernel reads the int8 rows directly (LDS-DMA of codes and scales, one conversion to exact fp16 integers
+ * per workgroup and tile): scores (sum_i q_i c_ti) * ks_t * RN32(1 / sqrt 128) in fp32, online softmax in fp32, un-normalised probabilities times
+ * vs_t / Sv (Sv: the largest V scale among the keys of a 64-key tile the row sees) rounded to fp16 before P.V, Sv applied in fp32.  A row's result
+ * depends on its q, its position and the cache bytes only -- not on pos0, S or batch: a prompt cut into chunks differently gives the same bits.
+ * Deterministic; no workspace.  Refused: null pointers (AMQ_EINVAL); head_dim != 128, more than 16 query heads per kv head, pos0 + S > max_seq,
+ * strides that are no multiples of 8 halves or smaller than a row, a sequence's codes at or beyond 2^32 bytes (AMQ_ESHAPE).
+ * amq_attn_prefill_kv8_xfrag_f16: ONE sequence, the result in fragment order (as amq_attn_prefill_xfrag_f16). */
+int amq_attn_prefill_kv8_f16(const void* q, const void* kc8, const void* ks, const void* vc8, const void* vs, void* out, int batch, int S, int pos0,
+                             int n_heads, int n_kv_heads, int head_dim, int max_seq, long long q_rstride, long long q_bstride,
+                             long long o_rstride, long long o_bstride, void* stream);
+int amq_attn_prefill_kv8_xfrag_f16(const void* q, const void* kc8, const void* ks, const void* vc8, const void* vs, void* out_xf, int S, int pos0,
+                                   int n_heads, int n_kv_heads, int head_dim, int max_seq, long long q_rstride, void* stream);
 
 /* End of a greedy token step in one launch: token[0] = argmax(logits[0..vocab)) (first maximum), pos[0] += 1,
  * x[0..hidden) = embed[token][0..hidden); when rope_table / rope_cur are given (both or neither) also

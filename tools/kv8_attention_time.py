@@ -15,7 +15,13 @@
            (amq_attn_decode_kv8_gqa_f16), alternating with the other two in the same run, and the whole-step tokens/s of the synthetic
            Meta-Llama-3-8B shape (32 / 8 heads) at 64 and 4000 cached keys with kv_bits 16, 8 ("dot") and 8 ("mfma").
 
-usage: kv8_attention_time.py [--out profiles/kv8_attention.json] [--part launch,step,drift | gqa] [--rounds 3]"""
+  prefill  (--part prefill -> profiles/kv8_prefill_attention.json) the PROMPT side: ops.attn_prefill_kv8 (amq_attn_prefill_kv8_f16) against
+           ops.attn_prefill(kv_cache=True) over an fp16 cache of the same shape, chunks of S = 512 and 2048 rows behind pos0 = 0, 2048, 8192,
+           30720 cached rows, batch 1, the launch method above (distinct caches per layer, graph replays, legs alternating, medians and rounds);
+           and a whole 8192-token prompt fed in chunks of 2048 to the synthetic Meta-Llama-3-8B shape, kv_bits=8 with kv8_prompt="cache" against
+           kv_bits=16, with the peak bytes allocated during each.
+
+usage: kv8_attention_time.py [--out profiles/kv8_attention.json] [--part launch,step,drift | gqa | prefill] [--rounds 3]"""
 import argparse
 import json
 import os
@@ -120,6 +126,76 @@ def launch_shape(nh, nkv, T, B, rounds, mfma=False):
                 fp16_us_rounds=[round(t * 1e6, 2) for t in t16], kv8_us_rounds=[round(t * 1e6, 2) for t in t8],
                 fp16_read_gbps=round(row16 / m16 / 1e9, 1), kv8_read_gbps=round(row8 / m8 / 1e9, 1),
                 fp16_splits=ops.attn_decode_splits(max_seq, nh, B, nkv), kv8_splits=ops.attn_decode_kv8_splits(max_seq, nh, B, nkv))
+
+
+PREFILL_S = (512, 2048)
+PREFILL_POS0 = (0, 2048, 8192, 30720)
+
+
+def prefill_shape(nh, nkv, S, pos0, rounds):
+    T = pos0 + S
+    L = max(2, min(32, -(-LEG_BYTES // (2 * nkv * T * 256))))
+    gen = torch.Generator(device=DEV).manual_seed(T + nh)
+    kc = [torch.randn(1, nkv, T, 128, device=DEV, generator=gen).half() for _ in range(L)]
+    vc = [torch.randn(1, nkv, T, 128, device=DEV, generator=gen).half() for _ in range(L)]
+    c8 = []
+    for l in range(L):
+        kc8, ks, vc8, vs = ops.kv8_alloc(1, nkv, T, DEV)
+        kc8.random_(-127, 128, generator=gen); vc8.random_(-127, 128, generator=gen)
+        ks.uniform_(0.005, 0.03, generator=gen); vs.uniform_(0.005, 0.03, generator=gen)
+        c8.append((kc8, ks, vc8, vs))
+    q = torch.randn(S, nh * 128, device=DEV, generator=gen).half()
+    out = torch.empty_like(q)
+
+    def leg16():
+        for l in range(L):
+            ops.attn_prefill(q, kc[l], vc[l], out, S, nh, nkv, pos0=pos0, kv_cache=True)
+
+    def leg8():
+        for l in range(L):
+            ops.attn_prefill_kv8(q, *c8[l], out, S, nh, nkv, pos0=pos0)
+
+    g16, g8 = graph_of(leg16), graph_of(leg8)
+    reps = max(3, int(0.04 / max(timed(g16, 2), 1e-6)) + 1)
+    t16, t8 = [], []
+    for _ in range(rounds):                                  # the legs alternate
+        t16.append(timed(g16, reps) / L)
+        t8.append(timed(g8, reps) / L)
+    m16, m8 = statistics.median(t16), statistics.median(t8)
+    flop = 4.0 * 128 * nh * (S * pos0 + S * (S + 1) / 2)     # causal: query s meets pos0 + s + 1 keys, twice 2 x 128 flop each
+    return dict(n_heads=nh, n_kv_heads=nkv, S=S, pos0=pos0, layers=L, replays=reps, rounds=rounds, fp16_us=round(m16 * 1e6, 1),
+                kv8_us=round(m8 * 1e6, 1), kv8_over_fp16=round(m8 / m16, 3), fp16_us_rounds=[round(t * 1e6, 1) for t in t16],
+                kv8_us_rounds=[round(t * 1e6, 1) for t in t8], fp16_tflops=round(flop / m16 / 1e12, 1), kv8_tflops=round(flop / m8 / 1e12, 1))
+
+
+def chunked_prompt(tokens=8192, chunk=2048, rounds=3):
+    """a whole prompt in chunks on the synthetic Meta-Llama-3-8B shape: seconds and peak bytes allocated, kv_bits=8 / kv8_prompt="cache" against kv_bits=16"""
+    cfg = arch_mod.MODEL_CONFIGS["Meta-Llama-3-8B"]
+    linear = arch_mod.synthesize_arch(cfg, 3.0, seed=0)[0]["linear"]
+    ids = torch.randint(0, 31999, (tokens,), generator=torch.Generator().manual_seed(tokens)).to(DEV)
+    res = dict(tokens=tokens, chunk=chunk, model="Meta-Llama-3-8B shape (32 / 8 heads), synthetic weights, 3.0 bits on average")
+    for name, kw in (("kv16", dict(kv_bits=16)), ("kv8_cache", dict(kv_bits=8, kv8_prompt="cache"))):
+        torch.cuda.empty_cache()
+        m = QuantLlama(cfg, linear, device="cuda:0", max_seq=tokens + 64, seed=0, **kw)
+        secs = []
+        for rnd in range(rounds + 1):                        # (the first round captures nothing and warms: eager launches throughout)
+            m.reset()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(DEV)
+            t0 = time.perf_counter()
+            for a in range(0, tokens, chunk):
+                m.prefill(ids[a:a + chunk], use_graph=False, start_pos=a)
+            torch.cuda.synchronize()
+            if rnd:
+                secs.append(time.perf_counter() - t0)
+        m.check()
+        res[name + "_s"] = round(statistics.median(secs), 4)
+        res[name + "_s_rounds"] = [round(t, 4) for t in secs]
+        res[name + "_peak_bytes"] = int(torch.cuda.max_memory_allocated(DEV))
+        res[name + "_cache_bytes"] = int(sum(blk[k].numel() * blk[k].element_size() for blk in m.blocks for k in m.cache_keys))
+        del m
+    res["kv8_cache_over_kv16"] = round(res["kv8_cache_s"] / res["kv16_s"], 3)
+    return res
 
 
 def synthetic_7b(max_seq, kv_bits):
@@ -227,6 +303,21 @@ def main():
             print(json.dumps(r), flush=True)
             torch.cuda.empty_cache()
             save()
+    if "prefill" in parts:
+        if args.out.endswith("kv8_attention.json"):
+            args.out = args.out[:-len("kv8_attention.json")] + "kv8_prefill_attention.json"
+        res["prefill"] = []
+        for nh, nkv in HEADS:
+            for S in PREFILL_S:
+                for pos0 in PREFILL_POS0:
+                    r = prefill_shape(nh, nkv, S, pos0, args.rounds)
+                    res["prefill"].append(r)
+                    print(json.dumps(r), flush=True)
+                    torch.cuda.empty_cache()
+                    save()
+        res["chunked_prompt"] = chunked_prompt(rounds=args.rounds)
+        print(json.dumps(res["chunked_prompt"]), flush=True)
+        save()
     if "drift" in parts:
         cfg = dict(arch_mod._cfg(2, 512, 1024, 4, 2, 1, vocab=1024))
         tiny = [QuantLlama(cfg, None, device="cuda:0", max_seq=128, seed=3, kv_bits=kb) for kb in (16, 8)]
