@@ -154,6 +154,8 @@ SIGNATURES = {
     "amq_attn_decode_kv8_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _sz, _vp, _vp]),
     "amq_attn_decode_kv8_gqa_workspace_bytes": (_sz, [_i, _i, _i]),
     "amq_attn_decode_kv8_gqa_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _sz, _vp, _vp]),
+    "amq_attn_decode_kv8_i8_workspace_bytes": (_sz, [_i, _i, _i]),
+    "amq_attn_decode_kv8_i8_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _sz, _vp, _vp]),
     "amq_gemm_xfrag_grouped_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _i, _i, _i, _vp]),
     "amq_gemm_xfrag_grouped_form_f16": (_i, [ctypes.POINTER(Segment), _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "amq_attn_prefill_kv8_f16": (_i, [_vp] * 6 + [_i] * 7 + [ctypes.c_longlong] * 4 + [_vp]),

@@ -1104,6 +1104,7 @@ struct AttnForm {
     const char* rows;       // what `batch` counts, in messages
     bool grouped = false;   // the matrix-core grouped-query kernels only: 2 <= n_heads / n_kv_heads <= 16, their fixed LDS, tickets unused
     bool kv8 = false;       // ... over the 8-bit cache: kcache / vcache are the int8 codes (16-byte aligned), the fp32 scales are required pointers
+    bool i8 = false;        // ... on the integer matrix cores (amq_attn_kv8_i8.hip): 1 <= n_heads / n_kv_heads <= 16, multi-head models included
 };
 constexpr int NO_BOUND = 0x7fffffff;
 constexpr AttnForm ATTN_POS{POS_HOST | POS_DEV, 1, NO_BOUND, SPLITS_NONE, 0, "attn_decode", "batch"};
@@ -1114,6 +1115,7 @@ constexpr AttnForm ATTN_SEQ{POS_BLOCKS, 1, 65535, SPLITS_OPTIONAL, 0, "attn_deco
 constexpr AttnForm ATTN_ROWS{POS_ROWS, 2, AMQ_LOOKUP_MAX_ROWS, SPLITS_OPTIONAL, 2 * 7 * 128 * 2 + 16, "attn_decode_rows", "rows"};
 constexpr AttnForm ATTN_ROWS_GQA{POS_ROWS, 2, AMQ_LOOKUP_MAX_ROWS, SPLITS_REQUIRED, 0, "attn_decode_rows_gqa", "rows", true};
 constexpr AttnForm ATTN_KV8_GQA{POS_HOST | POS_DEV | POS_BLOCK, 1, 65535, SPLITS_REQUIRED, 0, "attn_decode_kv8_gqa", "batch", true, true};
+constexpr AttnForm ATTN_KV8_I8{POS_HOST | POS_DEV | POS_BLOCK, 1, 65535, SPLITS_REQUIRED, 0, "attn_decode_kv8_i8", "batch", true, true, true};
 
 size_t amq_attn_decode_split_workspace_bytes(int batch, int n_heads, int n_splits) {
     if (batch < 1 || n_heads < 1 || n_splits < 1) return 0;
@@ -1136,11 +1138,11 @@ static int attn_decode(const AttnForm& f, const amq_qk_norm* norm, const void* q
     if (batch < f.batch_min || batch > f.batch_max) return fail(AMQ_ESHAPE, "%s must be %d..%d (got %d)", f.rows, f.batch_min, f.batch_max, batch);
     if (n_heads < 1 || n_heads > 255 || n_kv_heads < 1 || (n_heads % n_kv_heads) != 0)
         return fail(AMQ_ESHAPE, "bad head configuration (%d q heads, %d kv heads)", n_heads, n_kv_heads);
-    if (f.kv8 && n_heads == n_kv_heads)
+    if (f.kv8 && !f.i8 && n_heads == n_kv_heads)
         return fail(AMQ_ESHAPE, "%s serves grouped-query models (got %d / %d heads); multi-head models: the per-head 8-bit kernel (amq_attn_decode_kv8_f16)",
                     f.what, n_heads, n_kv_heads);
-    if (f.grouped && (n_heads / n_kv_heads < 2 || n_heads / n_kv_heads > 16))
-        return fail(AMQ_ESHAPE, "%s serves 2..16 query heads per kv head (got %d / %d)", f.what, n_heads, n_kv_heads);
+    if (f.grouped && (n_heads / n_kv_heads < (f.i8 ? 1 : 2) || n_heads / n_kv_heads > 16))
+        return fail(AMQ_ESHAPE, "%s serves %d..16 query heads per kv head (got %d / %d)", f.what, f.i8 ? 1 : 2, n_heads, n_kv_heads);
     if (max_seq < 1 || (!state && !pos_dev && (pos < 0 || pos >= max_seq)))
         return fail(AMQ_ESHAPE, "position %d outside the cache (max_seq=%d)", pos, max_seq);
     if (f.grouped && max_seq > (1 << 24)) return fail(AMQ_ESHAPE, "%s forms a key's byte offset in 32 bits: max_seq <= 2^24 (got %d)", f.what, max_seq);
@@ -1163,7 +1165,8 @@ static int attn_decode(const AttnForm& f, const amq_qk_norm* norm, const void* q
     a.norm = nrm;
     if (f.kv8) {
         amq::Kv8Args a8{q, k, v, kcache, ks, vcache, vs, out, a.pos_dev, pos, n_heads, n_kv_heads, max_seq, a.rope_theta, a.rope_table, state};
-        return check_hip(amq::launch_attn_decode_kv8_gqa(a8, batch, n_splits, workspace, (hipStream_t)stream), f.what);
+        return check_hip((f.i8 ? amq::launch_attn_decode_kv8_i8 : amq::launch_attn_decode_kv8_gqa)(a8, batch, n_splits, workspace, (hipStream_t)stream),
+                         f.what);
     }
     const hipError_t e = f.grouped ? amq::launch_attn_decode_gqa_rows(a, batch, n_splits, workspace, (hipStream_t)stream)
                          : n_splits ? amq::launch_attn_decode_split(a, batch, n_splits, workspace, tickets, (hipStream_t)stream)
@@ -1259,6 +1262,18 @@ int amq_attn_decode_kv8_gqa_f16(const void* q, const void* k, const void* v, voi
                                 int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
                                 void* tickets, void* stream) {
     return attn_decode(ATTN_KV8_GQA, nullptr, q, k, v, kc8, vc8, out, step_state, pos_dev, pos, batch, n_heads, n_kv_heads, head_dim, max_seq, rope_theta,
+                       rope_table, n_splits, workspace, workspace_bytes, tickets, stream, ks, vs);
+}
+
+size_t amq_attn_decode_kv8_i8_workspace_bytes(int batch, int n_heads, int n_splits) {
+    return amq_attn_decode_split_workspace_bytes(batch, n_heads, n_splits);
+}
+
+int amq_attn_decode_kv8_i8_f16(const void* q, const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, void* out,
+                               const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
+                               int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
+                               void* tickets, void* stream) {
+    return attn_decode(ATTN_KV8_I8, nullptr, q, k, v, kc8, vc8, out, step_state, pos_dev, pos, batch, n_heads, n_kv_heads, head_dim, max_seq, rope_theta,
                        rope_table, n_splits, workspace, workspace_bytes, tickets, stream, ks, vs);
 }
 

@@ -224,6 +224,9 @@ hipError_t launch_attn_decode_kv8(const Kv8Args& a, int batch, int n_splits, voi
 // 128 * attn_decode_kv8_gqa_iters keys, ws as above, no tickets -- attn_gqa_combine_kernel (launch_attn_gqa_combine) adds the chunks
 int attn_decode_kv8_gqa_iters(int max_seq, int n_splits);
 hipError_t launch_attn_decode_kv8_gqa(const Kv8Args& a, int batch, int n_splits, void* ws, hipStream_t st);
+// ... of ANY model of 1 .. 16 query heads per kv head on the integer matrix cores (amq_attn_kv8_i8.hip: v_mfma_i32_16x16x64_i8 on the raw codes,
+// q and the probability weights as two int8 planes): the same chunks, workspace records and combine launch
+hipError_t launch_attn_decode_kv8_i8(const Kv8Args& a, int batch, int n_splits, void* ws, hipStream_t st);
 hipError_t launch_attn_gqa_combine(const void* ws, void* out, const void* state, int pos, int cur_mode, int n_heads, int batch, int max_seq,
                                    int n_splits, int chunk, hipStream_t st);
 hipError_t launch_rmsnorm(const void* x, const void* gamma, void* y, int M, int K, float eps, hipStream_t st);

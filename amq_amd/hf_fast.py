@@ -398,7 +398,7 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
     returns HF's shifted cross-entropy as ``loss``; ``kv_bits=8``: the runners keep an 8-bit KV cache (int8 rows with a scale per row, DESIGN.md 3.13:
     ``generate`` greedy and sampled, one-row ``model(ids, start_pos=p)`` steps; a many-row call at ``start_pos`` > 0 raises; refused together with
     ``lookup=True`` / ``padded=True``; ``kv8_kernel="mfma"``: grouped-query models take the matrix-core 8-bit attention kernel,
-    QuantLlama(kv8_kernel=)); ``kv8_prompt="cache"``: the runners' prompt passes attend the 8-bit cache rows (QuantLlama(kv8_prompt=)), so
+    ``kv8_kernel="i8"``: models of 1 .. 16 query heads per kv head take the integer matrix-core one, QuantLlama(kv8_kernel=)); ``kv8_prompt="cache"``: the runners' prompt passes attend the 8-bit cache rows (QuantLlama(kv8_prompt=)), so
     ``model(ids, start_pos=p, use_cache=False)`` with several rows behind cached rows is served; ``lm_head_bits=8`` / ``4``: the runners read a packed lm_head (QuantLlama(lm_head_bits=)),
     quantized once from ``model.lm_head.weight`` and shared by every runner of the model; the module itself keeps its fp16 weight, so HF's own
     forward and a reverted model are untouched.  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
@@ -410,7 +410,7 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
         raise ValueError("kv_bits=8 is not offered together with " + ("lookup=True" if lookup else "padded=True") + ": the 8-bit attention kernel "
                          "runs one row per sequence at one position for the batch (QuantLlama(kv_bits=8))")
     check_lm_head_bits(lm_head_bits)
-    if kv8_kernel != "dot":                                     # (the model's head counts matter to "mfma" only)
+    if kv8_kernel != "dot":                                     # (the model's head counts matter to "mfma" and "i8" only)
         check_kv8_kernel(kv8_kernel, kv_bits, model.config.num_attention_heads,
                          getattr(model.config, "num_key_value_heads", None) or model.config.num_attention_heads)
     check_kv8_prompt(kv8_prompt, kv_bits)

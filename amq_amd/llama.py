@@ -161,6 +161,12 @@ def check_kv8_kernel(kv8_kernel, kv_bits, n_heads, n_kv_heads):
         if not 2 <= n_heads // n_kv_heads <= 16:
             raise ValueError(f"kv8_kernel='mfma' is the grouped-query kernel (2 .. 16 query heads per kv head share a matrix-core row block): "
                              f"a model of {n_heads} / {n_kv_heads} heads keeps kv8_kernel='dot'")
+    if kv8_kernel == "i8":
+        if kv_bits != 8:
+            raise ValueError(f"kv8_kernel='i8' chooses among the 8-bit cache's attention kernels: it needs kv_bits=8 (got kv_bits={kv_bits})")
+        if not 1 <= n_heads // n_kv_heads <= 16:
+            raise ValueError(f"kv8_kernel='i8' puts the 1 .. 16 query heads of a kv head into one matrix-core row block: "
+                             f"a model of {n_heads} / {n_kv_heads} heads keeps kv8_kernel='dot'")
     return kv8_kernel
 
 
@@ -396,7 +402,9 @@ class QuantLlama:
         ops.attn_decode_kv8, the prompt pass stays exact fp16 and stores its rows with one ops.kv8_store; no prompt pass at start_pos > 0).
         kv8_kernel: the attention kernel of a kv_bits=8 token step.  "dot" -- the per-head kernel on the vector units, the launch the option has
         always issued; "mfma" -- grouped-query models only: the group's heads on the matrix cores from one staging of the raw rows
-        (ops.attn_decode_kv8(kernel="mfma")): the same cache bytes, probabilities rounded to fp16 before P.V.
+        (ops.attn_decode_kv8(kernel="mfma")): the same cache bytes, probabilities rounded to fp16 before P.V; "i8" -- models of 1 .. 16 query
+        heads per kv head, multi-head ones included, on the integer matrix cores (ops.attn_decode_kv8(kernel="i8")): the raw codes are the
+        operands, q and the probability weights two int8 planes each, the same cache bytes.
         kv8_prompt: how a kv_bits=8 runner's cached prompt pass attends.  "exact" -- the behaviour above: bits of the fp16-cache runner's prompt
         logits, and ``prefill(..., start_pos > 0)`` refused.  "cache" -- EVERY cached prompt pass (start_pos 0 included) rotates, stores its rows
         with ops.kv8_store and attends the dequantized cache rows 0 .. its own through ops.attn_prefill_kv8, the kernel that reads the int8 rows

@@ -2065,12 +2065,13 @@ def attn_decode_kv8_chunk(max_seq, n_splits):
 
 
 KV8_GQA_STAGE = 128        # keys per stage of the matrix-core kernel (amq_attn_kv8_gqa.hip): its chunks are whole stages
-KV8_KERNELS = ("dot", "mfma")
+KV8_KERNELS = ("dot", "mfma", "i8")
 
 
 def check_kv8_kernel(kernel):
     if kernel not in KV8_KERNELS:
-        raise ValueError(f"the 8-bit attention kernel must be 'dot' (per-head, vector units) or 'mfma' (grouped-query, matrix cores), got {kernel!r}")
+        raise ValueError(f"the 8-bit attention kernel must be 'dot' (per-head, vector units), 'mfma' (grouped-query, matrix cores) or 'i8' (1 .. 16 query heads per "
+                         f"kv head, integer matrix cores), got {kernel!r}")
     return kernel
 
 
@@ -2083,19 +2084,42 @@ def attn_decode_kv8_gqa_splits(max_seq, n_heads=32, batch=1, n_kv_heads=8):
     return -(-stages // per)
 
 
+def attn_decode_kv8_i8_splits(max_seq, n_heads=32, batch=1, n_kv_heads=32):
+    """chunks per (sequence, kv head) the auto policy gives the integer matrix-core kernel (amq_attn_kv8_i8.hip): enough chunks of whole 128-key
+    stages for KV8_WGS workgroups in the launch (two of its 67 KiB, two-wave workgroups fit a CU's LDS; chunks beyond the position leave at
+    once).  The matrix-core kernel's rule, chosen before any measurement and not tuned to one."""
+    stages = -(-max_seq // KV8_GQA_STAGE)
+    want = -(-KV8_WGS // max(1, n_kv_heads * batch))
+    per = -(-stages // max(1, min(want, stages, 1024)))          # stages per chunk
+    return -(-stages // per)
+
+
+def attn_decode_kv8_i8_chunk(max_seq, n_splits):
+    """keys per workgroup of the two matrix-core launches over ``n_splits`` chunks (attn_decode_kv8_gqa_iters: whole stages)"""
+    return -(-(-(-max_seq // n_splits)) // KV8_GQA_STAGE) * KV8_GQA_STAGE
+
+
+_KV8_ENTRY = {"dot": ("amq_attn_decode_kv8_workspace_bytes", "amq_attn_decode_kv8_f16", attn_decode_kv8_splits),
+              "mfma": ("amq_attn_decode_kv8_gqa_workspace_bytes", "amq_attn_decode_kv8_gqa_f16", attn_decode_kv8_gqa_splits),
+              "i8": ("amq_attn_decode_kv8_i8_workspace_bytes", "amq_attn_decode_kv8_i8_f16", attn_decode_kv8_i8_splits)}
+
+
 def attn_decode_kv8(q, k, v, kc8, ks, vc8, vs, out, pos, n_heads, n_kv_heads, table=None, cur=None, n_splits=0, rope_theta=10000.0, kernel="dot"):
     """One new token per sequence over the 8-bit caches (ops.kv8_alloc): q [B, n_heads*128], k / v [B, n_kv_heads*128] un-rotated; the new row is
     quantized and appended at ``pos`` (shared by the batch) and out [B, n_heads*128] is the attention over the dequantized rows 0 .. pos.  ``pos``:
     an int with ``table`` (or neither: cos/sin computed in the kernel), or with ``cur`` the two views of one step-state block (ops.new_step_state).
-    ``n_splits``: workgroups per (sequence, kv head); 0 = :func:`attn_decode_kv8_splits` (``"mfma"``: :func:`attn_decode_kv8_gqa_splits`).
+    ``n_splits``: workgroups per (sequence, kv head); 0 = :func:`attn_decode_kv8_splits` (``"mfma"``: :func:`attn_decode_kv8_gqa_splits`, ``"i8"``:
+    :func:`attn_decode_kv8_i8_splits`).
     ``kernel``: ``"dot"`` -- the per-head kernel on the vector units; ``"mfma"`` -- grouped-query models (2 .. 16 query heads per kv head) on the
-    matrix cores, the same cache bytes, probabilities rounded to fp16 before P.V (amq_attn_decode_kv8_gqa_f16)."""
-    mfma = check_kv8_kernel(kernel) == "mfma"
+    matrix cores, the same cache bytes, probabilities rounded to fp16 before P.V (amq_attn_decode_kv8_gqa_f16); ``"i8"`` -- models of 1 .. 16 query heads per kv
+    head (multi-head ones included) on the integer matrix cores: the raw codes are the operands, q and the probability weights two int8 planes
+    each, the same cache bytes (amq_attn_decode_kv8_i8_f16)."""
+    ws_bytes, entry, policy = _KV8_ENTRY[check_kv8_kernel(kernel)]
     B, nkv, max_seq = _need_kv8(kc8, ks, vc8, vs)
     if nkv != n_kv_heads:
         raise ValueError(f"caches of {nkv} kv heads, n_kv_heads={n_kv_heads}")
     if n_splits == 0:
-        n_splits = (attn_decode_kv8_gqa_splits if mfma else attn_decode_kv8_splits)(max_seq, n_heads, B, n_kv_heads)
+        n_splits = policy(max_seq, n_heads, B, n_kv_heads)
     _need(q, torch.float16, "q", B * n_heads * 128)
     _need(k, torch.float16, "k", B * n_kv_heads * 128)
     _need(v, torch.float16, "v", B * n_kv_heads * 128)
@@ -2114,9 +2138,9 @@ def attn_decode_kv8(q, k, v, kc8, ks, vc8, vs, out, pos, n_heads, n_kv_heads, ta
     if table is not None:
         _need(table, torch.float16, "rope table", max_seq * 128)
     lib = _lib.load()
-    wsb = (lib.amq_attn_decode_kv8_gqa_workspace_bytes if mfma else lib.amq_attn_decode_kv8_workspace_bytes)(B, n_heads, n_splits)
+    wsb = getattr(lib, ws_bytes)(B, n_heads, n_splits)
     ws, tickets = _ATTN_WS.get(q.device, wsb // 4), _ATTN_TICKETS.get(q.device, B * n_kv_heads * 2)
-    launch = lib.amq_attn_decode_kv8_gqa_f16 if mfma else lib.amq_attn_decode_kv8_f16
+    launch = getattr(lib, entry)
     _lib.check(launch(*map(_lib.ptr, (q, k, v, kc8, ks, vc8, vs, out, cur)), pos_dev, pos_i, B, n_heads, n_kv_heads, 128, max_seq,
                       ctypes.c_float(rope_theta), _lib.ptr(table), n_splits, _lib.ptr(ws), wsb, _lib.ptr(tickets), _lib.current_stream()))
     return out

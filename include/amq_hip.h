@@ -629,6 +629,18 @@ int amq_attn_prefill_kv8_f16(const void* q, const void* kc8, const void* ks, con
                              long long o_rstride, long long o_bstride, void* stream);
 int amq_attn_prefill_kv8_xfrag_f16(const void* q, const void* kc8, const void* ks, const void* vc8, const void* vs, void* out_xf, int S, int pos0,
                                    int n_heads, int n_kv_heads, int head_dim, int max_seq, long long q_rstride, void* stream);
+/* amq_attn_decode_kv8_i8_f16: the same step, arguments and cache bytes for models of 1 .. 16 query heads per kv head (multi-head models
+ * included) on the INTEGER matrix cores: the raw int8 rows are the operands of v_mfma_i32_16x16x64_i8 as they lie in memory.  Per head the
+ * rotated q becomes two int8 planes (sq = max |q| / 127, x = q / sq, qh = rint x, ql = rint((x - qh) 254)); a score is
+ * float(254 sum qh c + sum ql c) (sq / 254) ks RN32(1 / sqrt 128), the integer exact.  Softmax in fp32, the sum over the unquantized p.  Per 64
+ * keys w = p vs (fp32), S = max w, y = 127 w / S as two planes the same way, O <- alpha O + S / (127 * 254) float(254 sum wh c + sum wl c).
+ * Chunks, the second launch, the cache bits and the refusals are amq_attn_decode_kv8_gqa_f16's, except that one query head per kv head is served.
+ * workspace: amq_attn_decode_kv8_i8_workspace_bytes bytes, no initialisation; tickets: accepted for the shared signature, never touched. */
+size_t amq_attn_decode_kv8_i8_workspace_bytes(int batch, int n_heads, int n_splits);
+int amq_attn_decode_kv8_i8_f16(const void* q, const void* k, const void* v, void* kc8, void* ks, void* vc8, void* vs, void* out,
+                               const void* step_state, const int* pos_dev, int pos, int batch, int n_heads, int n_kv_heads, int head_dim,
+                               int max_seq, float rope_theta, const void* rope_table, int n_splits, void* workspace, size_t workspace_bytes,
+                               void* tickets, void* stream);
 
 /* End of a greedy token step in one launch: token[0] = argmax(logits[0..vocab)) (first maximum), pos[0] += 1,
  * x[0..hidden) = embed[token][0..hidden); when rope_table / rope_cur are given (both or neither) also

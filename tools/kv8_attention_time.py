@@ -21,7 +21,12 @@
            and a whole 8192-token prompt fed in chunks of 2048 to the synthetic Meta-Llama-3-8B shape, kv_bits=8 with kv8_prompt="cache" against
            kv_bits=16, with the peak bytes allocated during each.
 
-usage: kv8_attention_time.py [--out profiles/kv8_attention.json] [--part launch,step,drift | gqa | prefill] [--rounds 3]"""
+  i8       (--part i8 -> profiles/kv8_i8_attention.json) the whole launch grid, the (32, 32) rows included, with FOUR legs alternating in the
+           same run: the fp16 cache, "dot", "mfma" where it applies (grouped-query rows) and ops.attn_decode_kv8(kernel="i8")
+           (amq_attn_decode_kv8_i8_f16); and the whole-step tokens/s of the synthetic Llama-2-7B (32 / 32 heads) and Meta-Llama-3-8B (32 / 8)
+           shapes at 64 and 4000 cached keys with kv_bits 16, 8 ("dot"), 8 ("mfma", the 8B shape) and 8 ("i8").
+
+usage: kv8_attention_time.py [--out profiles/kv8_attention.json] [--part launch,step,drift | gqa | prefill | i8] [--rounds 3]"""
 import argparse
 import json
 import os
@@ -69,7 +74,7 @@ def timed(g, reps):
     return e0.elapsed_time(e1) * 1e-3 / reps
 
 
-def launch_shape(nh, nkv, T, B, rounds, mfma=False):
+def launch_shape(nh, nkv, T, B, rounds, mfma=False, i8=False):
     max_seq = T + 64
     row16, row8 = 2 * B * nkv * (T + 1) * 256, 2 * B * nkv * (T + 1) * 132          # K + V bytes one launch reads
     L = max(2, min(32, -(-LEG_BYTES // (2 * B * nkv * max_seq * 256))))
@@ -104,15 +109,22 @@ def launch_shape(nh, nkv, T, B, rounds, mfma=False):
         for l in range(L):
             ops.attn_decode_kv8(q, k, v, *c8[l], out, pos, nh, nkv, cur=cur, kernel="mfma")
 
+    def leg8i():
+        for l in range(L):
+            ops.attn_decode_kv8(q, k, v, *c8[l], out, pos, nh, nkv, cur=cur, kernel="i8")
+
     g16, g8 = graph_of(leg16), graph_of(leg8)
     g8m = graph_of(leg8m) if mfma else None
+    g8i = graph_of(leg8i) if i8 else None
     reps = max(3, int(0.04 / max(timed(g16, 2), 1e-6)) + 1)
-    t16, t8, t8m = [], [], []
+    t16, t8, t8m, t8i = [], [], [], []
     for _ in range(rounds):                                  # the legs alternate
         t16.append(timed(g16, reps) / L)
         t8.append(timed(g8, reps) / L)
         if mfma:
             t8m.append(timed(g8m, reps) / L)
+        if i8:
+            t8i.append(timed(g8i, reps) / L)
     assert int(err.item()) == 0
     m16, m8 = statistics.median(t16), statistics.median(t8)
     extra = {}
@@ -121,6 +133,13 @@ def launch_shape(nh, nkv, T, B, rounds, mfma=False):
         extra = dict(kv8_mfma_us=round(mm * 1e6, 2), kv8_mfma_over_fp16=round(mm / m16, 3), kv8_mfma_over_kv8=round(mm / m8, 3),
                      kv8_mfma_us_rounds=[round(t * 1e6, 2) for t in t8m], kv8_mfma_read_gbps=round(row8 / mm / 1e9, 1),
                      kv8_mfma_splits=ops.attn_decode_kv8_gqa_splits(max_seq, nh, B, nkv))
+    if i8:
+        mi = statistics.median(t8i)
+        extra.update(kv8_i8_us=round(mi * 1e6, 2), kv8_i8_over_fp16=round(mi / m16, 3), kv8_i8_over_kv8=round(mi / m8, 3),
+                     kv8_i8_us_rounds=[round(t * 1e6, 2) for t in t8i], kv8_i8_read_gbps=round(row8 / mi / 1e9, 1),
+                     kv8_i8_splits=ops.attn_decode_kv8_i8_splits(max_seq, nh, B, nkv))
+        if mfma:
+            extra.update(kv8_i8_over_mfma=round(mi / statistics.median(t8m), 3))
     return dict(**extra, n_heads=nh, n_kv_heads=nkv, keys=T, batch=B, layers=L, replays=reps, rounds=rounds,
                 fp16_us=round(m16 * 1e6, 2), kv8_us=round(m8 * 1e6, 2), kv8_over_fp16=round(m8 / m16, 3),
                 fp16_us_rounds=[round(t * 1e6, 2) for t in t16], kv8_us_rounds=[round(t * 1e6, 2) for t in t8],
@@ -198,18 +217,21 @@ def chunked_prompt(tokens=8192, chunk=2048, rounds=3):
     return res
 
 
+def _kv_leg(kv_bits):
+    """a step leg's runner options: 16, 8 (the per-head kernel), "8mfma" or "8i8" (the matrix-core kernels)"""
+    return dict(kv_bits=16 if kv_bits == 16 else 8, kv8_kernel={"8mfma": "mfma", "8i8": "i8"}.get(kv_bits, "dot"))
+
+
 def synthetic_7b(max_seq, kv_bits):
     cfg = arch_mod.MODEL_CONFIGS["Llama-2-7b-hf"]
     linear = arch_mod.synthesize_arch(cfg, 3.0, seed=0, pinned=arch_mod.PINNED_7B)[0]["linear"]
-    return QuantLlama(cfg, linear, device="cuda:0", max_seq=max_seq, seed=0, kv_bits=kv_bits)
+    return QuantLlama(cfg, linear, device="cuda:0", max_seq=max_seq, seed=0, **_kv_leg(kv_bits))
 
 
 def synthetic_gqa(max_seq, kv_bits):
-    """kv_bits: 16, 8 (the per-head kernel) or "8mfma" (the matrix-core kernel)"""
     cfg = arch_mod.MODEL_CONFIGS["Meta-Llama-3-8B"]
     linear = arch_mod.synthesize_arch(cfg, 3.0, seed=0)[0]["linear"]
-    return QuantLlama(cfg, linear, device="cuda:0", max_seq=max_seq, seed=0, kv_bits=16 if kv_bits == 16 else 8,
-                      kv8_kernel="mfma" if kv_bits == "8mfma" else "dot")
+    return QuantLlama(cfg, linear, device="cuda:0", max_seq=max_seq, seed=0, **_kv_leg(kv_bits))
 
 
 def step_rate(keys, steps=64, rounds=3, legs=(16, 8), build=synthetic_7b, model="Llama-2-7b-hf, synthetic weights, 3.0 bits on average"):
@@ -303,6 +325,27 @@ def main():
             print(json.dumps(r), flush=True)
             torch.cuda.empty_cache()
             save()
+    if "i8" in parts:
+        if args.out.endswith("kv8_attention.json"):
+            args.out = args.out[:-len("kv8_attention.json")] + "kv8_i8_attention.json"
+        res["launch"], res["step"] = [], []
+        for nh, nkv in HEADS:
+            for T in KEYS:
+                for B in BATCHES:
+                    r = launch_shape(nh, nkv, T, B, args.rounds, mfma=nh != nkv, i8=True)
+                    res["launch"].append(r)
+                    print(json.dumps(r), flush=True)
+                    torch.cuda.empty_cache()
+                    save()
+        for build, legs, model in ((synthetic_7b, (16, 8, "8i8"), "Llama-2-7b-hf (32 / 32 heads), synthetic weights, 3.0 bits on average"),
+                                   (synthetic_gqa, (16, 8, "8mfma", "8i8"),
+                                    "Meta-Llama-3-8B shape (32 / 8 heads), synthetic weights, 3.0 bits on average")):
+            for keys in (64, 4000):
+                r = step_rate(keys, rounds=args.rounds, legs=legs, build=build, model=model)
+                res["step"].append(r)
+                print(json.dumps(r), flush=True)
+                torch.cuda.empty_cache()
+                save()
     if "prefill" in parts:
         if args.out.endswith("kv8_attention.json"):
             args.out = args.out[:-len("kv8_attention.json")] + "kv8_prefill_attention.json"
