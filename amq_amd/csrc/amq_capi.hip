@@ -1074,6 +1074,21 @@ int amq_lm8_gemv_f16(const void* x, const void* codes, const void* meta, void* y
     return check_hip(amq::launch_lm8_gemv(x, codes, meta, y, gamma, eps, M, N, K, (hipStream_t)stream), "lm8_gemv");
 }
 
+int amq_lm8_gemm_f16(const void* x, const void* codes, const void* meta, void* y, const void* gamma, float eps, int M, int N, int K, int group,
+                     void* stream) {
+    const char* who = "amq_lm8_gemm_f16";
+    if (!x || !codes || !meta || !y) return fail(AMQ_EINVAL, "%s: null pointer", who);
+    if (int rc = check_lm8_aligned(who, "x", x, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "codes", codes, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "meta", meta, 4)) return rc;
+    if (int rc = check_lm8_aligned(who, "gamma", gamma, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "y", y, 2)) return rc;
+    if (M < 1 || M > 16) return fail(AMQ_ESHAPE, "%s: M must be 1..16 (got %d)", who, M);
+    if (int rc = check_lm8(who, N, K, group)) return rc;
+    if (amq::lm8_gemm_lds_bytes(M, K) > LDS_LIMIT) return fail(AMQ_ESHAPE, "%s: %d rows of K=%d do not fit LDS", who, M, K);
+    return check_hip(amq::launch_lm8_gemm(x, codes, meta, y, gamma, eps, M, N, K, (hipStream_t)stream), "lm8_gemm");
+}
+
 int amq_lm8_dequantize_f16(const void* codes, const void* meta, void* out, int row0, int rows, int N, int K, int group, void* stream) {
     const char* who = "amq_lm8_dequantize_f16";
     if (!codes || !meta || !out) return fail(AMQ_EINVAL, "%s: null pointer", who);

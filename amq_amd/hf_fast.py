@@ -139,7 +139,7 @@ def _lm_head_build(model):
     kept = model.__dict__.get("_amq_lm_head_packed")
     if kept is None or kept[0] != (bits, w.data_ptr(), w._version):
         kept = model.__dict__["_amq_lm_head_packed"] = ((bits, w.data_ptr(), w._version), QuantLlama.pack_lm_head(w.detach().to(torch.float16), bits))
-    return dict(lm_head_bits=bits, lm_head_packed=kept[1])
+    return dict(lm_head_bits=bits, lm_head_packed=kept[1], lm8_kernel=model.__dict__.get("_amq_lm8_kernel", "dot"))
 
 
 def _lookup_runner(model, need, k, g):
@@ -387,7 +387,8 @@ def _fast_generate(self, inputs=None, generation_config=None, logits_processor=N
     return torch.cat([ids, new.view(B, -1).to(ids.dtype)], dim=1)
 
 
-def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scoring=False, kv_bits=16, lm_head_bits=16, kv8_kernel="dot", kv8_prompt="exact"):
+def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scoring=False, kv_bits=16, lm_head_bits=16, kv8_kernel="dot", kv8_prompt="exact",
+                         lm8_kernel="dot"):
     """convert_model_to_ft(model) + replace_generate_functions() (ftllama_modeling.py:569-580, ftllama_generate.py:613-622) for the HIP backend:
     call it on the model ``prepare_for_inference(model, backend='hip')`` returned (a Llama-family ``*ForCausalLM`` whose decoder linears are
     HIPQuantLinear modules on one GPU).  Patches THIS instance's ``forward`` and ``generate`` (see the module docstring); idempotent; returns the
@@ -401,10 +402,11 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
     ``kv8_kernel="i8"``: models of 1 .. 16 query heads per kv head take the integer matrix-core one, QuantLlama(kv8_kernel=)); ``kv8_prompt="cache"``: the runners' prompt passes attend the 8-bit cache rows (QuantLlama(kv8_prompt=)), so
     ``model(ids, start_pos=p, use_cache=False)`` with several rows behind cached rows is served; ``lm_head_bits=8`` / ``4``: the runners read a packed lm_head (QuantLlama(lm_head_bits=)),
     quantized once from ``model.lm_head.weight`` and shared by every runner of the model; the module itself keeps its fp16 weight, so HF's own
-    forward and a reverted model are untouched.  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
+    forward and a reverted model are untouched; ``lm8_kernel="mfma"`` (with ``lm_head_bits=8``): the runners' 2 .. 16-row lm_head calls take the
+    matrix-core kernel (QuantLlama(lm8_kernel=)).  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
-    from .llama import check_kv8_kernel, check_kv8_prompt, check_kv_bits, check_lm_head_bits
+    from .llama import check_kv8_kernel, check_kv8_prompt, check_kv_bits, check_lm8_kernel, check_lm_head_bits
     check_kv_bits(kv_bits)
     if kv_bits == 8 and (lookup or padded):
         raise ValueError("kv_bits=8 is not offered together with " + ("lookup=True" if lookup else "padded=True") + ": the 8-bit attention kernel "
@@ -414,13 +416,16 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
         check_kv8_kernel(kv8_kernel, kv_bits, model.config.num_attention_heads,
                          getattr(model.config, "num_key_value_heads", None) or model.config.num_attention_heads)
     check_kv8_prompt(kv8_prompt, kv_bits)
+    check_lm8_kernel(lm8_kernel, lm_head_bits)
     if model.__dict__.get("_amq_kv_bits", kv_bits) != kv_bits or model.__dict__.get("_amq_lm_head_bits", 16) != lm_head_bits or \
-            model.__dict__.get("_amq_kv8_kernel", "dot") != kv8_kernel or model.__dict__.get("_amq_kv8_prompt", "exact") != kv8_prompt:
+            model.__dict__.get("_amq_kv8_kernel", "dot") != kv8_kernel or model.__dict__.get("_amq_kv8_prompt", "exact") != kv8_prompt or \
+            model.__dict__.get("_amq_lm8_kernel", "dot") != lm8_kernel:
         _RUNNERS.pop(model, None)                               # runners hold a cache of the other format / another lm_head
         model.__dict__.pop("_amq_lm_head_packed", None)
     model.__dict__["_amq_kv_bits"] = int(kv_bits)
     model.__dict__["_amq_kv8_kernel"] = kv8_kernel
     model.__dict__["_amq_kv8_prompt"] = kv8_prompt
+    model.__dict__["_amq_lm8_kernel"] = lm8_kernel
     if lm_head_bits == 16:
         model.__dict__.pop("_amq_lm_head_bits", None)
     else:
@@ -456,6 +461,7 @@ def revert_model_to_hf(model):
     model.__dict__.pop("_amq_kv_bits", None)
     model.__dict__.pop("_amq_kv8_kernel", None)
     model.__dict__.pop("_amq_kv8_prompt", None)
+    model.__dict__.pop("_amq_lm8_kernel", None)
     model.__dict__.pop("_amq_lm_head_bits", None)
     model.__dict__.pop("_amq_lm_head_packed", None)
     _RUNNERS.pop(model, None)

@@ -181,6 +181,17 @@ def check_kv8_prompt(kv8_prompt, kv_bits):
     return kv8_prompt
 
 
+def check_lm8_kernel(lm8_kernel, lm_head_bits):
+    """-> lm8_kernel, or ValueError: the kernel behind an lm_head_bits=8 runner's logits ("dot": ops.lm8_gemv, at most 8 rows a launch; "mfma":
+    ops.lm8_gemm for 2 .. 16 rows).  A step of its own behind runner_options (whose answers it does not change)"""
+    if lm8_kernel not in ops.LM8_KERNELS:
+        raise ValueError(f"lm8_kernel must be 'dot' (the dot-product kernel, 1 .. 8 rows a launch) or 'mfma' (the matrix-core kernel for 2 .. 16 "
+                         f"rows), got {lm8_kernel!r}")
+    if lm8_kernel == "mfma" and lm_head_bits != 8:
+        raise ValueError(f"lm8_kernel='mfma' chooses among the 8-bit lm_head's kernels: it needs lm_head_bits=8 (got lm_head_bits={lm_head_bits})")
+    return lm8_kernel
+
+
 def check_lm_head_bits(lm_head_bits):
     if lm_head_bits not in (16, 8, 4):
         raise ValueError(f"lm_head_bits must be 16 (fp16 lm_head), 8 (the LM8 layer) or 4 (a packed 4-bit layer), got {lm_head_bits!r}")
@@ -374,7 +385,8 @@ class QuantLlama:
 
     def __init__(self, config, arch_linear=None, device="cuda:0", max_seq=256, seed=0, synthetic=True,
                  hqq_layers=None, dense=None, batch=1, engine=None, prebuilt=None, group=128, rope=None, ragged=False, lookup=0, ngram_max=2,
-                 lookup_sampling=False, kv_bits=16, lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot", kv8_prompt="exact"):
+                 lookup_sampling=False, kv_bits=16, lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot", kv8_prompt="exact",
+                 lm8_kernel="dot"):
         """config: an entry of arch.MODEL_CONFIGS (or its name).
         arch_linear: {'self_attn.q_proj': [bits]*n_block, ...}; default uniform 4.
         hqq_layers: {(block, name): HQQWeights} real quantized layers (else synthetic).
@@ -413,11 +425,17 @@ class QuantLlama:
         lm_head_bits: 16 -- the fp16 lm_head, the object, graphs and bits the runner has always had; 8 -- the lm_head is quantized once, here, to
         the LM8 layer (hqq_format.quantize_lm8) and every logit comes from ops.lm8_gemv; 4 -- ops.hqq_quantize(W, 4) and the packed
         GEMV / GEMM kernels of the block linears.  The runner then keeps no fp16 lm_head (self.lm_head is None; self.lm_head_q is the packed layer).
+        lm8_kernel: the kernel behind an lm_head_bits=8 runner's logits.  "dot" -- ops.lm8_gemv, every launch the option has always issued (at most
+        8 rows each); "mfma" -- calls of 2 .. 16 rows (a batch, a lookup runner's verify rows, the pieces of a many-row pass below LM8_SLICED_FROM
+        rows) go to ops.lm8_gemm, the matrix-core kernel over the same bytes: one launch whose cost does not grow with its rows; the last bits of
+        those logits differ from "dot"'s (another summation order).  One row stays on ops.lm8_gemv.
         lm_head_packed: the packed layer of an earlier runner over the same weights (hf_fast shares one among the runners it builds), instead of
         quantizing again.  What is not offered with what: runner_options, route_reasons ("Runner options")."""
         config = MODEL_CONFIGS[config] if isinstance(config, str) else config
         opts = runner_options(batch, ragged, lookup, ngram_max, lookup_sampling, kv_bits, lm_head_bits, engine, self.FUSE_QKV_ATTN, config.get("qk_norm"))
+        check_lm8_kernel(lm8_kernel, opts.lm_head_bits)
         self._frame(config, device, max_seq, opts)
+        self.lm8_kernel = lm8_kernel
         self.kv8_kernel = check_kv8_kernel(kv8_kernel, self.kv_bits, self.nh, self.nkv)
         self.kv8_prompt = check_kv8_prompt(kv8_prompt, self.kv_bits)
         self.arch_linear = arch_linear or uniform_arch(config, 4)["linear"]
@@ -437,7 +455,7 @@ class QuantLlama:
         """what a runner knows before it has weights: its options (a RunnerOptions) and the model's dimensions"""
         self.B, self.R, self.ragged, self.lookup, self.ngram_max, self.lookup_sampling, self.kv_bits, self.lm_head_bits = opts[:8]
         self.cache_keys = ("kc8", "ks", "vc8", "vs") if self.kv_bits == 8 else ("kc", "vc")     # a block's cache tensors: codes and scales, or fp16 rows
-        self.kv8_kernel, self.kv8_prompt = "dot", "exact"
+        self.kv8_kernel, self.kv8_prompt, self.lm8_kernel = "dot", "exact", "dot"
         self.cfg, self.dev = config, torch.device(device)
         _prime_graph_state(self.dev)
         self.H, self.I = config["hidden_size"], config["intermediate_size"]
@@ -667,7 +685,7 @@ class QuantLlama:
 
     @classmethod
     def from_hf(cls, model, max_seq=256, batch=1, engine=None, ragged=False, lookup=0, ngram_max=2, lookup_sampling=False, kv_bits=16,
-                lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot", kv8_prompt="exact"):
+                lm_head_bits=16, lm_head_packed=None, kv8_kernel="dot", kv8_prompt="exact", lm8_kernel="dot"):
         """The hipGraph runner over a SWAPPED HF causal LM of the Llama family (``HF_MODEL_TYPES``: Llama 2 / 3.x, Mistral, Qwen2.5) -- what
         ``prepare_for_inference(model, backend="hip")`` (or the reference's deepcopy + setattr assembly of a mixed-precision model,
         amq_speed_benchmark.py:231-256) leaves behind.  The runner shares the modules' native weight buffers and biases, the embedding, lm_head and
@@ -712,7 +730,8 @@ class QuantLlama:
             dense["kn"] = [f16(l.self_attn.k_norm.weight).contiguous() for l in layers]
         return cls(cfg, arch_linear, device=dev, max_seq=max_seq, dense=dense, batch=batch, engine=engine, prebuilt=pre, synthetic=False, rope=rope,
                    ragged=ragged, lookup=lookup, ngram_max=ngram_max, lookup_sampling=lookup_sampling, kv_bits=kv_bits,
-                   lm_head_bits=lm_head_bits, lm_head_packed=lm_head_packed, kv8_kernel=kv8_kernel, kv8_prompt=kv8_prompt)
+                   lm_head_bits=lm_head_bits, lm_head_packed=lm_head_packed, kv8_kernel=kv8_kernel, kv8_prompt=kv8_prompt,
+                   lm8_kernel=lm8_kernel)
 
     # ----------------------------------------------------------------- the lm_head
     @staticmethod
@@ -755,11 +774,13 @@ class QuantLlama:
     def _lm_logits(self, x, out):
         """out = lm_head(final RMSNorm(x)) for up to 8 hidden rows -- x [H] -> out [vocab], or x [M, H] -> out [M, vocab] --: the ONE place a token
         step, a prompt pass' last rows and the streamed many-row loop form logits.  16: the fp16 weight-streaming kernel with the norm as its
-        prologue; 8: ops.lm8_gemv, the same shape; 4: the packed GEMV with the RMSNorm prologue as far as its LDS stage reaches
+        prologue; 8: ops.lm8_gemv, the same shape (lm8_kernel="mfma": ops.lm8_gemm from 2 rows on, up to _lm8_rows()); 4: the packed GEMV with the RMSNorm prologue as far as its LDS stage reaches
         (ops.gemv_max_rows(H)), an rmsnorm launch + the plain GEMV beyond (what _behind_norm does), the GEMM past that"""
         if self.lm_head_bits == 16:
             return ops.gemv_f16w(x, self.lm_head, gamma=self.norm, eps=self.eps, out=out)
         if self.lm_head_bits == 8:
+            if self.lm8_kernel == "mfma" and x.dim() == 2 and 2 <= x.shape[0] <= self._lm8_rows():
+                return ops.lm8_gemm(x, self.lm_head_q, gamma=self.norm, eps=self.eps, out=out)
             return ops.lm8_gemv(x, self.lm_head_q, gamma=self.norm, eps=self.eps, out=out)
         q = self.lm_head_q
         x2, y = x.reshape(-1, self.H), out.view(-1, self.vocab)
@@ -771,6 +792,10 @@ class QuantLlama:
         else:
             ops.gemm(ops.rmsnorm(x2, self.norm, self.eps), q.qn, q.mn, q.bits, q.mode, q.N, q.K, out=y)
         return out
+
+    def _lm8_rows(self):
+        """rows one launch of the 8-bit lm_head takes: 8 (ops.lm8_gemv), or with lm8_kernel="mfma" 16 / as many as fit LDS (ops.lm8_gemm)"""
+        return max(8, ops.lm8_gemm_max_rows(self.H)) if self.lm8_kernel == "mfma" else 8
 
     def _lm_logits_many(self, x, out=None):
         """out [n, vocab] = lm_head(final RMSNorm(x [n, H])) for any number of rows (an all-logits prompt pass, a piece of score_rows).  16: one
@@ -1426,10 +1451,12 @@ class QuantLlama:
         return rows
 
     def _lm_head_streamed(self, x, out):
-        """out [n, vocab] = lm_head(final RMSNorm(x [n, H])) through the weight-streaming kernel, 8 rows a launch (any vocabulary)"""
+        """out [n, vocab] = lm_head(final RMSNorm(x [n, H])) through the weight-streaming kernel, 8 rows a launch (any vocabulary); an 8-bit
+        lm_head with lm8_kernel="mfma": _lm8_rows() rows a launch"""
         n = x.shape[0]
-        for r0 in range(0, n, 8):
-            r1 = min(n, r0 + 8)
+        step = self._lm8_rows() if self.lm_head_bits == 8 else 8
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
             if r1 - r0 == 1:
                 self._lm_logits(x[r0], out[r0])
             else:

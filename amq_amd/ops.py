@@ -1372,6 +1372,36 @@ def lm8_gemv(x, w8, gamma=None, eps=0.0, out=None):
     return y
 
 
+LM8_KERNELS = ("dot", "mfma")
+LM8_GEMM_ROWS = 16
+
+
+def lm8_gemm_max_rows(K):
+    """rows of x one ops.lm8_gemm launch takes at this K: 16, or as many as fit LDS behind the kernel's 256-byte zero block (row stride K + 8 halves)"""
+    return max(0, min(LM8_GEMM_ROWS, (160 * 1024 - 256) // ((K + 8) * 2)))
+
+
+def lm8_gemm(x, w8, gamma=None, eps=0.0, out=None):
+    """ops.lm8_gemv's product on the matrix cores (include/amq_hip.h amq_lm8_gemm_f16): x [K] -> y [N], or x [M, K] with 1 <= M <= 16 (and M rows
+    inside LDS: lm8_gemm_max_rows(K)) -> y [M, N], one launch whose cost does not grow with M.  The weights are lm8_gemv's bit for bit, the
+    fp32 sum runs in another order: the last bits of y differ from lm8_gemv's.  Rows of an M-row call equal one-row calls of this op bit for bit."""
+    M = x.shape[0] if x.dim() == 2 else 1
+    if M < 1 or M > LM8_GEMM_ROWS:
+        raise ValueError(f"lm8_gemm takes 1 .. {LM8_GEMM_ROWS} rows (got {M})")
+    if M > lm8_gemm_max_rows(w8.shape[1]):
+        raise ValueError(f"lm8_gemm: {M} rows of K={w8.shape[1]} do not fit LDS (at most {lm8_gemm_max_rows(w8.shape[1])})")
+    N, K = _lm8_layer(w8)
+    _need(x, torch.float16, "x", M * K)
+    if gamma is not None:
+        _need(gamma, torch.float16, "gamma", K)
+    shape = (M, N) if x.dim() == 2 else (N,)
+    y = out if out is not None else torch.empty(shape, dtype=torch.float16, device=x.device)
+    _need(y, torch.float16, "y", M * N)
+    _lib.check(_lib.load().amq_lm8_gemm_f16(_lib.ptr(x), _lib.ptr(w8.codes), _lib.ptr(w8.meta), _lib.ptr(y), _lib.ptr(gamma), ctypes.c_float(eps),
+                                            M, N, K, GROUP, _lib.current_stream()))
+    return y
+
+
 def lm8_dequantize(w8, row0=0, rows=None, out=None):
     """rows row0 .. row0 + rows - 1 (default: to the last) of the 8-bit lm_head's weights as fp16 [rows, K]: w = fp16(fp16(fp16(c) - zero) * scale)"""
     N, K = _lm8_layer(w8)
@@ -2316,7 +2346,7 @@ def _on_tensor_device(fn):
 
 
 for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_hinv", "gptq_hessian_launch", "gptq_hinv_launch", "gptq_quantize", "gptq_quantize_launch", "gptq_quantize_static_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
-              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "lm8_gemv", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
+              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "lm8_gemv", "lm8_gemm", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup", "decode_tail_lookup_sample"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name

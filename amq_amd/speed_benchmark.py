@@ -25,7 +25,7 @@ import torch
 
 from . import arch as arch_mod
 from . import checkpoint
-from .llama import DenseLlama, QuantLlama, get_memory_footprint
+from .llama import DenseLlama, QuantLlama, check_lm8_kernel, get_memory_footprint
 from .speed import benchmark_speed, cleanup
 
 
@@ -57,6 +57,9 @@ def build_parser():
                    help="(extension) KV cache of the quantized runner: 16 = fp16 rows, 8 = int8 rows with a scale per row")
     p.add_argument("--lm_head_bits", type=int, default=16, choices=(16, 8, 4),
                    help="(extension) lm_head of the quantized runner: 16 = fp16 as the reference keeps it, 8 = the LM8 layer, 4 = a packed 4-bit layer")
+    p.add_argument("--lm8_kernel", type=str, default="dot", choices=("dot", "mfma"),
+                   help="(extension) kernel of an --lm_head_bits 8 runner's 2 .. 16-row lm_head calls: dot = the dot-product kernel, mfma = the "
+                        "matrix-core kernel")
     return p
 
 
@@ -140,8 +143,10 @@ def main(argv=None):
             raise FileNotFoundError(f"the arch needs HQQ checkpoints that are not there: {missing}")
         model = checkpoint.load_mixed({b: ckpt_dir(b) for b in used}, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits,
                                       lm_head_bits=args.lm_head_bits)
+        model.lm8_kernel = check_lm8_kernel(args.lm8_kernel, args.lm_head_bits)      # (read at every lm_head call: nothing is captured yet)
     else:
-        model = QuantLlama(cfg, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits, lm_head_bits=args.lm_head_bits)
+        model = QuantLlama(cfg, linear, max_seq=max_seq, batch=run_batch, kv_bits=args.kv_bits, lm_head_bits=args.lm_head_bits,
+                           lm8_kernel=args.lm8_kernel)
     run(model, f"{args.target_bits}bit")
     del model
     cleanup()
@@ -151,6 +156,8 @@ def main(argv=None):
         del shown["kv_bits"]                     # the default: the reference-compatible output as it was
     if shown.get("lm_head_bits") == 16:
         del shown["lm_head_bits"]
+    if shown.get("lm8_kernel") == "dot":
+        del shown["lm8_kernel"]
     result.update({"args": shown})
     if args.file_name:
         out_path = os.path.join("benchmark/outputs", args.file_name)      # amq_speed_benchmark.py:290-293

@@ -526,6 +526,12 @@ int amq_gemv_f16w_rows(const void* x, const void* W, const void* bias, void* y, 
 int amq_lm8_gemv_f16(const void* x, const void* codes, const void* meta, void* y, const void* gamma, float eps, int M, int N, int K, int group,
                      void* stream);
 int amq_lm8_dequantize_f16(const void* codes, const void* meta, void* out, int row0, int rows, int N, int K, int group, void* stream);
+/* amq_lm8_gemm_f16 (additive, AMQ_VERSION unchanged): amq_lm8_gemv_f16's product on the matrix cores for 1 <= M <= 16 rows of x -- the same
+ * arguments, alignment rules and weights bit for bit; the fp32 sum runs in another order (v_mfma_f32_16x16x32_f16 over a permuted k), so results
+ * differ from amq_lm8_gemv_f16's in the last bits.  Rows of an M-row call equal M one-row calls of THIS entry point bit for bit.  256 bytes +
+ * M rows of K + 8 halves must fit LDS (16 rows at K = 4096, 8 at K = 8192; AMQ_ESHAPE otherwise). */
+int amq_lm8_gemm_f16(const void* x, const void* codes, const void* meta, void* y, const void* gamma, float eps, int M, int N, int K, int group,
+                     void* stream);
 /* one new token per sequence: RoPE(q, k) at position *pos_dev (or pos if pos_dev is NULL), append k/v to the
  * cache [B, n_kv_heads, max_seq, 128], out = softmax(q K^T / sqrt(128)) V.  head_dim must be 128.
  * Replaces FT single_query_attention (ft/attention/decoder_masked_multihead_attention.cu:30-61) with HF-Llama numerics. */

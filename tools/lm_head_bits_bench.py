@@ -11,7 +11,11 @@
   (iv)  what the lm_head of a 2048-row scoring window costs: the fp16 MFMA GEMM against the 8-bit weight-streaming kernel, 8 rows a launch, and
         against the route the runner takes from 64 rows on (slices of the layer dequantized into a scratch + the fp16 GEMM, per 512-row piece).
 
-usage: lm_head_bits_bench.py [--out profiles/lm_head_bits.json] [--quick] [--only window]"""
+  (v)   --only gemm (-> profiles/lm8_gemm.json): the 8-bit lm_head's matrix-core kernel (ops.lm8_gemm, QuantLlama(lm8_kernel="mfma")) against the
+        fp16 and ops.lm8_gemv launches of the SAME run at R = 1, 2, 4, 8, 16 rows (16 rows: the two 8-row launches the other two need), and the
+        whole token step of the synthetic Llama-3.1-8B shape at lm_head_bits=8 with lm8_kernel "dot" | "mfma", for batch 8 and for lookup=7.
+
+usage: lm_head_bits_bench.py [--out profiles/lm_head_bits.json] [--quick] [--only window | gemm]"""
 import argparse
 import json
 import math
@@ -158,6 +162,94 @@ def step_leg(rounds, steps):
     return out
 
 
+def gemm_launch_leg(rounds):
+    rows_out = []
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for name, n, k in SHAPES:
+        nbytes = {"fp16": n * k * 2, "8bit": n * k + n * (k // 128) * 4}
+        nbytes["mfma"] = nbytes["8bit"]
+        copies = {leg: max(2, -(-ROTATION_BYTES // b)) for leg, b in nbytes.items()}
+        w16 = [(torch.randn(n, k, device=DEV, generator=gen) / math.sqrt(k)).to(torch.float16) for _ in range(copies["fp16"])]
+        w8 = [synthetic_lm8(n, k, gen) for _ in range(copies["8bit"])]
+        gamma = (1.0 + 0.05 * torch.randn(k, device=DEV, generator=gen)).to(torch.float16)
+        for R in (1, 2, 4, 8, 16):
+            x = torch.randn(R, k, device=DEV, generator=gen).to(torch.float16)
+            y = torch.empty(R, n, dtype=torch.float16, device=DEV)
+            pieces = [(x[0], y[0])] if R == 1 else [(x[r0:r0 + 8], y[r0:r0 + 8]) for r0 in range(0, R, 8)]       # (the 1 .. 8-row kernels: 8 rows a launch)
+
+            def f16(c):
+                for xi, yi in pieces:
+                    ops.gemv_f16w(xi, w16[c], gamma=gamma, eps=EPS, out=yi)
+
+            def dot(c):
+                for xi, yi in pieces:
+                    ops.lm8_gemv(xi, w8[c], gamma=gamma, eps=EPS, out=yi)
+
+            graphs = {"fp16": _graph(f16, copies["fp16"]), "8bit": _graph(dot, copies["8bit"]),
+                      "mfma": _graph(lambda c: ops.lm8_gemm(x[0] if R == 1 else x, w8[c], gamma=gamma, eps=EPS, out=y[0] if R == 1 else y), copies["mfma"])}
+            us = _alternate(graphs, copies, rounds)
+            rec = {"leg": "launch", "model": name, "N": n, "K": k, "rows": R, "launches": {"fp16": len(pieces), "8bit": len(pieces), "mfma": 1}}
+            for leg in graphs:
+                st = _stats(us[leg])
+                rec[leg] = dict(st, bytes=nbytes[leg], gb_per_s=round(nbytes[leg] * rec["launches"][leg] / st["us"] / 1e3, 1), copies=copies[leg])
+            for other in ("fp16", "8bit"):                  # ahead or behind by more than the spread of the rounds, else "level"
+                rec["mfma_vs_" + other] = ("ahead" if rec["mfma"]["us_max"] < rec[other]["us_min"] else
+                                           "behind" if rec["mfma"]["us_min"] > rec[other]["us_max"] else "level")
+            print(json.dumps(rec), flush=True)
+            rows_out.append(rec)
+            del graphs
+        del w16, w8
+        torch.cuda.empty_cache()
+    return rows_out
+
+
+class _RunnerSteps(_Steps):
+    """_Steps for batch and lookup runners: every round starts from the state behind the prompt (lookup: the history block too)"""
+
+    def __init__(self, m, n):
+        self.m, self.n = m, n
+        self.saved = (m.token.clone(), m.pos.clone(), m.lookup_state.clone() if m.lookup else None)
+
+    def prepare(self):
+        self.m._restore_step_inputs(self.saved)
+        torch.cuda.synchronize()
+
+
+def gemm_step_leg(rounds, steps):
+    name = SHAPES[1][0]
+    cfg = arch_mod.MODEL_CONFIGS[name]
+    linear = arch_mod.synthesize_arch(cfg, 3.0, seed=0)[0]["linear"]
+    out = []
+    for what, kw in (("batch 8", dict(batch=8)), ("lookup 7", dict(lookup=7))):
+        runners, graphs, packed = {}, {}, None
+        for kernel in ("dot", "mfma"):
+            m = QuantLlama(cfg, linear, device=DEV, max_seq=512, seed=0, lm_head_bits=8, lm_head_packed=packed, lm8_kernel=kernel, **kw)
+            packed = m.lm_head_q
+            B = kw.get("batch", 1)
+            m.prefill(torch.randint(0, cfg["vocab_size"], (B, 64) if B > 1 else (64,), generator=torch.Generator().manual_seed(1)))
+            m.capture()
+            runners[kernel], graphs[kernel] = m, _RunnerSteps(m, steps)
+        for g in graphs.values():
+            g.prepare()
+            g.replay()
+        torch.cuda.synchronize()
+        us = _alternate(graphs, {k: steps for k in graphs}, rounds)
+        rec = {"leg": "step", "model": name, "runner": what, "arch": "synthesized avg 3.0 bit, group 128", "context": 64, "steps_per_round": steps,
+               "lm_head_rows_per_step": runners["dot"].R}
+        for kernel, m in runners.items():
+            m.check()
+            st = _stats(us[kernel])
+            rec[kernel] = dict(st, steps_per_s=round(1e6 / st["us"], 1))
+            if "batch" in kw:
+                rec[kernel]["tokens_per_s"] = round(kw["batch"] * 1e6 / st["us"], 1)
+        rec["mfma_vs_dot"] = ("ahead" if rec["mfma"]["us_max"] < rec["dot"]["us_min"] else "behind" if rec["mfma"]["us_min"] > rec["dot"]["us_max"] else "level")
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+        del runners, graphs
+        torch.cuda.empty_cache()
+    return out
+
+
 def drift_leg():
     out = []
     for name, n, k in SHAPES:
@@ -218,15 +310,27 @@ def window_leg(rounds, rows=2048):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "lm_head_bits.json"))
-    p.add_argument("--only", default=None, choices=("window",))
+    p.add_argument("--out", default=None, help="default: profiles/lm_head_bits.json (--only gemm: profiles/lm8_gemm.json)")
+    p.add_argument("--only", default=None, choices=("window", "gemm"))
     p.add_argument("--quick", action="store_true", help="fewer rounds (a rehearsal of the script, not a measurement)")
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("lm_head_bits_bench.py measures on the GPU: none found")
     rounds = 3 if args.quick else 9
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "lm8_gemm.json" if args.only == "gemm" else "lm_head_bits.json")
     res = {"device": torch.cuda.get_device_name(0), "method": "one process, legs alternating per round, hipGraph replay, HIP events; median (min, max) "
            "over the rounds; launch legs rotate > 600 MB of layer copies", "rounds": rounds}
+    if args.only == "gemm":                             # leg (v) alone, into a file of its own
+        res["launch"] = gemm_launch_leg(rounds)
+        res["step"] = gemm_step_leg(rounds, 8 if args.quick else 32)
+        res["not_measured"] = "a real checkpoint, perplexity, counters; lookup steps run without accepted drafts (synthetic weights)"
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print("wrote", args.out, flush=True)
+        return
     if args.only == "window":                           # (re-measure leg (iv) alone into an existing file)
         with open(args.out) as f:
             res = json.load(f)
