@@ -166,6 +166,7 @@ SIGNATURES = {
     "amq_lm8_gemv_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
     "amq_lm8_dequantize_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "amq_lm8_gemm_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    "amq_lm8_gemm_rows_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),       # (x, codes, meta, y, M, N, K, group, stream)
     "amq_decode_tail_batch_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "amq_decode_tail_suppress_f16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "amq_sample_f16": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

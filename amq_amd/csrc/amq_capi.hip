@@ -1089,6 +1089,23 @@ int amq_lm8_gemm_f16(const void* x, const void* codes, const void* meta, void* y
     return check_hip(amq::launch_lm8_gemm(x, codes, meta, y, gamma, eps, M, N, K, (hipStream_t)stream), "lm8_gemm");
 }
 
+int amq_lm8_gemm_rows_f16(const void* x, const void* codes, const void* meta, void* y, int M, int N, int K, int group, void* stream) {
+    const char* who = "amq_lm8_gemm_rows_f16";
+    if (!x || !codes || !meta || !y) return fail(AMQ_EINVAL, "%s: null pointer", who);
+    if (int rc = check_lm8_aligned(who, "x", x, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "codes", codes, 16)) return rc;
+    if (int rc = check_lm8_aligned(who, "meta", meta, 4)) return rc;
+    if (int rc = check_lm8_aligned(who, "y", y, 2)) return rc;
+    if (M < 1) return fail(AMQ_ESHAPE, "%s: M must be >= 1 (got %d)", who, M);
+    if (int rc = check_lm8(who, N, K, group)) return rc;
+    // the kernel's offsets into x and codes are 32-bit byte counts, and a tile of y is one workgroup of a one-dimensional grid
+    if ((unsigned long long)M * K * 2 >= (1ull << 32)) return fail(AMQ_ESHAPE, "%s: x must span fewer than 2^32 bytes (M=%d K=%d)", who, M, K);
+    if ((unsigned long long)N * K >= (1ull << 32)) return fail(AMQ_ESHAPE, "%s: codes must span fewer than 2^32 bytes (N=%d K=%d)", who, N, K);
+    const unsigned long long tiles = ((unsigned long long)(M + amq::LM8_ROWS_BM - 1) / amq::LM8_ROWS_BM) * ((N + amq::LM8_ROWS_BN - 1) / amq::LM8_ROWS_BN);
+    if (tiles >= (1ull << 31)) return fail(AMQ_ESHAPE, "%s: %llu tiles of y are more than one launch takes (M=%d N=%d)", who, tiles, M, N);
+    return check_hip(amq::launch_lm8_gemm_rows(x, codes, meta, y, M, N, K, (hipStream_t)stream), "lm8_gemm_rows");
+}
+
 int amq_lm8_dequantize_f16(const void* codes, const void* meta, void* out, int row0, int rows, int N, int K, int group, void* stream) {
     const char* who = "amq_lm8_dequantize_f16";
     if (!codes || !meta || !out) return fail(AMQ_EINVAL, "%s: null pointer", who);

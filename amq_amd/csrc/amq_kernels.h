@@ -274,6 +274,9 @@ hipError_t launch_lm8_dequantize(const void* codes, const void* meta, void* out,
 size_t lm8_gemm_lds_bytes(int M, int K);
 hipError_t launch_lm8_gemm(const void* x, const void* codes, const void* meta, void* y, const void* gamma, float eps, int M, int N, int K,
                            hipStream_t st);
+// the same layer for any number of (normed) rows (amq_lm8_gemm_rows.hip): LM8_ROWS_BM x LM8_ROWS_BN tiles of y, one workgroup each
+enum { LM8_ROWS_BM = 128, LM8_ROWS_BN = 256 };
+hipError_t launch_lm8_gemm_rows(const void* x, const void* codes, const void* meta, void* y, int M, int N, int K, hipStream_t st);
 
 // sampling tail / row sampler (amq_sample.hip).  state: the 128-byte device block of include/amq_hip.h (int32 word indices below)
 enum { SMP_TEMPERATURE = 0, SMP_TOP_K = 1, SMP_TOP_P = 2, SMP_PAD_ID = 3, SMP_SEED = 4, SMP_DRAW = 6, SMP_EOS = 8, SMP_FINISHED = 16,

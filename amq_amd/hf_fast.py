@@ -403,7 +403,8 @@ def convert_model_to_hip(model, sampling=False, padded=False, lookup=False, scor
     ``model(ids, start_pos=p, use_cache=False)`` with several rows behind cached rows is served; ``lm_head_bits=8`` / ``4``: the runners read a packed lm_head (QuantLlama(lm_head_bits=)),
     quantized once from ``model.lm_head.weight`` and shared by every runner of the model; the module itself keeps its fp16 weight, so HF's own
     forward and a reverted model are untouched; ``lm8_kernel="mfma"`` (with ``lm_head_bits=8``): the runners' 2 .. 16-row lm_head calls take the
-    matrix-core kernel (QuantLlama(lm8_kernel=)).  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
+    matrix-core kernel (QuantLlama(lm8_kernel=)), ``lm8_kernel="tiled"``: those, and an all-logits prompt pass of 17 .. 128 rows is one tiled
+    matrix-core launch over the 8-bit bytes.  Calling it again on a converted model only updates the flags.  ``revert_model_to_hf(model)`` undoes it."""
     if not (hasattr(model, "lm_head") and hasattr(getattr(model, "model", None), "layers")):
         raise TypeError("convert_model_to_hip expects a Llama-family causal LM (model.model.layers, model.lm_head)")
     from .llama import check_kv8_kernel, check_kv8_prompt, check_kv_bits, check_lm8_kernel, check_lm_head_bits

@@ -183,12 +183,13 @@ def check_kv8_prompt(kv8_prompt, kv_bits):
 
 def check_lm8_kernel(lm8_kernel, lm_head_bits):
     """-> lm8_kernel, or ValueError: the kernel behind an lm_head_bits=8 runner's logits ("dot": ops.lm8_gemv, at most 8 rows a launch; "mfma":
-    ops.lm8_gemm for 2 .. 16 rows).  A step of its own behind runner_options (whose answers it does not change)"""
+    ops.lm8_gemm for 2 .. 16 rows; "tiled": that, and ops.lm8_gemm_rows for many-row calls of 17 .. QuantLlama.LM8_TILED_TO rows).  A step of its own behind
+    runner_options (whose answers it does not change)"""
     if lm8_kernel not in ops.LM8_KERNELS:
-        raise ValueError(f"lm8_kernel must be 'dot' (the dot-product kernel, 1 .. 8 rows a launch) or 'mfma' (the matrix-core kernel for 2 .. 16 "
-                         f"rows), got {lm8_kernel!r}")
-    if lm8_kernel == "mfma" and lm_head_bits != 8:
-        raise ValueError(f"lm8_kernel='mfma' chooses among the 8-bit lm_head's kernels: it needs lm_head_bits=8 (got lm_head_bits={lm_head_bits})")
+        raise ValueError(f"lm8_kernel must be 'dot' (the dot-product kernel, 1 .. 8 rows a launch), 'mfma' (the matrix-core kernel for 2 .. 16 "
+                         f"rows) or 'tiled' ('mfma' and the tiled matrix-core kernel for 17 .. 128 rows), got {lm8_kernel!r}")
+    if lm8_kernel != "dot" and lm_head_bits != 8:
+        raise ValueError(f"lm8_kernel={lm8_kernel!r} chooses among the 8-bit lm_head's kernels: it needs lm_head_bits=8 (got lm_head_bits={lm_head_bits})")
     return lm8_kernel
 
 
@@ -367,6 +368,11 @@ class QuantLlama:
     # Reasoned, not tuned; profiles/lm_head_bits.json has both routes at 2048 rows.
     LM8_SLICE_ROWS = 16384
     LM8_SLICED_FROM = 64
+    # lm8_kernel="tiled": the row count up to which a many-row call is ONE ops.lm8_gemm_rows launch -- one M panel of the kernel.  Measured
+    # (profiles/lm8_gemm_rows.json, three vocabularies): at 64 and 128 rows it is 1.4 - 2.6x ahead of the dequantized slices, at 512 and 2048 rows
+    # 1.4 - 2.7x behind them (its time grows with the M panels, 322 us each at 128256 x 4096); 129 .. 511 rows were not measured and keep the
+    # route they had.
+    LM8_TILED_TO = 128
     _lm8_scratch = None
     ENGINE_DEFAULT = False      # what engine=None means (the engine is opt-in until it beats the five-launch step: HISTORY.md 3.2b)
     # prompt passes also leave the logits of EVERY prompt row in self.logits_rows [B, S, vocab] (HF's forward returns them all; the runner's own
@@ -428,7 +434,10 @@ class QuantLlama:
         lm8_kernel: the kernel behind an lm_head_bits=8 runner's logits.  "dot" -- ops.lm8_gemv, every launch the option has always issued (at most
         8 rows each); "mfma" -- calls of 2 .. 16 rows (a batch, a lookup runner's verify rows, the pieces of a many-row pass below LM8_SLICED_FROM
         rows) go to ops.lm8_gemm, the matrix-core kernel over the same bytes: one launch whose cost does not grow with its rows; the last bits of
-        those logits differ from "dot"'s (another summation order).  One row stays on ops.lm8_gemv.
+        those logits differ from "dot"'s (another summation order).  One row stays on ops.lm8_gemv.  "tiled" -- "mfma", and a many-row call
+        of 17 .. LM8_TILED_TO rows (an all-logits prompt pass, a short piece of score_rows) is ops.rmsnorm + ONE ops.lm8_gemm_rows launch over the
+        8-bit bytes instead of the 16-row pieces and the dequantized slices, with no fp16 scratch of the lm_head; more rows keep the slices,
+        which measured faster there.
         lm_head_packed: the packed layer of an earlier runner over the same weights (hf_fast shares one among the runners it builds), instead of
         quantizing again.  What is not offered with what: runner_options, route_reasons ("Runner options")."""
         config = MODEL_CONFIGS[config] if isinstance(config, str) else config
@@ -774,12 +783,12 @@ class QuantLlama:
     def _lm_logits(self, x, out):
         """out = lm_head(final RMSNorm(x)) for up to 8 hidden rows -- x [H] -> out [vocab], or x [M, H] -> out [M, vocab] --: the ONE place a token
         step, a prompt pass' last rows and the streamed many-row loop form logits.  16: the fp16 weight-streaming kernel with the norm as its
-        prologue; 8: ops.lm8_gemv, the same shape (lm8_kernel="mfma": ops.lm8_gemm from 2 rows on, up to _lm8_rows()); 4: the packed GEMV with the RMSNorm prologue as far as its LDS stage reaches
+        prologue; 8: ops.lm8_gemv, the same shape (lm8_kernel="mfma" / "tiled": ops.lm8_gemm from 2 rows on, up to _lm8_rows()); 4: the packed GEMV with the RMSNorm prologue as far as its LDS stage reaches
         (ops.gemv_max_rows(H)), an rmsnorm launch + the plain GEMV beyond (what _behind_norm does), the GEMM past that"""
         if self.lm_head_bits == 16:
             return ops.gemv_f16w(x, self.lm_head, gamma=self.norm, eps=self.eps, out=out)
         if self.lm_head_bits == 8:
-            if self.lm8_kernel == "mfma" and x.dim() == 2 and 2 <= x.shape[0] <= self._lm8_rows():
+            if self.lm8_kernel != "dot" and x.dim() == 2 and 2 <= x.shape[0] <= self._lm8_rows():
                 return ops.lm8_gemm(x, self.lm_head_q, gamma=self.norm, eps=self.eps, out=out)
             return ops.lm8_gemv(x, self.lm_head_q, gamma=self.norm, eps=self.eps, out=out)
         q = self.lm_head_q
@@ -794,16 +803,20 @@ class QuantLlama:
         return out
 
     def _lm8_rows(self):
-        """rows one launch of the 8-bit lm_head takes: 8 (ops.lm8_gemv), or with lm8_kernel="mfma" 16 / as many as fit LDS (ops.lm8_gemm)"""
-        return max(8, ops.lm8_gemm_max_rows(self.H)) if self.lm8_kernel == "mfma" else 8
+        """rows one launch of _lm_logits takes: 8 (ops.lm8_gemv), or with lm8_kernel="mfma" / "tiled" 16 / as many as fit LDS (ops.lm8_gemm)"""
+        return max(8, ops.lm8_gemm_max_rows(self.H)) if self.lm8_kernel != "dot" else 8
 
     def _lm_logits_many(self, x, out=None):
         """out [n, vocab] = lm_head(final RMSNorm(x [n, H])) for any number of rows (an all-logits prompt pass, a piece of score_rows).  16: one
         fp16 MFMA GEMM (the weight-streaming kernel, 8 rows a launch, for a vocabulary that is no multiple of 16: test models); 4: ops.gemm over
         the packed layer; 8: from LM8_SLICED_FROM rows on (and a vocabulary the fp16 GEMM takes) slices of LM8_SLICE_ROWS vocabulary rows dequantized
         into one bounded fp16 scratch and the fp16 GEMM on each slice, writing its columns of ``out`` (lm8_logits_sliced); fewer rows: the
-        weight-streaming kernel, 8 rows a launch.  profiles/lm_head_bits.json has what a 2048-row window costs either way."""
+        weight-streaming kernel, 8 rows a launch.  profiles/lm_head_bits.json has what a 2048-row window costs either way.  8 with
+        lm8_kernel="tiled": more than _lm8_rows() and up to LM8_TILED_TO rows are one ops.lm8_gemm_rows launch behind the norm, whatever the
+        vocabulary -- no slices, no scratch; more rows keep the routes above, which measured faster there (profiles/lm8_gemm_rows.json)."""
         n = x.shape[0]
+        if self.lm_head_bits == 8 and self.lm8_kernel == "tiled" and self._lm8_rows() < n <= self.LM8_TILED_TO:
+            return ops.lm8_gemm_rows(ops.rmsnorm(x, self.norm, self.eps), self.lm_head_q, out=out)
         if self.lm_head_bits == 8 and n >= self.LM8_SLICED_FROM and self.vocab % 16 == 0:
             if out is None:
                 out = torch.empty(n, self.vocab, dtype=torch.float16, device=x.device)
@@ -1452,7 +1465,7 @@ class QuantLlama:
 
     def _lm_head_streamed(self, x, out):
         """out [n, vocab] = lm_head(final RMSNorm(x [n, H])) through the weight-streaming kernel, 8 rows a launch (any vocabulary); an 8-bit
-        lm_head with lm8_kernel="mfma": _lm8_rows() rows a launch"""
+        lm_head with lm8_kernel="mfma" / "tiled": _lm8_rows() rows a launch"""
         n = x.shape[0]
         step = self._lm8_rows() if self.lm_head_bits == 8 else 8
         for r0 in range(0, n, step):

@@ -1372,7 +1372,7 @@ def lm8_gemv(x, w8, gamma=None, eps=0.0, out=None):
     return y
 
 
-LM8_KERNELS = ("dot", "mfma")
+LM8_KERNELS = ("dot", "mfma", "tiled")
 LM8_GEMM_ROWS = 16
 
 
@@ -1399,6 +1399,29 @@ def lm8_gemm(x, w8, gamma=None, eps=0.0, out=None):
     _need(y, torch.float16, "y", M * N)
     _lib.check(_lib.load().amq_lm8_gemm_f16(_lib.ptr(x), _lib.ptr(w8.codes), _lib.ptr(w8.meta), _lib.ptr(y), _lib.ptr(gamma), ctypes.c_float(eps),
                                             M, N, K, GROUP, _lib.current_stream()))
+    return y
+
+
+LM8_ROWS_BM = 128      # rows of x in one tile of ops.lm8_gemm_rows (csrc/amq_kernels.h LM8_ROWS_BM): M = LM8_ROWS_BM + 1 is the first with two M panels
+
+
+def lm8_gemm_rows(x, w8, out=None):
+    """y [M, N] = x [M, K] . W^T over the 8-bit lm_head ``w8`` for ANY number of rows, x already normed (include/amq_hip.h amq_lm8_gemm_rows_f16):
+    one launch of 128 x 256 tiles on the matrix cores, the layer's bytes read as they are (once per 128 rows of x), no fp16 copy of them.  The
+    weights are lm8_gemv's bit for bit, the fp32 sum runs in an order of its own.  Row m of a call equals row m of any other call bit for bit."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError(f"x: expected [M, K] with at least one row, got {tuple(getattr(x, 'shape', ()))}")
+    M = x.shape[0]
+    if x.shape[1] != w8.shape[1]:
+        raise ValueError(f"x: expected rows of K={w8.shape[1]}, got {x.shape[1]}")
+    _need(x, torch.float16, "x", M * w8.shape[1])
+    N, K = _lm8_layer(w8)
+    if M * K * 2 >= 2 ** 32 or N * K >= 2 ** 32:
+        raise ValueError(f"lm8_gemm_rows: x and the codes must each span fewer than 2^32 bytes (M={M}, N={N}, K={K})")
+    y = out if out is not None else torch.empty(M, N, dtype=torch.float16, device=x.device)
+    _need(y, torch.float16, "y", M * N)
+    _lib.check(_lib.load().amq_lm8_gemm_rows_f16(_lib.ptr(x), _lib.ptr(w8.codes), _lib.ptr(w8.meta), _lib.ptr(y), M, N, K, GROUP,
+                                                 _lib.current_stream()))
     return y
 
 
@@ -2346,7 +2369,7 @@ def _on_tensor_device(fn):
 
 
 for _name in ("hqq_quantize", "hqq_quantize_launch", "gptq_hinv", "gptq_hessian_launch", "gptq_hinv_launch", "gptq_quantize", "gptq_quantize_launch", "gptq_quantize_static_launch", "awq_quantize", "awq_quantize_launch", "awq_clip", "awq_clip_launch", "owq_range", "owq_range_launch", "owq_select", "owq_quantize", "owq_quantize_launch", "owq_gather", "owq_outlier_add", "repack_from_hqq", "repack_from_gptq", "repack_from_awq", "dequantize", "dequantize_hqq", "dequantize_bf16", "linear_bf16", "gemv", "gemm", "gemm_f16w", "xfrag",
-              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "lm8_gemv", "lm8_gemm", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
+              "rmsnorm_xfrag", "gemm_xfrag", "gemm_xfrag_grouped", "linear", "gemv_grouped", "rmsnorm", "gemv_f16w", "lm8_gemv", "lm8_gemm", "lm8_gemm_rows", "decode_tail", "sample", "logit_nll", "logit_jsd", "decode_tail_sample", "rope_cache",
               "attn_prefill", "rope_rows", "silu_mul", "gemv_qkv_attn", "attn_decode", "attn_decode_rows", "decode_tail_lookup", "decode_tail_lookup_sample"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name

@@ -184,7 +184,7 @@ def benchmark_speed(model, tokenizer=None, use_ft=True, iteration=1, sizes=(1, 1
     ``generate`` is timed (HFForwardRunner: the reference's non-FT loops).  ``tokenizer``: used by TTFT mode as in
     the reference (None: ids are used directly).  ``kv_bits`` (extension): the KV cache of the runner built over an HF model here (8: int8 rows
     with a scale per row; a runner handed in keeps the cache it was built with); ``lm_head_bits`` / ``lm8_kernel`` (extensions): the lm_head of
-    that runner and, at 8 bits, its kernel (QuantLlama(lm8_kernel=))."""
+    that runner and, at 8 bits, its kernel ("dot", "mfma" or "tiled": QuantLlama(lm8_kernel=))."""
     from .llama import check_lm8_kernel
     check_lm8_kernel(lm8_kernel, lm_head_bits)
     assert mode.lower() in ["tps", "gemv", "gemm", "ttft"], \

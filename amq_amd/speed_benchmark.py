@@ -57,9 +57,9 @@ def build_parser():
                    help="(extension) KV cache of the quantized runner: 16 = fp16 rows, 8 = int8 rows with a scale per row")
     p.add_argument("--lm_head_bits", type=int, default=16, choices=(16, 8, 4),
                    help="(extension) lm_head of the quantized runner: 16 = fp16 as the reference keeps it, 8 = the LM8 layer, 4 = a packed 4-bit layer")
-    p.add_argument("--lm8_kernel", type=str, default="dot", choices=("dot", "mfma"),
+    p.add_argument("--lm8_kernel", type=str, default="dot", choices=("dot", "mfma", "tiled"),
                    help="(extension) kernel of an --lm_head_bits 8 runner's 2 .. 16-row lm_head calls: dot = the dot-product kernel, mfma = the "
-                        "matrix-core kernel")
+                        "matrix-core kernel, tiled = mfma and the tiled matrix-core kernel for calls of 17 .. 128 rows")
     return p
 
 

@@ -532,6 +532,12 @@ int amq_lm8_dequantize_f16(const void* codes, const void* meta, void* out, int r
  * M rows of K + 8 halves must fit LDS (16 rows at K = 4096, 8 at K = 8192; AMQ_ESHAPE otherwise). */
 int amq_lm8_gemm_f16(const void* x, const void* codes, const void* meta, void* y, const void* gamma, float eps, int M, int N, int K, int group,
                      void* stream);
+/* amq_lm8_gemm_rows_f16 (additive, AMQ_VERSION unchanged): y [M, N] = x [M, K] . W^T over the same layer for ANY M >= 1, as tiles of 128 rows of x
+ * by 256 vocabulary rows on v_mfma_f32_32x32x16_f16 -- one launch, the layer read once per 128 rows of x, no workspace.  x is taken as it is
+ * (normed by the caller: no gamma / eps).  x and codes 16-byte aligned, meta 4, y 2; x and codes must each span fewer than 2^32 bytes
+ * (AMQ_ESHAPE otherwise).  The weights are amq_lm8_gemv_f16's bit for bit, the fp32 sum runs in an order of its own; row m of an M-row call
+ * equals row m of any other call of THIS entry point bit for bit. */
+int amq_lm8_gemm_rows_f16(const void* x, const void* codes, const void* meta, void* y, int M, int N, int K, int group, void* stream);
 /* one new token per sequence: RoPE(q, k) at position *pos_dev (or pos if pos_dev is NULL), append k/v to the
  * cache [B, n_kv_heads, max_seq, 128], out = softmax(q K^T / sqrt(128)) V.  head_dim must be 128.
  * Replaces FT single_query_attention (ft/attention/decoder_masked_multihead_attention.cu:30-61) with HF-Llama numerics. */
